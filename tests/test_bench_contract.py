@@ -126,3 +126,28 @@ def test_host_cores_respects_the_cgroup_quota(tmp_path, monkeypatch):
     assert 1 <= n <= info["cores_available"] and n <= info.get("affinity", n)
     if "cgroup_cpu_quota" in info:
         assert n <= max(1, int(info["cgroup_cpu_quota"] + 0.5))
+
+
+def test_dump_outputs_writes_the_image_or_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the gathered image as float32; above the byte cap a sample of whole pixels that is the same on every run"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    assert b.DUMP_BYTES + 4096 < 64e6
+    img = np.random.default_rng(3).random((27, 48, 4), dtype=np.float32)
+    b.dump_outputs(str(tmp_path / "full"), img)
+    got = np.load(tmp_path / "full" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    monkeypatch.setattr(b, "DUMP_BYTES", 100 * 16)
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), img)
+    s1, s2 = np.load(tmp_path / "s1" / "image_sample.npy"), np.load(tmp_path / "s2" / "image_sample.npy")
+    assert s1.shape == (100, 4) and s1.dtype == np.float32 and np.array_equal(s1, s2)
+    assert all(any(np.array_equal(p, q) for q in img.reshape(-1, 4)) for p in s1[:5])
+    assert not (tmp_path / "s1" / "image.npy").exists()
+
+
+def test_bench_refuses_zero_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert out.returncode != 0 and "--steps" in out.stderr

@@ -81,11 +81,11 @@ def test_k8_flatten_two_objects(pt):
     assert b[5].tolist() == [0.0] and b[7].tolist() == [0.0]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/objs/table - Copy.obj"), reason="reference checkout not present (GPU box)")
 def test_k8_shipped_obj(pt):
+    """the reference's only shipped asset (src/objs/table - Copy.obj), stored as a fixture under tests/golden/"""
     sc = pt.hostlib.Scene()
     sc.addMaterial("default")
-    sc.addObject("/root/reference/src/objs/table - Copy.obj", 0)
+    sc.addObject(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "table - Copy.obj"), 0)
     b = sc.pack()
     assert sc.count("triangles") == 60 and sc.count("objects") == 5
     _check_tree(b, 60, 5)
