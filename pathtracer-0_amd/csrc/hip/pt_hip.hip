@@ -557,10 +557,12 @@ __global__ void __launch_bounds__(TPB, PT_EP_WAVES) k_extend_persist(DevScene sc
 // ran one instruction stream each; once the kernel had become memory-bound the permuted accesses cost more than the
 // divergence saved: 2-4 % per step on C2-C5, profiles/; likewise the dense LDS-listed pass that used to compute the camera
 // rays of new samples for the whole block.)
+// fcp is __restrict__: nothing the kernel stores aliases the frame constants, so their reads stay scalar loads after its first store; without it
+// each read in a divergent branch (bounce budget, SAMPLE_RES, the camera) became a vector load with a wait of its own (profiles/r07_shade_load_tiers.txt).
 template <int STK, bool STATS, bool DIRECT, bool TEX, bool FAST = false>
 // (the texture-map variants are asked for 5 waves per SIMD: left alone the compiler spends 104-110 registers on them, 4 waves; at 96 it spills two and a
 //  scene with a map on every material gains 3 %: profiles/r05_k_textured_materials.txt.  The float-stack variant would spill ten: left alone.)
-__global__ void __launch_bounds__(SHADE_BLOCK, (TEX && !STATS && STK != 32) ? 5 : 1) k_shade(DevScene sc, Batch b, const FrameConst* fcp, State st, const unsigned* qIn, unsigned* qOut, int iter,
+__global__ void __launch_bounds__(SHADE_BLOCK, (TEX && !STATS && STK != 32) ? 5 : 1) k_shade(DevScene sc, Batch b, const FrameConst* __restrict__ fcp, State st, const unsigned* qIn, unsigned* qOut, int iter,
                                                  int nSlots, Control* ctl) {
     constexpr bool TRANS = STK != 0;
     __shared__ unsigned sCntA[SHADE_BLOCK / 64], sCntB[SHADE_BLOCK / 64], sBase;
