@@ -25,6 +25,7 @@
 // instruction, fully coalesced).  No MFMA: the path is divergent scalar fp32 + pointer chasing.
 #include "../../../include/pt_api.h"
 #include "../../../include/pt_debug.h"
+#include "../../../include/pt_adaptive.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -825,11 +826,14 @@ __global__ void __launch_bounds__(BLOCK) k_scan_inflight(State st, int nSlots, S
 }
 
 // fragColor -> UNORM8 framebuffer -> glReadPixels(GL_RGB) -> Java signed-byte packing -> vertical flip (dispatch.java:804-833)
+// PER_PIXEL (pt_read_display_mean, adaptive images): every pixel divided by its own count F.w; a count of 0 gives 0/0 = NaN, which the clamp shows as 0
+template <bool PER_PIXEL>
 __global__ void __launch_bounds__(BLOCK) k_display(const float4* frame, int W, int H, float frameCount, int javaBytes, unsigned char* out) {
     int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= W * H) return;
     int x = i % W, y = i / W;
     float4 F = frame[i];
+    if (PER_PIXEL) frameCount = F.w;
     float v[3] = {F.x / frameCount, F.y / frameCount, F.z / frameCount};
     int q[3];
 #pragma unroll
@@ -844,6 +848,107 @@ __global__ void __launch_bounds__(BLOCK) k_display(const float4* frame, int W, i
     }
     unsigned char* o = out + 3 * ((size_t)(H - 1 - y) * W + x);
     o[0] = (unsigned char)r; o[1] = (unsigned char)g; o[2] = (unsigned char)b;
+}
+
+// ---- adaptive sampling (include/pt_adaptive.h).  The selection rule over the per-slot statistics T = (sY, sYY, n, 0), in the order the header states it
+// (float32, no contraction: the build's -ffp-contract=off, IEEE divides).  NaN anywhere: every comparison false, the pixel stays inactive.
+struct AdaptRule { float relErr, absErr, mouseX, mouseY, resolution; int minFrames, maxFrames; };
+__device__ __forceinline__ bool adaptiveActive(const AdaptRule& r, float4 T, int px, int py) {
+    FrameConst fc{};
+    fc.mouse[0] = r.mouseX; fc.mouse[1] = r.mouseY; fc.resolution = r.resolution;
+    if (inMouseOverlay(fc, px, py)) return false;
+    const float n = T.z;
+    if (r.maxFrames > 0 && n >= (float)r.maxFrames) return false;
+    if (n < (float)r.minFrames) return true;
+    const float mean = T.x / n;
+    const float var = (T.y - T.x * mean) / (n - 1.0f);
+    const float err2 = var / n;
+    const float tol = fmaxf(r.relErr * fabsf(mean), r.absErr);
+    return err2 > tol * tol;
+}
+// Stable compaction of the active pixels of the job-order list pixXY, in three passes: (1) the rule per pixel, a flag byte and the block's count
+// (wave64 ballot / popcount), (2) one block turns the counts into exclusive block offsets and the total, (3) every active pixel writes its entry at
+// block offset + the active pixels before it in its block.  The order is the list's: deterministic, and the tiles stay together.
+__global__ void __launch_bounds__(BLOCK) k_adaptive_select(const unsigned* pixXY, int nLocal, int W, int shardCount, const float4* stats, AdaptRule r,
+                                                           unsigned char* flag, unsigned* blkCount) {
+    __shared__ unsigned sCnt[BLOCK / 64];
+    const unsigned k = blockIdx.x * BLOCK + threadIdx.x;
+    bool on = false;
+    if (k < (unsigned)nLocal) {
+        const unsigned xy = pixXY[k];
+        const int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
+        const unsigned slot = shardCount == 1 ? (unsigned)(py * W + px) : k;
+        on = adaptiveActive(r, stats[slot], px, py);
+        flag[k] = on ? 1 : 0;
+    }
+    const unsigned long long mask = __ballot(on);
+    if ((threadIdx.x & 63) == 0) sCnt[threadIdx.x >> 6] = (unsigned)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; w++) t += sCnt[w];
+        blkCount[blockIdx.x] = t;
+    }
+}
+// one block of BLOCK threads: blk[0..nb) counts -> exclusive offsets in place, *total = their sum
+__global__ void __launch_bounds__(BLOCK) k_adaptive_scan(unsigned* blk, int nb, unsigned* total) {
+    __shared__ unsigned sv[BLOCK];
+    unsigned carry = 0;
+    for (int base = 0; base < nb; base += BLOCK) {
+        const int i = base + (int)threadIdx.x;
+        const unsigned v = i < nb ? blk[i] : 0u;
+        sv[threadIdx.x] = v;
+        __syncthreads();
+        for (int d = 1; d < BLOCK; d <<= 1) {                     // inclusive Hillis-Steele scan
+            const unsigned a = threadIdx.x >= (unsigned)d ? sv[threadIdx.x - d] : 0u;
+            __syncthreads();
+            sv[threadIdx.x] += a;
+            __syncthreads();
+        }
+        if (i < nb) blk[i] = carry + sv[threadIdx.x] - v;
+        carry += sv[BLOCK - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+// outXY: the stream's pixXY; outSlot (shards only): the accumulator slot of every entry
+__global__ void __launch_bounds__(BLOCK) k_adaptive_compact(const unsigned* pixXY, int nLocal, const unsigned char* flag, const unsigned* blkOff,
+                                                            unsigned* outXY, int* outSlot) {
+    __shared__ unsigned sCnt[BLOCK / 64];
+    const unsigned k = blockIdx.x * BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool on = k < (unsigned)nLocal && flag[k] != 0;
+    const unsigned long long mask = __ballot(on);
+    if (lane == 0) sCnt[wave] = (unsigned)__popcll(mask);
+    __syncthreads();
+    if (!on) return;
+    unsigned off = blkOff[blockIdx.x];
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; w++) off += (w < wave) ? sCnt[w] : 0u;
+    off += (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+    outXY[off] = pixXY[k];
+    if (outSlot) outSlot[off] = (int)k;
+}
+// FRAME accumulation of an adaptive batch (k_accumulate's rule, frag.glsl:924-933) over the active list, and the statistics, both in u_frameCount order.
+// The list entry i is the stream's pixel i: its frame rows sit at colbuf slot py*W+px (one shard) or i (shards: startJob's ls = k); its accumulator
+// slot is py*W+px or b.pixList[i] (an adaptive stream's pixList holds the entries' slots).  Mouse-overlay pixels are never on the list.
+__global__ void __launch_bounds__(BLOCK) k_accumulate_adaptive(Batch b, float4* frame, float4* stats, unsigned f0, int nFrames, int firstFrame) {
+    const unsigned i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (unsigned)b.nLocal) return;
+    const unsigned xy = b.pixXY[i];
+    const unsigned slot = b.shardCount == 1 ? (xy >> 16) * (unsigned)b.W + (xy & 0xffffu) : (unsigned)b.pixList[i];
+    const unsigned cs = b.shardCount == 1 ? slot : i;
+    float4 F = frame[slot], T = stats[slot];
+    for (int f = 0; f < nFrames; f++) {
+        const float4 c = ldS(b.colbuf + (size_t)((f0 + (unsigned)f) % b.ringFrames) * b.nSlots + cs);
+        if ((float)(firstFrame + f) == 1.0f) F = make_float4(c.x, c.y, c.z, 1.0f);
+        else F = make_float4(F.x + c.x, F.y + c.y, F.z + c.z, F.w + 1.0f);
+        const float Y = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+        T = make_float4(T.x + Y, T.y + Y * Y, T.z + 1.0f, 0.0f);
+    }
+    frame[slot] = F;
+    stats[slot] = T;
 }
 
 __global__ void k_unshard(const float4* gathered, const int* maps, int nSlots, int shardCount, float4* full) {
@@ -973,6 +1078,10 @@ struct pt_ctx {
     int pLdsNodes = 0, pLdsTris = 0; int extendMaxBlocksPerCU = 0; int innerKeepEighths = 6;
     int bfsNodes = 0x7fffffff;      // inner-node records kept in breadth-first order (whole levels); the rest follow depth-first (buildScene)
     uint64_t hostCnt[PT_CNT_N] = {0};
+    // adaptive sampling (include/pt_adaptive.h): per accumulator slot (sY, sYY, n, 0), allocated by the first pt_render_adaptive; the selection's scratch;
+    // while adaptOn the running frame stream's pixel list is the active list (streamBatch), its nLocal adaptN
+    float4* dStats = nullptr; unsigned char* dAdaptFlag = nullptr; unsigned* dAdaptBlk = nullptr; unsigned* dAdaptXY = nullptr; int* dAdaptSlot = nullptr;
+    unsigned* hAdaptCount = nullptr; bool adaptOn = false; int adaptN = 0;
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -1534,8 +1643,10 @@ Batch streamBatch(const pt_ctx* c) {
     Batch b;
     b.W = c->W; b.H = c->H; b.nLocal = c->nLocal; b.nSlots = c->nSlotsImg; b.shardCount = c->shardCount;
     b.ringFrames = (unsigned)c->ringFrames; b.seeds = c->dSeeds; b.pixList = c->dPixList; b.pixXY = c->dPixXY; b.colbuf = c->dColbuf;
-    if (c->nLocal >= 2) {                                     // ceil(2^(31+l)/d), exact for every job < 2^31
-        unsigned d = (unsigned)c->nLocal; int l = 0;
+    // an adaptive stream runs on the compacted subsequence of the list; pixList then holds each entry's accumulator slot (k_accumulate_adaptive)
+    if (c->adaptOn) { b.nLocal = c->adaptN; b.pixXY = c->dAdaptXY; b.pixList = c->dAdaptSlot; }
+    if (b.nLocal >= 2) {                                      // ceil(2^(31+l)/d), exact for every job < 2^31
+        unsigned d = (unsigned)b.nLocal; int l = 0;
         while ((1ull << l) < d) l++;
         unsigned long long m = ((1ull << (31 + l)) + d - 1) / d;
         b.divM = (unsigned)m; b.divS = (unsigned)(l - 1);
@@ -1548,6 +1659,11 @@ int retireFront(pt_ctx* c) {
     c->pending.pop_front();
     hipStream_t s = c->stream;
     Batch b = streamBatch(c);
+    if (c->adaptOn) {
+        TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_adaptive, dim3((c->adaptN + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, b, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     int gridA = (c->nSlotsImg + BLOCK - 1) / BLOCK;
     TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], e.f0, e.nFrames, e.firstFrame));
     HIP_TRY(hipGetLastError());
@@ -1804,7 +1920,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     // the loop bounds are floats in the shader (frag.glsl:820, :898); the slot's counters have 12 bits each
     if (!(P[4] >= 1.0f) || P[4] > 2047.0f) return fail(PT_ERR_ARG, "SAMPLE_RES must be in [1,2047]");
     if (!(P[5] > 0.0f) || P[5] > 4095.0f) return fail(PT_ERR_ARG, "MAX_BOUNCES must be in (0,4095]");
-    size_t nJobs64 = (size_t)c->nLocal * (size_t)nFrames;
+    size_t nJobs64 = (size_t)(c->adaptOn ? c->adaptN : c->nLocal) * (size_t)nFrames;
     if (nJobs64 >= (1ull << 31)) return fail(PT_ERR_ARG, "batch too large: pixels * frames must stay below 2^31 (split the batch)");
     FrameIn fin;
     std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->origin.data(), 12); std::memcpy(fin.rotation, c->rotation.data(), 12); std::memcpy(fin.mouse, c->mouse.data(), 12);
@@ -2059,11 +2175,13 @@ int pt_destroy(pt_ctx* c) {
     hipStreamSynchronize(c->stream);
     for (hipModule_t m : c->asmModule) if (m) hipModuleUnload(m);
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
-                    c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay};
+                    c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
+                    c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
     if (c->hSeeds) hipHostFree(c->hSeeds);
+    if (c->hAdaptCount) hipHostFree(c->hAdaptCount);
     for (auto& k : c->kt) for (auto& e : k.ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (c->sExt) { hipStreamSynchronize(c->sExt); giveStream((c->device + 1) * 100 + c->cuPartitionBuilt, c->sExt); }
     if (c->sShade) { hipStreamSynchronize(c->sShade); giveStream((c->device + 1) * 100 + 50 + c->cuPartitionBuilt, c->sShade); }
@@ -2131,6 +2249,7 @@ int pt_reset_frame(pt_ctx* c) {
     int rc;
     if ((rc = flushStream(c))) return rc;
     HIP_TRY(hipMemsetAsync(c->dImage[c->curImage], 0, (size_t)c->nSlotsImg * 16, c->stream));
+    if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));      // the statistics describe this image
     return PT_OK;
 }
 
@@ -2163,6 +2282,7 @@ int pt_next_image(pt_ctx* c) {
     if (c->jobsThisImage) c->jobsPerImage = c->jobsThisImage;
     c->jobsThisImage = 0;
     HIP_TRY(hipMemsetAsync(c->dImage[next], 0, (size_t)c->nSlotsImg * 16, c->stream));
+    if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
     return PT_OK;
 }
 
@@ -2242,6 +2362,7 @@ int pt_write_frame(pt_ctx* c, const float* in) {
     MULTI_ALL(c, pt_write_frame(k, in));                           // every stream takes the pixels of its own tile shard
     HIP_TRY(hipSetDevice(c->device));
     { int rc; if ((rc = flushStream(c))) return rc; }
+    if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
     float4* const dFrame = c->dImage[c->curImage];
     if (c->shardCount == 1) {
         HIP_TRY(hipMemcpyAsync(dFrame, in, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice, c->stream));
@@ -2255,8 +2376,9 @@ int pt_write_frame(pt_ctx* c, const float* in) {
     return PT_OK;
 }
 
-int pt_read_display(pt_ctx* c, int frame_count, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display: null argument");
+namespace {
+// pt_read_display (perPixel false: one frame_count for every pixel) and pt_read_display_mean (perPixel true: each pixel's own count)
+int readDisplay(pt_ctx* c, int frame_count, bool perPixel, int java_bytes, uint8_t* rgb_out) {
     const float4* frame = nullptr; pt_ctx* on = c;
     if (c->multi) {
         if (c->multi->shardTotal != c->multi->n) return fail(PT_ERR_ARG, "pt_read_display needs the whole image: this group holds a part of it (pt_create_multi_part)");
@@ -2273,11 +2395,96 @@ int pt_read_display(pt_ctx* c, int frame_count, int java_bytes, uint8_t* rgb_out
     HIP_TRY(hipSetDevice(on->device));
     const size_t bytes = (size_t)c->W * c->H * 3;
     if (!on->dDisplay) HIP_TRY(hipMalloc((void**)&on->dDisplay, bytes));
-    hipLaunchKernelGGL(k_display, dim3((unsigned)(((size_t)c->W * c->H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, on->stream, frame, c->W, c->H, (float)frame_count, java_bytes, on->dDisplay);
+    const dim3 grid((unsigned)(((size_t)c->W * c->H + BLOCK - 1) / BLOCK));
+    if (perPixel) hipLaunchKernelGGL(k_display<true>, grid, dim3(BLOCK), 0, on->stream, frame, c->W, c->H, 0.0f, java_bytes, on->dDisplay);
+    else hipLaunchKernelGGL(k_display<false>, grid, dim3(BLOCK), 0, on->stream, frame, c->W, c->H, (float)frame_count, java_bytes, on->dDisplay);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rgb_out, on->dDisplay, bytes, hipMemcpyDeviceToHost, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     return PT_OK;
+}
+}  // namespace
+
+int pt_read_display(pt_ctx* c, int frame_count, int java_bytes, uint8_t* rgb_out) {
+    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display: null argument");
+    return readDisplay(c, frame_count, false, java_bytes, rgb_out);
+}
+int pt_read_display_mean(pt_ctx* c, int java_bytes, uint8_t* rgb_out) {
+    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_mean: null argument");
+    return readDisplay(c, 0, true, java_bytes, rgb_out);
+}
+
+// ---- adaptive sampling (include/pt_adaptive.h): select the still-noisy pixels of each stream's shard, then ONE frame stream over their compacted list
+namespace {
+int renderAdaptive(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const AdaptRule& r, int64_t* nActive) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    if (c->params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_render_adaptive: DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
+    int rc;
+    if ((rc = flushStream(c))) return rc;                         // batches in flight land in FRAME, not in the statistics
+    hipStream_t s = c->stream;
+    const int nb = (c->nLocal + BLOCK - 1) / BLOCK;
+    if (!c->dStats) {
+        HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
+        HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, s));
+    }
+    if (!c->dAdaptXY) {
+        HIP_TRY(hipMalloc((void**)&c->dAdaptFlag, (size_t)c->nLocal));
+        HIP_TRY(hipMalloc((void**)&c->dAdaptBlk, ((size_t)nb + 1) * 4));
+        if (c->shardCount > 1) HIP_TRY(hipMalloc((void**)&c->dAdaptSlot, (size_t)c->nLocal * 4));
+        HIP_TRY(hipHostMalloc((void**)&c->hAdaptCount, 4, hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void**)&c->dAdaptXY, (size_t)c->nLocal * 4));      // (last: its presence says the others exist)
+    }
+    AdaptRule rr = r;
+    if (c->mouse.size() >= 2) { rr.mouseX = c->mouse[0]; rr.mouseY = c->mouse[1]; }
+    rr.resolution = c->params[2];
+    hipLaunchKernelGGL(k_adaptive_select, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, c->shardCount, (const float4*)c->dStats, rr, c->dAdaptFlag, c->dAdaptBlk);
+    hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(BLOCK), 0, s, c->dAdaptBlk, nb, c->dAdaptBlk + nb);
+    hipLaunchKernelGGL(k_adaptive_compact, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, (const unsigned char*)c->dAdaptFlag, (const unsigned*)c->dAdaptBlk,
+                       c->dAdaptXY, c->shardCount > 1 ? c->dAdaptSlot : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->hAdaptCount, c->dAdaptBlk + nb, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const unsigned n = *c->hAdaptCount;
+    if (n > (unsigned)c->nLocal) return fail(PT_ERR_HIP, "pt_render_adaptive: active count beyond the pixel list (internal error)");
+    *nActive = n;
+    if (n == 0) return PT_OK;
+    // a new frame stream on the active list (the pending queue is empty, so submitBatch cannot join the last stream); it ends with the batch, so the
+    // next ordinary call starts a fresh stream over the whole list.  The override holds exactly while this batch is in the scheduler.
+    c->adaptOn = true; c->adaptN = (int)n;
+    rc = submitBatch(c, firstFrame, nFrames, seeds, false);
+    if (rc) c->pending.clear();                                   // a failed stream must not be retired later with the full list
+    c->adaptOn = false; c->adaptN = 0;
+    return rc;
+}
+}  // namespace
+
+int pt_render_adaptive(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, float rel_err, float abs_err, int min_frames, int max_frames, int64_t* n_active) {
+    if (!c || !seeds) return fail(PT_ERR_ARG, "pt_render_adaptive: null argument");
+    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_adaptive: n_frames must be >= 1");
+    if (min_frames < 2) return fail(PT_ERR_ARG, "pt_render_adaptive: min_frames must be >= 2 (a variance needs two frames)");
+    if (max_frames < 0) return fail(PT_ERR_ARG, "pt_render_adaptive: max_frames must be >= 0 (0 = no cap)");
+    if (!(rel_err >= 0.0f) || !(abs_err >= 0.0f)) return fail(PT_ERR_ARG, "pt_render_adaptive: rel_err and abs_err must be >= 0 and not NaN");
+    AdaptRule r{};
+    r.relErr = rel_err; r.absErr = abs_err; r.minFrames = min_frames; r.maxFrames = max_frames;
+    if (n_active) *n_active = 0;
+    if (c->multi) {                                               // every stream selects within its own shard: no collective
+        MultiCtx& M = *c->multi;
+        if (!M.staleBindings.empty()) return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
+        std::vector<int64_t> counts((size_t)M.n, 0);
+        int64_t* cp = counts.data();
+        const std::vector<pt_ctx*>& kids = M.kids;
+        const int rc = multiRun(M, [=, &kids](pt_ctx* k) {
+            const size_t i = (size_t)(std::find(kids.begin(), kids.end(), k) - kids.begin());
+            return renderAdaptive(k, first_frame, n_frames, seeds, r, cp + i);
+        });
+        if (n_active) for (int64_t v : counts) *n_active += v;
+        return rc;
+    }
+    int64_t n = 0;
+    const int rc = renderAdaptive(c, first_frame, n_frames, seeds, r, &n);
+    if (n_active) *n_active = n;
+    return rc;
 }
 
 namespace {

@@ -113,6 +113,9 @@ def lib():
         L.pt_kernel_time_median.argtypes = [vp, ci, C.POINTER(C.c_double)]
         L.pt_debug_math.argtypes = [vp, ci, vp, vp, vp, sz]
         L.pt_debug_intersect.argtypes = [vp, vp, vp, vp, sz]
+        if hasattr(L, "pt_render_adaptive"):                  # include/pt_adaptive.h
+            L.pt_render_adaptive.argtypes = [vp, ci, ci, vp, C.c_float, C.c_float, ci, ci, C.POINTER(C.c_int64)]
+            L.pt_read_display_mean.argtypes = [vp, ci, vp]
         _LIB = L
     return _LIB
 
@@ -253,6 +256,22 @@ class Renderer:
         """The reference's screenshot image: (H, W, 3) uint8, top row first (functions.screenshot, dispatch.java:804-851)."""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
         _check(self._L.pt_read_display(self._h, int(frame_count), 1 if java_bytes else 0, out.ctypes.data))
+        return out
+
+    # --- adaptive sampling (include/pt_adaptive.h) -----------------------------------------------
+    def render_adaptive(self, first_frame, seeds, rel_err, abs_err=0.0, min_frames=4, max_frames=0):
+        """Frames first_frame.. (one per seed) for the pixels whose per-pixel luminance statistics still say noisy (pt_render_adaptive);
+        returns how many pixels were rendered.  FRAME alpha then holds every pixel's own frame count: show it with read_display_mean."""
+        s = np.ascontiguousarray(seeds, dtype=np.int32)
+        n = C.c_int64(0)
+        _check(self._L.pt_render_adaptive(self._h, int(first_frame), int(s.size), s.ctypes.data, float(rel_err), float(abs_err),
+                                          int(min_frames), int(max_frames), C.byref(n)))
+        return n.value
+
+    def read_display_mean(self, java_bytes=True):
+        """read_display with every pixel divided by its own frame count (FRAME alpha): (H, W, 3) uint8, top row first"""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        _check(self._L.pt_read_display_mean(self._h, 1 if java_bytes else 0, out.ctypes.data))
         return out
 
     def screenshot(self, path, frame_count, java_bytes=True):

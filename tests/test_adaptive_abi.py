@@ -1,0 +1,80 @@
+"""CPU: the adaptive-sampling surface (include/pt_adaptive.h) — exported symbols, a strict-C99 client, and a float32 model of the selection rule."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _declared(header):
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(pts?_[a-z_0-9]+)\s*\(", txt)))
+
+
+def select(T, rel_err, abs_err, min_frames, max_frames, overlay=None):
+    """the selection rule of include/pt_adaptive.h over T = (..., 4) float32 (sY, sYY, n, 0), evaluated in float32 in the header's order"""
+    T = np.asarray(T, np.float32)
+    sY, sYY, n = T[..., 0], T[..., 1], T[..., 2]
+    with np.errstate(all="ignore"):
+        mean = sY / n
+        var = (sYY - sY * mean) / (n - np.float32(1.0))
+        err2 = var / n
+        tol = np.fmax(np.float32(rel_err) * np.abs(mean), np.float32(abs_err))
+        act = err2 > tol * tol
+    act = act | (n < np.float32(min_frames))
+    if max_frames > 0:
+        act = act & ~(n >= np.float32(max_frames))
+    if overlay is not None:
+        act = act & ~overlay
+    return act
+
+
+def test_hip_library_exports_the_adaptive_symbols(pt):
+    from pathtracer_0_amd import build
+    lib = ctypes.CDLL(build.build_hip())
+    names = _declared("pt_adaptive.h")
+    assert names == ["pt_read_display_mean", "pt_render_adaptive"]
+    for n in names:
+        assert hasattr(lib, n), n
+    assert not set(names) & set(_declared("pt_api.h"))         # the boundary header is unchanged
+
+
+def test_adaptive_header_compiles_as_c99(tmp_path):
+    src = tmp_path / "client.c"
+    src.write_text('#include "pt_api.h"\n#include "pt_adaptive.h"\n#include <stddef.h>\n'
+                   "int main(void) {\n"
+                   "    int (*r)(pt_ctx*, int, int, const int32_t*, float, float, int, int, int64_t*) = pt_render_adaptive;\n"
+                   "    int (*d)(pt_ctx*, int, uint8_t*) = pt_read_display_mean;\n"
+                   "    return (r == NULL) + (d == NULL);\n}\n")
+    out = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include"), "-c", str(src),
+                          "-o", str(tmp_path / "client.o")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+
+
+def test_selection_rule_hand_computed_cases():
+    nan = np.float32("nan")
+    cases = [
+        # (sY, sYY, n), rel, abs, min, max, expected
+        ((2.0, 1.0, 4.0), 0.01, 0.0, 4, 0, False),        # four frames of 0.5: zero variance
+        ((0.0, 0.0, 8.0), 0.0, 0.0, 4, 0, False),         # black, zero variance, zero tolerance: 0 > 0 is false
+        ((1.0, 1.0, 1.0), 0.5, 0.0, 2, 0, True),          # n < min_frames
+        ((0.0, 0.0, 0.0), 0.5, 0.0, 2, 0, True),          # never rendered
+        ((0.0, 0.0, 0.0), 0.5, 0.0, 2, 4, True),
+        ((1.0, 1.0, 3.0), 0.0, 0.0, 2, 3, False),         # the max_frames cap, although noisy
+        ((1.0, 1.0, 3.0), 0.0, 0.0, 2, 4, True),          # ... below the cap
+        ((nan, nan, 6.0), 0.1, 0.0, 4, 0, False),         # NaN pixel: inactive
+        ((nan, nan, 1.0), 0.1, 0.0, 4, 0, True),          # ... but a pixel below min_frames is rendered whatever its sums
+        # samples 0, 1, 0, 1: mean 0.5, var = (2 - 2*0.5) / 3 = 1/3, err2 = 1/12 = 0.0833
+        ((2.0, 2.0, 4.0), 0.5, 0.0, 4, 0, True),          # tol 0.25, tol^2 0.0625 < 0.0833
+        ((2.0, 2.0, 4.0), 0.6, 0.0, 4, 0, False),         # tol 0.3, tol^2 0.09 > 0.0833
+        ((2.0, 2.0, 4.0), 0.0, 0.3, 4, 0, False),         # the abs_err floor alone
+        ((2.0, 2.0, 4.0), 0.5, 0.3, 4, 0, False),         # floor wins over the relative tolerance
+        ((2.0, 2.0, 4.0), 0.5, 0.2, 4, 0, True),
+    ]
+    for (sY, sYY, n), rel, ab, mn, mx, want in cases:
+        T = np.array([sY, sYY, n, 0.0], np.float32)
+        assert bool(select(T, rel, ab, mn, mx)) is want, (sY, sYY, n, rel, ab, mn, mx)
+    assert not bool(select(np.array([1.0, 1.0, 4.0, 0.0], np.float32), 0.0, 0.0, 2, 0, overlay=np.array(True)))
