@@ -582,6 +582,28 @@ PM_DEV bool segmentEndsSample(const FrameConst& fc, const Path& p, float ht, int
 // randLambertianDistVec, which the lens jitter of new samples shares
 struct LobePending { vec3 N; float Pcr; int w; bool needG; };
 
+// The surface of a hit as shadeSegment below decodes it (rayScene :622-626 for ellipsoids, rayBVH :501-506 for triangles): the hit point, the normal before
+// map_norm and the face-forward flip, and the material index.  For the first-hit feature records (include/pt_denoise.h); the shading kernel keeps its own
+// copy of these lines, which compiles to different code when shared.
+template <bool FAST = false>
+PM_DEV void surfaceAt(const DevScene& sc, vec3 O, vec3 D, float ht, float hu, float hv, int prim, vec3& loc, vec3& N, int& mat) {
+    vec3 o = madd(D, 1e-4f, O);
+    loc = madd(D, ht, o);                                     // result.loc = o + closest_t*d (:635)
+    if (prim & PRIM_ELLIPSOID) {
+        const EllipRec& E = sc.ellip[prim & 0xffffff];
+        vec3 c = v3(E.c[0], E.c[1], E.c[2]);
+        if (E.rotated) N = normalizeT<FAST>(vecmat(loc - c, E.RB)); else N = normalizeT<FAST>(loc - c);     // :622-626
+        mat = E.mat;
+    } else {
+        const float4* S = sc.shade + 4 * (size_t)prim;
+        float4 s0 = S[0], s1 = S[1], s2 = S[2];
+        vec3 vn1 = v3(s0.x, s0.y, s0.z), vn2 = v3(s0.w, s1.x, s1.y);
+        if (vn1.x != 0.0f && vn1.y != 0.0f && vn1.z != 0.0f) N = normalizeT<FAST>(vn2 * hu + vn2 * hv + vn1 * (1.0f - hu - hv));   // :501-504 (Q-3)
+        else N = vn2;                                                                                              // :506 (Q-4)
+        mat = __float_as_int(s2.w);
+    }
+}
+
 // One iteration of trace()'s while loop AFTER rayScene returned (frag.glsl:823-879), up to the Gaussian draw of chooseRay: the transmission lobe's direction is
 // set here, the others' (L.needG) by the caller — p.D = lobeDirection(L.w, G, L.N, p.D, ., L.Pcr) with G = randLambertianDistVec(p.rng) — or, when the sample
 // ends here, not at all: the six draws then only advance the stream (skipSixDraws).

@@ -26,6 +26,7 @@
 #include "../../../include/pt_api.h"
 #include "../../../include/pt_debug.h"
 #include "../../../include/pt_adaptive.h"
+#include "../../../include/pt_denoise.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -850,6 +851,43 @@ __global__ void __launch_bounds__(BLOCK) k_display(const float4* frame, int W, i
     o[0] = (unsigned char)r; o[1] = (unsigned char)g; o[2] = (unsigned char)b;
 }
 
+// ---- first-hit feature records (include/pt_denoise.h).  One ray per pixel of the whole image, slot = y*W + x: main()'s camera ray with the lens offset
+// zero (cameraRayFrom, G = 0), as a live path-state record of an intersect launch; lanes beyond the image are dead records.
+__global__ void __launch_bounds__(BLOCK) k_feature_rays(const FrameConst* fcp, int W, int H, State st, int nSlots) {
+    const unsigned i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (unsigned)nSlots) return;
+    if (i >= (unsigned)(W * H)) { st.G0[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); st.G1[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); return; }
+    vec3 O, D;
+    cameraRayFrom(*fcp, W, H, (int)(i % (unsigned)W), (int)(i / (unsigned)W), v3(0.0f), O, D);
+    st.G0[i] = make_float4(O.x, O.y, O.z, D.x);
+    st.G1[i] = make_float4(D.y, D.z, 0.0f, __uint_as_float(FL_ALIVE));
+    st.H[i] = make_float4(1e30f, 0.0f, 0.0f, __int_as_float(PRIM_NONE));
+}
+// The 64-B record of each pixel from its ray and hit record (and the side record HX of an ellipsoid hit): what trace() decodes at :823-830
+__global__ void __launch_bounds__(BLOCK) k_feature_record(DevScene sc, State st, int n, float4* feat) {
+    const unsigned i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    const float4 g0 = st.G0[i], g1 = st.G1[i], h = st.H[i];
+    const vec3 O = v3(g0.x, g0.y, g0.z), D = v3(g0.w, g1.x, g1.y);
+    const int prim = __float_as_int(h.w);
+    float4 f0 = make_float4(-1.0f, 0.0f, 0.0f, 0.0f), f1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1)), f3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int mat = -1;
+    if (segmentHit(h.x, prim)) {                                   // rayScene's result.distance is -1 on a miss (:651)
+        vec3 loc, N;
+        surfaceAt(sc, O, D, h.x, h.y, h.z, prim, loc, N, mat);
+        MatRec m = sc.mats[mat];
+        float uvx, uvy;
+        uvOfHit(sc, prim, h.y, h.z, st.HX, i, uvx, uvy);
+        if (m.hasMaps) applyMaps(sc, m, uvx, uvy, N);
+        const int code = (prim & PRIM_ELLIPSOID) ? 3 * 0x1000000 + (prim & 0xffffff) : 0x1000000 + prim;     // hit.type * 0x1000000 + hit.id
+        f0 = make_float4(h.x, N.x, N.y, N.z);
+        f1 = make_float4(m.Kd[0], m.Kd[1], m.Kd[2], __int_as_float(code));
+        f3 = make_float4(uvx, uvy, 0.0f, 0.0f);
+    }
+    float4* r = feat + 4 * (size_t)i;
+    r[0] = f0; r[1] = f1; r[2] = make_float4(D.x, D.y, D.z, __int_as_float(mat)); r[3] = f3;
+}
+
 // ---- adaptive sampling (include/pt_adaptive.h).  The selection rule over the per-slot statistics T = (sY, sYY, n, 0), in the order the header states it
 // (float32, no contraction: the build's -ffp-contract=off, IEEE divides).  NaN anywhere: every comparison false, the pixel stays inactive.
 struct AdaptRule { float relErr, absErr, mouseX, mouseY, resolution; int minFrames, maxFrames; };
@@ -1082,6 +1120,10 @@ struct pt_ctx {
     // while adaptOn the running frame stream's pixel list is the active list (streamBatch), its nLocal adaptN
     float4* dStats = nullptr; unsigned char* dAdaptFlag = nullptr; unsigned* dAdaptBlk = nullptr; unsigned* dAdaptXY = nullptr; int* dAdaptSlot = nullptr;
     unsigned* hAdaptCount = nullptr; bool adaptOn = false; int adaptN = 0;
+    // first-hit feature records (include/pt_denoise.h): W*H x 4 float4, valid until the next pt_set_buffer / pt_set_texture; the denoiser's ping-pong
+    // colour buffers, its packed guide (2 float4 per pixel) and its output, all allocated on first use
+    float4* dFeat = nullptr; bool featValid = false;
+    float4* dDnCol[2] = {nullptr, nullptr}; float4* dDnGuide = nullptr; float4* dDnOut = nullptr;
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -2038,6 +2080,9 @@ int resolveTimes(pt_ctx* c) {
 // ------------------------------------------------------------------------------------------------ C ABI
 
 int pt_set_error_(int code, const std::string& msg) { return fail(code, msg); }      // for pt_bvh.hip
+// the a-trous filter of include/pt_denoise.h (pt_denoise.hip): device pointers only, enqueued on `s`
+hipError_t denoiseLaunch(const float4* frame, const float4* feat, int W, int H, int iterations, const float sigma[4], float4* col0, float4* col1,
+                         float4* guide, float4* out, hipStream_t s);
 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
@@ -2176,7 +2221,7 @@ int pt_destroy(pt_ctx* c) {
     for (hipModule_t m : c->asmModule) if (m) hipModuleUnload(m);
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
-                    c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot};
+                    c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -2204,6 +2249,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         return PT_OK;
     }
     if (bytes % 4) return fail(PT_ERR_ARG, "pt_set_buffer: size must be a multiple of 4 bytes");
+    c->featValid = false;                                         // any binding may move the camera or the scene under the feature records
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
         case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
@@ -2235,6 +2281,7 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
         return PT_OK;
     }
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
+    c->featValid = false;
     if (index == 0) { c->sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->skyW = w; c->skyH = h; }
     if ((size_t)index >= c->textures.size()) c->textures.resize((size_t)index + 1);
     c->textures[index].rgba.assign(rgba8, rgba8 + (size_t)w * h * 4); c->textures[index].w = w; c->textures[index].h = h;
@@ -2747,6 +2794,29 @@ int pt_debug_math(pt_ctx* c, int fn, const float* x, const float* y, float* out,
     return PT_OK;
 }
 
+namespace {
+// rayScene for the np slots (a multiple of BLOCK) of a probe pool that is no stream's (pt_debug_intersect, the feature records), on the context's stream behind
+// k_frame_setup: the kernel pt_set_option 2 selects, with the exact numeric contract.  A pool with a side record HX in a scene whose intersect kernels do not
+// write one (no ellipsoid carries a mapped material) runs on k_extend, which writes it whenever it is given.
+int probeIntersect(pt_ctx* c, const State& st, size_t np, const FrameIn& fin) {
+    size_t ldsBytes = (size_t)c->sc.ldsNodes * 64 + (size_t)c->sc.ldsTris * 48 + (size_t)c->stackDepth * BLOCK * 4;
+    hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, c->stream, c->dCtl);
+    if (c->extendMode == 0 || (st.HX && !c->ellipMaps)) {
+        hipLaunchKernelGGL(k_extend<false>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), ldsBytes, c->stream, c->sc, st, (const unsigned*)nullptr, 0, (int)np, c->dCtl);
+    } else {                                                      // the production kernels (persistent blocks; hand-written or compiled), as pump() launches them
+        std::memcpy(c->streamIn.params, fin.params, 48); c->streamIn.params[9] = 1.0f;      // no thickness probes in this pool
+        PoolRun pr; pr.stream = c->stream; pr.st = st; pr.launched = (unsigned)np; pr.iter = 0;
+        c->debugExactExtend = true;
+        TIMED_LAUNCH_ON(c->stream, 0, launchExtendPersist(c, pr));       // (pt_set_timing: scripts/coherence_probe.py times the production kernel on ray sets of its own)
+        c->debugExactExtend = false;
+        std::memset(&c->streamIn, 0xff, sizeof(FrameIn));
+    }
+    HIP_TRY(hipGetLastError());
+    if (!c->asmError.empty()) { const std::string m = c->asmError; c->asmError.clear(); return fail(PT_ERR_HIP, m); }
+    return 0;
+}
+}  // namespace
+
 int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, size_t n) {
     if (!c || !o || !d || !out || n < 1 || n > (1u << 24)) return fail(PT_ERR_ARG, "pt_debug_intersect: bad argument");
     if (c->multi) c = c->multi->kids[0];
@@ -2772,20 +2842,7 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
     fin.params[11] = 0.0f;
     HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);
-    size_t ldsBytes = (size_t)c->sc.ldsNodes * 64 + (size_t)c->sc.ldsTris * 48 + (size_t)c->stackDepth * BLOCK * 4;
-    hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, c->stream, c->dCtl);
-    if (c->extendMode == 0) {
-        hipLaunchKernelGGL(k_extend<false>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), ldsBytes, c->stream, c->sc, st, (const unsigned*)nullptr, 0, (int)np, c->dCtl);
-    } else {                                                      // the production kernels (persistent blocks; hand-written or compiled), as pump() launches them
-        std::memcpy(c->streamIn.params, fin.params, 48); c->streamIn.params[9] = 1.0f;      // no thickness probes in this pool
-        PoolRun pr; pr.stream = c->stream; pr.st = st; pr.launched = (unsigned)np; pr.iter = 0;
-        c->debugExactExtend = true;
-        TIMED_LAUNCH_ON(c->stream, 0, launchExtendPersist(c, pr));       // (pt_set_timing: scripts/coherence_probe.py times the production kernel on ray sets of its own)
-        c->debugExactExtend = false;
-        std::memset(&c->streamIn, 0xff, sizeof(FrameIn));
-    }
-    HIP_TRY(hipGetLastError());
-    if (!c->asmError.empty()) { const std::string m = c->asmError; c->asmError.clear(); return fail(PT_ERR_HIP, m); }
+    if ((rc = probeIntersect(c, st, np, fin))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<float> h(np * 4);
     HIP_TRY(hipMemcpy(h.data(), st.H, np * 16, hipMemcpyDeviceToHost));
@@ -2797,6 +2854,105 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
     }
 #endif
     std::memcpy(out, h.data(), n * 16);
+    return PT_OK;
+}
+
+// ---- first-hit feature records and the denoised image (include/pt_denoise.h).  A group context works on its first stream's context: the scene is replicated.
+namespace {
+int ensureFeatures(pt_ctx* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->featValid) return 0;
+    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
+    int rc;
+    if ((rc = flushStream(c))) return rc;                         // before the frame constants of a running stream are overwritten
+    std::memset(&c->streamIn, 0xff, sizeof(FrameIn));             // ... which are no stream's any more afterwards
+    if (c->sceneDirty && (rc = buildScene(c))) return rc;
+    const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
+    if (!c->dFeat) HIP_TRY(hipMalloc((void**)&c->dFeat, n * 64));
+    State st{};
+    Scratch scratch{{(void**)&st.G0, (void**)&st.G1, (void**)&st.H, (void**)&st.HX}};      // freed on every return path
+    HIP_TRY(hipMalloc((void**)&st.G0, np * 16)); HIP_TRY(hipMalloc((void**)&st.G1, np * 16)); HIP_TRY(hipMalloc((void**)&st.H, np * 16));
+    if (c->sc.numEllip > 0) {                                     // the uv an ellipsoid hit inherits (uvOfHit)
+        HIP_TRY(hipMalloc((void**)&st.HX, np * 16));
+        HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
+    }
+    FrameIn fin;
+    std::memcpy(fin.params, c->params.data(), 48); std::memcpy(fin.origin, c->origin.data(), 12); std::memcpy(fin.rotation, c->rotation.data(), 12);
+    std::memcpy(fin.mouse, c->mouse.data(), 12);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);      // auto-focus, camera and ellipsoid rotations
+    hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
+    if ((rc = probeIntersect(c, st, np, fin))) return rc;
+    hipLaunchKernelGGL(k_feature_record, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, c->dFeat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->featValid = true;
+    return 0;
+}
+
+// the denoised image of the context's current FRAME into on->dDnOut (W*H float4 on the device of *on), enqueued on on->stream
+int denoiseImage(pt_ctx* c, int iterations, const float sigma[4], pt_ctx** onOut) {
+    if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise: iterations must be in [0,8]");
+    for (int k = 0; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, "pt_denoise: every sigma must be > 0 (+inf switches its term off)");
+    pt_ctx* on = c->multi ? c->multi->kids[0] : c;
+    if (c->multi ? c->multi->shardTotal != c->multi->n : c->shardCount != 1)
+        return fail(PT_ERR_UNSUPPORTED, "pt_denoise needs the whole image: this context holds a part of it");
+    int rc;
+    if ((rc = ensureFeatures(on))) return rc;
+    const float4* frame = nullptr;
+    if (c->multi) {
+        float4* full = nullptr;
+        if ((rc = multiGather(c, 0, &full))) return rc;
+        frame = full;
+    } else {
+        if ((rc = flushStream(c))) return rc;
+        frame = c->dImage[c->curImage];
+    }
+    HIP_TRY(hipSetDevice(on->device));
+    const size_t n = (size_t)c->W * c->H;
+    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
+    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
+    HIP_TRY(denoiseLaunch(frame, on->dFeat, c->W, c->H, iterations, sigma, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
+    *onOut = on;
+    return 0;
+}
+}  // namespace
+
+int pt_read_features(pt_ctx* c, float* out) {
+    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features: null argument");
+    pt_ctx* on = c->multi ? c->multi->kids[0] : c;
+    int rc;
+    if ((rc = ensureFeatures(on))) return rc;
+    HIP_TRY(hipMemcpy(out, on->dFeat, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_denoise(pt_ctx* c, int iterations, float sigma_color, float sigma_normal, float sigma_depth, float sigma_albedo, float* rgba_out) {
+    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise: null argument");
+    const float sigma[4] = {sigma_color, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = denoiseImage(c, iterations, sigma, &on))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    return PT_OK;
+}
+
+int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float sigma_normal, float sigma_depth, float sigma_albedo, int java_bytes, uint8_t* rgb_out) {
+    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised: null argument");
+    const float sigma[4] = {sigma_color, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = denoiseImage(c, iterations, sigma, &on))) return rc;
+    const size_t bytes = (size_t)c->W * c->H * 3;
+    if (!on->dDisplay) HIP_TRY(hipMalloc((void**)&on->dDisplay, bytes));
+    // the denoised image is a mean already: k_display's conversion with a frame count of 1 (x / 1.0f is exact)
+    hipLaunchKernelGGL(k_display<false>, dim3((unsigned)((c->W * (size_t)c->H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, on->stream, on->dDnOut, c->W, c->H, 1.0f, java_bytes, on->dDisplay);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rgb_out, on->dDisplay, bytes, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
     return PT_OK;
 }
 

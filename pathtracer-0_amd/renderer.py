@@ -116,6 +116,11 @@ def lib():
         if hasattr(L, "pt_render_adaptive"):                  # include/pt_adaptive.h
             L.pt_render_adaptive.argtypes = [vp, ci, ci, vp, C.c_float, C.c_float, ci, ci, C.POINTER(C.c_int64)]
             L.pt_read_display_mean.argtypes = [vp, ci, vp]
+        if hasattr(L, "pt_denoise"):                          # include/pt_denoise.h
+            cf = C.c_float
+            L.pt_read_features.argtypes = [vp, vp]
+            L.pt_denoise.argtypes = [vp, ci, cf, cf, cf, cf, vp]
+            L.pt_read_display_denoised.argtypes = [vp, ci, cf, cf, cf, cf, ci, vp]
         _LIB = L
     return _LIB
 
@@ -272,6 +277,42 @@ class Renderer:
         """read_display with every pixel divided by its own frame count (FRAME alpha): (H, W, 3) uint8, top row first"""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
         _check(self._L.pt_read_display_mean(self._h, 1 if java_bytes else 0, out.ctypes.data))
+        return out
+
+    # --- first-hit features and the denoised image (include/pt_denoise.h) -------------------------
+    # default sigmas of denoise / read_display_denoised (colour, normal, depth, albedo): the lowest RMSE of scripts/denoise_quality.py's grid on C3
+    # and C6 at 1080p, 4 and 16 frames (profiles/r09_denoise_quality.txt, DESIGN.md 2.8)
+    DENOISE_SIGMAS = (4.0, 0.3, 0.05, 0.1)
+
+    def read_features(self):
+        """the raw feature records (pt_read_features): (H, W, 16) float32, FRAME order (row 0 = y 0)"""
+        out = np.zeros((self.H, self.W, 16), dtype=np.float32)
+        _check(self._L.pt_read_features(self._h, out.ctypes.data))
+        return out
+
+    def features(self):
+        """first-hit feature buffers of the lens-centre camera ray of every pixel, as (H, W[, k]) arrays: t (rayScene's distance, -1 on a miss),
+        normal (before the face-forward flip), albedo (Kd after mapMtl), hit (type * 0x1000000 + id, -1 on a miss), dir, material (-1 on a miss), uv"""
+        f = self.read_features()
+        return {"t": f[..., 0].copy(), "normal": f[..., 1:4].copy(), "albedo": f[..., 4:7].copy(), "hit": f[..., 7].copy().view(np.int32),
+                "dir": f[..., 8:11].copy(), "material": f[..., 11].copy().view(np.int32), "uv": f[..., 12:14].copy()}
+
+    def _sigmas(self, sigma_color, sigma_normal, sigma_depth, sigma_albedo):
+        d = self.DENOISE_SIGMAS
+        return [float(d[k] if v is None else v) for k, v in enumerate((sigma_color, sigma_normal, sigma_depth, sigma_albedo))]
+
+    def denoise(self, iterations=5, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
+        """the edge-avoiding a-trous filter over FRAME.rgb / FRAME.a (pt_denoise): (H, W, 4) float32, rgb = denoised mean, a = FRAME.a.
+        FRAME is not modified.  A sigma of None takes DENOISE_SIGMAS; float('inf') switches its term off."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        _check(self._L.pt_denoise(self._h, int(iterations), *self._sigmas(sigma_color, sigma_normal, sigma_depth, sigma_albedo), out.ctypes.data))
+        return out
+
+    def read_display_denoised(self, iterations=5, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, java_bytes=True):
+        """denoise()'s image converted to 8 bits as read_display converts a mean: (H, W, 3) uint8, top row first"""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        _check(self._L.pt_read_display_denoised(self._h, int(iterations), *self._sigmas(sigma_color, sigma_normal, sigma_depth, sigma_albedo),
+                                                1 if java_bytes else 0, out.ctypes.data))
         return out
 
     def screenshot(self, path, frame_count, java_bytes=True):
