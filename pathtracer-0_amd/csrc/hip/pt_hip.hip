@@ -27,6 +27,7 @@
 #include "../../../include/pt_debug.h"
 #include "../../../include/pt_adaptive.h"
 #include "../../../include/pt_denoise.h"
+#include "../../../include/pt_reproject.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -1124,6 +1125,14 @@ struct pt_ctx {
     // colour buffers, its packed guide (2 float4 per pixel) and its output, all allocated on first use
     float4* dFeat = nullptr; bool featValid = false;
     float4* dDnCol[2] = {nullptr, nullptr}; float4* dDnGuide = nullptr; float4* dDnOut = nullptr;
+    // reprojection (include/pt_reproject.h): the camera of each ring image (the frame inputs it was rendered or written with, and the scene
+    // generation then: sceneGen counts uploads of scene buffers and textures); the feature records under the current image's camera (Rh, cached
+    // like dFeat, for the inputs featHIn); one flag byte per material (1 = view-dependent, buildScene); the scratch images, the kept count
+    struct Cam { FrameIn in; uint64_t sceneGen = 0; bool valid = false; } cam[IMAGES];
+    uint64_t sceneGen = 0;
+    float4* dFeatH = nullptr; bool featHValid = false; FrameIn featHIn{};
+    unsigned char* dMatVD = nullptr;
+    float4* dRpFrame = nullptr; float4* dRpStats = nullptr; float4* dRpStatsIn = nullptr; unsigned* dRpKept = nullptr;
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -1409,6 +1418,14 @@ int buildScene(pt_ctx* c) {
     if ((rc = uploadVec((void**)&c->dRoots, roots.data(), roots.size() * sizeof(ObjRoot), s))) return rc;
     if ((rc = uploadVec((void**)&c->dEllip, er.data(), er.size() * sizeof(EllipRec), s))) return rc;
     if ((rc = uploadVec((void**)&c->dMats, mats.data(), mats.size() * sizeof(MatRec), s))) return rc;
+    {   // the view-dependent materials of include/pt_reproject.h: a mirror, clearcoat or transmission lobe in chooseRay (frag.glsl:745-809)
+        std::vector<unsigned char> vd(mats.size(), 0);
+        for (int m = 0; m < nMat; m++) {
+            const MatRec& r = mats[m];
+            vd[m] = (r.Pr != 1.0f || r.Pc != 0.0f || r.Tr > 0.0f || r.Tf[0] > 0.0f || r.illum == 5 || r.illum == 7 || r.map_Pr >= 0 || r.map_Pc >= 0 || r.map_Tr >= 0) ? 1 : 0;
+        }
+        if ((rc = uploadVec((void**)&c->dMatVD, vd.data(), vd.size(), s))) return rc;
+    }
     // textures stay the RGBA8 texels the caller uploaded (dispatch.java:349-354: GL_RGBA8); byte / 255.0f happens at fetch (unorm8, pt_device.hpp)
     if ((rc = uploadVec((void**)&c->dSky, c->sky.data(), (size_t)c->skyW * c->skyH * 4, s))) return rc;
     if ((rc = uploadVec((void**)&c->dNiTable, niDict.data(), niDict.size() * 4, s))) return rc;
@@ -1932,6 +1949,20 @@ int flushStream(pt_ctx* c) {
     return pump(c, PUMP_IDLE, 0);
 }
 
+// the frame inputs current at the call; false while Parameters, ORIGIN or ROTATION are not set
+bool currentInputs(const pt_ctx* c, FrameIn& fin) {
+    if (c->params.size() < 12 || c->origin.size() < 3 || c->rotation.size() < 3 || c->mouse.size() < 3) return false;
+    std::memcpy(fin.params, c->params.data(), 48); std::memcpy(fin.origin, c->origin.data(), 12); std::memcpy(fin.rotation, c->rotation.data(), 12);
+    std::memcpy(fin.mouse, c->mouse.data(), 12);
+    return true;
+}
+// pt_write_frame: the current image's camera is the inputs current at the call (include/pt_reproject.h)
+void recordCamera(pt_ctx* c) {
+    pt_ctx::Cam& k = c->cam[c->curImage];
+    k.valid = currentInputs(c, k.in);
+    k.sceneGen = c->sceneGen;
+}
+
 int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bool async) {
     if (nFrames < 1) return fail(PT_ERR_ARG, "n_frames must be >= 1");
     HIP_TRY(hipSetDevice(c->device));
@@ -1956,6 +1987,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
         DevScene dsc = c->sc; dsc.ldsNodes = 0; dsc.ldsTris = 0;                    // no LDS tile in this kernel
         hipLaunchKernelGGL(k_debug_heatmap, dim3((c->nLocal + 63) / 64), dim3(64), 0, s, dsc, b, c->dFc, c->dImage[c->curImage], firstFrame, nFrames);
         HIP_TRY(hipGetLastError());
+        c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true};
         return 0;
     }
     if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
@@ -2053,6 +2085,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     c->lastSubmitJobs = nJobs64; c->jobsThisImage += nJobs64;
     pt_ctx::Entry e; e.jobEnd = c->streamJobs; e.f0 = f0; e.nFrames = nFrames; e.firstFrame = firstFrame; e.image = c->curImage;
     c->pending.push_back(e);
+    c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true};   // the image's camera (include/pt_reproject.h)
     c->draining = false; c->launched = (unsigned)N;              // (if the pool had run dry, k_submit dropped the tail queue)
     c->submitEpoch++;                                            // the groups in flight were launched for another tail: their view of it no longer counts
     HIP_TRY(hipGetLastError());
@@ -2083,6 +2116,10 @@ int pt_set_error_(int code, const std::string& msg) { return fail(code, msg); } 
 // the a-trous filter of include/pt_denoise.h (pt_denoise.hip): device pointers only, enqueued on `s`
 hipError_t denoiseLaunch(const float4* frame, const float4* feat, int W, int H, int iterations, const float sigma[4], float4* col0, float4* col1,
                          float4* guide, float4* out, hipStream_t s);
+// the reprojection of include/pt_reproject.h (pt_reproject.hip): device pointers only, enqueued on `s`
+hipError_t reprojectLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
+                           int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float4* outFrame, float4* outStats,
+                           unsigned* kept, hipStream_t s);
 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
@@ -2221,7 +2258,8 @@ int pt_destroy(pt_ctx* c) {
     for (hipModule_t m : c->asmModule) if (m) hipModuleUnload(m);
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
-                    c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut};
+                    c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
+                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dRpStatsIn, c->dRpKept};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -2249,7 +2287,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         return PT_OK;
     }
     if (bytes % 4) return fail(PT_ERR_ARG, "pt_set_buffer: size must be a multiple of 4 bytes");
-    c->featValid = false;                                         // any binding may move the camera or the scene under the feature records
+    c->featValid = false; c->featHValid = false;                  // any binding may move the camera or the scene under the feature records
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
         case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
@@ -2267,6 +2305,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         default: return fail(PT_ERR_ARG, "pt_set_buffer: binding point not consumed by the render path (frag.glsl declares 0-5,7,10-15)");
     }
     c->sceneDirty = true;
+    c->sceneGen++;
     return PT_OK;
 }
 
@@ -2281,7 +2320,8 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
         return PT_OK;
     }
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
-    c->featValid = false;
+    c->featValid = false; c->featHValid = false;
+    c->sceneGen++;
     if (index == 0) { c->sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->skyW = w; c->skyH = h; }
     if ((size_t)index >= c->textures.size()) c->textures.resize((size_t)index + 1);
     c->textures[index].rgba.assign(rgba8, rgba8 + (size_t)w * h * 4); c->textures[index].w = w; c->textures[index].h = h;
@@ -2297,6 +2337,7 @@ int pt_reset_frame(pt_ctx* c) {
     if ((rc = flushStream(c))) return rc;
     HIP_TRY(hipMemsetAsync(c->dImage[c->curImage], 0, (size_t)c->nSlotsImg * 16, c->stream));
     if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));      // the statistics describe this image
+    c->cam[c->curImage].valid = false;
     return PT_OK;
 }
 
@@ -2326,6 +2367,7 @@ int pt_next_image(pt_ctx* c) {
     int rc;
     if ((rc = pump(c, PUMP_IMAGE, next))) return rc;              // nothing may still be on its way into the image taken over
     c->curImage = next;
+    c->cam[next].valid = false;
     if (c->jobsThisImage) c->jobsPerImage = c->jobsThisImage;
     c->jobsThisImage = 0;
     HIP_TRY(hipMemsetAsync(c->dImage[next], 0, (size_t)c->nSlotsImg * 16, c->stream));
@@ -2410,6 +2452,7 @@ int pt_write_frame(pt_ctx* c, const float* in) {
     HIP_TRY(hipSetDevice(c->device));
     { int rc; if ((rc = flushStream(c))) return rc; }
     if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
+    recordCamera(c);
     float4* const dFrame = c->dImage[c->curImage];
     if (c->shardCount == 1) {
         HIP_TRY(hipMemcpyAsync(dFrame, in, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice, c->stream));
@@ -2859,17 +2902,16 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
 
 // ---- first-hit feature records and the denoised image (include/pt_denoise.h).  A group context works on its first stream's context: the scene is replicated.
 namespace {
-int ensureFeatures(pt_ctx* c) {
+// the feature records of the frame inputs `fin` into *buf (W*H x 4 float4, allocated on first use); *valid says they are there
+int ensureFeaturesFor(pt_ctx* c, const FrameIn& fin, float4** buf, bool* valid) {
     HIP_TRY(hipSetDevice(c->device));
-    if (c->featValid) return 0;
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
+    if (*valid) return 0;
     int rc;
     if ((rc = flushStream(c))) return rc;                         // before the frame constants of a running stream are overwritten
     std::memset(&c->streamIn, 0xff, sizeof(FrameIn));             // ... which are no stream's any more afterwards
     if (c->sceneDirty && (rc = buildScene(c))) return rc;
     const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
-    if (!c->dFeat) HIP_TRY(hipMalloc((void**)&c->dFeat, n * 64));
+    if (!*buf) HIP_TRY(hipMalloc((void**)buf, n * 64));
     State st{};
     Scratch scratch{{(void**)&st.G0, (void**)&st.G1, (void**)&st.H, (void**)&st.HX}};      // freed on every return path
     HIP_TRY(hipMalloc((void**)&st.G0, np * 16)); HIP_TRY(hipMalloc((void**)&st.G1, np * 16)); HIP_TRY(hipMalloc((void**)&st.H, np * 16));
@@ -2877,19 +2919,26 @@ int ensureFeatures(pt_ctx* c) {
         HIP_TRY(hipMalloc((void**)&st.HX, np * 16));
         HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
     }
-    FrameIn fin;
-    std::memcpy(fin.params, c->params.data(), 48); std::memcpy(fin.origin, c->origin.data(), 12); std::memcpy(fin.rotation, c->rotation.data(), 12);
-    std::memcpy(fin.mouse, c->mouse.data(), 12);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);      // auto-focus, camera and ellipsoid rotations
     hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
     if ((rc = probeIntersect(c, st, np, fin))) return rc;
-    hipLaunchKernelGGL(k_feature_record, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, c->dFeat);
+    hipLaunchKernelGGL(k_feature_record, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, *buf);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->featValid = true;
+    *valid = true;
     return 0;
+}
+// the records of the current frame inputs (c->dFeat)
+int ensureFeatures(pt_ctx* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->featValid) return 0;
+    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
+    FrameIn fin;
+    currentInputs(c, fin);
+    return ensureFeaturesFor(c, fin, &c->dFeat, &c->featValid);
 }
 
 // the denoised image of the context's current FRAME into on->dDnOut (W*H float4 on the device of *on), enqueued on on->stream
@@ -2954,6 +3003,128 @@ int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float
     HIP_TRY(hipMemcpyAsync(rgb_out, on->dDisplay, bytes, hipMemcpyDeviceToHost, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     return PT_OK;
+}
+
+// ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
+// every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
+namespace {
+// FRAME and T of the whole image (host, pixel order) into the accumulators of one stream of a group; T only where it is allocated
+int putShard(pt_ctx* k, const float* frame, const float* stats) {
+    HIP_TRY(hipSetDevice(k->device));
+    std::vector<float> tmp((size_t)k->nSlotsImg * 4, 0.0f);      // shard-local order, the padding slots zero
+    for (int i = 0; i < k->nLocal; i++) std::memcpy(tmp.data() + 4 * (size_t)i, frame + 4 * (size_t)k->pixList[i], 16);
+    HIP_TRY(hipMemcpyAsync(k->dImage[k->curImage], tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, k->stream));
+    HIP_TRY(hipStreamSynchronize(k->stream));
+    if (k->dStats && stats) {
+        for (int i = 0; i < k->nLocal; i++) std::memcpy(tmp.data() + 4 * (size_t)i, stats + 4 * (size_t)k->pixList[i], 16);
+        HIP_TRY(hipMemcpyAsync(k->dStats, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, k->stream));
+        HIP_TRY(hipStreamSynchronize(k->stream));
+    }
+    return 0;
+}
+
+int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, int64_t* nKept) {
+    if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: max_history must be >= 1");
+    if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: depth_tol must be > 0");
+    if (!(normalTol >= -1.0f && normalTol <= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: normal_tol must be in [-1, 1]");
+    if (flags & ~PT_REPROJECT_ALL_MATERIALS) return fail(PT_ERR_ARG, "pt_reproject_frame: unknown flags");
+    if (c->multi ? c->multi->shardTotal != c->multi->n : c->shardCount != 1)
+        return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame needs the whole image: this context holds a part of it");
+    pt_ctx* on = c->multi ? c->multi->kids[0] : c;
+    int rc;
+    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
+    else if ((rc = pt_synchronize(c))) return rc;                 // all submitted work lands in FRAME and T first
+    FrameIn cur;
+    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
+    const float* P = on->params.data();
+    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
+    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame: DEBUG != 0 renders the traversal heat map, which has no surfaces to carry");
+    const pt_ctx::Cam h = on->cam[on->curImage];
+    if (!h.valid) return PT_OK;                                   // no camera: nothing to map from
+    if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_reproject_frame: a scene buffer or texture was uploaded since the image's camera was recorded");
+    if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame: the image was rendered with DEBUG != 0");
+    if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
+        return fail(PT_ERR_ARG, "pt_reproject_frame: the image's camera has Parameters that do not match the image size");
+    // Rn and Rh; with the camera unchanged they are the same records
+    if ((rc = ensureFeaturesFor(on, cur, &on->dFeat, &on->featValid))) return rc;
+    const bool same = std::memcmp(&h.in, &cur, sizeof(FrameIn)) == 0;
+    if (!same) {
+        if (on->featHValid && std::memcmp(&on->featHIn, &h.in, sizeof(FrameIn)) != 0) on->featHValid = false;
+        if ((rc = ensureFeaturesFor(on, h.in, &on->dFeatH, &on->featHValid))) return rc;
+        on->featHIn = h.in;
+    }
+    HIP_TRY(hipSetDevice(on->device));
+    const size_t n = (size_t)c->W * c->H;
+    if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
+    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
+    // the image's T in pixel order, when allocated (group: through the host)
+    const float4* frame = nullptr; const float4* stats = nullptr;
+    std::vector<float> hostStats;
+    if (c->multi) {
+        const MultiCtx& M = *c->multi;
+        bool anyStats = false;
+        for (pt_ctx* k : M.kids) anyStats = anyStats || k->dStats;
+        if (anyStats) {
+            hostStats.assign(n * 4, 0.0f);
+            std::vector<float> tmp;
+            for (pt_ctx* k : M.kids) {
+                if (!k->dStats) continue;
+                HIP_TRY(hipSetDevice(k->device));
+                tmp.assign((size_t)k->nSlotsImg * 4, 0.0f);
+                HIP_TRY(hipMemcpy(tmp.data(), k->dStats, tmp.size() * 4, hipMemcpyDeviceToHost));
+                for (int i = 0; i < k->nLocal; i++) std::memcpy(hostStats.data() + 4 * (size_t)k->pixList[i], tmp.data() + 4 * (size_t)i, 16);
+            }
+            HIP_TRY(hipSetDevice(on->device));
+            if (!on->dRpStatsIn) HIP_TRY(hipMalloc((void**)&on->dRpStatsIn, n * 16));
+            HIP_TRY(hipMemcpyAsync(on->dRpStatsIn, hostStats.data(), n * 16, hipMemcpyHostToDevice, on->stream));
+            stats = on->dRpStatsIn;
+        }
+        float4* full = nullptr;
+        if ((rc = multiGather(c, 0, &full))) return rc;           // stream-ordered on on->stream
+        frame = full;
+        HIP_TRY(hipSetDevice(on->device));
+    } else {
+        frame = c->dImage[c->curImage];
+        stats = c->dStats;
+    }
+    if (stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
+    // the image's camera as k_frame_setup builds it (camRot), in the frame constants, which are no stream's afterwards
+    *on->hFrameIn = h.in;
+    HIP_TRY(hipMemcpyAsync(on->dFrameIn, on->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, on->stream));
+    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, on->stream, on->sc, on->dFrameIn, on->dFc, on->dEllip);
+    std::memset(&on->streamIn, 0xff, sizeof(FrameIn));
+    const float curIn[6] = {cur.origin[0], cur.origin[1], cur.origin[2], cur.mouse[0], cur.mouse[1], cur.params[2]};
+    const float rule[3] = {maxHistory, depthTol, normalTol};
+    HIP_TRY(reprojectLaunch(on->dFeat, same ? on->dFeat : on->dFeatH, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
+                            (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept, on->stream));
+    unsigned kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, on->dRpKept, 4, hipMemcpyDeviceToHost, on->stream));
+    if (!c->multi) {                                              // the result into the current image (a copy: pt_frame_device pointers stay valid)
+        HIP_TRY(hipMemcpyAsync(c->dImage[c->curImage], on->dRpFrame, n * 16, hipMemcpyDeviceToDevice, c->stream));
+        if (stats) HIP_TRY(hipMemcpyAsync(c->dStats, on->dRpStats, n * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->cam[c->curImage] = pt_ctx::Cam{cur, c->sceneGen, true};
+    } else {
+        std::vector<float> hf(n * 4);
+        HIP_TRY(hipMemcpyAsync(hf.data(), on->dRpFrame, n * 16, hipMemcpyDeviceToHost, on->stream));
+        if (stats) HIP_TRY(hipMemcpyAsync(hostStats.data(), on->dRpStats, n * 16, hipMemcpyDeviceToHost, on->stream));
+        HIP_TRY(hipStreamSynchronize(on->stream));
+        const float* pf = hf.data(); const float* ps = stats ? hostStats.data() : nullptr;
+        if ((rc = multiRun(*c->multi, [pf, ps](pt_ctx* k) { return putShard(k, pf, ps); }))) return rc;
+        for (pt_ctx* k : c->multi->kids) { FrameIn kin; if (currentInputs(k, kin)) k->cam[k->curImage] = pt_ctx::Cam{kin, k->sceneGen, true}; }
+    }
+    *nKept = kept;
+    return 0;
+}
+}  // namespace
+
+int pt_reproject_frame(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, int64_t* n_kept) {
+    if (n_kept) *n_kept = 0;
+    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame: null context");
+    int64_t n = 0;
+    const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, &n);
+    if (n_kept) *n_kept = n;
+    return rc;
 }
 
 }  // extern "C"

@@ -121,6 +121,8 @@ def lib():
             L.pt_read_features.argtypes = [vp, vp]
             L.pt_denoise.argtypes = [vp, ci, cf, cf, cf, cf, vp]
             L.pt_read_display_denoised.argtypes = [vp, ci, cf, cf, cf, cf, ci, vp]
+        if hasattr(L, "pt_reproject_frame"):                  # include/pt_reproject.h
+            L.pt_reproject_frame.argtypes = [vp, C.c_float, C.c_float, C.c_float, ci, C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -314,6 +316,19 @@ class Renderer:
         _check(self._L.pt_read_display_denoised(self._h, int(iterations), *self._sigmas(sigma_color, sigma_normal, sigma_depth, sigma_albedo),
                                                 1 if java_bytes else 0, out.ctypes.data))
         return out
+
+    # --- reprojection across a camera move (include/pt_reproject.h) --------------------------------
+    REPROJECT_ALL_MATERIALS = 1
+
+    def reproject_frame(self, max_history=64, depth_tol=0.02, normal_tol=0.9, all_materials=False):
+        """Carry the current image across the camera move since it was rendered (pt_reproject_frame): every pixel of the current view takes over
+        the sum and count of the old pixel that saw the same surface point, capped at max_history frames; the others restart from zero.
+        Returns how many pixels kept their history.  Continue with frame numbers other than 1 and show the image with read_display_mean.
+        The defaults: scripts/reproject_quality.py on C2 and C3 at 1080p (profiles/r10_reproject_quality.txt)."""
+        n = C.c_int64(0)
+        _check(self._L.pt_reproject_frame(self._h, float(max_history), float(depth_tol), float(normal_tol),
+                                          self.REPROJECT_ALL_MATERIALS if all_materials else 0, C.byref(n)))
+        return n.value
 
     def screenshot(self, path, frame_count, java_bytes=True):
         """functions.screenshot(fileName) (dispatch.java:804-851): the display image as a PNG file, written by the library (pt_save_png)"""
