@@ -1956,11 +1956,44 @@ bool currentInputs(const pt_ctx* c, FrameIn& fin) {
     std::memcpy(fin.mouse, c->mouse.data(), 12);
     return true;
 }
-// pt_write_frame: the current image's camera is the inputs current at the call (include/pt_reproject.h)
+// pt_write_frame, pt_reproject_frame: the current image's camera is the inputs current at the call (include/pt_reproject.h)
 void recordCamera(pt_ctx* c) {
     pt_ctx::Cam& k = c->cam[c->curImage];
     k.valid = currentInputs(c, k.in);
     k.sceneGen = c->sceneGen;
+}
+
+// A single context's accumulator slots (FRAME or T) to and from a whole image in host pixel order, on k->stream, synchronised.  A whole-image
+// context's slot of a pixel is the pixel (nLocal = nSlotsImg = W*H); a shard's slots follow its pixel list, zero-padded to nSlotsImg as pt_reset_frame
+// leaves them.
+int shardToHost(pt_ctx* k, const float4* devSlots, float* img) {
+    const bool whole = k->shardCount == 1;
+    std::vector<float> tmp(whole ? 0 : (size_t)k->nLocal * 4);
+    HIP_TRY(hipMemcpyAsync(whole ? img : tmp.data(), devSlots, (size_t)k->nLocal * 16, hipMemcpyDeviceToHost, k->stream));
+    HIP_TRY(hipStreamSynchronize(k->stream));
+    for (int i = 0; !whole && i < k->nLocal; i++) std::memcpy(img + 4 * (size_t)k->pixList[i], tmp.data() + 4 * (size_t)i, 16);
+    return 0;
+}
+int hostToShard(pt_ctx* k, const float* img, float4* devSlots) {
+    const bool whole = k->shardCount == 1;
+    std::vector<float> tmp(whole ? 0 : (size_t)k->nSlotsImg * 4, 0.0f);
+    for (int i = 0; !whole && i < k->nLocal; i++) std::memcpy(tmp.data() + 4 * (size_t)i, img + 4 * (size_t)k->pixList[i], 16);
+    HIP_TRY(hipMemcpyAsync(devSlots, whole ? img : tmp.data(), (size_t)k->nSlotsImg * 16, hipMemcpyHostToDevice, k->stream));
+    HIP_TRY(hipStreamSynchronize(k->stream));
+    return 0;
+}
+
+// pt_write_frame of a single context: FRAME from the whole host image; T from `stats` when given, else zeroed (where allocated); the camera recorded
+int writeFrame(pt_ctx* c, const float* frame, const float* stats) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = flushStream(c))) return rc;
+    if (c->dStats) {
+        if (stats) { if ((rc = hostToShard(c, stats, c->dStats))) return rc; }
+        else HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
+    }
+    recordCamera(c);
+    return hostToShard(c, frame, c->dImage[c->curImage]);
 }
 
 int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bool async) {
@@ -2416,7 +2449,7 @@ int pt_read_frame(pt_ctx* c, float* out) {
         int rc = multiGather(c, 0, &full);
         if (rc) return rc;
         MultiCtx& M = *c->multi;
-        pt_ctx* root = M.kids[0];
+        pt_ctx* root = firstStream(c);
         if (M.shardTotal == M.n) {
             HIP_TRY(hipMemcpyAsync(out, full, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, root->stream));
             HIP_TRY(hipStreamSynchronize(root->stream));
@@ -2431,67 +2464,53 @@ int pt_read_frame(pt_ctx* c, float* out) {
     }
     HIP_TRY(hipSetDevice(c->device));
     { int rc; if ((rc = flushStream(c))) return rc; }
-    float4* const dFrame = c->dImage[c->curImage];
-    if (c->shardCount == 1) {
-        HIP_TRY(hipMemcpyAsync(out, dFrame, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return PT_OK;
-    }
-    std::vector<float> tmp((size_t)c->nLocal * 4);
-    HIP_TRY(hipMemcpyAsync(tmp.data(), dFrame, tmp.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < c->nLocal; k++) std::memcpy(out + 4 * (size_t)c->pixList[k], tmp.data() + 4 * (size_t)k, 16);
-    return PT_OK;
+    return shardToHost(c, c->dImage[c->curImage], out);
 }
 
 /* The inverse of pt_read_frame: FRAME is the path tracer's only persistent state (frag.glsl:924-933: rgb = running sum, a = count), so a saved image written
  * back lets an interrupted accumulation go on — N frames, read, (new context,) write, M frames more = N + M frames, bit for bit. */
 int pt_write_frame(pt_ctx* c, const float* in) {
     if (!c || !in) return fail(PT_ERR_ARG, "pt_write_frame: null argument");
-    MULTI_ALL(c, pt_write_frame(k, in));                           // every stream takes the pixels of its own tile shard
-    HIP_TRY(hipSetDevice(c->device));
-    { int rc; if ((rc = flushStream(c))) return rc; }
-    if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
-    recordCamera(c);
-    float4* const dFrame = c->dImage[c->curImage];
-    if (c->shardCount == 1) {
-        HIP_TRY(hipMemcpyAsync(dFrame, in, (size_t)c->W * c->H * 16, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return PT_OK;
-    }
-    std::vector<float> tmp((size_t)c->nSlotsImg * 4, 0.0f);       // shard-local order, the padding slots zero as pt_reset_frame leaves them
-    for (int k = 0; k < c->nLocal; k++) std::memcpy(tmp.data() + 4 * (size_t)k, in + 4 * (size_t)c->pixList[k], 16);
-    HIP_TRY(hipMemcpyAsync(dFrame, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return PT_OK;
+    MULTI_ALL(c, writeFrame(k, in, nullptr));                      // every stream takes the pixels of its own tile shard
+    return writeFrame(c, in, nullptr);
 }
 
 namespace {
-// pt_read_display (perPixel false: one frame_count for every pixel) and pt_read_display_mean (perPixel true: each pixel's own count)
-int readDisplay(pt_ctx* c, int frame_count, bool perPixel, int java_bytes, uint8_t* rgb_out) {
-    const float4* frame = nullptr; pt_ctx* on = c;
-    if (c->multi) {
-        if (c->multi->shardTotal != c->multi->n) return fail(PT_ERR_ARG, "pt_read_display needs the whole image: this group holds a part of it (pt_create_multi_part)");
-        float4* full = nullptr;
-        int rc = multiGather(c, 0, &full);
-        if (rc) return rc;
-        frame = full; on = c->multi->kids[0];
-    } else {
-        if (c->shardCount != 1) return fail(PT_ERR_ARG, "pt_read_display needs the whole image: a single shard of several cannot show it (use a pt_create_multi context)");
+// The context's whole FRAME image, complete and ordered on the stream of *on, whose device is made current: a group gathers it on its first stream's
+// context.  A context that holds only a part of the image (a single shard, a pt_create_multi_part group) fails with `code`.
+int wholeFrame(pt_ctx* c, int code, const char* who, pt_ctx** on, const float4** frame) {
+    if (c->multi ? c->multi->shardTotal != c->multi->n : c->shardCount != 1)
+        return fail(code, std::string(who) + " needs the whole image: this context holds a part of it (use a pt_create_multi context)");
+    *on = firstStream(c);
+    if (!c->multi) {
         HIP_TRY(hipSetDevice(c->device));
-        { int rc; if ((rc = flushStream(c))) return rc; }
-        frame = c->dImage[c->curImage];
+        *frame = c->dImage[c->curImage];
+        return flushStream(c);
     }
-    HIP_TRY(hipSetDevice(on->device));
-    const size_t bytes = (size_t)c->W * c->H * 3;
+    float4* full = nullptr;
+    const int rc = multiGather(c, 0, &full);                      // (leaves devices[0], kids[0]'s device, current)
+    *frame = full;
+    return rc;
+}
+
+// k_display of the W x H image src (on's device) into rgb_out (host), on on->stream, synchronised: every pixel divided by `count`, or by its own count
+// (FRAME alpha) when perPixel
+int displayInto(pt_ctx* on, const float4* src, int W, int H, bool perPixel, float count, int java_bytes, uint8_t* rgb_out) {
+    const size_t bytes = (size_t)W * H * 3;
     if (!on->dDisplay) HIP_TRY(hipMalloc((void**)&on->dDisplay, bytes));
-    const dim3 grid((unsigned)(((size_t)c->W * c->H + BLOCK - 1) / BLOCK));
-    if (perPixel) hipLaunchKernelGGL(k_display<true>, grid, dim3(BLOCK), 0, on->stream, frame, c->W, c->H, 0.0f, java_bytes, on->dDisplay);
-    else hipLaunchKernelGGL(k_display<false>, grid, dim3(BLOCK), 0, on->stream, frame, c->W, c->H, (float)frame_count, java_bytes, on->dDisplay);
+    hipLaunchKernelGGL(perPixel ? k_display<true> : k_display<false>, dim3((unsigned)(((size_t)W * H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, on->stream,
+                       src, W, H, count, java_bytes, on->dDisplay);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rgb_out, on->dDisplay, bytes, hipMemcpyDeviceToHost, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     return PT_OK;
+}
+
+// pt_read_display (perPixel false: one frame_count for every pixel) and pt_read_display_mean (perPixel true: each pixel's own count)
+int readDisplay(pt_ctx* c, int frame_count, bool perPixel, int java_bytes, uint8_t* rgb_out) {
+    pt_ctx* on = nullptr; const float4* frame = nullptr;
+    const int rc = wholeFrame(c, PT_ERR_ARG, perPixel ? "pt_read_display_mean" : "pt_read_display", &on, &frame);
+    return rc ? rc : displayInto(on, frame, c->W, c->H, perPixel, (float)frame_count, java_bytes, rgb_out);
 }
 }  // namespace
 
@@ -2670,15 +2689,13 @@ int pt_shard_map(int width, int height, int shard_rank, int shard_count, int32_t
 
 int pt_unshard(pt_ctx* c, const void* gathered_dev, void* full_dev) {
     if (!c || !gathered_dev || !full_dev) return fail(PT_ERR_ARG, "pt_unshard: null argument");
-    if (c->multi) {
-        if (c->multi->shardTotal == c->multi->n) return fail(PT_ERR_ARG, "pt_unshard: a whole-image context gathers and un-tiles by itself (pt_gather_image, pt_read_frame)");
-        c = c->multi->kids[0];                                    // a part of the image: any of its shards knows the layout of all shard_total blocks
-    }
+    if (c->multi && c->multi->shardTotal == c->multi->n) return fail(PT_ERR_ARG, "pt_unshard: a whole-image context gathers and un-tiles by itself (pt_gather_image, pt_read_frame)");
+    c = firstStream(c);                                           // a part of the image: any of its shards knows the layout of all shard_total blocks
     HIP_TRY(hipSetDevice(c->device));
     size_t total = (size_t)c->nSlotsImg * c->shardCount;
     if (!c->dAllMaps) {
-        std::vector<int32_t> maps(total);
-        for (int r = 0; r < c->shardCount; r++) { int rc = pt_shard_map(c->W, c->H, r, c->shardCount, maps.data() + (size_t)r * c->nSlotsImg, (size_t)c->nSlotsImg); if (rc) return rc; }
+        std::vector<int32_t> maps;
+        { const int rc = shardMaps(c->W, c->H, 0, c->shardCount, c->shardCount, (size_t)c->nSlotsImg, maps); if (rc) return rc; }
         HIP_TRY(hipMalloc((void**)&c->dAllMaps, total * 4));
         HIP_TRY(hipMemcpy(c->dAllMaps, maps.data(), total * 4, hipMemcpyHostToDevice));
     }
@@ -2769,7 +2786,7 @@ int pt_reset_counters(pt_ctx* c) {
 
 int pt_debug_phase_stats(pt_ctx* c, uint64_t* out, int n) {
     if (!c || !out) return fail(PT_ERR_ARG, "pt_debug_phase_stats: null argument");
-    if (c->multi) c = c->multi->kids[0];
+    c = firstStream(c);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));                     // what the launches so far left; submitted batches are NOT completed first
     Control h;
@@ -2810,7 +2827,7 @@ int pt_kernel_time(pt_ctx* c, int kernel, int64_t* launches, double* total_ms) {
 
 int pt_kernel_time_median(pt_ctx* c, int kernel, double* median_ms) {
     if (!c || kernel < 0 || kernel > 3 || !median_ms) return fail(PT_ERR_ARG, "pt_kernel_time_median: bad argument");
-    if (c->multi) c = c->multi->kids[0];
+    c = firstStream(c);
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     int rc = resolveTimes(c);
@@ -2824,7 +2841,7 @@ int pt_kernel_time_median(pt_ctx* c, int kernel, double* median_ms) {
 
 int pt_debug_math(pt_ctx* c, int fn, const float* x, const float* y, float* out, size_t n) {
     if (!c || !x || !out) return fail(PT_ERR_ARG, "pt_debug_math: null argument");
-    if (c->multi) c = c->multi->kids[0];
+    c = firstStream(c);
     HIP_TRY(hipSetDevice(c->device));
     float *dx = nullptr, *dy = nullptr, *dout = nullptr;
     Scratch scratch{{(void**)&dx, (void**)&dy, (void**)&dout}};       // freed on every return path
@@ -2858,16 +2875,33 @@ int probeIntersect(pt_ctx* c, const State& st, size_t np, const FrameIn& fin) {
     if (!c->asmError.empty()) { const std::string m = c->asmError; c->asmError.clear(); return fail(PT_ERR_HIP, m); }
     return 0;
 }
-}  // namespace
 
-int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, size_t n) {
-    if (!c || !o || !d || !out || n < 1 || n > (1u << 24)) return fail(PT_ERR_ARG, "pt_debug_intersect: bad argument");
-    if (c->multi) c = c->multi->kids[0];
-    HIP_TRY(hipSetDevice(c->device));
+// the frame constants (dFrameIn, dFc) taken over by a call of its own (a probe pool), with the scene built
+int claimFrameConstants(pt_ctx* c) {
     int rc;
     if ((rc = flushStream(c))) return rc;                         // before the frame constants of a running stream are overwritten
     std::memset(&c->streamIn, 0xff, sizeof(FrameIn));             // ... which are no stream's any more afterwards
     if (c->sceneDirty && (rc = buildScene(c))) return rc;
+    return 0;
+}
+
+// G0, G1, H and, with hx, HX of a probe pool of np slots, released with `scratch`; their contents are the caller's
+int probePool(Scratch& scratch, State& st, size_t np, bool hx) {
+    for (float4** p : {&st.G0, &st.G1, &st.H, &st.HX}) {
+        if (p == &st.HX && !hx) break;
+        scratch.ptrs.push_back((void**)p);
+        HIP_TRY(hipMalloc((void**)p, np * 16));
+    }
+    return 0;
+}
+}  // namespace
+
+int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, size_t n) {
+    if (!c || !o || !d || !out || n < 1 || n > (1u << 24)) return fail(PT_ERR_ARG, "pt_debug_intersect: bad argument");
+    c = firstStream(c);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = claimFrameConstants(c))) return rc;
     size_t np = (n + BLOCK - 1) / BLOCK * BLOCK;
     std::vector<float> g0(np * 4, 0.0f), g1(np * 4, 0.0f);
     for (size_t i = 0; i < n; i++) {
@@ -2875,8 +2909,8 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
         g1[4 * i] = d[3 * i + 1]; g1[4 * i + 1] = d[3 * i + 2]; uint32_t fl = FL_ALIVE; std::memcpy(&g1[4 * i + 3], &fl, 4);
     }
     State st{};
-    Scratch scratch{{(void**)&st.G0, (void**)&st.G1, (void**)&st.H}};  // freed on every return path
-    HIP_TRY(hipMalloc((void**)&st.G0, np * 16)); HIP_TRY(hipMalloc((void**)&st.G1, np * 16)); HIP_TRY(hipMalloc((void**)&st.H, np * 16));
+    Scratch scratch;
+    if ((rc = probePool(scratch, st, np, false))) return rc;
     HIP_TRY(hipMemcpy(st.G0, g0.data(), np * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(st.G1, g1.data(), np * 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(st.H, 0, np * 16, c->stream));       // ordered before the kernels below (the context's stream does not wait for the null stream)
     // the ellipsoid rotation matrices are produced by k_frame_setup
@@ -2907,18 +2941,13 @@ int ensureFeaturesFor(pt_ctx* c, const FrameIn& fin, float4** buf, bool* valid) 
     HIP_TRY(hipSetDevice(c->device));
     if (*valid) return 0;
     int rc;
-    if ((rc = flushStream(c))) return rc;                         // before the frame constants of a running stream are overwritten
-    std::memset(&c->streamIn, 0xff, sizeof(FrameIn));             // ... which are no stream's any more afterwards
-    if (c->sceneDirty && (rc = buildScene(c))) return rc;
+    if ((rc = claimFrameConstants(c))) return rc;
     const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
     if (!*buf) HIP_TRY(hipMalloc((void**)buf, n * 64));
     State st{};
-    Scratch scratch{{(void**)&st.G0, (void**)&st.G1, (void**)&st.H, (void**)&st.HX}};      // freed on every return path
-    HIP_TRY(hipMalloc((void**)&st.G0, np * 16)); HIP_TRY(hipMalloc((void**)&st.G1, np * 16)); HIP_TRY(hipMalloc((void**)&st.H, np * 16));
-    if (c->sc.numEllip > 0) {                                     // the uv an ellipsoid hit inherits (uvOfHit)
-        HIP_TRY(hipMalloc((void**)&st.HX, np * 16));
-        HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
-    }
+    Scratch scratch;
+    if ((rc = probePool(scratch, st, np, c->sc.numEllip > 0))) return rc;      // HX: the uv an ellipsoid hit inherits (uvOfHit)
+    if (st.HX) HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);      // auto-focus, camera and ellipsoid rotations
@@ -2945,21 +2974,10 @@ int ensureFeatures(pt_ctx* c) {
 int denoiseImage(pt_ctx* c, int iterations, const float sigma[4], pt_ctx** onOut) {
     if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise: iterations must be in [0,8]");
     for (int k = 0; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, "pt_denoise: every sigma must be > 0 (+inf switches its term off)");
-    pt_ctx* on = c->multi ? c->multi->kids[0] : c;
-    if (c->multi ? c->multi->shardTotal != c->multi->n : c->shardCount != 1)
-        return fail(PT_ERR_UNSUPPORTED, "pt_denoise needs the whole image: this context holds a part of it");
+    pt_ctx* on = nullptr; const float4* frame = nullptr;
     int rc;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise", &on, &frame))) return rc;
     if ((rc = ensureFeatures(on))) return rc;
-    const float4* frame = nullptr;
-    if (c->multi) {
-        float4* full = nullptr;
-        if ((rc = multiGather(c, 0, &full))) return rc;
-        frame = full;
-    } else {
-        if ((rc = flushStream(c))) return rc;
-        frame = c->dImage[c->curImage];
-    }
-    HIP_TRY(hipSetDevice(on->device));
     const size_t n = (size_t)c->W * c->H;
     for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
     if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
@@ -2971,7 +2989,7 @@ int denoiseImage(pt_ctx* c, int iterations, const float sigma[4], pt_ctx** onOut
 
 int pt_read_features(pt_ctx* c, float* out) {
     if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features: null argument");
-    pt_ctx* on = c->multi ? c->multi->kids[0] : c;
+    pt_ctx* on = firstStream(c);
     int rc;
     if ((rc = ensureFeatures(on))) return rc;
     HIP_TRY(hipMemcpy(out, on->dFeat, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
@@ -2995,43 +3013,21 @@ int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float
     pt_ctx* on = nullptr;
     int rc;
     if ((rc = denoiseImage(c, iterations, sigma, &on))) return rc;
-    const size_t bytes = (size_t)c->W * c->H * 3;
-    if (!on->dDisplay) HIP_TRY(hipMalloc((void**)&on->dDisplay, bytes));
     // the denoised image is a mean already: k_display's conversion with a frame count of 1 (x / 1.0f is exact)
-    hipLaunchKernelGGL(k_display<false>, dim3((unsigned)((c->W * (size_t)c->H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, on->stream, on->dDnOut, c->W, c->H, 1.0f, java_bytes, on->dDisplay);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rgb_out, on->dDisplay, bytes, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    return PT_OK;
+    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
 }
 
 // ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
 // every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
 namespace {
-// FRAME and T of the whole image (host, pixel order) into the accumulators of one stream of a group; T only where it is allocated
-int putShard(pt_ctx* k, const float* frame, const float* stats) {
-    HIP_TRY(hipSetDevice(k->device));
-    std::vector<float> tmp((size_t)k->nSlotsImg * 4, 0.0f);      // shard-local order, the padding slots zero
-    for (int i = 0; i < k->nLocal; i++) std::memcpy(tmp.data() + 4 * (size_t)i, frame + 4 * (size_t)k->pixList[i], 16);
-    HIP_TRY(hipMemcpyAsync(k->dImage[k->curImage], tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, k->stream));
-    HIP_TRY(hipStreamSynchronize(k->stream));
-    if (k->dStats && stats) {
-        for (int i = 0; i < k->nLocal; i++) std::memcpy(tmp.data() + 4 * (size_t)i, stats + 4 * (size_t)k->pixList[i], 16);
-        HIP_TRY(hipMemcpyAsync(k->dStats, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, k->stream));
-        HIP_TRY(hipStreamSynchronize(k->stream));
-    }
-    return 0;
-}
-
 int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, int64_t* nKept) {
     if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: max_history must be >= 1");
     if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: depth_tol must be > 0");
     if (!(normalTol >= -1.0f && normalTol <= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: normal_tol must be in [-1, 1]");
     if (flags & ~PT_REPROJECT_ALL_MATERIALS) return fail(PT_ERR_ARG, "pt_reproject_frame: unknown flags");
-    if (c->multi ? c->multi->shardTotal != c->multi->n : c->shardCount != 1)
-        return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame needs the whole image: this context holds a part of it");
-    pt_ctx* on = c->multi ? c->multi->kids[0] : c;
+    pt_ctx* on = nullptr; const float4* frame = nullptr;
     int rc;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_reproject_frame", &on, &frame))) return rc;      // a group: gathered on on->stream
     if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
     else if ((rc = pt_synchronize(c))) return rc;                 // all submitted work lands in FRAME and T first
     FrameIn cur;
@@ -3058,7 +3054,7 @@ int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol,
     if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
     if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
     // the image's T in pixel order, when allocated (group: through the host)
-    const float4* frame = nullptr; const float4* stats = nullptr;
+    const float4* stats = c->multi ? nullptr : c->dStats;
     std::vector<float> hostStats;
     if (c->multi) {
         const MultiCtx& M = *c->multi;
@@ -3066,26 +3062,16 @@ int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol,
         for (pt_ctx* k : M.kids) anyStats = anyStats || k->dStats;
         if (anyStats) {
             hostStats.assign(n * 4, 0.0f);
-            std::vector<float> tmp;
             for (pt_ctx* k : M.kids) {
                 if (!k->dStats) continue;
                 HIP_TRY(hipSetDevice(k->device));
-                tmp.assign((size_t)k->nSlotsImg * 4, 0.0f);
-                HIP_TRY(hipMemcpy(tmp.data(), k->dStats, tmp.size() * 4, hipMemcpyDeviceToHost));
-                for (int i = 0; i < k->nLocal; i++) std::memcpy(hostStats.data() + 4 * (size_t)k->pixList[i], tmp.data() + 4 * (size_t)i, 16);
+                if ((rc = shardToHost(k, k->dStats, hostStats.data()))) return rc;
             }
             HIP_TRY(hipSetDevice(on->device));
             if (!on->dRpStatsIn) HIP_TRY(hipMalloc((void**)&on->dRpStatsIn, n * 16));
             HIP_TRY(hipMemcpyAsync(on->dRpStatsIn, hostStats.data(), n * 16, hipMemcpyHostToDevice, on->stream));
             stats = on->dRpStatsIn;
         }
-        float4* full = nullptr;
-        if ((rc = multiGather(c, 0, &full))) return rc;           // stream-ordered on on->stream
-        frame = full;
-        HIP_TRY(hipSetDevice(on->device));
-    } else {
-        frame = c->dImage[c->curImage];
-        stats = c->dStats;
     }
     if (stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
     // the image's camera as k_frame_setup builds it (camRot), in the frame constants, which are no stream's afterwards
@@ -3103,15 +3089,14 @@ int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol,
         HIP_TRY(hipMemcpyAsync(c->dImage[c->curImage], on->dRpFrame, n * 16, hipMemcpyDeviceToDevice, c->stream));
         if (stats) HIP_TRY(hipMemcpyAsync(c->dStats, on->dRpStats, n * 16, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->cam[c->curImage] = pt_ctx::Cam{cur, c->sceneGen, true};
+        recordCamera(c);
     } else {
         std::vector<float> hf(n * 4);
         HIP_TRY(hipMemcpyAsync(hf.data(), on->dRpFrame, n * 16, hipMemcpyDeviceToHost, on->stream));
         if (stats) HIP_TRY(hipMemcpyAsync(hostStats.data(), on->dRpStats, n * 16, hipMemcpyDeviceToHost, on->stream));
         HIP_TRY(hipStreamSynchronize(on->stream));
         const float* pf = hf.data(); const float* ps = stats ? hostStats.data() : nullptr;
-        if ((rc = multiRun(*c->multi, [pf, ps](pt_ctx* k) { return putShard(k, pf, ps); }))) return rc;
-        for (pt_ctx* k : c->multi->kids) { FrameIn kin; if (currentInputs(k, kin)) k->cam[k->curImage] = pt_ctx::Cam{kin, k->sceneGen, true}; }
+        if ((rc = multiRun(*c->multi, [pf, ps](pt_ctx* k) { return writeFrame(k, pf, ps); }))) return rc;
     }
     *nKept = kept;
     return 0;

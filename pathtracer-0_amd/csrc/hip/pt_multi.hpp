@@ -106,6 +106,16 @@ struct MultiCtx {
 
 namespace {
 
+// the context a group works on for a call that needs one device (its first stream's: the scene is replicated); a single context itself
+pt_ctx* firstStream(pt_ctx* c) { return c->multi ? c->multi->kids[0] : c; }
+
+// slot -> pixel of shards first .. first+count-1 of `total` into maps: nSlots per shard, shard-major, -1 = padding
+int shardMaps(int W, int H, int first, int count, int total, size_t nSlots, std::vector<int32_t>& maps) {
+    maps.resize((size_t)count * nSlots);
+    for (int r = 0; r < count; r++) { const int rc = pt_shard_map(W, H, first + r, total, maps.data() + (size_t)r * nSlots, nSlots); if (rc) return rc; }
+    return 0;
+}
+
 int multiRun(MultiCtx& M, const std::function<int(pt_ctx*)>& f) {
     for (int i = 0; i < M.n; i++) { pt_ctx* k = M.kids[i]; M.workers[i]->post([&f, k] { return f(k); }); }
     int rc = 0; std::string err;
@@ -159,8 +169,7 @@ int multiGather(pt_ctx* g, int age, float4** out) {
         for (float4** p : {&M.dGathered, &M.dFull}) if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; }
         if (M.dAllMaps) { HIP_TRY(hipFree(M.dAllMaps)); M.dAllMaps = nullptr; }
         HIP_TRY(hipMalloc((void**)&M.dGathered, total * 16));
-        M.maps.resize(total);
-        for (int r = 0; r < M.n; r++) if ((rc = pt_shard_map(g->W, g->H, M.shardBase + r, M.shardTotal, M.maps.data() + (size_t)r * nSlots, nSlots))) return rc;
+        if ((rc = shardMaps(g->W, g->H, M.shardBase, M.n, M.shardTotal, nSlots, M.maps))) return rc;
         if (M.shardTotal == M.n) {
             HIP_TRY(hipMalloc((void**)&M.dFull, (size_t)g->W * g->H * 16));
             HIP_TRY(hipMalloc((void**)&M.dAllMaps, total * 4));

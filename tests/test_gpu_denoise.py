@@ -103,6 +103,10 @@ def test_errors_and_unsupported_contexts(pt, renderer_mod):
         assert e.value.code == -5                                   # PT_ERR_UNSUPPORTED
         with pytest.raises(PtError):
             p.read_display_denoised()
+        for show in (lambda: p.read_display(1), p.read_display_mean):
+            with pytest.raises(PtError) as e:
+                show()
+            assert e.value.code == -1                               # PT_ERR_ARG
         p.close()
 
 

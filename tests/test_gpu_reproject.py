@@ -135,13 +135,15 @@ def _sequence(r, wl, seeds):
 def test_multi_stream_context_equals_one_stream(pt, renderer_mod):
     seeds = [pt.scenes.frame_seed(f) for f in range(1, 9)]
     out = []
-    for kw in ({}, {"devices": [0, 0]}):
+    for kw in ({}, {"devices": [0, 0]}, {"devices": [0]}):      # [0]: a group of one stream, whose context holds the whole image
         r, wl = _ctx(pt, renderer_mod, "C3", **kw)
         out.append(_sequence(r, wl, seeds))
         r.close()
-    (k0, m0, n0, f0), (k1, m1, n1, f1) = out
-    assert k0 == k1 and n0 == n1 and 0 < k0 < W * H and n0 == W * H - k0
-    assert frames_equal(m0, m1) and frames_equal(f0, f1)
+    k0, m0, n0, f0 = out[0]
+    assert 0 < k0 < W * H and n0 == W * H - k0
+    for kw, (k1, m1, n1, f1) in zip(({"devices": [0, 0]}, {"devices": [0]}), out[1:]):
+        assert k0 == k1 and n0 == n1, kw
+        assert frames_equal(m0, m1) and frames_equal(f0, f1), kw
 
 
 def test_renders_after_a_reprojection_equal_renders_on_its_written_image(pt, renderer_mod):
