@@ -6,30 +6,14 @@ import subprocess
 
 import numpy as np
 
+from _adaptive_model import select
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declared(header):
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
     return sorted(set(re.findall(r"\b(pts?_[a-z_0-9]+)\s*\(", txt)))
-
-
-def select(T, rel_err, abs_err, min_frames, max_frames, overlay=None):
-    """the selection rule of include/pt_adaptive.h over T = (..., 4) float32 (sY, sYY, n, 0), evaluated in float32 in the header's order"""
-    T = np.asarray(T, np.float32)
-    sY, sYY, n = T[..., 0], T[..., 1], T[..., 2]
-    with np.errstate(all="ignore"):
-        mean = sY / n
-        var = (sYY - sY * mean) / (n - np.float32(1.0))
-        err2 = var / n
-        tol = np.fmax(np.float32(rel_err) * np.abs(mean), np.float32(abs_err))
-        act = err2 > tol * tol
-    act = act | (n < np.float32(min_frames))
-    if max_frames > 0:
-        act = act & ~(n >= np.float32(max_frames))
-    if overlay is not None:
-        act = act & ~overlay
-    return act
 
 
 def test_hip_library_exports_the_adaptive_symbols(pt):

@@ -6,49 +6,14 @@ accumulation; the GPU image must equal it bit for bit (NaN == NaN)."""
 import numpy as np
 import pytest
 
+from _adaptive_model import Model
 from conftest import frames_equal
-from test_adaptive_abi import select
 from test_gpu_parity import _no_vn_workload
 
 pytestmark = pytest.mark.gpu
 
 W, H = 128, 72
 NF = 16                                   # frames the oracle renders per scene
-
-
-class Model:
-    """FRAME and T = (sY, sYY, n, 0) of one image, as pt_render_adaptive / pt_render_batch update them"""
-
-    def __init__(self, cols):
-        self.cols = cols                                # cols[f - 1] = (H, W, 3) float32 rgb frame f adds
-        self.F = np.zeros((H, W, 4), np.float32)
-        self.T = np.zeros((H, W, 4), np.float32)
-
-    def _add(self, f, m):
-        c = self.cols[f - 1]
-        if f == 1:
-            self.F[m] = np.concatenate([c[m], np.ones((int(m.sum()), 1), np.float32)], axis=1)
-        else:
-            self.F[m, :3] = self.F[m, :3] + c[m]
-            self.F[m, 3] = self.F[m, 3] + np.float32(1.0)
-
-    def adaptive(self, first, n, rel_err, abs_err=0.0, min_frames=4, max_frames=0):
-        act = select(self.T, rel_err, abs_err, min_frames, max_frames)
-        for f in range(first, first + n):
-            self._add(f, act)
-            c = self.cols[f - 1][act]
-            Y = (np.float32(0.2126) * c[:, 0] + np.float32(0.7152) * c[:, 1]) + np.float32(0.0722) * c[:, 2]
-            self.T[act, 0] = self.T[act, 0] + Y
-            self.T[act, 1] = self.T[act, 1] + Y * Y
-            self.T[act, 2] = self.T[act, 2] + np.float32(1.0)
-        return act
-
-    def uniform(self, first, n):
-        for f in range(first, first + n):
-            self._add(f, np.ones((H, W), bool))
-
-    def reset_stats(self):
-        self.T[:] = 0
 
 
 def _seeds(pt, first, n):

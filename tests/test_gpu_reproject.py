@@ -6,6 +6,7 @@ import math
 import numpy as np
 import pytest
 
+from _adaptive_model import Model, select
 from _reproject_model import cam_rot, frame_in, material_flags, reproject as model
 from conftest import frames_equal, rmse
 
@@ -259,3 +260,58 @@ def test_reprojection_lowers_the_error_after_a_small_move(pt, renderer_mod):
     assert kept > 0.8 * W * H
     e_rp, e_rs = rmse(reproj, ref), rmse(reset, ref)
     assert e_rp < e_rs, (e_rp, e_rs)
+
+
+def _adaptive_then_reproject(pt, renderer_mod, w, h, cols, mv, case):
+    """C3 at w x h: two adaptive calls (every pixel 4 frames, then a partial one), a move, the reprojection; FRAME and the kept count against
+    the model, then T through the selection of one more adaptive call (T has no reader: its active set is where FRAME's count grows)"""
+    wl = pt.scenes.build("C3", w, h)
+    r = renderer_mod.Renderer(w, h)
+    r.load_workload(wl)
+    A = (wl.buffers[0], wl.buffers[1])
+    m = Model(cols)
+    for first, n, rel, mn in ((1, 4, 0.0, 100), (5, 2, 0.5, 2)):
+        got_n = r.render_adaptive(first, [pt.scenes.frame_seed(f) for f in range(first, first + n)], rel, 0.0, mn)
+        assert got_n == int(m.adaptive(first, n, rel, 0.0, mn).sum())
+    fr = r.read_frame()
+    assert frames_equal(fr, m.F)
+    rh = r.read_features()
+    B = move(*A, **mv)
+    _setcam(r, *B)
+    rn = r.read_features()
+    kept = r.reproject_frame(case["mh"], case["dt"], case["nt"], case["allm"])
+    got = r.read_frame()
+    want, wantT, wkept = _want(r, wl, rn, rh, fr, A, B, wl.buffers[2], T=m.T, **case)
+    assert frames_equal(got, want), (w, h, mv, case, int((got.view(np.uint32) != want.view(np.uint32)).any(-1).sum()))
+    assert kept == wkept and 0 < kept < w * h, (w, h, mv, case, kept, wkept)
+    n = r.render_adaptive(7, [pt.scenes.frame_seed(7)], 0.3, 0.0, 3)
+    act = r.read_frame()[..., 3] > got[..., 3]
+    r.close()
+    sel = select(wantT, 0.3, 0.0, 3, 0)
+    assert np.array_equal(act, sel) and n == int(sel.sum()), (w, h, mv, case, n, int(sel.sum()), int((act != sel).sum()))
+    if w * h > 100000:                                                      # the kept statistics decide: some kept pixels stay, some go
+        assert 0 < int((sel & (want[..., 3] > 0)).sum()) < kept
+
+
+def _uniform_cols(pt, renderer_mod, w, h, nf):
+    wl = pt.scenes.build("C3", w, h)
+    r = renderer_mod.Renderer(w, h)
+    r.load_workload(wl)
+    cols = []
+    for f in range(1, nf + 1):                  # frame number 1 overwrites FRAME: the colour frame f adds (tests/test_gpu_adaptive_sizes.py)
+        r.reset_frame()
+        r.render(1, pt.scenes.frame_seed(f))
+        cols.append(r.read_frame()[..., :3].copy())
+    r.close()
+    return cols
+
+
+MOVES = [dict(forward=0.02, strafe=0.01), dict(yaw=0.03)]
+
+
+@pytest.mark.parametrize("w,h", [(1920, 1080), (100, 7)])           # 100 x 7: a partial block of 64 columns, every block below its 16 rows
+def test_full_size_and_edge_shapes_with_carried_statistics(pt, renderer_mod, w, h):
+    cols = _uniform_cols(pt, renderer_mod, w, h, 6)
+    for mv in MOVES:
+        for case in CASES:
+            _adaptive_then_reproject(pt, renderer_mod, w, h, cols, mv, case)
