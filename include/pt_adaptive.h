@@ -6,8 +6,9 @@
  * Per-pixel statistics.  Every context keeps T = (sY, sYY, n, 0) per accumulator slot: the sum and the sum of squares of the luminance
  * Y = (0.2126*r + 0.7152*g) + 0.0722*b of the frames the pixel received from pt_render_adaptive (r, g, b = what the frame adds to FRAME),
  * and their number, all float32 without contraction.  T is allocated zeroed by the first pt_render_adaptive call and
- * zeroed again whenever FRAME is zeroed or replaced: pt_reset_frame, pt_write_frame, pt_next_image.  ONLY pt_render_adaptive updates T:
- * frames rendered by pt_render / pt_render_batch / pt_render_batch_async still go into FRAME but not into the statistics.
+ * zeroed again whenever FRAME is zeroed or replaced: pt_reset_frame, pt_write_frame, pt_next_image.  pt_render_adaptive always updates T;
+ * frames rendered by pt_render / pt_render_batch / pt_render_batch_async go into FRAME, and into the statistics only while moment
+ * recording is on (pt_record_moments, include/pt_guided.h).
  *
  * Selection, once per call before any frame is rendered; a pixel is active iff
  *   it is not under the mouse overlay, and not (max_frames > 0 && n >= max_frames), and

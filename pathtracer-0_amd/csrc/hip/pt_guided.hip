@@ -1,0 +1,173 @@
+// pt_guided.hip — the variance-guided filter of include/pt_guided.h (the spatial half of Schied et al. 2017) for gfx950.
+//
+// Device pointers only: pt_hip.hip owns the buffers (the a-trous filter's scratch, shared), computes the feature records, brings T into pixel
+// order and calls guidedLaunch on its stream.
+//   k_gd_prep    per pixel: the mean FRAME.rgb / FRAME.a (raw rgb when FRAME.a <= 0) and the guide (t, N), (Kd, class) packed into 32 B, the
+//                pixel's class (0 invalid, 1 hit, 2 miss) in the second record's w
+//   k_gd_var     per pixel: the variance of the mean v = s2 / FRAME.a into the colour record's w; s2 from the pixel's own moments, or pooled
+//                over its 7x7 window (same class, same material) when it has fewer than min_frames
+//   k_gd_pass    one pass of step 2^i, the 3x3 prefilter of v fused in: one pixel per lane, a wave = 64 pixels of a row, a block = 4 rows; the
+//                9 + 25 taps are served by L2 like k_dn_pass's (a tap row of a wave is 1 KiB of colour + 2 KiB of guide, contiguous)
+//   k_gd_finish  (filtered rgb, FRAME.a)
+// Not under the bit-exact contract of the render path: __expf, sqrtf, and the summation order is the tap loop's.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace {
+
+constexpr int GD_BX = 64, GD_BY = 4;
+
+__device__ __forceinline__ bool finite3(float a, float b, float c) { return __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c); }
+__device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+// max(x, 0) of the header: a NaN is no estimate
+__device__ __forceinline__ float clampVar(float x) { return x >= 0.0f ? x : (x < 0.0f ? 0.0f : __builtin_inff()); }
+
+__global__ void __launch_bounds__(256) k_gd_prep(const float4* frame, const float4* feat, int n, float4* col, float4* guide) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 F = frame[i], f0 = feat[4 * (size_t)i], f1 = feat[4 * (size_t)i + 1];
+    const float a = F.w;
+    const float mx = F.x / a, my = F.y / a, mz = F.z / a;
+    const bool valid = a > 0.0f && finite3(mx, my, mz) && __builtin_isfinite(f0.x) && finite3(f0.y, f0.z, f0.w) && finite3(f1.x, f1.y, f1.z);
+    const float cls = valid ? (__float_as_int(f1.w) >= 0 ? 1.0f : 2.0f) : 0.0f;
+    col[i] = a > 0.0f ? make_float4(mx, my, mz, 0.0f) : make_float4(F.x, F.y, F.z, 0.0f);
+    guide[2 * (size_t)i] = f0;
+    guide[2 * (size_t)i + 1] = make_float4(f1.x, f1.y, f1.z, cls);
+}
+
+__global__ void __launch_bounds__(GD_BX * GD_BY) k_gd_var(const float4* __restrict__ frame, const float4* __restrict__ feat, const float4* __restrict__ stats,
+                                                         const float4* __restrict__ guide, float4* __restrict__ col, int W, int H, float minFrames) {
+    const int x = blockIdx.x * GD_BX + threadIdx.x, y = blockIdx.y * GD_BY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    const float cls = guide[2 * p + 1].w;
+    if (cls == 0.0f) return;                                      // invalid: v is never read
+    const float4 T = stats[p];
+    float s2;
+    if (T.z >= minFrames) {
+        const float m = T.x / T.z;
+        s2 = clampVar((T.y - T.x * m) / (T.z - 1.0f));
+    } else {
+        const bool hit = cls == 1.0f;
+        const int mat = hit ? __float_as_int(feat[4 * p + 2].w) : 0;
+        float S = 0.0f, Q = 0.0f, N = 0.0f;
+        for (int dy = -3; dy <= 3; dy++) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= H) continue;
+            for (int dx = -3; dx <= 3; dx++) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= W) continue;
+                const size_t q = (size_t)yy * W + xx;
+                if (guide[2 * q + 1].w != cls) continue;
+                if (hit && __float_as_int(feat[4 * q + 2].w) != mat) continue;
+                const float4 Tq = stats[q];
+                if (!(Tq.z >= 1.0f)) continue;
+                S = S + Tq.x; Q = Q + Tq.y; N = N + Tq.z;
+            }
+        }
+        s2 = N >= 2.0f ? clampVar((Q - S * (S / N)) / (N - 1.0f)) : __builtin_inff();
+    }
+    reinterpret_cast<float*>(col + p)[3] = s2 / frame[p].w;
+}
+
+// inv = (1 / sn^2, 1 / sd^2, 1 / sa^2), each clamped to FLT_MAX; sigmaLum = +inf switches the luminance term off
+__global__ void __launch_bounds__(GD_BX * GD_BY) k_gd_pass(const float4* __restrict__ in, const float4* __restrict__ guide, float4* __restrict__ out, int W, int H,
+                                                          int step, float sigmaLum, float3 inv) {
+    const int x = blockIdx.x * GD_BX + threadIdx.x, y = blockIdx.y * GD_BY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    const float4 cp = in[p];
+    const float4 gp1 = guide[2 * p + 1];
+    const float cls = gp1.w;
+    if (cls == 0.0f) { out[p] = cp; return; }                     // invalid: passed through, weighs no neighbour
+    const bool hit = cls == 1.0f;
+    // g_p: the 3x3 binomial prefilter of v over p's valid neighbours of its class
+    const float k3[3] = {0.25f, 0.5f, 0.25f};
+    float gs = 0.0f, gw = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= H) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= W) continue;
+            const size_t q = (size_t)yy * W + xx;
+            if (guide[2 * q + 1].w != cls) continue;
+            const float k = k3[dy + 1] * k3[dx + 1];
+            gs += k * in[q].w; gw += k;
+        }
+    }
+    const float g = gs / gw;
+    const bool lumOn = __builtin_isfinite(sigmaLum) && g != __builtin_inff();
+    const float invDen = lumOn ? 1.0f / (sigmaLum * sqrtf(g) + 1e-10f) : 0.0f;
+    const float lp = lum(cp.x, cp.y, cp.z);
+    const float4 gp0 = hit ? guide[2 * p] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float invT = 1.0f / gp0.x;
+    const float h[5] = {1.0f / 16.0f, 4.0f / 16.0f, 6.0f / 16.0f, 4.0f / 16.0f, 1.0f / 16.0f};
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, sv = 0.0f;
+    bool vInf = false;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int yy = y + dy * step;
+        if (yy < 0 || yy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int xx = x + dx * step;
+            if (xx < 0 || xx >= W) continue;
+            const size_t q = (size_t)yy * W + xx;
+            const float4 g1 = guide[2 * q + 1];
+            if (g1.w != cls) continue;                            // invalid, or hit against miss
+            const float4 cq = in[q];
+            float e = lumOn ? __builtin_fabsf(lp - lum(cq.x, cq.y, cq.z)) * invDen : 0.0f;
+            if (hit) {
+                const float4 g0 = guide[2 * q];
+                const float nx = gp0.y - g0.y, ny = gp0.z - g0.z, nz = gp0.w - g0.w;
+                const float dt = (gp0.x - g0.x) * invT;
+                const float ar = gp1.x - g1.x, ag = gp1.y - g1.y, ab = gp1.z - g1.z;
+                e += (nx * nx + ny * ny + nz * nz) * inv.x + (dt * dt) * inv.y + (ar * ar + ag * ag + ab * ab) * inv.z;
+            }
+            const float w = (h[dy + 2] * h[dx + 2]) * __expf(-e);
+            if (w < 1e-30f) continue;                             // the header's cut: __expf's underflow is no part of the rule
+            sr += w * cq.x; sg += w * cq.y; sb += w * cq.z; sw += w;
+            if (cq.w == __builtin_inff()) vInf = true;
+            else sv += (w * w) * cq.w;
+        }
+    }
+    out[p] = make_float4(sr / sw, sg / sw, sb / sw, vInf ? __builtin_inff() : sv / (sw * sw));
+}
+
+__global__ void __launch_bounds__(256) k_gd_finish(const float4* col, const float4* frame, int n, float4* out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 c = col[i];
+    out[i] = make_float4(c.x, c.y, c.z, frame[i].w);
+}
+
+float clampInv(float v) { return v > 3.402823466e38f ? 3.402823466e38f : v; }
+
+}  // namespace
+
+// frame, stats: W*H float4 (FRAME and T in pixel order), feat: W*H*4 float4 (all read only); col0, col1: W*H float4 ping-pong; guide: 2*W*H float4;
+// out: W*H float4.  sigma = (luminance, normal, depth, albedo) and minFrames already checked by the caller.  Enqueued on `s`; returns the first
+// launch error.
+hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                        float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s) {
+    const int n = W * H;
+    const dim3 lin((unsigned)((n + 255) / 256));
+    const dim3 grid((unsigned)((W + GD_BX - 1) / GD_BX), (unsigned)((H + GD_BY - 1) / GD_BY));
+    hipLaunchKernelGGL(k_gd_prep, lin, dim3(256), 0, s, frame, feat, n, col0, guide);
+    float4* src = col0;
+    float4* dst = col1;
+    if (iterations > 0) {
+        hipLaunchKernelGGL(k_gd_var, grid, dim3(GD_BX, GD_BY), 0, s, frame, feat, stats, guide, col0, W, H, (float)minFrames);
+        const float3 inv = make_float3(clampInv(1.0f / (sigma[1] * sigma[1])), clampInv(1.0f / (sigma[2] * sigma[2])), clampInv(1.0f / (sigma[3] * sigma[3])));
+        for (int i = 0; i < iterations; i++) {
+            hipLaunchKernelGGL(k_gd_pass, grid, dim3(GD_BX, GD_BY), 0, s, src, guide, dst, W, H, 1 << i, sigma[0], inv);
+            float4* t = src; src = dst; dst = t;
+        }
+    }
+    hipLaunchKernelGGL(k_gd_finish, lin, dim3(256), 0, s, src, frame, n, out);
+    return hipGetLastError();
+}

@@ -28,6 +28,7 @@
 #include "../../../include/pt_adaptive.h"
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_reproject.h"
+#include "../../../include/pt_guided.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -763,6 +764,27 @@ __global__ void __launch_bounds__(BLOCK) k_accumulate(Batch b, const FrameConst*
     frame[ls] = F;
 }
 
+// k_accumulate with the luminance moments of include/pt_guided.h: the same slots, overlay and FRAME arithmetic, and T += (Y, Y*Y, 1, 0) per frame in
+// u_frameCount order (k_accumulate_adaptive's update), restarted with FRAME by a frame numbered 1
+__global__ void __launch_bounds__(BLOCK) k_accumulate_moments(Batch b, const FrameConst* fcp, float4* frame, float4* stats, unsigned f0, int nFrames, int firstFrame) {
+    unsigned ls = blockIdx.x * BLOCK + threadIdx.x;
+    if (ls >= (unsigned)b.nSlots) return;
+    int gp;
+    if (b.shardCount == 1) gp = (int)ls;
+    else { if (ls >= (unsigned)b.nLocal) return; gp = b.pixList[ls]; }
+    const FrameConst& fc = *fcp;
+    if (inMouseOverlay(fc, gp % b.W, gp / b.W)) return;
+    float4 F = frame[ls], T = stats[ls];
+    for (int f = 0; f < nFrames; f++) {
+        float4 c = ldS(b.colbuf + (size_t)((f0 + (unsigned)f) % b.ringFrames) * b.nSlots + ls);
+        const float Y = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+        if ((float)(firstFrame + f) == 1.0f) { F = make_float4(c.x, c.y, c.z, 1.0f); T = make_float4(Y, Y * Y, 1.0f, 0.0f); }
+        else { F = make_float4(F.x + c.x, F.y + c.y, F.z + c.z, F.w + 1.0f); T = make_float4(T.x + Y, T.y + Y * Y, T.z + 1.0f, 0.0f); }
+    }
+    frame[ls] = F;
+    stats[ls] = T;
+}
+
 // DEBUG != 0 (frag.glsl:916-918): the traversal heat-map of debugRayScene (:539-547) — no random numbers, no samples.  One thread per
 // local pixel; every BVH is traversed on its own from closest_t = 1e30 with the un-offset ORIGIN and the un-normalised primary
 // direction (exactly the thickness probe's rayBVH call), and rayBVH's .col (:534) is rebuilt from the traversal counters:
@@ -1121,6 +1143,7 @@ struct pt_ctx {
     // while adaptOn the running frame stream's pixel list is the active list (streamBatch), its nLocal adaptN
     float4* dStats = nullptr; unsigned char* dAdaptFlag = nullptr; unsigned* dAdaptBlk = nullptr; unsigned* dAdaptXY = nullptr; int* dAdaptSlot = nullptr;
     unsigned* hAdaptCount = nullptr; bool adaptOn = false; int adaptN = 0;
+    bool recordMoments = false;     // include/pt_guided.h: the frames of pt_render* also go into T (k_accumulate_moments) when they land in the current image
     // first-hit feature records (include/pt_denoise.h): W*H x 4 float4, valid until the next pt_set_buffer / pt_set_texture; the denoiser's ping-pong
     // colour buffers, its packed guide (2 float4 per pixel) and its output, all allocated on first use
     float4* dFeat = nullptr; bool featValid = false;
@@ -1132,7 +1155,8 @@ struct pt_ctx {
     uint64_t sceneGen = 0;
     float4* dFeatH = nullptr; bool featHValid = false; FrameIn featHIn{};
     unsigned char* dMatVD = nullptr;
-    float4* dRpFrame = nullptr; float4* dRpStats = nullptr; float4* dRpStatsIn = nullptr; unsigned* dRpKept = nullptr;
+    float4* dRpFrame = nullptr; float4* dRpStats = nullptr; unsigned* dRpKept = nullptr;
+    float4* dStatsWhole = nullptr;  // a group's T gathered in pixel order on its first stream (reprojection, the guided filter)
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -1724,7 +1748,8 @@ int retireFront(pt_ctx* c) {
         return 0;
     }
     int gridA = (c->nSlotsImg + BLOCK - 1) / BLOCK;
-    TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], e.f0, e.nFrames, e.firstFrame));
+    if (c->recordMoments && e.image == c->curImage) TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_moments, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
+    else TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], e.f0, e.nFrames, e.firstFrame));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2153,6 +2178,9 @@ hipError_t denoiseLaunch(const float4* frame, const float4* feat, int W, int H, 
 hipError_t reprojectLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
                            int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float4* outFrame, float4* outStats,
                            unsigned* kept, hipStream_t s);
+// the variance-guided filter of include/pt_guided.h (pt_guided.hip): device pointers only, enqueued on `s`
+hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                        float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s);
 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
@@ -2292,7 +2320,7 @@ int pt_destroy(pt_ctx* c) {
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
                     c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
-                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dRpStatsIn, c->dRpKept};
+                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -2476,11 +2504,16 @@ int pt_write_frame(pt_ctx* c, const float* in) {
 }
 
 namespace {
+// false for a context that holds only a part of the image (a single shard, a pt_create_multi_part group)
+bool holdsWholeImage(const pt_ctx* c) { return c->multi ? c->multi->shardTotal == c->multi->n : c->shardCount == 1; }
+int needWholeImage(const pt_ctx* c, int code, const char* who) {
+    return holdsWholeImage(c) ? 0 : fail(code, std::string(who) + " needs the whole image: this context holds a part of it (use a pt_create_multi context)");
+}
+
 // The context's whole FRAME image, complete and ordered on the stream of *on, whose device is made current: a group gathers it on its first stream's
-// context.  A context that holds only a part of the image (a single shard, a pt_create_multi_part group) fails with `code`.
+// context.  A context that holds only a part of the image fails with `code`.
 int wholeFrame(pt_ctx* c, int code, const char* who, pt_ctx** on, const float4** frame) {
-    if (c->multi ? c->multi->shardTotal != c->multi->n : c->shardCount != 1)
-        return fail(code, std::string(who) + " needs the whole image: this context holds a part of it (use a pt_create_multi context)");
+    if (int rc = needWholeImage(c, code, who)) return rc;
     *on = firstStream(c);
     if (!c->multi) {
         HIP_TRY(hipSetDevice(c->device));
@@ -2934,6 +2967,75 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
     return PT_OK;
 }
 
+// ---- T in pixel order (include/pt_adaptive.h, include/pt_guided.h): a group's streams each hold the slots of their own shard, so T travels through the host
+namespace {
+// T of the whole image into host[W*H*4], pixel order: zeros where no stream holds T; *any = some stream does.  Work in flight is the caller's to complete.
+int statsToHost(pt_ctx* c, float* host, bool* any) {
+    std::fill(host, host + (size_t)c->W * c->H * 4, 0.0f);
+    *any = false;
+    const std::vector<pt_ctx*> kids = c->multi ? c->multi->kids : std::vector<pt_ctx*>{c};
+    for (pt_ctx* k : kids) {
+        if (!k->dStats) continue;
+        *any = true;
+        HIP_TRY(hipSetDevice(k->device));
+        if (int rc = shardToHost(k, k->dStats, host)) return rc;
+    }
+    return 0;
+}
+// The whole image's T in pixel order on the device of `on` (firstStream(c)), or nullptr when no stream holds T: a single context's own T; a group's
+// gathered through the host into on->dStatsWhole.  Work in flight is the caller's to complete.
+int wholeStats(pt_ctx* c, pt_ctx* on, const float4** stats) {
+    *stats = c->multi ? nullptr : c->dStats;
+    if (!c->multi) return 0;
+    const size_t n = (size_t)c->W * c->H;
+    std::vector<float> host(n * 4);
+    bool any = false;
+    if (int rc = statsToHost(c, host.data(), &any)) return rc;
+    if (!any) return 0;
+    HIP_TRY(hipSetDevice(on->device));
+    if (!on->dStatsWhole) HIP_TRY(hipMalloc((void**)&on->dStatsWhole, n * 16));
+    HIP_TRY(hipMemcpyAsync(on->dStatsWhole, host.data(), n * 16, hipMemcpyHostToDevice, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    *stats = on->dStatsWhole;
+    return 0;
+}
+int writeMoments(pt_ctx* c, const float* in) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = flushStream(c)) return rc;
+    if (!c->dStats) HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
+    return hostToShard(c, in, c->dStats);
+}
+}  // namespace
+
+int pt_record_moments(pt_ctx* c, int on) {
+    if (!c) return fail(PT_ERR_ARG, "pt_record_moments: null context");
+    MULTI_ALL(c, pt_record_moments(k, on));
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = flushStream(c)) return rc;                       // batches in flight retire under the previous setting
+    if (on && !c->dStats) {
+        HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
+        HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
+    }
+    c->recordMoments = on != 0;
+    return PT_OK;
+}
+
+int pt_read_moments(pt_ctx* c, float* out) {
+    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_moments: null argument");
+    int rc;
+    if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_read_moments"))) return rc;
+    if ((rc = pt_synchronize(c))) return rc;
+    bool any = false;
+    return statsToHost(c, out, &any);
+}
+
+int pt_write_moments(pt_ctx* c, const float* in) {
+    if (!c || !in) return fail(PT_ERR_ARG, "pt_write_moments: null argument");
+    if (int rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_write_moments")) return rc;
+    MULTI_ALL(c, writeMoments(k, in));                            // every stream takes the pixels of its own tile shard
+    return writeMoments(c, in);
+}
+
 // ---- first-hit feature records and the denoised image (include/pt_denoise.h).  A group context works on its first stream's context: the scene is replicated.
 namespace {
 // the feature records of the frame inputs `fin` into *buf (W*H x 4 float4, allocated on first use); *valid says they are there
@@ -3017,6 +3119,48 @@ int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float
     return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
 }
 
+// ---- the variance-guided filter (include/pt_guided.h): pt_denoise's plumbing and scratch, with T in pixel order beside FRAME
+namespace {
+int guidedImage(pt_ctx* c, int iterations, const float sigma[4], int minFrames, pt_ctx** onOut) {
+    if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise_guided: iterations must be in [0,8]");
+    if (minFrames < 2) return fail(PT_ERR_ARG, "pt_denoise_guided: min_frames must be >= 2");
+    for (int k = 0; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, "pt_denoise_guided: every sigma must be > 0 (+inf switches its term off)");
+    pt_ctx* on = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
+    int rc;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise_guided", &on, &frame))) return rc;
+    if ((rc = wholeStats(c, on, &stats))) return rc;
+    if (!stats) return fail(PT_ERR_ARG, "pt_denoise_guided: the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
+    if ((rc = ensureFeatures(on))) return rc;
+    const size_t n = (size_t)c->W * c->H;
+    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
+    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
+    HIP_TRY(guidedLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
+    *onOut = on;
+    return 0;
+}
+}  // namespace
+
+int pt_denoise_guided(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames, float* rgba_out) {
+    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided: null argument");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = guidedImage(c, iterations, sigma, min_frames, &on))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    return PT_OK;
+}
+
+int pt_read_display_denoised_guided(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
+                                    int java_bytes, uint8_t* rgb_out) {
+    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided: null argument");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = guidedImage(c, iterations, sigma, min_frames, &on))) return rc;
+    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
+}
+
 // ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
 // every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
 namespace {
@@ -3054,25 +3198,8 @@ int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol,
     if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
     if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
     // the image's T in pixel order, when allocated (group: through the host)
-    const float4* stats = c->multi ? nullptr : c->dStats;
-    std::vector<float> hostStats;
-    if (c->multi) {
-        const MultiCtx& M = *c->multi;
-        bool anyStats = false;
-        for (pt_ctx* k : M.kids) anyStats = anyStats || k->dStats;
-        if (anyStats) {
-            hostStats.assign(n * 4, 0.0f);
-            for (pt_ctx* k : M.kids) {
-                if (!k->dStats) continue;
-                HIP_TRY(hipSetDevice(k->device));
-                if ((rc = shardToHost(k, k->dStats, hostStats.data()))) return rc;
-            }
-            HIP_TRY(hipSetDevice(on->device));
-            if (!on->dRpStatsIn) HIP_TRY(hipMalloc((void**)&on->dRpStatsIn, n * 16));
-            HIP_TRY(hipMemcpyAsync(on->dRpStatsIn, hostStats.data(), n * 16, hipMemcpyHostToDevice, on->stream));
-            stats = on->dRpStatsIn;
-        }
-    }
+    const float4* stats = nullptr;
+    if ((rc = wholeStats(c, on, &stats))) return rc;
     if (stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
     // the image's camera as k_frame_setup builds it (camRot), in the frame constants, which are no stream's afterwards
     *on->hFrameIn = h.in;
@@ -3091,7 +3218,7 @@ int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol,
         HIP_TRY(hipStreamSynchronize(c->stream));
         recordCamera(c);
     } else {
-        std::vector<float> hf(n * 4);
+        std::vector<float> hf(n * 4), hostStats(stats ? n * 4 : 0);
         HIP_TRY(hipMemcpyAsync(hf.data(), on->dRpFrame, n * 16, hipMemcpyDeviceToHost, on->stream));
         if (stats) HIP_TRY(hipMemcpyAsync(hostStats.data(), on->dRpStats, n * 16, hipMemcpyDeviceToHost, on->stream));
         HIP_TRY(hipStreamSynchronize(on->stream));

@@ -123,6 +123,13 @@ def lib():
             L.pt_read_display_denoised.argtypes = [vp, ci, cf, cf, cf, cf, ci, vp]
         if hasattr(L, "pt_reproject_frame"):                  # include/pt_reproject.h
             L.pt_reproject_frame.argtypes = [vp, C.c_float, C.c_float, C.c_float, ci, C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_denoise_guided"):                   # include/pt_guided.h
+            cf = C.c_float
+            L.pt_record_moments.argtypes = [vp, ci]
+            L.pt_read_moments.argtypes = [vp, vp]
+            L.pt_write_moments.argtypes = [vp, vp]
+            L.pt_denoise_guided.argtypes = [vp, ci, cf, cf, cf, cf, ci, vp]
+            L.pt_read_display_denoised_guided.argtypes = [vp, ci, cf, cf, cf, cf, ci, ci, vp]
         _LIB = L
     return _LIB
 
@@ -329,6 +336,49 @@ class Renderer:
         _check(self._L.pt_reproject_frame(self._h, float(max_history), float(depth_tol), float(normal_tol),
                                           self.REPROJECT_ALL_MATERIALS if all_materials else 0, C.byref(n)))
         return n.value
+
+    # --- luminance moments and the variance-guided filter (include/pt_guided.h) ---------------------
+    # defaults of denoise_guided / read_display_denoised_guided: sigma_lum and min_frames from scripts/guided_quality.py's grid on C3 and C6
+    # at 1080p (profiles/r11_guided_quality.txt); the geometric sigmas are DENOISE_SIGMAS'
+    GUIDED_SIGMA_LUM = 2.0
+    GUIDED_MIN_FRAMES = 4
+
+    def record_moments(self, on=True):
+        """Record T = (sY, sYY, n, 0), the per-pixel luminance moments, for every frame rendered from now on (pt_record_moments)"""
+        _check(self._L.pt_record_moments(self._h, 1 if on else 0))
+
+    def read_moments(self):
+        """T of the current image (pt_read_moments): (H, W, 4) float32 (sY, sYY, n, 0), FRAME order; zeros when never recorded"""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        _check(self._L.pt_read_moments(self._h, out.ctypes.data))
+        return out
+
+    def write_moments(self, moments):
+        """replace T of the current image (pt_write_moments); pt_write_frame zeroes T, so restore FRAME first"""
+        m = np.ascontiguousarray(moments, dtype=np.float32)
+        assert m.size == self.W * self.H * 4
+        _check(self._L.pt_write_moments(self._h, m.ctypes.data))
+
+    def _guided_args(self, sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames):
+        g = self._sigmas(None, sigma_normal, sigma_depth, sigma_albedo)
+        g[0] = float(self.GUIDED_SIGMA_LUM if sigma_lum is None else sigma_lum)
+        return g + [int(self.GUIDED_MIN_FRAMES if min_frames is None else min_frames)]
+
+    def denoise_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None):
+        """the variance-guided filter over FRAME.rgb / FRAME.a, steered by T (pt_denoise_guided): (H, W, 4) float32, rgb = filtered mean,
+        a = FRAME.a.  Needs moments (record_moments before rendering, or write_moments).  None takes the defaults above."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        _check(self._L.pt_denoise_guided(self._h, int(iterations), *self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames),
+                                         out.ctypes.data))
+        return out
+
+    def read_display_denoised_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None,
+                                     java_bytes=True):
+        """denoise_guided()'s image converted to 8 bits as read_display converts a mean: (H, W, 3) uint8, top row first"""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        _check(self._L.pt_read_display_denoised_guided(self._h, int(iterations), *self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames),
+                                                       1 if java_bytes else 0, out.ctypes.data))
+        return out
 
     def screenshot(self, path, frame_count, java_bytes=True):
         """functions.screenshot(fileName) (dispatch.java:804-851): the display image as a PNG file, written by the library (pt_save_png)"""
