@@ -9,10 +9,14 @@
 //   k_gd_pass    one pass of step 2^i, the 3x3 prefilter of v fused in: one pixel per lane, a wave = 64 pixels of a row, a block = 4 rows; the
 //                9 + 25 taps are served by L2 like k_dn_pass's (a tap row of a wave is 1 KiB of colour + 2 KiB of guide, contiguous)
 //   k_gd_finish  (filtered rgb, FRAME.a)
+//   k_gd_select  include/pt_steer.h's rule over the final (c_K, v_K), T and the class: one flag byte per pixel, the active pixels counted with a
+//                ballot popcount per wave, summed in LDS, one global atomic per block (pt_reproject.hip's k_reproject counts its kept pixels so)
 // Not under the bit-exact contract of the render path: __expf, sqrtf, and the summation order is the tap loop's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "pt_device.hpp"
 
 namespace {
 
@@ -145,6 +149,47 @@ __global__ void __launch_bounds__(256) k_gd_finish(const float4* col, const floa
     out[i] = make_float4(c.x, c.y, c.z, frame[i].w);
 }
 
+// steps 1-5 of include/pt_steer.h.  cv: (c_K, v_K) per pixel; guide: k_gd_prep's (the class in the second record's w); mask: W*H bytes;
+// count: zeroed by the caller.  rule = (rel_err, abs_err), ov = (mouse x, mouse y, resolution) of the overlay test.
+__global__ void __launch_bounds__(GD_BX * GD_BY) k_gd_select(const float4* __restrict__ cv, const float4* __restrict__ stats, const float4* __restrict__ guide,
+                                                            int W, int H, float minFrames, int maxFrames, float2 rule, float3 ov,
+                                                            unsigned char* __restrict__ mask, unsigned* __restrict__ count) {
+    __shared__ unsigned sCnt[GD_BY];
+    const int x = blockIdx.x * GD_BX + threadIdx.x, y = blockIdx.y * GD_BY + threadIdx.y;
+    bool on = false;
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * W + x;
+        ptd::FrameConst fc{};
+        fc.mouse[0] = ov.x; fc.mouse[1] = ov.y; fc.resolution = ov.z;
+        const float4 T = stats[p];
+        const float n = T.z;
+        if (ptd::inMouseOverlay(fc, x, y)) on = false;                                     // 1
+        else if (maxFrames > 0 && n >= (float)maxFrames) on = false;                       // 2
+        else if (n < minFrames) on = true;                                                 // 3
+        else if (guide[2 * p + 1].w == 0.0f) {                                             // 4: invalid, the own-moment rule of include/pt_adaptive.h
+            const float mean = T.x / n;
+            const float var = (T.y - T.x * mean) / (n - 1.0f);
+            const float err2 = var / n;
+            const float tol = fmaxf(rule.x * fabsf(mean), rule.y);
+            on = err2 > tol * tol;
+        } else {                                                                           // 5: the filtered mean and its carried variance
+            const float4 c = cv[p];
+            const float tol = fmaxf(rule.x * fabsf(lum(c.x, c.y, c.z)), rule.y);
+            on = c.w == __builtin_inff() || c.w > tol * tol;
+        }
+        mask[p] = on ? 1 : 0;
+    }
+    const unsigned long long b = __ballot(on);
+    if (threadIdx.x == 0) sCnt[threadIdx.y] = (unsigned)__popcll(b);                      // a wave is one row of the block
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < GD_BY; w++) t += sCnt[w];
+        if (t) atomicAdd(count, t);
+    }
+}
+
 float clampInv(float v) { return v > 3.402823466e38f ? 3.402823466e38f : v; }
 
 }  // namespace
@@ -169,5 +214,30 @@ hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* s
         }
     }
     hipLaunchKernelGGL(k_gd_finish, lin, dim3(256), 0, s, src, frame, n, out);
+    return hipGetLastError();
+}
+
+// include/pt_steer.h's selection: k_gd_prep, k_gd_var (always, K = 0 included), K passes, k_gd_select into mask[W*H] and *count (zeroed here).
+// Arguments as guidedLaunch's; rule = (rel_err, abs_err), ov = (mouse x, mouse y, resolution), all checked by the caller.  Enqueued on `s`;
+// returns the first launch error.
+hipError_t guidedSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                              int maxFrames, const float rule[2], const float ov[3], float4* col0, float4* col1, float4* guide, unsigned char* mask,
+                              unsigned* count, hipStream_t s) {
+    const int n = W * H;
+    const dim3 lin((unsigned)((n + 255) / 256));
+    const dim3 grid((unsigned)((W + GD_BX - 1) / GD_BX), (unsigned)((H + GD_BY - 1) / GD_BY));
+    hipError_t e = hipMemsetAsync(count, 0, 4, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gd_prep, lin, dim3(256), 0, s, frame, feat, n, col0, guide);
+    hipLaunchKernelGGL(k_gd_var, grid, dim3(GD_BX, GD_BY), 0, s, frame, feat, stats, guide, col0, W, H, (float)minFrames);
+    const float3 inv = make_float3(clampInv(1.0f / (sigma[1] * sigma[1])), clampInv(1.0f / (sigma[2] * sigma[2])), clampInv(1.0f / (sigma[3] * sigma[3])));
+    float4* src = col0;
+    float4* dst = col1;
+    for (int i = 0; i < iterations; i++) {
+        hipLaunchKernelGGL(k_gd_pass, grid, dim3(GD_BX, GD_BY), 0, s, src, guide, dst, W, H, 1 << i, sigma[0], inv);
+        float4* t = src; src = dst; dst = t;
+    }
+    hipLaunchKernelGGL(k_gd_select, grid, dim3(GD_BX, GD_BY), 0, s, src, stats, guide, W, H, (float)minFrames, maxFrames, make_float2(rule[0], rule[1]),
+                       make_float3(ov[0], ov[1], ov[2]), mask, count);
     return hipGetLastError();
 }

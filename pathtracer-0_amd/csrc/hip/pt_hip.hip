@@ -29,6 +29,7 @@
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_reproject.h"
 #include "../../../include/pt_guided.h"
+#include "../../../include/pt_steer.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -952,6 +953,31 @@ __global__ void __launch_bounds__(BLOCK) k_adaptive_select(const unsigned* pixXY
         blkCount[blockIdx.x] = t;
     }
 }
+// k_adaptive_select's output contract for a given selection (include/pt_steer.h, pt_render_mask): entry k of the job-order list is active iff
+// mask[py*W + px] != 0 (the whole image's W*H bytes, FRAME order) and it is not under the overlay (r's mouse fields; the rule fields unused)
+__global__ void __launch_bounds__(BLOCK) k_adaptive_select_mask(const unsigned* pixXY, int nLocal, int W, const unsigned char* mask, AdaptRule r,
+                                                                unsigned char* flag, unsigned* blkCount) {
+    __shared__ unsigned sCnt[BLOCK / 64];
+    const unsigned k = blockIdx.x * BLOCK + threadIdx.x;
+    bool on = false;
+    if (k < (unsigned)nLocal) {
+        const unsigned xy = pixXY[k];
+        const int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
+        FrameConst fc{};
+        fc.mouse[0] = r.mouseX; fc.mouse[1] = r.mouseY; fc.resolution = r.resolution;
+        on = mask[(size_t)py * W + px] != 0 && !inMouseOverlay(fc, px, py);
+        flag[k] = on ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(on);
+    if ((threadIdx.x & 63) == 0) sCnt[threadIdx.x >> 6] = (unsigned)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; w++) t += sCnt[w];
+        blkCount[blockIdx.x] = t;
+    }
+}
 // one block of BLOCK threads: blk[0..nb) counts -> exclusive offsets in place, *total = their sum
 __global__ void __launch_bounds__(BLOCK) k_adaptive_scan(unsigned* blk, int nb, unsigned* total) {
     __shared__ unsigned sv[BLOCK];
@@ -1143,6 +1169,8 @@ struct pt_ctx {
     // while adaptOn the running frame stream's pixel list is the active list (streamBatch), its nLocal adaptN
     float4* dStats = nullptr; unsigned char* dAdaptFlag = nullptr; unsigned* dAdaptBlk = nullptr; unsigned* dAdaptXY = nullptr; int* dAdaptSlot = nullptr;
     unsigned* hAdaptCount = nullptr; bool adaptOn = false; int adaptN = 0;
+    // include/pt_steer.h: the whole image's selection mask (W*H bytes, pixel order), then, 4-byte aligned, k_gd_select's active count
+    unsigned char* dSelMask = nullptr;
     bool recordMoments = false;     // include/pt_guided.h: the frames of pt_render* also go into T (k_accumulate_moments) when they land in the current image
     // first-hit feature records (include/pt_denoise.h): W*H x 4 float4, valid until the next pt_set_buffer / pt_set_texture; the denoiser's ping-pong
     // colour buffers, its packed guide (2 float4 per pixel) and its output, all allocated on first use
@@ -2181,6 +2209,10 @@ hipError_t reprojectLaunch(const float4* rn, const float4* rh, const float4* fra
 // the variance-guided filter of include/pt_guided.h (pt_guided.hip): device pointers only, enqueued on `s`
 hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
                         float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s);
+// ... and include/pt_steer.h's selection over it (pt_guided.hip)
+hipError_t guidedSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                              int maxFrames, const float rule[2], const float ov[3], float4* col0, float4* col1, float4* guide, unsigned char* mask,
+                              unsigned* count, hipStream_t s);
 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
@@ -2320,7 +2352,7 @@ int pt_destroy(pt_ctx* c) {
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
                     c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
-                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept};
+                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -2558,10 +2590,15 @@ int pt_read_display_mean(pt_ctx* c, int java_bytes, uint8_t* rgb_out) {
 
 // ---- adaptive sampling (include/pt_adaptive.h): select the still-noisy pixels of each stream's shard, then ONE frame stream over their compacted list
 namespace {
-int renderAdaptive(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const AdaptRule& r, int64_t* nActive) {
+// The frame stream over a selection of the stream's job-order list, shared by pt_render_adaptive and include/pt_steer.h's calls.  `select` enqueues
+// the kernel that writes c->dAdaptFlag (one byte per list entry) and c->dAdaptBlk[0..nb) (per-block counts) on stream s, or returns an error; T is
+// allocated zeroed before it runs.  Then scan, compact, read the count back (*nActive) and, if it is nonzero, submit the batch under the list
+// override, which is cleared on every path.
+int renderSelected(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const char* who, const std::function<int(hipStream_t, int)>& select,
+                   int64_t* nActive) {
     HIP_TRY(hipSetDevice(c->device));
     if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_render_adaptive: DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
+    if (c->params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
     int rc;
     if ((rc = flushStream(c))) return rc;                         // batches in flight land in FRAME, not in the statistics
     hipStream_t s = c->stream;
@@ -2577,10 +2614,7 @@ int renderAdaptive(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds,
         HIP_TRY(hipHostMalloc((void**)&c->hAdaptCount, 4, hipHostMallocDefault));
         HIP_TRY(hipMalloc((void**)&c->dAdaptXY, (size_t)c->nLocal * 4));      // (last: its presence says the others exist)
     }
-    AdaptRule rr = r;
-    if (c->mouse.size() >= 2) { rr.mouseX = c->mouse[0]; rr.mouseY = c->mouse[1]; }
-    rr.resolution = c->params[2];
-    hipLaunchKernelGGL(k_adaptive_select, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, c->shardCount, (const float4*)c->dStats, rr, c->dAdaptFlag, c->dAdaptBlk);
+    if ((rc = select(s, nb))) return rc;
     hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(BLOCK), 0, s, c->dAdaptBlk, nb, c->dAdaptBlk + nb);
     hipLaunchKernelGGL(k_adaptive_compact, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, (const unsigned char*)c->dAdaptFlag, (const unsigned*)c->dAdaptBlk,
                        c->dAdaptXY, c->shardCount > 1 ? c->dAdaptSlot : nullptr);
@@ -2588,7 +2622,7 @@ int renderAdaptive(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds,
     HIP_TRY(hipMemcpyAsync(c->hAdaptCount, c->dAdaptBlk + nb, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const unsigned n = *c->hAdaptCount;
-    if (n > (unsigned)c->nLocal) return fail(PT_ERR_HIP, "pt_render_adaptive: active count beyond the pixel list (internal error)");
+    if (n > (unsigned)c->nLocal) return fail(PT_ERR_HIP, std::string(who) + ": active count beyond the pixel list (internal error)");
     *nActive = n;
     if (n == 0) return PT_OK;
     // a new frame stream on the active list (the pending queue is empty, so submitBatch cannot join the last stream); it ends with the batch, so the
@@ -2597,6 +2631,40 @@ int renderAdaptive(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds,
     rc = submitBatch(c, firstFrame, nFrames, seeds, false);
     if (rc) c->pending.clear();                                   // a failed stream must not be retired later with the full list
     c->adaptOn = false; c->adaptN = 0;
+    return rc;
+}
+// the overlay fields of the selection kernels: the context's current MOUSE_POS and resolution (Parameters are checked by renderSelected first)
+AdaptRule withOverlay(const pt_ctx* c, AdaptRule r) {
+    if (c->mouse.size() >= 2) { r.mouseX = c->mouse[0]; r.mouseY = c->mouse[1]; }
+    r.resolution = c->params.size() >= 12 ? c->params[2] : 0.0f;
+    return r;
+}
+int renderAdaptive(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const AdaptRule& r, int64_t* nActive) {
+    return renderSelected(c, firstFrame, nFrames, seeds, "pt_render_adaptive", [c, &r](hipStream_t s, int nb) {
+        hipLaunchKernelGGL(k_adaptive_select, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, c->shardCount, (const float4*)c->dStats,
+                           withOverlay(c, r), c->dAdaptFlag, c->dAdaptBlk);
+        return 0;
+    }, nActive);
+}
+// fn on every stream of the context (a group: each on its own host thread, no collective), their counts summed into *nActive (may be NULL)
+int onEveryStream(pt_ctx* c, const std::function<int(pt_ctx*, int64_t*)>& fn, int64_t* nActive) {
+    if (nActive) *nActive = 0;
+    if (c->multi) {
+        MultiCtx& M = *c->multi;
+        if (!M.staleBindings.empty()) return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
+        std::vector<int64_t> counts((size_t)M.n, 0);
+        int64_t* cp = counts.data();
+        const std::vector<pt_ctx*>& kids = M.kids;
+        const int rc = multiRun(M, [&fn, cp, &kids](pt_ctx* k) {
+            const size_t i = (size_t)(std::find(kids.begin(), kids.end(), k) - kids.begin());
+            return fn(k, cp + i);
+        });
+        if (nActive) for (int64_t v : counts) *nActive += v;
+        return rc;
+    }
+    int64_t n = 0;
+    const int rc = fn(c, &n);
+    if (nActive) *nActive = n;
     return rc;
 }
 }  // namespace
@@ -2609,24 +2677,7 @@ int pt_render_adaptive(pt_ctx* c, int first_frame, int n_frames, const int32_t* 
     if (!(rel_err >= 0.0f) || !(abs_err >= 0.0f)) return fail(PT_ERR_ARG, "pt_render_adaptive: rel_err and abs_err must be >= 0 and not NaN");
     AdaptRule r{};
     r.relErr = rel_err; r.absErr = abs_err; r.minFrames = min_frames; r.maxFrames = max_frames;
-    if (n_active) *n_active = 0;
-    if (c->multi) {                                               // every stream selects within its own shard: no collective
-        MultiCtx& M = *c->multi;
-        if (!M.staleBindings.empty()) return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
-        std::vector<int64_t> counts((size_t)M.n, 0);
-        int64_t* cp = counts.data();
-        const std::vector<pt_ctx*>& kids = M.kids;
-        const int rc = multiRun(M, [=, &kids](pt_ctx* k) {
-            const size_t i = (size_t)(std::find(kids.begin(), kids.end(), k) - kids.begin());
-            return renderAdaptive(k, first_frame, n_frames, seeds, r, cp + i);
-        });
-        if (n_active) for (int64_t v : counts) *n_active += v;
-        return rc;
-    }
-    int64_t n = 0;
-    const int rc = renderAdaptive(c, first_frame, n_frames, seeds, r, &n);
-    if (n_active) *n_active = n;
-    return rc;
+    return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderAdaptive(k, first_frame, n_frames, seeds, r, n); }, n_active);   // every stream selects within its own shard
 }
 
 namespace {
@@ -3237,6 +3288,111 @@ int pt_reproject_frame(pt_ctx* c, float max_history, float depth_tol, float norm
     const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, &n);
     if (n_kept) *n_kept = n;
     return rc;
+}
+
+
+// ---- adaptive sampling steered by the guided filter (include/pt_steer.h).  The selection needs the whole image (the filter's plumbing: wholeFrame,
+// wholeStats, ensureFeatures on the first stream's context); the render takes each stream's own pixels from the W*H-byte mask.
+namespace {
+size_t maskBytes(const pt_ctx* c) { return ((size_t)c->W * c->H + 3) & ~(size_t)3; }      // the active count follows, 4-byte aligned
+
+int checkRule(const pt_guided_rule& r, const char* who) {
+    const std::string w(who);
+    if (r.iterations < 0 || r.iterations > 8) return fail(PT_ERR_ARG, w + ": rule.iterations must be in [0,8]");
+    for (float v : {r.sigma_lum, r.sigma_normal, r.sigma_depth, r.sigma_albedo})
+        if (!(v > 0.0f)) return fail(PT_ERR_ARG, w + ": every sigma of the rule must be > 0 (+inf switches its term off)");
+    if (r.min_frames < 2) return fail(PT_ERR_ARG, w + ": rule.min_frames must be >= 2");
+    if (!(r.rel_err >= 0.0f) || !(r.abs_err >= 0.0f)) return fail(PT_ERR_ARG, w + ": rule.rel_err and rule.abs_err must be >= 0 and not NaN");
+    if (r.max_frames < 0) return fail(PT_ERR_ARG, w + ": rule.max_frames must be >= 0 (0 = no cap)");
+    return 0;
+}
+
+// The rule over the context's current image into (*onOut)->dSelMask (W*H bytes, pixel order, on the device of firstStream(c)); *nActive = its count.
+// FRAME and T are not modified; T never allocated reads as zeros (the filter's scratch output, zeroed).
+int selectGuided(pt_ctx* c, const pt_guided_rule& r, const char* who, pt_ctx** onOut, int64_t* nActive) {
+    pt_ctx* on = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
+    int rc;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &frame))) return rc;
+    if ((rc = wholeStats(c, on, &stats))) return rc;
+    if ((rc = ensureFeatures(on))) return rc;                     // (Parameters, ORIGIN and ROTATION are set from here on)
+    HIP_TRY(hipSetDevice(on->device));
+    const size_t n = (size_t)c->W * c->H;
+    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
+    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
+    if (!on->dSelMask) HIP_TRY(hipMalloc((void**)&on->dSelMask, maskBytes(on) + 4));
+    if (!stats) {
+        HIP_TRY(hipMemsetAsync(on->dDnOut, 0, n * 16, on->stream));
+        stats = on->dDnOut;
+    }
+    unsigned* count = reinterpret_cast<unsigned*>(on->dSelMask + maskBytes(on));
+    const float sigma[4] = {r.sigma_lum, r.sigma_normal, r.sigma_depth, r.sigma_albedo};
+    const float rule[2] = {r.rel_err, r.abs_err};
+    const AdaptRule ovr = withOverlay(on, AdaptRule{});
+    const float ov[3] = {ovr.mouseX, ovr.mouseY, ovr.resolution};
+    HIP_TRY(guidedSelectLaunch(frame, on->dFeat, stats, c->W, c->H, r.iterations, sigma, r.min_frames, r.max_frames, rule, ov, on->dDnCol[0], on->dDnCol[1],
+                               on->dDnGuide, on->dSelMask, count, on->stream));
+    unsigned hc = 0;
+    HIP_TRY(hipMemcpyAsync(&hc, count, 4, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    *nActive = hc;
+    *onOut = on;
+    return 0;
+}
+
+// pt_render_mask on one stream: hostMask (W*H bytes) into c->dSelMask, or, when hostMask is null, the mask already there (pt_render_adaptive_guided
+// on a one-stream context); then the frame stream over the list entries it selects
+int renderMask(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const uint8_t* hostMask, const char* who, int64_t* nActive) {
+    return renderSelected(c, firstFrame, nFrames, seeds, who, [c, hostMask](hipStream_t s, int nb) {
+        if (hostMask) {
+            if (!c->dSelMask) HIP_TRY(hipMalloc((void**)&c->dSelMask, maskBytes(c) + 4));
+            HIP_TRY(hipMemcpyAsync(c->dSelMask, hostMask, (size_t)c->W * c->H, hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(k_adaptive_select_mask, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, (const unsigned char*)c->dSelMask,
+                           withOverlay(c, AdaptRule{}), c->dAdaptFlag, c->dAdaptBlk);
+        return 0;
+    }, nActive);
+}
+}  // namespace
+
+int pt_render_mask(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const uint8_t* mask, int64_t* n_active) {
+    if (n_active) *n_active = 0;
+    if (!c || !seeds || !mask) return fail(PT_ERR_ARG, "pt_render_mask: null argument");
+    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_mask: n_frames must be >= 1");
+    return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderMask(k, first_frame, n_frames, seeds, mask, "pt_render_mask", n); }, n_active);
+}
+
+int pt_select_guided(pt_ctx* c, const pt_guided_rule* rule, uint8_t* mask_out, int64_t* n_active) {
+    if (n_active) *n_active = 0;
+    if (!c || !rule || !mask_out) return fail(PT_ERR_ARG, "pt_select_guided: null argument");
+    int rc;
+    if ((rc = checkRule(*rule, "pt_select_guided"))) return rc;
+    pt_ctx* on = nullptr; int64_t n = 0;
+    if ((rc = selectGuided(c, *rule, "pt_select_guided", &on, &n))) return rc;
+    HIP_TRY(hipMemcpyAsync(mask_out, on->dSelMask, (size_t)c->W * c->H, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    if (n_active) *n_active = n;
+    return PT_OK;
+}
+
+int pt_render_adaptive_guided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, int64_t* n_active) {
+    static const char* who = "pt_render_adaptive_guided";
+    if (n_active) *n_active = 0;
+    if (!c || !seeds || !rule) return fail(PT_ERR_ARG, "pt_render_adaptive_guided: null argument");
+    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_adaptive_guided: n_frames must be >= 1");
+    int rc;
+    if ((rc = checkRule(*rule, who))) return rc;
+    const pt_ctx* f = firstStream(c);
+    if (f->params.size() >= 12 && f->params[10] != 0.0f)          // before the selection, as renderSelected would after it
+        return fail(PT_ERR_UNSUPPORTED, "pt_render_adaptive_guided: DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
+    pt_ctx* on = nullptr; int64_t n = 0;
+    if ((rc = selectGuided(c, *rule, who, &on, &n))) return rc;
+    if (!c->multi)                                                // one stream (holds the whole image): on == c, the mask stays in c->dSelMask
+        return onEveryStream(c, [=](pt_ctx* k, int64_t* cnt) { return renderMask(k, first_frame, n_frames, seeds, nullptr, who, cnt); }, n_active);
+    std::vector<uint8_t> host((size_t)c->W * c->H);               // a group: every stream selects from its own copy
+    HIP_TRY(hipMemcpyAsync(host.data(), on->dSelMask, host.size(), hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    const uint8_t* hm = host.data();
+    return onEveryStream(c, [=](pt_ctx* k, int64_t* cnt) { return renderMask(k, first_frame, n_frames, seeds, hm, who, cnt); }, n_active);
 }
 
 }  // extern "C"

@@ -130,8 +130,18 @@ def lib():
             L.pt_write_moments.argtypes = [vp, vp]
             L.pt_denoise_guided.argtypes = [vp, ci, cf, cf, cf, cf, ci, vp]
             L.pt_read_display_denoised_guided.argtypes = [vp, ci, cf, cf, cf, cf, ci, ci, vp]
+        if hasattr(L, "pt_render_mask"):                      # include/pt_steer.h
+            L.pt_render_mask.argtypes = [vp, ci, ci, vp, vp, C.POINTER(C.c_int64)]
+            L.pt_select_guided.argtypes = [vp, C.POINTER(GuidedRule), vp, C.POINTER(C.c_int64)]
+            L.pt_render_adaptive_guided.argtypes = [vp, ci, ci, vp, C.POINTER(GuidedRule), C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
+
+
+class GuidedRule(C.Structure):
+    """pt_guided_rule of include/pt_steer.h"""
+    _fields_ = [("iterations", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
+                ("min_frames", C.c_int), ("rel_err", C.c_float), ("abs_err", C.c_float), ("max_frames", C.c_int)]
 
 
 class PtError(RuntimeError):
@@ -379,6 +389,41 @@ class Renderer:
         _check(self._L.pt_read_display_denoised_guided(self._h, int(iterations), *self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames),
                                                        1 if java_bytes else 0, out.ctypes.data))
         return out
+
+    # --- adaptive sampling steered by the guided filter (include/pt_steer.h) ---------------------------
+    def render_mask(self, first_frame, seeds, mask):
+        """Frames first_frame.. (one per seed) for the pixels where mask != 0 ((H, W), FRAME order, row 0 = bottom) and not under the mouse
+        overlay (pt_render_mask); FRAME and T as render_adaptive updates them.  Returns how many pixels were rendered."""
+        s = np.ascontiguousarray(seeds, dtype=np.int32)
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert m.size == self.W * self.H
+        n = C.c_int64(0)
+        _check(self._L.pt_render_mask(self._h, int(first_frame), int(s.size), s.ctypes.data, m.ctypes.data, C.byref(n)))
+        return n.value
+
+    def guided_rule(self, rel_err, abs_err=0.0, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None,
+                    max_frames=0):
+        """the pt_guided_rule of these arguments; None takes denoise_guided's defaults"""
+        sl, sn, sd, sa, mf = self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames)
+        return GuidedRule(int(iterations), sl, sn, sd, sa, mf, float(rel_err), float(abs_err), int(max_frames))
+
+    def select_guided(self, rel_err, abs_err=0.0, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None,
+                      max_frames=0):
+        """The pixels the guided filter still finds uncertain (pt_select_guided): (H, W) bool, FRAME order.  FRAME and T are not modified."""
+        out = np.zeros((self.H, self.W), dtype=np.uint8)
+        rule = self.guided_rule(rel_err, abs_err, iterations, sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames, max_frames)
+        n = C.c_int64(0)
+        _check(self._L.pt_select_guided(self._h, C.byref(rule), out.ctypes.data, C.byref(n)))
+        return out.astype(bool)
+
+    def render_adaptive_guided(self, first_frame, seeds, rel_err, abs_err=0.0, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None,
+                               sigma_albedo=None, min_frames=None, max_frames=0):
+        """select_guided, then render_mask on its selection (pt_render_adaptive_guided); returns how many pixels were rendered"""
+        s = np.ascontiguousarray(seeds, dtype=np.int32)
+        rule = self.guided_rule(rel_err, abs_err, iterations, sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames, max_frames)
+        n = C.c_int64(0)
+        _check(self._L.pt_render_adaptive_guided(self._h, int(first_frame), int(s.size), s.ctypes.data, C.byref(rule), C.byref(n)))
+        return n.value
 
     def screenshot(self, path, frame_count, java_bytes=True):
         """functions.screenshot(fileName) (dispatch.java:804-851): the display image as a PNG file, written by the library (pt_save_png)"""
