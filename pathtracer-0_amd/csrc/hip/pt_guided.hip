@@ -11,6 +11,7 @@
 //   k_gd_finish  (filtered rgb, FRAME.a)
 //   k_gd_select  include/pt_steer.h's rule over the final (c_K, v_K), T and the class: one flag byte per pixel, the active pixels counted with a
 //                ballot popcount per wave, summed in LDS, one global atomic per block (pt_reproject.hip's k_reproject counts its kept pixels so)
+//   k_dm_prep, k_dm_var, k_dm_finish, k_dm_select  include/pt_demod.h: the same four on the illumination mean / albedo, around the shared k_gd_pass
 // Not under the bit-exact contract of the render path: __expf, sqrtf, and the summation order is the tap loop's.
 #include <hip/hip_runtime.h>
 
@@ -190,6 +191,136 @@ __global__ void __launch_bounds__(GD_BX * GD_BY) k_gd_select(const float4* __res
     }
 }
 
+// ---- albedo demodulation (include/pt_demod.h): the same pipeline on the illumination I = c / a.  k_gd_pass runs unchanged on (I, v); the four
+// kernels around it have a variant each.  The guide keeps the raw Kd (the albedo edge term compares it), so a pixel's a and L are recomputed
+// from the 16-B guide record that gives its class: no further loads.
+
+// a_p and L_p of the header from the second guide record (Kd, class): the floored Kd of a valid hit, (1, 1, 1) and exactly 1 otherwise
+__device__ __forceinline__ float3 albedoOf(const float4 g1, float floorA) {
+    return g1.w == 1.0f ? make_float3(fmaxf(g1.x, floorA), fmaxf(g1.y, floorA), fmaxf(g1.z, floorA)) : make_float3(1.0f, 1.0f, 1.0f);
+}
+__device__ __forceinline__ float albedoLum(const float4 g1, float floorA) {
+    if (g1.w != 1.0f) return 1.0f;
+    const float3 a = albedoOf(g1, floorA);
+    return lum(a.x, a.y, a.z);
+}
+
+// k_gd_prep with I = mean / a in the colour record of a valid hit; a valid hit whose I is not finite becomes invalid (class 0, its mean passed through)
+__global__ void __launch_bounds__(256) k_dm_prep(const float4* frame, const float4* feat, int n, float floorA, float4* col, float4* guide) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 F = frame[i], f0 = feat[4 * (size_t)i], f1 = feat[4 * (size_t)i + 1];
+    const float a = F.w;
+    const float mx = F.x / a, my = F.y / a, mz = F.z / a;
+    bool valid = a > 0.0f && finite3(mx, my, mz) && __builtin_isfinite(f0.x) && finite3(f0.y, f0.z, f0.w) && finite3(f1.x, f1.y, f1.z);
+    const bool hit = valid && __float_as_int(f1.w) >= 0;
+    float4 c = a > 0.0f ? make_float4(mx, my, mz, 0.0f) : make_float4(F.x, F.y, F.z, 0.0f);
+    if (hit) {
+        const float ix = mx / fmaxf(f1.x, floorA), iy = my / fmaxf(f1.y, floorA), iz = mz / fmaxf(f1.z, floorA);
+        if (finite3(ix, iy, iz)) c = make_float4(ix, iy, iz, 0.0f);
+        else valid = false;
+    }
+    const float cls = valid ? (hit ? 1.0f : 2.0f) : 0.0f;
+    col[i] = c;
+    guide[2 * (size_t)i] = f0;
+    guide[2 * (size_t)i + 1] = make_float4(f1.x, f1.y, f1.z, cls);
+}
+
+// k_gd_var on T' = (sY / L, (sYY / L) / L, n): the pixel's own L for its own moments, each tap's own L in the pooled sums
+__global__ void __launch_bounds__(GD_BX * GD_BY) k_dm_var(const float4* __restrict__ frame, const float4* __restrict__ feat, const float4* __restrict__ stats,
+                                                         const float4* __restrict__ guide, float4* __restrict__ col, int W, int H, float minFrames, float floorA) {
+    const int x = blockIdx.x * GD_BX + threadIdx.x, y = blockIdx.y * GD_BY + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    const float4 gp1 = guide[2 * p + 1];
+    const float cls = gp1.w;
+    if (cls == 0.0f) return;                                      // invalid: v is never read
+    const bool hit = cls == 1.0f;
+    const float4 T = stats[p];
+    float s2;
+    if (T.z >= minFrames) {
+        float sY = T.x, sYY = T.y;
+        if (hit) { const float L = albedoLum(gp1, floorA); sY = T.x / L; sYY = (T.y / L) / L; }
+        const float m = sY / T.z;
+        s2 = clampVar((sYY - sY * m) / (T.z - 1.0f));
+    } else {
+        const int mat = hit ? __float_as_int(feat[4 * p + 2].w) : 0;
+        float S = 0.0f, Q = 0.0f, N = 0.0f;
+        for (int dy = -3; dy <= 3; dy++) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= H) continue;
+            for (int dx = -3; dx <= 3; dx++) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= W) continue;
+                const size_t q = (size_t)yy * W + xx;
+                const float4 gq1 = guide[2 * q + 1];
+                if (gq1.w != cls) continue;
+                if (hit && __float_as_int(feat[4 * q + 2].w) != mat) continue;
+                const float4 Tq = stats[q];
+                if (!(Tq.z >= 1.0f)) continue;
+                float sY = Tq.x, sYY = Tq.y;
+                if (hit) { const float L = albedoLum(gq1, floorA); sY = Tq.x / L; sYY = (Tq.y / L) / L; }
+                S = S + sY; Q = Q + sYY; N = N + Tq.z;
+            }
+        }
+        s2 = N >= 2.0f ? clampVar((Q - S * (S / N)) / (N - 1.0f)) : __builtin_inff();
+    }
+    reinterpret_cast<float*>(col + p)[3] = s2 / frame[p].w;
+}
+
+// k_gd_finish with the pixel's own albedo put back: (a_p * I_K, FRAME.a)
+__global__ void __launch_bounds__(256) k_dm_finish(const float4* col, const float4* guide, const float4* frame, int n, float floorA, float4* out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 c = col[i];
+    const float3 a = albedoOf(guide[2 * (size_t)i + 1], floorA);
+    out[i] = make_float4(a.x * c.x, a.y * c.y, a.z * c.z, frame[i].w);
+}
+
+// k_gd_select with include/pt_demod.h's step 5; steps 1-4 as there, on the raw T
+__global__ void __launch_bounds__(GD_BX * GD_BY) k_dm_select(const float4* __restrict__ cv, const float4* __restrict__ stats, const float4* __restrict__ guide,
+                                                            int W, int H, float minFrames, int maxFrames, float2 rule, float3 ov, float floorA,
+                                                            unsigned char* __restrict__ mask, unsigned* __restrict__ count) {
+    __shared__ unsigned sCnt[GD_BY];
+    const int x = blockIdx.x * GD_BX + threadIdx.x, y = blockIdx.y * GD_BY + threadIdx.y;
+    bool on = false;
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * W + x;
+        ptd::FrameConst fc{};
+        fc.mouse[0] = ov.x; fc.mouse[1] = ov.y; fc.resolution = ov.z;
+        const float4 T = stats[p];
+        const float n = T.z;
+        const float4 g1 = guide[2 * p + 1];
+        if (ptd::inMouseOverlay(fc, x, y)) on = false;                                     // 1
+        else if (maxFrames > 0 && n >= (float)maxFrames) on = false;                       // 2
+        else if (n < minFrames) on = true;                                                 // 3
+        else if (g1.w == 0.0f) {                                                           // 4: invalid, the own-moment rule of include/pt_adaptive.h
+            const float mean = T.x / n;
+            const float var = (T.y - T.x * mean) / (n - 1.0f);
+            const float err2 = var / n;
+            const float tol = fmaxf(rule.x * fabsf(mean), rule.y);
+            on = err2 > tol * tol;
+        } else {                                                                           // 5: the filtered colour, the variance brought back to colour
+            const float4 c = cv[p];
+            const float3 a = albedoOf(g1, floorA);
+            const float tol = fmaxf(rule.x * fabsf(lum(a.x * c.x, a.y * c.y, a.z * c.z)), rule.y);
+            float v = c.w;
+            if (g1.w == 1.0f) { const float L = lum(a.x, a.y, a.z); v = (c.w * L) * L; }
+            on = c.w == __builtin_inff() || v > tol * tol;
+        }
+        mask[p] = on ? 1 : 0;
+    }
+    const unsigned long long b = __ballot(on);
+    if (threadIdx.x == 0) sCnt[threadIdx.y] = (unsigned)__popcll(b);                      // a wave is one row of the block
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < GD_BY; w++) t += sCnt[w];
+        if (t) atomicAdd(count, t);
+    }
+}
+
 float clampInv(float v) { return v > 3.402823466e38f ? 3.402823466e38f : v; }
 
 }  // namespace
@@ -239,5 +370,50 @@ hipError_t guidedSelectLaunch(const float4* frame, const float4* feat, const flo
     }
     hipLaunchKernelGGL(k_gd_select, grid, dim3(GD_BX, GD_BY), 0, s, src, stats, guide, W, H, (float)minFrames, maxFrames, make_float2(rule[0], rule[1]),
                        make_float3(ov[0], ov[1], ov[2]), mask, count);
+    return hipGetLastError();
+}
+
+// include/pt_demod.h's filter: guidedLaunch with k_dm_prep, k_dm_var and k_dm_finish around the shared passes.  floorA = albedo_floor, checked by
+// the caller; the other arguments as guidedLaunch's.
+hipError_t guidedDemodLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                             float floorA, float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s) {
+    const int n = W * H;
+    const dim3 lin((unsigned)((n + 255) / 256));
+    const dim3 grid((unsigned)((W + GD_BX - 1) / GD_BX), (unsigned)((H + GD_BY - 1) / GD_BY));
+    hipLaunchKernelGGL(k_dm_prep, lin, dim3(256), 0, s, frame, feat, n, floorA, col0, guide);
+    float4* src = col0;
+    float4* dst = col1;
+    if (iterations > 0) {
+        hipLaunchKernelGGL(k_dm_var, grid, dim3(GD_BX, GD_BY), 0, s, frame, feat, stats, guide, col0, W, H, (float)minFrames, floorA);
+        const float3 inv = make_float3(clampInv(1.0f / (sigma[1] * sigma[1])), clampInv(1.0f / (sigma[2] * sigma[2])), clampInv(1.0f / (sigma[3] * sigma[3])));
+        for (int i = 0; i < iterations; i++) {
+            hipLaunchKernelGGL(k_gd_pass, grid, dim3(GD_BX, GD_BY), 0, s, src, guide, dst, W, H, 1 << i, sigma[0], inv);
+            float4* t = src; src = dst; dst = t;
+        }
+    }
+    hipLaunchKernelGGL(k_dm_finish, lin, dim3(256), 0, s, src, guide, frame, n, floorA, out);
+    return hipGetLastError();
+}
+
+// include/pt_demod.h's selection: guidedSelectLaunch with k_dm_prep, k_dm_var and k_dm_select around the shared passes.
+hipError_t guidedDemodSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4],
+                                   int minFrames, int maxFrames, const float rule[2], const float ov[3], float floorA, float4* col0, float4* col1,
+                                   float4* guide, unsigned char* mask, unsigned* count, hipStream_t s) {
+    const int n = W * H;
+    const dim3 lin((unsigned)((n + 255) / 256));
+    const dim3 grid((unsigned)((W + GD_BX - 1) / GD_BX), (unsigned)((H + GD_BY - 1) / GD_BY));
+    hipError_t e = hipMemsetAsync(count, 0, 4, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_dm_prep, lin, dim3(256), 0, s, frame, feat, n, floorA, col0, guide);
+    hipLaunchKernelGGL(k_dm_var, grid, dim3(GD_BX, GD_BY), 0, s, frame, feat, stats, guide, col0, W, H, (float)minFrames, floorA);
+    const float3 inv = make_float3(clampInv(1.0f / (sigma[1] * sigma[1])), clampInv(1.0f / (sigma[2] * sigma[2])), clampInv(1.0f / (sigma[3] * sigma[3])));
+    float4* src = col0;
+    float4* dst = col1;
+    for (int i = 0; i < iterations; i++) {
+        hipLaunchKernelGGL(k_gd_pass, grid, dim3(GD_BX, GD_BY), 0, s, src, guide, dst, W, H, 1 << i, sigma[0], inv);
+        float4* t = src; src = dst; dst = t;
+    }
+    hipLaunchKernelGGL(k_dm_select, grid, dim3(GD_BX, GD_BY), 0, s, src, stats, guide, W, H, (float)minFrames, maxFrames, make_float2(rule[0], rule[1]),
+                       make_float3(ov[0], ov[1], ov[2]), floorA, mask, count);
     return hipGetLastError();
 }

@@ -30,6 +30,7 @@
 #include "../../../include/pt_reproject.h"
 #include "../../../include/pt_guided.h"
 #include "../../../include/pt_steer.h"
+#include "../../../include/pt_demod.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -2213,6 +2214,15 @@ hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* s
 hipError_t guidedSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
                               int maxFrames, const float rule[2], const float ov[3], float4* col0, float4* col1, float4* guide, unsigned char* mask,
                               unsigned* count, hipStream_t s);
+// include/pt_demod.h: the three above on the illumination (pt_guided.hip, pt_reproject.hip); floorA = albedo_floor
+hipError_t guidedDemodLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                             float floorA, float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s);
+hipError_t guidedDemodSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4],
+                                   int minFrames, int maxFrames, const float rule[2], const float ov[3], float floorA, float4* col0, float4* col1,
+                                   float4* guide, unsigned char* mask, unsigned* count, hipStream_t s);
+hipError_t reprojectDemodLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
+                                int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float floorA, float4* outFrame,
+                                float4* outStats, unsigned* kept, hipStream_t s);
 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
@@ -3172,7 +3182,11 @@ int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float
 
 // ---- the variance-guided filter (include/pt_guided.h): pt_denoise's plumbing and scratch, with T in pixel order beside FRAME
 namespace {
-int guidedImage(pt_ctx* c, int iterations, const float sigma[4], int minFrames, pt_ctx** onOut) {
+// include/pt_demod.h's albedo_floor: finite and > 0
+bool floorOk(float floorA) { return floorA > 0.0f && __builtin_isfinite(floorA); }
+
+// floorA == 0: the plain filter; > 0: include/pt_demod.h's, with that albedo_floor (checked by the caller)
+int guidedImage(pt_ctx* c, int iterations, const float sigma[4], int minFrames, float floorA, pt_ctx** onOut) {
     if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise_guided: iterations must be in [0,8]");
     if (minFrames < 2) return fail(PT_ERR_ARG, "pt_denoise_guided: min_frames must be >= 2");
     for (int k = 0; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, "pt_denoise_guided: every sigma must be > 0 (+inf switches its term off)");
@@ -3185,7 +3199,11 @@ int guidedImage(pt_ctx* c, int iterations, const float sigma[4], int minFrames, 
     const size_t n = (size_t)c->W * c->H;
     for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
     if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
-    HIP_TRY(guidedLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
+    if (floorA > 0.0f)
+        HIP_TRY(guidedDemodLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, floorA, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut,
+                                  on->stream));
+    else
+        HIP_TRY(guidedLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
     *onOut = on;
     return 0;
 }
@@ -3196,7 +3214,7 @@ int pt_denoise_guided(pt_ctx* c, int iterations, float sigma_lum, float sigma_no
     const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
     pt_ctx* on = nullptr;
     int rc;
-    if ((rc = guidedImage(c, iterations, sigma, min_frames, &on))) return rc;
+    if ((rc = guidedImage(c, iterations, sigma, min_frames, 0.0f, &on))) return rc;
     HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     return PT_OK;
@@ -3208,14 +3226,39 @@ int pt_read_display_denoised_guided(pt_ctx* c, int iterations, float sigma_lum, 
     const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
     pt_ctx* on = nullptr;
     int rc;
-    if ((rc = guidedImage(c, iterations, sigma, min_frames, &on))) return rc;
+    if ((rc = guidedImage(c, iterations, sigma, min_frames, 0.0f, &on))) return rc;
+    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
+}
+
+int pt_denoise_guided_demod(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
+                            float albedo_floor, float* rgba_out) {
+    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_demod: null argument");
+    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_denoise_guided_demod: albedo_floor must be finite and > 0");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = guidedImage(c, iterations, sigma, min_frames, albedo_floor, &on))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    return PT_OK;
+}
+
+int pt_read_display_denoised_guided_demod(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo,
+                                          int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
+    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_demod: null argument");
+    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_demod: albedo_floor must be finite and > 0");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = guidedImage(c, iterations, sigma, min_frames, albedo_floor, &on))) return rc;
     return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
 }
 
 // ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
 // every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
 namespace {
-int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, int64_t* nKept) {
+// floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor (checked by the caller)
+int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept) {
     if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: max_history must be >= 1");
     if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: depth_tol must be > 0");
     if (!(normalTol >= -1.0f && normalTol <= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: normal_tol must be in [-1, 1]");
@@ -3259,8 +3302,12 @@ int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol,
     std::memset(&on->streamIn, 0xff, sizeof(FrameIn));
     const float curIn[6] = {cur.origin[0], cur.origin[1], cur.origin[2], cur.mouse[0], cur.mouse[1], cur.params[2]};
     const float rule[3] = {maxHistory, depthTol, normalTol};
-    HIP_TRY(reprojectLaunch(on->dFeat, same ? on->dFeat : on->dFeatH, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
-                            (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept, on->stream));
+    if (floorA > 0.0f)
+        HIP_TRY(reprojectDemodLaunch(on->dFeat, same ? on->dFeat : on->dFeatH, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
+                                     (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, floorA, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept, on->stream));
+    else
+        HIP_TRY(reprojectLaunch(on->dFeat, same ? on->dFeat : on->dFeatH, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
+                                (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept, on->stream));
     unsigned kept = 0;
     HIP_TRY(hipMemcpyAsync(&kept, on->dRpKept, 4, hipMemcpyDeviceToHost, on->stream));
     if (!c->multi) {                                              // the result into the current image (a copy: pt_frame_device pointers stay valid)
@@ -3285,7 +3332,17 @@ int pt_reproject_frame(pt_ctx* c, float max_history, float depth_tol, float norm
     if (n_kept) *n_kept = 0;
     if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame: null context");
     int64_t n = 0;
-    const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, &n);
+    const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, 0.0f, &n);
+    if (n_kept) *n_kept = n;
+    return rc;
+}
+
+int pt_reproject_frame_demod(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
+    if (n_kept) *n_kept = 0;
+    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: null context");
+    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: albedo_floor must be finite and > 0");
+    int64_t n = 0;
+    const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
     if (n_kept) *n_kept = n;
     return rc;
 }
@@ -3309,7 +3366,8 @@ int checkRule(const pt_guided_rule& r, const char* who) {
 
 // The rule over the context's current image into (*onOut)->dSelMask (W*H bytes, pixel order, on the device of firstStream(c)); *nActive = its count.
 // FRAME and T are not modified; T never allocated reads as zeros (the filter's scratch output, zeroed).
-int selectGuided(pt_ctx* c, const pt_guided_rule& r, const char* who, pt_ctx** onOut, int64_t* nActive) {
+// floorA == 0: include/pt_steer.h's rule; > 0: include/pt_demod.h's step 5, with that albedo_floor (checked by the caller).
+int selectGuided(pt_ctx* c, const pt_guided_rule& r, float floorA, const char* who, pt_ctx** onOut, int64_t* nActive) {
     pt_ctx* on = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
     int rc;
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &frame))) return rc;
@@ -3329,8 +3387,12 @@ int selectGuided(pt_ctx* c, const pt_guided_rule& r, const char* who, pt_ctx** o
     const float rule[2] = {r.rel_err, r.abs_err};
     const AdaptRule ovr = withOverlay(on, AdaptRule{});
     const float ov[3] = {ovr.mouseX, ovr.mouseY, ovr.resolution};
-    HIP_TRY(guidedSelectLaunch(frame, on->dFeat, stats, c->W, c->H, r.iterations, sigma, r.min_frames, r.max_frames, rule, ov, on->dDnCol[0], on->dDnCol[1],
-                               on->dDnGuide, on->dSelMask, count, on->stream));
+    if (floorA > 0.0f)
+        HIP_TRY(guidedDemodSelectLaunch(frame, on->dFeat, stats, c->W, c->H, r.iterations, sigma, r.min_frames, r.max_frames, rule, ov, floorA, on->dDnCol[0],
+                                        on->dDnCol[1], on->dDnGuide, on->dSelMask, count, on->stream));
+    else
+        HIP_TRY(guidedSelectLaunch(frame, on->dFeat, stats, c->W, c->H, r.iterations, sigma, r.min_frames, r.max_frames, rule, ov, on->dDnCol[0], on->dDnCol[1],
+                                   on->dDnGuide, on->dSelMask, count, on->stream));
     unsigned hc = 0;
     HIP_TRY(hipMemcpyAsync(&hc, count, 4, hipMemcpyDeviceToHost, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
@@ -3361,31 +3423,34 @@ int pt_render_mask(pt_ctx* c, int first_frame, int n_frames, const int32_t* seed
     return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderMask(k, first_frame, n_frames, seeds, mask, "pt_render_mask", n); }, n_active);
 }
 
-int pt_select_guided(pt_ctx* c, const pt_guided_rule* rule, uint8_t* mask_out, int64_t* n_active) {
+namespace {
+// pt_select_guided (floorA == 0) and pt_select_guided_demod
+int selectInto(pt_ctx* c, const pt_guided_rule* rule, float floorA, const char* who, uint8_t* mask_out, int64_t* n_active) {
     if (n_active) *n_active = 0;
-    if (!c || !rule || !mask_out) return fail(PT_ERR_ARG, "pt_select_guided: null argument");
+    if (!c || !rule || !mask_out) return fail(PT_ERR_ARG, std::string(who) + ": null argument");
     int rc;
-    if ((rc = checkRule(*rule, "pt_select_guided"))) return rc;
+    if ((rc = checkRule(*rule, who))) return rc;
     pt_ctx* on = nullptr; int64_t n = 0;
-    if ((rc = selectGuided(c, *rule, "pt_select_guided", &on, &n))) return rc;
+    if ((rc = selectGuided(c, *rule, floorA, who, &on, &n))) return rc;
     HIP_TRY(hipMemcpyAsync(mask_out, on->dSelMask, (size_t)c->W * c->H, hipMemcpyDeviceToHost, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     if (n_active) *n_active = n;
     return PT_OK;
 }
 
-int pt_render_adaptive_guided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, int64_t* n_active) {
-    static const char* who = "pt_render_adaptive_guided";
+// pt_render_adaptive_guided (floorA == 0) and pt_render_adaptive_guided_demod
+int renderAdaptiveGuided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, float floorA, const char* who,
+                         int64_t* n_active) {
     if (n_active) *n_active = 0;
-    if (!c || !seeds || !rule) return fail(PT_ERR_ARG, "pt_render_adaptive_guided: null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_adaptive_guided: n_frames must be >= 1");
+    if (!c || !seeds || !rule) return fail(PT_ERR_ARG, std::string(who) + ": null argument");
+    if (n_frames < 1) return fail(PT_ERR_ARG, std::string(who) + ": n_frames must be >= 1");
     int rc;
     if ((rc = checkRule(*rule, who))) return rc;
     const pt_ctx* f = firstStream(c);
     if (f->params.size() >= 12 && f->params[10] != 0.0f)          // before the selection, as renderSelected would after it
-        return fail(PT_ERR_UNSUPPORTED, "pt_render_adaptive_guided: DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
+        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
     pt_ctx* on = nullptr; int64_t n = 0;
-    if ((rc = selectGuided(c, *rule, who, &on, &n))) return rc;
+    if ((rc = selectGuided(c, *rule, floorA, who, &on, &n))) return rc;
     if (!c->multi)                                                // one stream (holds the whole image): on == c, the mask stays in c->dSelMask
         return onEveryStream(c, [=](pt_ctx* k, int64_t* cnt) { return renderMask(k, first_frame, n_frames, seeds, nullptr, who, cnt); }, n_active);
     std::vector<uint8_t> host((size_t)c->W * c->H);               // a group: every stream selects from its own copy
@@ -3393,6 +3458,28 @@ int pt_render_adaptive_guided(pt_ctx* c, int first_frame, int n_frames, const in
     HIP_TRY(hipStreamSynchronize(on->stream));
     const uint8_t* hm = host.data();
     return onEveryStream(c, [=](pt_ctx* k, int64_t* cnt) { return renderMask(k, first_frame, n_frames, seeds, hm, who, cnt); }, n_active);
+}
+}  // namespace
+
+int pt_select_guided(pt_ctx* c, const pt_guided_rule* rule, uint8_t* mask_out, int64_t* n_active) {
+    return selectInto(c, rule, 0.0f, "pt_select_guided", mask_out, n_active);
+}
+
+int pt_render_adaptive_guided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, int64_t* n_active) {
+    return renderAdaptiveGuided(c, first_frame, n_frames, seeds, rule, 0.0f, "pt_render_adaptive_guided", n_active);
+}
+
+int pt_select_guided_demod(pt_ctx* c, const pt_guided_rule* rule, float albedo_floor, uint8_t* mask_out, int64_t* n_active) {
+    if (n_active) *n_active = 0;
+    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_select_guided_demod: albedo_floor must be finite and > 0");
+    return selectInto(c, rule, albedo_floor, "pt_select_guided_demod", mask_out, n_active);
+}
+
+int pt_render_adaptive_guided_demod(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, float albedo_floor,
+                                    int64_t* n_active) {
+    if (n_active) *n_active = 0;
+    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_render_adaptive_guided_demod: albedo_floor must be finite and > 0");
+    return renderAdaptiveGuided(c, first_frame, n_frames, seeds, rule, albedo_floor, "pt_render_adaptive_guided_demod", n_active);
 }
 
 }  // extern "C"

@@ -21,6 +21,10 @@ OPTIONS = {"path_slots": 0, "count_stats": 1, "lds_budget": 2, "none_min": 3, "e
            "refill_min": 7, "extend_blocks_per_cu": 8, "inner_keep_eighths": 9, "bfs_nodes": 10, "stack_mode": 11,
            "query_asm_eligible": 12, "query_asm_launches_above": 13, "asm_loop": 14, "numeric_contract": 16, "asm_tpb": 17, "index_stack_8bit": 18, "asm_node_layout": 19, "asm_root_cull": 20, "cu_partition": 21}
 
+# the albedo_floor to pass for the demodulated calls of include/pt_demod.h (albedo_floor=ALBEDO_FLOOR; the keyword's own default None makes the
+# plain call): scripts/demod_quality.py's grid on T1, C3 and C6 (profiles/r13_demod_quality.txt)
+ALBEDO_FLOOR = 0.2
+
 
 def hip_runtimes_mapped():
     """real paths of every libamdhip64 mapped into this process (Linux)"""
@@ -134,6 +138,13 @@ def lib():
             L.pt_render_mask.argtypes = [vp, ci, ci, vp, vp, C.POINTER(C.c_int64)]
             L.pt_select_guided.argtypes = [vp, C.POINTER(GuidedRule), vp, C.POINTER(C.c_int64)]
             L.pt_render_adaptive_guided.argtypes = [vp, ci, ci, vp, C.POINTER(GuidedRule), C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_denoise_guided_demod"):             # include/pt_demod.h
+            cf = C.c_float
+            L.pt_denoise_guided_demod.argtypes = [vp, ci, cf, cf, cf, cf, ci, cf, vp]
+            L.pt_read_display_denoised_guided_demod.argtypes = [vp, ci, cf, cf, cf, cf, ci, cf, ci, vp]
+            L.pt_select_guided_demod.argtypes = [vp, C.POINTER(GuidedRule), cf, vp, C.POINTER(C.c_int64)]
+            L.pt_render_adaptive_guided_demod.argtypes = [vp, ci, ci, vp, C.POINTER(GuidedRule), cf, C.POINTER(C.c_int64)]
+            L.pt_reproject_frame_demod.argtypes = [vp, cf, cf, cf, ci, cf, C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -337,14 +348,18 @@ class Renderer:
     # --- reprojection across a camera move (include/pt_reproject.h) --------------------------------
     REPROJECT_ALL_MATERIALS = 1
 
-    def reproject_frame(self, max_history=64, depth_tol=0.02, normal_tol=0.9, all_materials=False):
+    def reproject_frame(self, max_history=64, depth_tol=0.02, normal_tol=0.9, all_materials=False, albedo_floor=None):
         """Carry the current image across the camera move since it was rendered (pt_reproject_frame): every pixel of the current view takes over
         the sum and count of the old pixel that saw the same surface point, capped at max_history frames; the others restart from zero.
         Returns how many pixels kept their history.  Continue with frame numbers other than 1 and show the image with read_display_mean.
-        The defaults: scripts/reproject_quality.py on C2 and C3 at 1080p (profiles/r10_reproject_quality.txt)."""
+        The defaults: scripts/reproject_quality.py on C2 and C3 at 1080p (profiles/r10_reproject_quality.txt).
+        albedo_floor: a number carries illumination and gives every pixel its own albedo back (pt_reproject_frame_demod, include/pt_demod.h)."""
         n = C.c_int64(0)
-        _check(self._L.pt_reproject_frame(self._h, float(max_history), float(depth_tol), float(normal_tol),
-                                          self.REPROJECT_ALL_MATERIALS if all_materials else 0, C.byref(n)))
+        flags = self.REPROJECT_ALL_MATERIALS if all_materials else 0
+        if albedo_floor is None:
+            _check(self._L.pt_reproject_frame(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, C.byref(n)))
+        else:
+            _check(self._L.pt_reproject_frame_demod(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, float(albedo_floor), C.byref(n)))
         return n.value
 
     # --- luminance moments and the variance-guided filter (include/pt_guided.h) ---------------------
@@ -352,6 +367,8 @@ class Renderer:
     # at 1080p (profiles/r11_guided_quality.txt); the geometric sigmas are DENOISE_SIGMAS'
     GUIDED_SIGMA_LUM = 2.0
     GUIDED_MIN_FRAMES = 4
+    # albedo_floor=None on the calls below and on reproject_frame makes the plain call; a number (ALBEDO_FLOOR is the module's default for it) makes
+    # the albedo-demodulated one of include/pt_demod.h, where sigma_albedo=float('inf') is the natural setting
 
     def record_moments(self, on=True):
         """Record T = (sY, sYY, n, 0), the per-pixel luminance moments, for every frame rendered from now on (pt_record_moments)"""
@@ -374,20 +391,27 @@ class Renderer:
         g[0] = float(self.GUIDED_SIGMA_LUM if sigma_lum is None else sigma_lum)
         return g + [int(self.GUIDED_MIN_FRAMES if min_frames is None else min_frames)]
 
-    def denoise_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None):
+    def denoise_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None, albedo_floor=None):
         """the variance-guided filter over FRAME.rgb / FRAME.a, steered by T (pt_denoise_guided): (H, W, 4) float32, rgb = filtered mean,
-        a = FRAME.a.  Needs moments (record_moments before rendering, or write_moments).  None takes the defaults above."""
+        a = FRAME.a.  Needs moments (record_moments before rendering, or write_moments).  None takes the defaults above.
+        albedo_floor: a number filters the illumination mean / albedo instead (pt_denoise_guided_demod)."""
         out = np.zeros((self.H, self.W, 4), dtype=np.float32)
-        _check(self._L.pt_denoise_guided(self._h, int(iterations), *self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames),
-                                         out.ctypes.data))
+        g = self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames)
+        if albedo_floor is None:
+            _check(self._L.pt_denoise_guided(self._h, int(iterations), *g, out.ctypes.data))
+        else:
+            _check(self._L.pt_denoise_guided_demod(self._h, int(iterations), *g, float(albedo_floor), out.ctypes.data))
         return out
 
     def read_display_denoised_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None,
-                                     java_bytes=True):
+                                     java_bytes=True, albedo_floor=None):
         """denoise_guided()'s image converted to 8 bits as read_display converts a mean: (H, W, 3) uint8, top row first"""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
-        _check(self._L.pt_read_display_denoised_guided(self._h, int(iterations), *self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames),
-                                                       1 if java_bytes else 0, out.ctypes.data))
+        g = self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames)
+        if albedo_floor is None:
+            _check(self._L.pt_read_display_denoised_guided(self._h, int(iterations), *g, 1 if java_bytes else 0, out.ctypes.data))
+        else:
+            _check(self._L.pt_read_display_denoised_guided_demod(self._h, int(iterations), *g, float(albedo_floor), 1 if java_bytes else 0, out.ctypes.data))
         return out
 
     # --- adaptive sampling steered by the guided filter (include/pt_steer.h) ---------------------------
@@ -408,21 +432,29 @@ class Renderer:
         return GuidedRule(int(iterations), sl, sn, sd, sa, mf, float(rel_err), float(abs_err), int(max_frames))
 
     def select_guided(self, rel_err, abs_err=0.0, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None,
-                      max_frames=0):
-        """The pixels the guided filter still finds uncertain (pt_select_guided): (H, W) bool, FRAME order.  FRAME and T are not modified."""
+                      max_frames=0, albedo_floor=None):
+        """The pixels the guided filter still finds uncertain (pt_select_guided): (H, W) bool, FRAME order.  FRAME and T are not modified.
+        albedo_floor: a number asks the demodulated filter (pt_select_guided_demod)."""
         out = np.zeros((self.H, self.W), dtype=np.uint8)
         rule = self.guided_rule(rel_err, abs_err, iterations, sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames, max_frames)
         n = C.c_int64(0)
-        _check(self._L.pt_select_guided(self._h, C.byref(rule), out.ctypes.data, C.byref(n)))
+        if albedo_floor is None:
+            _check(self._L.pt_select_guided(self._h, C.byref(rule), out.ctypes.data, C.byref(n)))
+        else:
+            _check(self._L.pt_select_guided_demod(self._h, C.byref(rule), float(albedo_floor), out.ctypes.data, C.byref(n)))
         return out.astype(bool)
 
     def render_adaptive_guided(self, first_frame, seeds, rel_err, abs_err=0.0, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None,
-                               sigma_albedo=None, min_frames=None, max_frames=0):
-        """select_guided, then render_mask on its selection (pt_render_adaptive_guided); returns how many pixels were rendered"""
+                               sigma_albedo=None, min_frames=None, max_frames=0, albedo_floor=None):
+        """select_guided, then render_mask on its selection (pt_render_adaptive_guided, or pt_render_adaptive_guided_demod when albedo_floor is
+        a number); returns how many pixels were rendered"""
         s = np.ascontiguousarray(seeds, dtype=np.int32)
         rule = self.guided_rule(rel_err, abs_err, iterations, sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames, max_frames)
         n = C.c_int64(0)
-        _check(self._L.pt_render_adaptive_guided(self._h, int(first_frame), int(s.size), s.ctypes.data, C.byref(rule), C.byref(n)))
+        if albedo_floor is None:
+            _check(self._L.pt_render_adaptive_guided(self._h, int(first_frame), int(s.size), s.ctypes.data, C.byref(rule), C.byref(n)))
+        else:
+            _check(self._L.pt_render_adaptive_guided_demod(self._h, int(first_frame), int(s.size), s.ctypes.data, C.byref(rule), float(albedo_floor), C.byref(n)))
         return n.value
 
     def screenshot(self, path, frame_count, java_bytes=True):
