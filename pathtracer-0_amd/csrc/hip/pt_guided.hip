@@ -12,6 +12,8 @@
 //   k_gd_select  include/pt_steer.h's rule over the final (c_K, v_K), T and the class: one flag byte per pixel, the active pixels counted with a
 //                ballot popcount per wave, summed in LDS, one global atomic per block (pt_reproject.hip's k_reproject counts its kept pixels so)
 //   k_dm_prep, k_dm_var, k_dm_finish, k_dm_select  include/pt_demod.h: the same four on the illumination mean / albedo, around the shared k_gd_pass
+//   k_gd_fill    include/pt_fill.h: FRAME' = FRAME with every pixel nothing was rendered into reconstructed from the valid 5x5 neighbours of its
+//                surface (the prep kernels' colour and guide of the real FRAME); the passes then run on FRAME' as they run on a frame
 // Not under the bit-exact contract of the render path: __expf, sqrtf, and the summation order is the tap loop's.
 #include <hip/hip_runtime.h>
 
@@ -321,15 +323,86 @@ __global__ void __launch_bounds__(GD_BX * GD_BY) k_dm_select(const float4* __res
     }
 }
 
+// ---- the prefill of include/pt_fill.h: FRAME' for the pixels nothing was rendered into.  col, guide: k_gd_prep's (floorA == 0) or k_dm_prep's
+// (floorA > 0) of the real FRAME, so col holds every source's x_q (mean or illumination) and the guide's class says which taps are valid; a hole
+// is class 0 there, so its own hit or miss comes from the raw hit code.  Only holes read taps: the 24 of them are served by L2 like k_gd_pass's.
+// inv as k_gd_pass's.  count: zeroed by the caller, the holes that found a source (counted as k_gd_select counts).
+__global__ void __launch_bounds__(GD_BX * GD_BY) k_gd_fill(const float4* __restrict__ frame, const float4* __restrict__ feat, const float4* __restrict__ col,
+                                                          const float4* __restrict__ guide, float4* __restrict__ out, int W, int H, float3 inv, float floorA,
+                                                          unsigned* __restrict__ count) {
+    __shared__ unsigned sCnt[GD_BY];
+    const int x = blockIdx.x * GD_BX + threadIdx.x, y = blockIdx.y * GD_BY + threadIdx.y;
+    bool filled = false;
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * W + x;
+        float4 F = frame[p];
+        if (F.w <= 0.0f) {
+            const float4 gp0 = guide[2 * p], gp1 = guide[2 * p + 1];
+            if (__builtin_isfinite(gp0.x) && finite3(gp0.y, gp0.z, gp0.w) && finite3(gp1.x, gp1.y, gp1.z)) {
+                const bool hit = __float_as_int(feat[4 * p + 1].w) >= 0;
+                const float cls = hit ? 1.0f : 2.0f;
+                const int mat = hit ? __float_as_int(feat[4 * p + 2].w) : 0;
+                const float invT = 1.0f / gp0.x;
+                const float h[5] = {1.0f / 16.0f, 4.0f / 16.0f, 6.0f / 16.0f, 4.0f / 16.0f, 1.0f / 16.0f};
+                float sr = 0.0f, sg = 0.0f, sb = 0.0f, S = 0.0f, B = 0.0f;
+#pragma unroll
+                for (int dy = -2; dy <= 2; dy++) {
+                    const int yy = y + dy;
+                    if (yy < 0 || yy >= H) continue;
+#pragma unroll
+                    for (int dx = -2; dx <= 2; dx++) {
+                        const int xx = x + dx;
+                        if (xx < 0 || xx >= W || (dx == 0 && dy == 0)) continue;
+                        const size_t q = (size_t)yy * W + xx;
+                        const float4 g1 = guide[2 * q + 1];
+                        if (g1.w != cls) continue;                // invalid (a hole included), or hit against miss
+                        float w = h[dy + 2] * h[dx + 2];
+                        if (hit) {
+                            if (__float_as_int(feat[4 * q + 2].w) != mat) continue;
+                            const float4 g0 = guide[2 * q];
+                            const float nx = gp0.y - g0.y, ny = gp0.z - g0.z, nz = gp0.w - g0.w;
+                            const float dt = (gp0.x - g0.x) * invT;
+                            const float ar = gp1.x - g1.x, ag = gp1.y - g1.y, ab = gp1.z - g1.z;
+                            const float e = (nx * nx + ny * ny + nz * nz) * inv.x + (dt * dt) * inv.y + (ar * ar + ag * ag + ab * ab) * inv.z;
+                            w = w * __expf(-e);
+                        }
+                        if (w < 1e-30f) continue;
+                        const float4 cq = col[q];
+                        sr += w * cq.x; sg += w * cq.y; sb += w * cq.z; S += w;
+                        B += (w * w) / frame[q].w;
+                        filled = true;
+                    }
+                }
+                if (filled) {
+                    const float A = (S * S) / B;
+                    const bool demod = hit && floorA > 0.0f;
+                    const float ax = demod ? fmaxf(gp1.x, floorA) : 1.0f, ay = demod ? fmaxf(gp1.y, floorA) : 1.0f, az = demod ? fmaxf(gp1.z, floorA) : 1.0f;
+                    F = make_float4((ax * (sr / S)) * A, (ay * (sg / S)) * A, (az * (sb / S)) * A, A);
+                }
+            }
+        }
+        out[p] = F;
+    }
+    const unsigned long long b = __ballot(filled);
+    if (threadIdx.x == 0) sCnt[threadIdx.y] = (unsigned)__popcll(b);                      // a wave is one row of the block
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < GD_BY; w++) t += sCnt[w];
+        if (t) atomicAdd(count, t);
+    }
+}
+
 float clampInv(float v) { return v > 3.402823466e38f ? 3.402823466e38f : v; }
 
 }  // namespace
 
 // frame, stats: W*H float4 (FRAME and T in pixel order), feat: W*H*4 float4 (all read only); col0, col1: W*H float4 ping-pong; guide: 2*W*H float4;
-// out: W*H float4.  sigma = (luminance, normal, depth, albedo) and minFrames already checked by the caller.  Enqueued on `s`; returns the first
-// launch error.
+// out: W*H float4.  sigma = (luminance, normal, depth, albedo) and minFrames already checked by the caller.  alpha: the image whose .a the output
+// takes, nullptr = frame (include/pt_fill.h filters FRAME' and returns the real FRAME's count).  Enqueued on `s`; returns the first launch error.
 hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                        float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s) {
+                        float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s, const float4* alpha) {
     const int n = W * H;
     const dim3 lin((unsigned)((n + 255) / 256));
     const dim3 grid((unsigned)((W + GD_BX - 1) / GD_BX), (unsigned)((H + GD_BY - 1) / GD_BY));
@@ -344,7 +417,7 @@ hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* s
             float4* t = src; src = dst; dst = t;
         }
     }
-    hipLaunchKernelGGL(k_gd_finish, lin, dim3(256), 0, s, src, frame, n, out);
+    hipLaunchKernelGGL(k_gd_finish, lin, dim3(256), 0, s, src, alpha ? alpha : frame, n, out);
     return hipGetLastError();
 }
 
@@ -376,7 +449,7 @@ hipError_t guidedSelectLaunch(const float4* frame, const float4* feat, const flo
 // include/pt_demod.h's filter: guidedLaunch with k_dm_prep, k_dm_var and k_dm_finish around the shared passes.  floorA = albedo_floor, checked by
 // the caller; the other arguments as guidedLaunch's.
 hipError_t guidedDemodLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                             float floorA, float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s) {
+                             float floorA, float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s, const float4* alpha) {
     const int n = W * H;
     const dim3 lin((unsigned)((n + 255) / 256));
     const dim3 grid((unsigned)((W + GD_BX - 1) / GD_BX), (unsigned)((H + GD_BY - 1) / GD_BY));
@@ -391,7 +464,7 @@ hipError_t guidedDemodLaunch(const float4* frame, const float4* feat, const floa
             float4* t = src; src = dst; dst = t;
         }
     }
-    hipLaunchKernelGGL(k_dm_finish, lin, dim3(256), 0, s, src, guide, frame, n, floorA, out);
+    hipLaunchKernelGGL(k_dm_finish, lin, dim3(256), 0, s, src, guide, alpha ? alpha : frame, n, floorA, out);
     return hipGetLastError();
 }
 
@@ -416,4 +489,30 @@ hipError_t guidedDemodSelectLaunch(const float4* frame, const float4* feat, cons
     hipLaunchKernelGGL(k_dm_select, grid, dim3(GD_BX, GD_BY), 0, s, src, stats, guide, W, H, (float)minFrames, maxFrames, make_float2(rule[0], rule[1]),
                        make_float3(ov[0], ov[1], ov[2]), floorA, mask, count);
     return hipGetLastError();
+}
+
+// include/pt_fill.h's FRAME' into fill[W*H]: the prep kernel of the rule floorA selects (0: k_gd_prep, > 0: k_dm_prep) on the real FRAME, then
+// k_gd_fill; *count (zeroed here) = the holes filled.  sigma as guidedLaunch's (its luminance entry unused); col0, guide: scratch, free afterwards.
+hipError_t fillLaunch(const float4* frame, const float4* feat, int W, int H, const float sigma[4], float floorA, float4* col0, float4* guide, float4* fill,
+                      unsigned* count, hipStream_t s) {
+    const int n = W * H;
+    const dim3 lin((unsigned)((n + 255) / 256));
+    const dim3 grid((unsigned)((W + GD_BX - 1) / GD_BX), (unsigned)((H + GD_BY - 1) / GD_BY));
+    hipError_t e = hipMemsetAsync(count, 0, 4, s);
+    if (e != hipSuccess) return e;
+    if (floorA > 0.0f) hipLaunchKernelGGL(k_dm_prep, lin, dim3(256), 0, s, frame, feat, n, floorA, col0, guide);
+    else hipLaunchKernelGGL(k_gd_prep, lin, dim3(256), 0, s, frame, feat, n, col0, guide);
+    const float3 inv = make_float3(clampInv(1.0f / (sigma[1] * sigma[1])), clampInv(1.0f / (sigma[2] * sigma[2])), clampInv(1.0f / (sigma[3] * sigma[3])));
+    hipLaunchKernelGGL(k_gd_fill, grid, dim3(GD_BX, GD_BY), 0, s, frame, feat, (const float4*)col0, (const float4*)guide, fill, W, H, inv, floorA, count);
+    return hipGetLastError();
+}
+
+// include/pt_fill.h's filtered image: fillLaunch, then guidedLaunch (floorA == 0) or guidedDemodLaunch on FRAME' in place of the frame, the output's
+// alpha from the real FRAME.  Arguments as theirs; fill, count as fillLaunch's.
+hipError_t guidedFilledLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                              float floorA, float4* col0, float4* col1, float4* guide, float4* fill, float4* out, unsigned* count, hipStream_t s) {
+    const hipError_t e = fillLaunch(frame, feat, W, H, sigma, floorA, col0, guide, fill, count, s);
+    if (e != hipSuccess) return e;
+    if (floorA > 0.0f) return guidedDemodLaunch(fill, feat, stats, W, H, iterations, sigma, minFrames, floorA, col0, col1, guide, out, s, frame);
+    return guidedLaunch(fill, feat, stats, W, H, iterations, sigma, minFrames, col0, col1, guide, out, s, frame);
 }

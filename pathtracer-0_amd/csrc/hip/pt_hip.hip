@@ -31,6 +31,7 @@
 #include "../../../include/pt_guided.h"
 #include "../../../include/pt_steer.h"
 #include "../../../include/pt_demod.h"
+#include "../../../include/pt_fill.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -979,6 +980,13 @@ __global__ void __launch_bounds__(BLOCK) k_adaptive_select_mask(const unsigned* 
         blkCount[blockIdx.x] = t;
     }
 }
+// include/pt_fill.h's lattice as k_adaptive_select_mask's input: mask[y*W + x] = (x % stride == phaseX && y % stride == phaseY), W*H bytes
+__global__ void __launch_bounds__(BLOCK) k_lattice_mask(unsigned char* mask, int W, int n, int stride, int phaseX, int phaseY) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int y = i / W, x = i - y * W;
+    mask[i] = (x % stride == phaseX && y % stride == phaseY) ? 1 : 0;
+}
 // one block of BLOCK threads: blk[0..nb) counts -> exclusive offsets in place, *total = their sum
 __global__ void __launch_bounds__(BLOCK) k_adaptive_scan(unsigned* blk, int nb, unsigned* total) {
     __shared__ unsigned sv[BLOCK];
@@ -1186,6 +1194,7 @@ struct pt_ctx {
     unsigned char* dMatVD = nullptr;
     float4* dRpFrame = nullptr; float4* dRpStats = nullptr; unsigned* dRpKept = nullptr;
     float4* dStatsWhole = nullptr;  // a group's T gathered in pixel order on its first stream (reprojection, the guided filter)
+    float4* dFill = nullptr; unsigned* dFillCount = nullptr;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count, allocated on first use
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -2209,20 +2218,25 @@ hipError_t reprojectLaunch(const float4* rn, const float4* rh, const float4* fra
                            unsigned* kept, hipStream_t s);
 // the variance-guided filter of include/pt_guided.h (pt_guided.hip): device pointers only, enqueued on `s`
 hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                        float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s);
+                        float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s, const float4* alpha = nullptr);
 // ... and include/pt_steer.h's selection over it (pt_guided.hip)
 hipError_t guidedSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
                               int maxFrames, const float rule[2], const float ov[3], float4* col0, float4* col1, float4* guide, unsigned char* mask,
                               unsigned* count, hipStream_t s);
 // include/pt_demod.h: the three above on the illumination (pt_guided.hip, pt_reproject.hip); floorA = albedo_floor
 hipError_t guidedDemodLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                             float floorA, float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s);
+                             float floorA, float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s, const float4* alpha = nullptr);
 hipError_t guidedDemodSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4],
                                    int minFrames, int maxFrames, const float rule[2], const float ov[3], float floorA, float4* col0, float4* col1,
                                    float4* guide, unsigned char* mask, unsigned* count, hipStream_t s);
 hipError_t reprojectDemodLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
                                 int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float floorA, float4* outFrame,
                                 float4* outStats, unsigned* kept, hipStream_t s);
+// include/pt_fill.h (pt_guided.hip): FRAME' into fill, *count = the holes filled; and the guided filter (floorA == 0) or its demodulated variant on FRAME'
+hipError_t fillLaunch(const float4* frame, const float4* feat, int W, int H, const float sigma[4], float floorA, float4* col0, float4* guide, float4* fill,
+                      unsigned* count, hipStream_t s);
+hipError_t guidedFilledLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
+                              float floorA, float4* col0, float4* col1, float4* guide, float4* fill, float4* out, unsigned* count, hipStream_t s);
 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
@@ -2362,7 +2376,7 @@ int pt_destroy(pt_ctx* c) {
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
                     c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
-                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask};
+                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -3480,6 +3494,102 @@ int pt_render_adaptive_guided_demod(pt_ctx* c, int first_frame, int n_frames, co
     if (n_active) *n_active = 0;
     if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_render_adaptive_guided_demod: albedo_floor must be finite and > 0");
     return renderAdaptiveGuided(c, first_frame, n_frames, seeds, rule, albedo_floor, "pt_render_adaptive_guided_demod", n_active);
+}
+
+// ---- interleaved rendering (include/pt_fill.h): pt_render_mask over a lattice mask that every stream builds on its own device, and the prefill of
+// the unrendered pixels in front of the guided filter (its plumbing and scratch, with FRAME' and the filled count beside them)
+namespace {
+int renderLattice(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, int stride, int phaseX, int phaseY, int64_t* nActive) {
+    return renderSelected(c, firstFrame, nFrames, seeds, "pt_render_interleaved", [=](hipStream_t s, int nb) {
+        if (!c->dSelMask) HIP_TRY(hipMalloc((void**)&c->dSelMask, maskBytes(c) + 4));
+        const int n = c->W * c->H;
+        hipLaunchKernelGGL(k_lattice_mask, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, c->dSelMask, c->W, n, stride, phaseX, phaseY);
+        hipLaunchKernelGGL(k_adaptive_select_mask, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, (const unsigned char*)c->dSelMask,
+                           withOverlay(c, AdaptRule{}), c->dAdaptFlag, c->dAdaptBlk);
+        return 0;
+    }, nActive);
+}
+
+// include/pt_fill.h's albedo_floor: 0 (the plain rule) or include/pt_demod.h's
+bool fillFloorOk(float floorA) { return floorA == 0.0f || floorOk(floorA); }
+
+// FRAME' of the context's current image into on->dFill and, when `filter`, the guided filter over it into on->dDnOut; the filled count into
+// on->dFillCount.  All enqueued on on->stream.  sigma = (luminance, normal, depth, albedo); the luminance entry, iterations and minFrames count
+// only when `filter`.
+int filledImage(pt_ctx* c, bool filter, int iterations, const float sigma[4], int minFrames, float floorA, const char* who, pt_ctx** onOut) {
+    const std::string w(who);
+    if (filter && (iterations < 0 || iterations > 8)) return fail(PT_ERR_ARG, w + ": iterations must be in [0,8]");
+    if (filter && minFrames < 2) return fail(PT_ERR_ARG, w + ": min_frames must be >= 2");
+    for (int k = filter ? 0 : 1; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, w + ": every sigma must be > 0 (+inf switches its term off)");
+    pt_ctx* on = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
+    int rc;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &frame))) return rc;
+    if (filter) {
+        if ((rc = wholeStats(c, on, &stats))) return rc;
+        if (!stats) return fail(PT_ERR_ARG, w + ": the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
+    }
+    if ((rc = ensureFeatures(on))) return rc;
+    const size_t n = (size_t)c->W * c->H;
+    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut, &on->dFill}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
+    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
+    if (!on->dFillCount) HIP_TRY(hipMalloc((void**)&on->dFillCount, 4));
+    if (filter)
+        HIP_TRY(guidedFilledLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, floorA, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dFill,
+                                   on->dDnOut, on->dFillCount, on->stream));
+    else
+        HIP_TRY(fillLaunch(frame, on->dFeat, c->W, c->H, sigma, floorA, on->dDnCol[0], on->dDnGuide, on->dFill, on->dFillCount, on->stream));
+    *onOut = on;
+    return 0;
+}
+}  // namespace
+
+int pt_render_interleaved(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, int stride, int phase_x, int phase_y, int64_t* n_active) {
+    if (n_active) *n_active = 0;
+    if (!c || !seeds) return fail(PT_ERR_ARG, "pt_render_interleaved: null argument");
+    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_interleaved: n_frames must be >= 1");
+    if (stride < 1 || stride > 8) return fail(PT_ERR_ARG, "pt_render_interleaved: stride must be in [1,8]");
+    if (phase_x < 0 || phase_x >= stride || phase_y < 0 || phase_y >= stride) return fail(PT_ERR_ARG, "pt_render_interleaved: a phase must be in [0, stride)");
+    return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderLattice(k, first_frame, n_frames, seeds, stride, phase_x, phase_y, n); }, n_active);
+}
+
+int pt_fill_frame(pt_ctx* c, float sigma_normal, float sigma_depth, float sigma_albedo, float albedo_floor, float* rgba_out, int64_t* n_filled) {
+    if (n_filled) *n_filled = 0;
+    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_fill_frame: null argument");
+    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_fill_frame: albedo_floor must be 0 or finite and > 0");
+    const float sigma[4] = {1.0f, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = filledImage(c, false, 0, sigma, 2, albedo_floor, "pt_fill_frame", &on))) return rc;
+    unsigned filled = 0;
+    HIP_TRY(hipMemcpyAsync(rgba_out, on->dFill, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipMemcpyAsync(&filled, on->dFillCount, 4, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    if (n_filled) *n_filled = filled;
+    return PT_OK;
+}
+
+int pt_denoise_guided_filled(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
+                             float albedo_floor, float* rgba_out) {
+    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_filled: null argument");
+    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_denoise_guided_filled: albedo_floor must be 0 or finite and > 0");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_denoise_guided_filled", &on))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    return PT_OK;
+}
+
+int pt_read_display_denoised_guided_filled(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo,
+                                           int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
+    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_filled: null argument");
+    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_filled: albedo_floor must be 0 or finite and > 0");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    int rc;
+    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_read_display_denoised_guided_filled", &on))) return rc;
+    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
 }
 
 }  // extern "C"

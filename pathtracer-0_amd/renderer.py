@@ -145,6 +145,12 @@ def lib():
             L.pt_select_guided_demod.argtypes = [vp, C.POINTER(GuidedRule), cf, vp, C.POINTER(C.c_int64)]
             L.pt_render_adaptive_guided_demod.argtypes = [vp, ci, ci, vp, C.POINTER(GuidedRule), cf, C.POINTER(C.c_int64)]
             L.pt_reproject_frame_demod.argtypes = [vp, cf, cf, cf, ci, cf, C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_fill_frame"):                       # include/pt_fill.h
+            cf = C.c_float
+            L.pt_render_interleaved.argtypes = [vp, ci, ci, vp, ci, ci, ci, C.POINTER(C.c_int64)]
+            L.pt_fill_frame.argtypes = [vp, cf, cf, cf, cf, vp, C.POINTER(C.c_int64)]
+            L.pt_denoise_guided_filled.argtypes = [vp, ci, cf, cf, cf, cf, ci, cf, vp]
+            L.pt_read_display_denoised_guided_filled.argtypes = [vp, ci, cf, cf, cf, cf, ci, cf, ci, vp]
         _LIB = L
     return _LIB
 
@@ -391,28 +397,56 @@ class Renderer:
         g[0] = float(self.GUIDED_SIGMA_LUM if sigma_lum is None else sigma_lum)
         return g + [int(self.GUIDED_MIN_FRAMES if min_frames is None else min_frames)]
 
-    def denoise_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None, albedo_floor=None):
+    def denoise_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None, albedo_floor=None,
+                       fill=False):
         """the variance-guided filter over FRAME.rgb / FRAME.a, steered by T (pt_denoise_guided): (H, W, 4) float32, rgb = filtered mean,
         a = FRAME.a.  Needs moments (record_moments before rendering, or write_moments).  None takes the defaults above.
-        albedo_floor: a number filters the illumination mean / albedo instead (pt_denoise_guided_demod)."""
+        albedo_floor: a number filters the illumination mean / albedo instead (pt_denoise_guided_demod).
+        fill: reconstruct the pixels nothing was rendered into first (pt_denoise_guided_filled, include/pt_fill.h): after render_interleaved."""
         out = np.zeros((self.H, self.W, 4), dtype=np.float32)
         g = self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames)
-        if albedo_floor is None:
+        if fill:
+            _check(self._L.pt_denoise_guided_filled(self._h, int(iterations), *g, 0.0 if albedo_floor is None else float(albedo_floor), out.ctypes.data))
+        elif albedo_floor is None:
             _check(self._L.pt_denoise_guided(self._h, int(iterations), *g, out.ctypes.data))
         else:
             _check(self._L.pt_denoise_guided_demod(self._h, int(iterations), *g, float(albedo_floor), out.ctypes.data))
         return out
 
     def read_display_denoised_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None,
-                                     java_bytes=True, albedo_floor=None):
+                                     java_bytes=True, albedo_floor=None, fill=False):
         """denoise_guided()'s image converted to 8 bits as read_display converts a mean: (H, W, 3) uint8, top row first"""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
         g = self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames)
-        if albedo_floor is None:
-            _check(self._L.pt_read_display_denoised_guided(self._h, int(iterations), *g, 1 if java_bytes else 0, out.ctypes.data))
+        jb = 1 if java_bytes else 0
+        if fill:
+            _check(self._L.pt_read_display_denoised_guided_filled(self._h, int(iterations), *g, 0.0 if albedo_floor is None else float(albedo_floor), jb,
+                                                                  out.ctypes.data))
+        elif albedo_floor is None:
+            _check(self._L.pt_read_display_denoised_guided(self._h, int(iterations), *g, jb, out.ctypes.data))
         else:
-            _check(self._L.pt_read_display_denoised_guided_demod(self._h, int(iterations), *g, float(albedo_floor), 1 if java_bytes else 0, out.ctypes.data))
+            _check(self._L.pt_read_display_denoised_guided_demod(self._h, int(iterations), *g, float(albedo_floor), jb, out.ctypes.data))
         return out
+
+    # --- interleaved rendering (include/pt_fill.h) ------------------------------------------------------
+    def render_interleaved(self, first_frame, seeds, stride=2, phase_x=0, phase_y=0):
+        """Frames first_frame.. (one per seed) for the pixels x % stride == phase_x, y % stride == phase_y (FRAME order, row 0 = bottom):
+        render_mask with that mask, built on the device (pt_render_interleaved).  Returns how many pixels were rendered.  Show the image with
+        denoise_guided(fill=True) / read_display_denoised_guided(fill=True)."""
+        s = np.ascontiguousarray(seeds, dtype=np.int32)
+        n = C.c_int64(0)
+        _check(self._L.pt_render_interleaved(self._h, int(first_frame), int(s.size), s.ctypes.data, int(stride), int(phase_x), int(phase_y), C.byref(n)))
+        return n.value
+
+    def fill_frame(self, sigma_normal=None, sigma_depth=None, sigma_albedo=None, albedo_floor=None):
+        """FRAME with every pixel nothing was rendered into reconstructed from the rendered neighbours of its surface (pt_fill_frame):
+        ((H, W, 4) float32 in FRAME's layout, how many pixels were filled).  FRAME is not modified.  albedo_floor: a number interpolates
+        the illumination and gives a filled pixel its own albedo."""
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        g = self._sigmas(None, sigma_normal, sigma_depth, sigma_albedo)
+        n = C.c_int64(0)
+        _check(self._L.pt_fill_frame(self._h, g[1], g[2], g[3], 0.0 if albedo_floor is None else float(albedo_floor), out.ctypes.data, C.byref(n)))
+        return out, n.value
 
     # --- adaptive sampling steered by the guided filter (include/pt_steer.h) ---------------------------
     def render_mask(self, first_frame, seeds, mask):
