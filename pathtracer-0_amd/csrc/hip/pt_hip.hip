@@ -32,6 +32,7 @@
 #include "../../../include/pt_steer.h"
 #include "../../../include/pt_demod.h"
 #include "../../../include/pt_fill.h"
+#include "../../../include/pt_through.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -914,6 +915,124 @@ __global__ void __launch_bounds__(BLOCK) k_feature_record(DevScene sc, State st,
     r[0] = f0; r[1] = f1; r[2] = make_float4(D.x, D.y, D.z, __int_as_float(mat)); r[3] = f3;
 }
 
+// ---- seen-through feature records (include/pt_through.h).  One launch per link of the chain, behind the intersect launch of the same probe pool:
+// steps 2-8 of the header for every live lane.  The lane writes the record of the surface it found (and the segment that found it, the parity
+// probe's `rays`) and either its next ray into G0 / G1 with H reset, as k_feature_rays writes one, or a dead record.  The chain state between the
+// launches lives in X, planes of `plane` float4: X0 = (tint.rgb, L), X1 = (k | stack size << 8, first-hit material, sc0, sc1), X2 = (sc2, 0, 0, 0)
+// with 8-bit index-stack codes; STK == 32: X2, X3, X4 = the ten floats of the stack.  Exact numeric contract throughout.
+struct ThroughRule { int maxDepth; float minWeight; int lobes, flags; };
+PM_DEV bool finiteF(float x) { return __builtin_fabsf(x) <= 3.4028235e38f; }      // false for NaN and the infinities
+template <int STK>
+__global__ void __launch_bounds__(BLOCK) k_through_step(DevScene sc, State st, int n, ThroughRule rule, int step, float4* X, unsigned plane, float4* feat,
+                                                        float4* rays) {
+    const unsigned i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    const float4 g0 = st.G0[i], g1 = st.G1[i];
+    if (!(__float_as_uint(g1.w) & FL_ALIVE)) return;
+    const float4 h = st.H[i];
+    const vec3 O = v3(g0.x, g0.y, g0.z), D = v3(g0.w, g1.x, g1.y);
+    const int prim = __float_as_int(h.w);
+    float4* r = feat + 4 * (size_t)i;
+    float4* ry = rays + 2 * (size_t)i;
+    const float4 dead = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    Path p;
+    p.sc0 = p.sc1 = p.sc2 = 0u;
+#pragma unroll
+    for (int s = 0; s < 10; s++) p.sk[s] = 0u;
+    vec3 tint = v3(1.0f);
+    float L = 0.0f;
+    int k = 0, firstMat = -1;
+    if (step == 0) {                                              // trace()'s prologue (:816): {1.0029}
+        p.stackSize = 0;
+        if (STK) addToIndiceStack<STK>(p, stackElemAir<STK>()); else p.stackSize = 1;
+    } else {
+        const float4 x0 = X[i], x1 = X[plane + i];
+        tint = v3(x0.x, x0.y, x0.z); L = x0.w;
+        const unsigned ks = __float_as_uint(x1.x);
+        k = (int)(ks & 0xffu); p.stackSize = (int)(ks >> 8);
+        firstMat = __float_as_int(x1.y);
+        p.sc0 = __float_as_uint(x1.z); p.sc1 = __float_as_uint(x1.w);
+        if (STK == 8) p.sc2 = __float_as_uint(X[2 * (size_t)plane + i].x);
+        if (STK == 32) {
+            const float4 a = X[2 * (size_t)plane + i], b = X[3 * (size_t)plane + i], c = X[4 * (size_t)plane + i];
+            p.sk[0] = __float_as_uint(a.x); p.sk[1] = __float_as_uint(a.y); p.sk[2] = __float_as_uint(a.z); p.sk[3] = __float_as_uint(a.w);
+            p.sk[4] = __float_as_uint(b.x); p.sk[5] = __float_as_uint(b.y); p.sk[6] = __float_as_uint(b.z); p.sk[7] = __float_as_uint(b.w);
+            p.sk[8] = __float_as_uint(c.x); p.sk[9] = __float_as_uint(c.y);
+        }
+    }
+    if (!segmentHit(h.x, prim)) {                                  // step 1: the record written last stays; a first ray that misses gets k_feature_record's
+        if (step == 0) {
+            r[0] = make_float4(-1.0f, 0.0f, 0.0f, 0.0f); r[1] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+            r[2] = make_float4(D.x, D.y, D.z, __int_as_float(-1)); r[3] = dead;
+            ry[0] = make_float4(O.x, O.y, O.z, -1.0f); ry[1] = make_float4(D.x, D.y, D.z, __int_as_float(0));
+        }
+        st.G1[i] = dead;
+        return;
+    }
+    // step 2 (frag.glsl:823-830)
+    vec3 loc, N; int mat;
+    surfaceAt(sc, O, D, h.x, h.y, h.z, prim, loc, N, mat);
+    MatRec m = sc.mats[mat];
+    float uvx, uvy;
+    uvOfHit(sc, prim, h.y, h.z, st.HX, i, uvx, uvy);
+    if (m.hasMaps) applyMaps(sc, m, uvx, uvy, N);
+    L = L + h.x;
+    // step 3
+    const int code = (prim & PRIM_ELLIPSOID) ? 3 * 0x1000000 + (prim & 0xffffff) : 0x1000000 + prim;
+    const vec3 Kd = v3(m.Kd[0], m.Kd[1], m.Kd[2]);
+    const vec3 through = tint * Kd;
+    if (k == 0) firstMat = mat;
+    const int word = (k == 0 || !(rule.flags & 1)) ? mat : (int)(((unsigned)k << 24) | ((unsigned)firstMat << 12) | (unsigned)mat);
+    const float4 d0 = step == 0 ? make_float4(D.x, D.y, D.z, 0.0f) : r[2];
+    r[0] = make_float4(L, N.x, N.y, N.z);
+    r[1] = make_float4(through.x, through.y, through.z, __int_as_float(code));
+    r[2] = make_float4(d0.x, d0.y, d0.z, __int_as_float(word));
+    r[3] = make_float4(uvx, uvy, __int_as_float(k), 0.0f);
+    ry[0] = make_float4(O.x, O.y, O.z, h.x); ry[1] = make_float4(D.x, D.y, D.z, __int_as_float(k));
+    if (k >= rule.maxDepth) { st.G1[i] = dead; return; }          // step 4
+    // the rest of step 2 (:830-840)
+    const float ND = dot(N, D);
+    const vec3 Nf = N * (ND > 0.0f ? -1.0f : 1.0f);
+    float n1 = 1.0f, n2 = 1.0f;
+    if (STK) {                                                    // as shadeSegment restates :833-840, stale slot and full stack included
+        const float s0 = indiceStackSlot<STK>(sc, p, 0), s1 = indiceStackSlot<STK>(sc, p, 1);
+        if (ND < 0.0f) { const bool full = p.stackSize >= 10; n1 = (full || p.stackSize == 0) ? s1 : s0; n2 = full ? s0 : m.Ni; addToIndiceStack<STK>(p, stackElemOf<STK>(m)); }
+        else { n1 = s0; n2 = s1; removeFirstOfIndiceStack<STK>(p); }
+    }
+    // step 5: chooseRay's weights (:745-765), as chooseLobe computes them under the exact contract
+    float reflectionWeight = 1.0f - m.Pr;
+    const float clearcoatWeight = m.Pc;
+    float transmissionWeight = (m.Tr > 0.0f ? m.Tr : (m.Tf[0] > 0.0f ? (m.Tf[0] + m.Tf[1] + m.Tf[2]) / 3.0f : 0.0f));
+    float fresnel = 0.0f;
+    if (m.illum == 5 || m.illum == 7 || transmissionWeight > 0.0f) {
+        fresnel = fresnelReflectAmount<false>(n1, n2, Nf, D);
+        reflectionWeight += fresnel * m.Pr;
+        transmissionWeight *= (1.0f - fresnel);
+    }
+    const float diffuseWeight = (1.0f - m.Pm) * (1.0f - transmissionWeight) * (1.0f - fresnel);
+    const float totalWeight = diffuseWeight + reflectionWeight + clearcoatWeight + transmissionWeight;
+    reflectionWeight /= totalWeight; transmissionWeight /= totalWeight;
+    // steps 6 and 7
+    vec3 nd;
+    if ((rule.lobes & 1) && reflectionWeight >= rule.minWeight && reflectionWeight >= transmissionWeight) nd = reflect(D, Nf);
+    else if ((rule.lobes & 2) && transmissionWeight >= rule.minWeight) nd = refractT<false>(D, Nf, n1 / n2);
+    else { st.G1[i] = dead; return; }
+    if (!(finiteF(nd.x) && finiteF(nd.y) && finiteF(nd.z)) || (nd.x == 0.0f && nd.y == 0.0f && nd.z == 0.0f)) { st.G1[i] = dead; return; }
+    // step 8
+    k++;
+    st.G0[i] = make_float4(loc.x, loc.y, loc.z, nd.x);
+    st.G1[i] = make_float4(nd.y, nd.z, 0.0f, __uint_as_float(FL_ALIVE));
+    st.H[i] = make_float4(1e30f, 0.0f, 0.0f, __int_as_float(PRIM_NONE));
+    X[i] = make_float4(through.x, through.y, through.z, L);
+    X[plane + i] = make_float4(__uint_as_float((unsigned)k | ((unsigned)p.stackSize << 8)), __int_as_float(firstMat), __uint_as_float(p.sc0), __uint_as_float(p.sc1));
+    if (STK == 8) X[2 * (size_t)plane + i] = make_float4(__uint_as_float(p.sc2), 0.0f, 0.0f, 0.0f);
+    if (STK == 32) {
+        X[2 * (size_t)plane + i] = make_float4(__uint_as_float(p.sk[0]), __uint_as_float(p.sk[1]), __uint_as_float(p.sk[2]), __uint_as_float(p.sk[3]));
+        X[3 * (size_t)plane + i] = make_float4(__uint_as_float(p.sk[4]), __uint_as_float(p.sk[5]), __uint_as_float(p.sk[6]), __uint_as_float(p.sk[7]));
+        X[4 * (size_t)plane + i] = make_float4(__uint_as_float(p.sk[8]), __uint_as_float(p.sk[9]), 0.0f, 0.0f);
+    }
+}
+
 // ---- adaptive sampling (include/pt_adaptive.h).  The selection rule over the per-slot statistics T = (sY, sYY, n, 0), in the order the header states it
 // (float32, no contraction: the build's -ffp-contract=off, IEEE divides).  NaN anywhere: every comparison false, the pixel stays inactive.
 struct AdaptRule { float relErr, absErr, mouseX, mouseY, resolution; int minFrames, maxFrames; };
@@ -1195,6 +1314,8 @@ struct pt_ctx {
     float4* dRpFrame = nullptr; float4* dRpStats = nullptr; unsigned* dRpKept = nullptr;
     float4* dStatsWhole = nullptr;  // a group's T gathered in pixel order on its first stream (reprojection, the guided filter)
     float4* dFill = nullptr; unsigned* dFillCount = nullptr;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count, allocated on first use
+    // include/pt_through.h: the seen-through records (W*H x 4 float4) and their last segments (W*H x 2 float4) under thruRule, cached like dFeat
+    float4* dThru = nullptr; float4* dThruRays = nullptr; bool thruValid = false; pt_through_rule thruRule{};
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -2376,7 +2497,7 @@ int pt_destroy(pt_ctx* c) {
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
                     c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
-                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount};
+                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount, c->dThru, c->dThruRays};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -2404,7 +2525,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         return PT_OK;
     }
     if (bytes % 4) return fail(PT_ERR_ARG, "pt_set_buffer: size must be a multiple of 4 bytes");
-    c->featValid = false; c->featHValid = false;                  // any binding may move the camera or the scene under the feature records
+    c->featValid = false; c->featHValid = false; c->thruValid = false;                  // any binding may move the camera or the scene under the feature records
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
         case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
@@ -2437,7 +2558,7 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
         return PT_OK;
     }
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
-    c->featValid = false; c->featHValid = false;
+    c->featValid = false; c->featHValid = false; c->thruValid = false;
     c->sceneGen++;
     if (index == 0) { c->sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->skyW = w; c->skyH = h; }
     if ((size_t)index >= c->textures.size()) c->textures.resize((size_t)index + 1);
@@ -3147,6 +3268,65 @@ int ensureFeatures(pt_ctx* c) {
     return ensureFeaturesFor(c, fin, &c->dFeat, &c->featValid);
 }
 
+// include/pt_through.h's rule, checked
+int checkThrough(const pt_through_rule* r, const char* who) {
+    const std::string w(who);
+    if (!r) return fail(PT_ERR_ARG, w + ": null rule");
+    if (r->max_depth < 0 || r->max_depth > 8) return fail(PT_ERR_ARG, w + ": rule.max_depth must be in [0,8]");
+    if (!(r->min_weight > 0.0f && r->min_weight <= 1.0f)) return fail(PT_ERR_ARG, w + ": rule.min_weight must be in (0,1]");
+    if (r->lobes < 0 || r->lobes > 3) return fail(PT_ERR_ARG, w + ": rule.lobes must be in [0,3]");
+    if (r->flags & ~PT_THROUGH_KEY) return fail(PT_ERR_ARG, w + ": unknown rule.flags");
+    return 0;
+}
+// the seen-through records of the current frame inputs under `rule` (c->dThru) and their last segments (c->dThruRays): ensureFeaturesFor's probe
+// pool and ray kernel, then max_depth + 1 rounds of (intersect, k_through_step) — a fixed count, nothing read back in between: a round whose
+// lanes are all dead costs two launches that return at once
+int ensureThrough(pt_ctx* c, const pt_through_rule& rule, const char* who) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->thruValid && std::memcmp(&c->thruRule, &rule, sizeof(rule)) == 0) return 0;
+    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
+    FrameIn fin;
+    currentInputs(c, fin);
+    int rc;
+    if ((rc = claimFrameConstants(c))) return rc;
+    if ((rule.flags & PT_THROUGH_KEY) && c->sc.numMat > 4096)
+        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": PT_THROUGH_KEY packs a material index into 12 bits; the scene has more than 4096 materials");
+    c->thruValid = false;
+    const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
+    if (!c->dThru) HIP_TRY(hipMalloc((void**)&c->dThru, n * 64));
+    if (!c->dThruRays) HIP_TRY(hipMalloc((void**)&c->dThruRays, n * 32));
+    State st{};
+    Scratch scratch;
+    if ((rc = probePool(scratch, st, np, c->sc.numEllip > 0))) return rc;
+    float4* X = nullptr;
+    scratch.ptrs.push_back((void**)&X);
+    const int planes = c->niBits == 32 ? 5 : (c->niBits == 8 ? 3 : 2);
+    HIP_TRY(hipMalloc((void**)&X, np * 16 * planes));
+    if (st.HX) HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);
+    hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
+    // RAYTRACING == 0 (directDiffuse, frag.glsl:911-912) takes no step
+    const int depth = (rule.lobes == 0 || fin.params[9] != 1.0f) ? 0 : rule.max_depth;
+    const ThroughRule tr{depth, rule.min_weight, rule.lobes, rule.flags};
+    for (int step = 0; step <= depth; step++) {
+        if ((rc = probeIntersect(c, st, np, fin))) return rc;
+#define THROUGH_STEP(T) hipLaunchKernelGGL(k_through_step<T>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, tr, step, X, (unsigned)np, c->dThru, c->dThruRays)
+        if (c->niBits == 3) THROUGH_STEP(3);
+        else if (c->niBits == 8) THROUGH_STEP(8);
+        else if (c->niBits == 32) THROUGH_STEP(32);
+        else THROUGH_STEP(0);
+#undef THROUGH_STEP
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->thruRule = rule;
+    c->thruValid = true;
+    return 0;
+}
+
 // the denoised image of the context's current FRAME into on->dDnOut (W*H float4 on the device of *on), enqueued on on->stream
 int denoiseImage(pt_ctx* c, int iterations, const float sigma[4], pt_ctx** onOut) {
     if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise: iterations must be in [0,8]");
@@ -3516,7 +3696,9 @@ bool fillFloorOk(float floorA) { return floorA == 0.0f || floorOk(floorA); }
 // FRAME' of the context's current image into on->dFill and, when `filter`, the guided filter over it into on->dDnOut; the filled count into
 // on->dFillCount.  All enqueued on on->stream.  sigma = (luminance, normal, depth, albedo); the luminance entry, iterations and minFrames count
 // only when `filter`.
-int filledImage(pt_ctx* c, bool filter, int iterations, const float sigma[4], int minFrames, float floorA, const char* who, pt_ctx** onOut) {
+// thru: null = the first-hit records; else include/pt_through.h's records under that rule (checked by the caller) in their place
+int filledImage(pt_ctx* c, bool filter, int iterations, const float sigma[4], int minFrames, float floorA, const char* who, pt_ctx** onOut,
+                const pt_through_rule* thru = nullptr) {
     const std::string w(who);
     if (filter && (iterations < 0 || iterations > 8)) return fail(PT_ERR_ARG, w + ": iterations must be in [0,8]");
     if (filter && minFrames < 2) return fail(PT_ERR_ARG, w + ": min_frames must be >= 2");
@@ -3528,16 +3710,17 @@ int filledImage(pt_ctx* c, bool filter, int iterations, const float sigma[4], in
         if ((rc = wholeStats(c, on, &stats))) return rc;
         if (!stats) return fail(PT_ERR_ARG, w + ": the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
     }
-    if ((rc = ensureFeatures(on))) return rc;
+    if ((rc = thru ? ensureThrough(on, *thru, who) : ensureFeatures(on))) return rc;
+    const float4* feat = thru ? on->dThru : on->dFeat;
     const size_t n = (size_t)c->W * c->H;
     for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut, &on->dFill}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
     if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
     if (!on->dFillCount) HIP_TRY(hipMalloc((void**)&on->dFillCount, 4));
     if (filter)
-        HIP_TRY(guidedFilledLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, floorA, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dFill,
+        HIP_TRY(guidedFilledLaunch(frame, feat, stats, c->W, c->H, iterations, sigma, minFrames, floorA, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dFill,
                                    on->dDnOut, on->dFillCount, on->stream));
     else
-        HIP_TRY(fillLaunch(frame, on->dFeat, c->W, c->H, sigma, floorA, on->dDnCol[0], on->dDnGuide, on->dFill, on->dFillCount, on->stream));
+        HIP_TRY(fillLaunch(frame, feat, c->W, c->H, sigma, floorA, on->dDnCol[0], on->dDnGuide, on->dFill, on->dFillCount, on->stream));
     *onOut = on;
     return 0;
 }
@@ -3589,6 +3772,71 @@ int pt_read_display_denoised_guided_filled(pt_ctx* c, int iterations, float sigm
     pt_ctx* on = nullptr;
     int rc;
     if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_read_display_denoised_guided_filled", &on))) return rc;
+    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
+}
+
+// ---- seen-through feature records (include/pt_through.h): the records beside the first-hit ones, and include/pt_fill.h's calls on them
+int pt_read_features_through(pt_ctx* c, const pt_through_rule* rule, float* out) {
+    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features_through: null argument");
+    int rc;
+    if ((rc = checkThrough(rule, "pt_read_features_through"))) return rc;
+    pt_ctx* on = firstStream(c);
+    if ((rc = ensureThrough(on, *rule, "pt_read_features_through"))) return rc;
+    HIP_TRY(hipMemcpy(out, on->dThru, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_read_through_rays(pt_ctx* c, const pt_through_rule* rule, float* out) {
+    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_through_rays: null argument");
+    int rc;
+    if ((rc = checkThrough(rule, "pt_read_through_rays"))) return rc;
+    pt_ctx* on = firstStream(c);
+    if ((rc = ensureThrough(on, *rule, "pt_read_through_rays"))) return rc;
+    HIP_TRY(hipMemcpy(out, on->dThruRays, (size_t)c->W * c->H * 32, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_fill_frame_through(pt_ctx* c, const pt_through_rule* rule, float sigma_normal, float sigma_depth, float sigma_albedo, float albedo_floor,
+                          float* rgba_out, int64_t* n_filled) {
+    if (n_filled) *n_filled = 0;
+    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_fill_frame_through: null argument");
+    int rc;
+    if ((rc = checkThrough(rule, "pt_fill_frame_through"))) return rc;
+    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_fill_frame_through: albedo_floor must be 0 or finite and > 0");
+    const float sigma[4] = {1.0f, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    if ((rc = filledImage(c, false, 0, sigma, 2, albedo_floor, "pt_fill_frame_through", &on, rule))) return rc;
+    unsigned filled = 0;
+    HIP_TRY(hipMemcpyAsync(rgba_out, on->dFill, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipMemcpyAsync(&filled, on->dFillCount, 4, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    if (n_filled) *n_filled = filled;
+    return PT_OK;
+}
+
+int pt_denoise_guided_through(pt_ctx* c, const pt_through_rule* rule, int iterations, float sigma_lum, float sigma_normal, float sigma_depth,
+                              float sigma_albedo, int min_frames, float albedo_floor, float* rgba_out) {
+    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_through: null argument");
+    int rc;
+    if ((rc = checkThrough(rule, "pt_denoise_guided_through"))) return rc;
+    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_denoise_guided_through: albedo_floor must be 0 or finite and > 0");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_denoise_guided_through", &on, rule))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    return PT_OK;
+}
+
+int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* rule, int iterations, float sigma_lum, float sigma_normal,
+                                            float sigma_depth, float sigma_albedo, int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
+    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_through: null argument");
+    int rc;
+    if ((rc = checkThrough(rule, "pt_read_display_denoised_guided_through"))) return rc;
+    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_through: albedo_floor must be 0 or finite and > 0");
+    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
+    pt_ctx* on = nullptr;
+    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_read_display_denoised_guided_through", &on, rule))) return rc;
     return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
 }
 

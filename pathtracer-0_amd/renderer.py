@@ -151,6 +151,14 @@ def lib():
             L.pt_fill_frame.argtypes = [vp, cf, cf, cf, cf, vp, C.POINTER(C.c_int64)]
             L.pt_denoise_guided_filled.argtypes = [vp, ci, cf, cf, cf, cf, ci, cf, vp]
             L.pt_read_display_denoised_guided_filled.argtypes = [vp, ci, cf, cf, cf, cf, ci, cf, ci, vp]
+        if hasattr(L, "pt_read_features_through"):            # include/pt_through.h
+            cf = C.c_float
+            tr = C.POINTER(ThroughRule)
+            L.pt_read_features_through.argtypes = [vp, tr, vp]
+            L.pt_read_through_rays.argtypes = [vp, tr, vp]
+            L.pt_fill_frame_through.argtypes = [vp, tr, cf, cf, cf, cf, vp, C.POINTER(C.c_int64)]
+            L.pt_denoise_guided_through.argtypes = [vp, tr, ci, cf, cf, cf, cf, ci, cf, vp]
+            L.pt_read_display_denoised_guided_through.argtypes = [vp, tr, ci, cf, cf, cf, cf, ci, cf, ci, vp]
         _LIB = L
     return _LIB
 
@@ -159,6 +167,11 @@ class GuidedRule(C.Structure):
     """pt_guided_rule of include/pt_steer.h"""
     _fields_ = [("iterations", C.c_int), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
                 ("min_frames", C.c_int), ("rel_err", C.c_float), ("abs_err", C.c_float), ("max_frames", C.c_int)]
+
+
+class ThroughRule(C.Structure):
+    """pt_through_rule of include/pt_through.h"""
+    _fields_ = [("max_depth", C.c_int), ("min_weight", C.c_float), ("lobes", C.c_int), ("flags", C.c_int)]
 
 
 class PtError(RuntimeError):
@@ -398,14 +411,20 @@ class Renderer:
         return g + [int(self.GUIDED_MIN_FRAMES if min_frames is None else min_frames)]
 
     def denoise_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None, albedo_floor=None,
-                       fill=False):
+                       fill=False, through=None):
         """the variance-guided filter over FRAME.rgb / FRAME.a, steered by T (pt_denoise_guided): (H, W, 4) float32, rgb = filtered mean,
         a = FRAME.a.  Needs moments (record_moments before rendering, or write_moments).  None takes the defaults above.
         albedo_floor: a number filters the illumination mean / albedo instead (pt_denoise_guided_demod).
-        fill: reconstruct the pixels nothing was rendered into first (pt_denoise_guided_filled, include/pt_fill.h): after render_interleaved."""
+        fill: reconstruct the pixels nothing was rendered into first (pt_denoise_guided_filled, include/pt_fill.h): after render_interleaved.
+        through: with fill, a through_rule(): fill and filter on the seen-through records (pt_denoise_guided_through, include/pt_through.h)."""
         out = np.zeros((self.H, self.W, 4), dtype=np.float32)
         g = self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames)
-        if fill:
+        if through is not None:
+            if not fill:
+                raise ValueError("through= needs fill=True")
+            _check(self._L.pt_denoise_guided_through(self._h, C.byref(through), int(iterations), *g, 0.0 if albedo_floor is None else float(albedo_floor),
+                                                     out.ctypes.data))
+        elif fill:
             _check(self._L.pt_denoise_guided_filled(self._h, int(iterations), *g, 0.0 if albedo_floor is None else float(albedo_floor), out.ctypes.data))
         elif albedo_floor is None:
             _check(self._L.pt_denoise_guided(self._h, int(iterations), *g, out.ctypes.data))
@@ -414,12 +433,17 @@ class Renderer:
         return out
 
     def read_display_denoised_guided(self, iterations=5, sigma_lum=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None, min_frames=None,
-                                     java_bytes=True, albedo_floor=None, fill=False):
+                                     java_bytes=True, albedo_floor=None, fill=False, through=None):
         """denoise_guided()'s image converted to 8 bits as read_display converts a mean: (H, W, 3) uint8, top row first"""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
         g = self._guided_args(sigma_lum, sigma_normal, sigma_depth, sigma_albedo, min_frames)
         jb = 1 if java_bytes else 0
-        if fill:
+        if through is not None:
+            if not fill:
+                raise ValueError("through= needs fill=True")
+            _check(self._L.pt_read_display_denoised_guided_through(self._h, C.byref(through), int(iterations), *g,
+                                                                   0.0 if albedo_floor is None else float(albedo_floor), jb, out.ctypes.data))
+        elif fill:
             _check(self._L.pt_read_display_denoised_guided_filled(self._h, int(iterations), *g, 0.0 if albedo_floor is None else float(albedo_floor), jb,
                                                                   out.ctypes.data))
         elif albedo_floor is None:
@@ -438,15 +462,50 @@ class Renderer:
         _check(self._L.pt_render_interleaved(self._h, int(first_frame), int(s.size), s.ctypes.data, int(stride), int(phase_x), int(phase_y), C.byref(n)))
         return n.value
 
-    def fill_frame(self, sigma_normal=None, sigma_depth=None, sigma_albedo=None, albedo_floor=None):
+    def fill_frame(self, sigma_normal=None, sigma_depth=None, sigma_albedo=None, albedo_floor=None, through=None):
         """FRAME with every pixel nothing was rendered into reconstructed from the rendered neighbours of its surface (pt_fill_frame):
         ((H, W, 4) float32 in FRAME's layout, how many pixels were filled).  FRAME is not modified.  albedo_floor: a number interpolates
         the illumination and gives a filled pixel its own albedo."""
         out = np.zeros((self.H, self.W, 4), dtype=np.float32)
         g = self._sigmas(None, sigma_normal, sigma_depth, sigma_albedo)
         n = C.c_int64(0)
-        _check(self._L.pt_fill_frame(self._h, g[1], g[2], g[3], 0.0 if albedo_floor is None else float(albedo_floor), out.ctypes.data, C.byref(n)))
+        fl = 0.0 if albedo_floor is None else float(albedo_floor)
+        if through is not None:                                   # a through_rule(): the seen-through records in place of the first-hit ones
+            _check(self._L.pt_fill_frame_through(self._h, C.byref(through), g[1], g[2], g[3], fl, out.ctypes.data, C.byref(n)))
+        else:
+            _check(self._L.pt_fill_frame(self._h, g[1], g[2], g[3], fl, out.ctypes.data, C.byref(n)))
         return out, n.value
+
+    # --- seen-through feature records (include/pt_through.h) --------------------------------------------
+    THROUGH_REFLECT, THROUGH_TRANSMIT, THROUGH_KEY = 1, 2, 1
+    # defaults of through_rule: the variant of scripts/through_quality.py that is best on the filled metal pixels of C3 and C6 at 1080p among those
+    # that lose on no scene's overall clamped error at 16 lattice frames (profiles/r15_through_quality.txt, DESIGN.md 2.14): reflection only, at
+    # 0.8, without the key.  Both lobes at 0.5 lose on C3 and C6.  No call takes a rule unless it is given one (through=None).
+    THROUGH_DEPTH = 4
+    THROUGH_MIN_WEIGHT = 0.8
+    THROUGH_LOBES = 1
+    THROUGH_USE_KEY = False
+
+    def through_rule(self, max_depth=None, min_weight=None, lobes=None, key=None):
+        """the pt_through_rule of these arguments; None takes the defaults above"""
+        key = self.THROUGH_USE_KEY if key is None else key
+        return ThroughRule(int(self.THROUGH_DEPTH if max_depth is None else max_depth), float(self.THROUGH_MIN_WEIGHT if min_weight is None else min_weight),
+                           int(self.THROUGH_LOBES if lobes is None else lobes), self.THROUGH_KEY if key else 0)
+
+    def read_features_through(self, rule=None):
+        """the feature records followed through mirrors and glass (pt_read_features_through): (H, W, 16) float32 in read_features' layout, with
+        the chain's length L in place of t, tint * Kd in place of Kd, the surface word in place of the material and k in slot 14"""
+        rule = self.through_rule() if rule is None else rule
+        out = np.zeros((self.H, self.W, 16), dtype=np.float32)
+        _check(self._L.pt_read_features_through(self._h, C.byref(rule), out.ctypes.data))
+        return out
+
+    def read_through_rays(self, rule=None):
+        """(H, W, 8) float32: (O, t, D, k as int32 bits) of the segment that found each pixel's recorded surface (pt_read_through_rays)"""
+        rule = self.through_rule() if rule is None else rule
+        out = np.zeros((self.H, self.W, 8), dtype=np.float32)
+        _check(self._L.pt_read_through_rays(self._h, C.byref(rule), out.ctypes.data))
+        return out
 
     # --- adaptive sampling steered by the guided filter (include/pt_steer.h) ---------------------------
     def render_mask(self, first_frame, seeds, mask):
