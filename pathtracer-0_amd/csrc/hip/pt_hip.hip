@@ -33,6 +33,7 @@
 #include "../../../include/pt_demod.h"
 #include "../../../include/pt_fill.h"
 #include "../../../include/pt_through.h"
+#include "../../../include/pt_motion.h"
 #include "pt_device.hpp"
 
 #include <algorithm>
@@ -1316,6 +1317,13 @@ struct pt_ctx {
     float4* dFill = nullptr; unsigned* dFillCount = nullptr;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count, allocated on first use
     // include/pt_through.h: the seen-through records (W*H x 4 float4) and their last segments (W*H x 2 float4) under thruRule, cached like dFeat
     float4* dThru = nullptr; float4* dThruRays = nullptr; bool thruValid = false; pt_through_rule thruRule{};
+    // include/pt_motion.h.  otherGen counts the uploads that are not geometry (bindings 5, 14 and textures) beside sceneGen, which counts all;
+    // camWrites counts every write of a camera record, so that a mark can tell that its image's record is still the one it saw.  The mark: Rh
+    // (dMarkFeat), the primitives' positions then on the device (3 float4 each) and on the host (9 floats per triangle, 10 per ellipsoid); the
+    // positions now are packed per call into dMoveTri / dMoveEl
+    uint64_t otherGen = 0, camWrites = 0;
+    struct Mark { bool valid = false; int image = 0; uint64_t camWrites = 0, otherGen = 0; int nTri = 0, nEl = 0; std::vector<float> tri, el; } mark;
+    float4* dMarkFeat = nullptr; float4* dMarkTri = nullptr; float4* dMarkEl = nullptr; float4* dMoveTri = nullptr; float4* dMoveEl = nullptr;
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -2145,6 +2153,7 @@ void recordCamera(pt_ctx* c) {
     pt_ctx::Cam& k = c->cam[c->curImage];
     k.valid = currentInputs(c, k.in);
     k.sceneGen = c->sceneGen;
+    c->camWrites++;
 }
 
 // A single context's accumulator slots (FRAME or T) to and from a whole image in host pixel order, on k->stream, synchronised.  A whole-image
@@ -2204,7 +2213,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
         DevScene dsc = c->sc; dsc.ldsNodes = 0; dsc.ldsTris = 0;                    // no LDS tile in this kernel
         hipLaunchKernelGGL(k_debug_heatmap, dim3((c->nLocal + 63) / 64), dim3(64), 0, s, dsc, b, c->dFc, c->dImage[c->curImage], firstFrame, nFrames);
         HIP_TRY(hipGetLastError());
-        c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true};
+        c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true}; c->camWrites++;
         return 0;
     }
     if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
@@ -2302,7 +2311,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     c->lastSubmitJobs = nJobs64; c->jobsThisImage += nJobs64;
     pt_ctx::Entry e; e.jobEnd = c->streamJobs; e.f0 = f0; e.nFrames = nFrames; e.firstFrame = firstFrame; e.image = c->curImage;
     c->pending.push_back(e);
-    c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true};   // the image's camera (include/pt_reproject.h)
+    c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true}; c->camWrites++;   // the image's camera (include/pt_reproject.h)
     c->draining = false; c->launched = (unsigned)N;              // (if the pool had run dry, k_submit dropped the tail queue)
     c->submitEpoch++;                                            // the groups in flight were launched for another tail: their view of it no longer counts
     HIP_TRY(hipGetLastError());
@@ -2353,6 +2362,10 @@ hipError_t guidedDemodSelectLaunch(const float4* frame, const float4* feat, cons
 hipError_t reprojectDemodLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
                                 int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float floorA, float4* outFrame,
                                 float4* outStats, unsigned* kept, hipStream_t s);
+// include/pt_motion.h (pt_reproject.hip): geo = triangles now / then, ellipsoids now / then (3 float4 per primitive), counts likewise
+hipError_t reprojectMovedLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
+                                int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float floorA, const float4* const geo[4],
+                                const int counts[4], float4* outFrame, float4* outStats, unsigned* kept, hipStream_t s);
 // include/pt_fill.h (pt_guided.hip): FRAME' into fill, *count = the holes filled; and the guided filter (floorA == 0) or its demodulated variant on FRAME'
 hipError_t fillLaunch(const float4* frame, const float4* feat, int W, int H, const float sigma[4], float floorA, float4* col0, float4* guide, float4* fill,
                       unsigned* count, hipStream_t s);
@@ -2497,7 +2510,8 @@ int pt_destroy(pt_ctx* c) {
     void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
                     c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
-                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount, c->dThru, c->dThruRays};
+                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount, c->dThru, c->dThruRays,
+                    c->dMarkFeat, c->dMarkTri, c->dMarkEl, c->dMoveTri, c->dMoveEl};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -2544,6 +2558,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
     }
     c->sceneDirty = true;
     c->sceneGen++;
+    if (binding == PT_BIND_IMPLICITS || binding == PT_BIND_MATERIALS) c->otherGen++;      // not geometry (include/pt_motion.h)
     return PT_OK;
 }
 
@@ -2559,7 +2574,7 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
     }
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
     c->featValid = false; c->featHValid = false; c->thruValid = false;
-    c->sceneGen++;
+    c->sceneGen++; c->otherGen++;
     if (index == 0) { c->sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->skyW = w; c->skyH = h; }
     if ((size_t)index >= c->textures.size()) c->textures.resize((size_t)index + 1);
     c->textures[index].rgba.assign(rgba8, rgba8 + (size_t)w * h * 4); c->textures[index].w = w; c->textures[index].h = h;
@@ -2575,7 +2590,7 @@ int pt_reset_frame(pt_ctx* c) {
     if ((rc = flushStream(c))) return rc;
     HIP_TRY(hipMemsetAsync(c->dImage[c->curImage], 0, (size_t)c->nSlotsImg * 16, c->stream));
     if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));      // the statistics describe this image
-    c->cam[c->curImage].valid = false;
+    c->cam[c->curImage].valid = false; c->camWrites++;
     return PT_OK;
 }
 
@@ -2605,7 +2620,7 @@ int pt_next_image(pt_ctx* c) {
     int rc;
     if ((rc = pump(c, PUMP_IMAGE, next))) return rc;              // nothing may still be on its way into the image taken over
     c->curImage = next;
-    c->cam[next].valid = false;
+    c->cam[next].valid = false; c->camWrites++;
     if (c->jobsThisImage) c->jobsPerImage = c->jobsThisImage;
     c->jobsThisImage = 0;
     HIP_TRY(hipMemsetAsync(c->dImage[next], 0, (size_t)c->nSlotsImg * 16, c->stream));
@@ -3451,6 +3466,29 @@ int pt_read_display_denoised_guided_demod(pt_ctx* c, int iterations, float sigma
 // ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
 // every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
 namespace {
+// the reprojected image (on->dRpFrame, on->dRpStats when `stats`, on->dRpKept; enqueued on on->stream) into the current image of `c`, whose camera
+// becomes the current inputs
+int storeReprojected(pt_ctx* c, pt_ctx* on, bool stats, int64_t* nKept) {
+    const size_t n = (size_t)c->W * c->H;
+    int rc;
+    unsigned kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, on->dRpKept, 4, hipMemcpyDeviceToHost, on->stream));
+    if (!c->multi) {                                              // the result into the current image (a copy: pt_frame_device pointers stay valid)
+        HIP_TRY(hipMemcpyAsync(c->dImage[c->curImage], on->dRpFrame, n * 16, hipMemcpyDeviceToDevice, c->stream));
+        if (stats) HIP_TRY(hipMemcpyAsync(c->dStats, on->dRpStats, n * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        recordCamera(c);
+    } else {
+        std::vector<float> hf(n * 4), hostStats(stats ? n * 4 : 0);
+        HIP_TRY(hipMemcpyAsync(hf.data(), on->dRpFrame, n * 16, hipMemcpyDeviceToHost, on->stream));
+        if (stats) HIP_TRY(hipMemcpyAsync(hostStats.data(), on->dRpStats, n * 16, hipMemcpyDeviceToHost, on->stream));
+        HIP_TRY(hipStreamSynchronize(on->stream));
+        const float* pf = hf.data(); const float* ps = stats ? hostStats.data() : nullptr;
+        if ((rc = multiRun(*c->multi, [pf, ps](pt_ctx* k) { return writeFrame(k, pf, ps); }))) return rc;
+    }
+    *nKept = kept;
+    return 0;
+}
 // floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor (checked by the caller)
 int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept) {
     if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: max_history must be >= 1");
@@ -3502,23 +3540,7 @@ int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol,
     else
         HIP_TRY(reprojectLaunch(on->dFeat, same ? on->dFeat : on->dFeatH, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
                                 (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept, on->stream));
-    unsigned kept = 0;
-    HIP_TRY(hipMemcpyAsync(&kept, on->dRpKept, 4, hipMemcpyDeviceToHost, on->stream));
-    if (!c->multi) {                                              // the result into the current image (a copy: pt_frame_device pointers stay valid)
-        HIP_TRY(hipMemcpyAsync(c->dImage[c->curImage], on->dRpFrame, n * 16, hipMemcpyDeviceToDevice, c->stream));
-        if (stats) HIP_TRY(hipMemcpyAsync(c->dStats, on->dRpStats, n * 16, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        recordCamera(c);
-    } else {
-        std::vector<float> hf(n * 4), hostStats(stats ? n * 4 : 0);
-        HIP_TRY(hipMemcpyAsync(hf.data(), on->dRpFrame, n * 16, hipMemcpyDeviceToHost, on->stream));
-        if (stats) HIP_TRY(hipMemcpyAsync(hostStats.data(), on->dRpStats, n * 16, hipMemcpyDeviceToHost, on->stream));
-        HIP_TRY(hipStreamSynchronize(on->stream));
-        const float* pf = hf.data(); const float* ps = stats ? hostStats.data() : nullptr;
-        if ((rc = multiRun(*c->multi, [pf, ps](pt_ctx* k) { return writeFrame(k, pf, ps); }))) return rc;
-    }
-    *nKept = kept;
-    return 0;
+    return storeReprojected(c, on, stats != nullptr, nKept);
 }
 }  // namespace
 
@@ -3537,6 +3559,161 @@ int pt_reproject_frame_demod(pt_ctx* c, float max_history, float depth_tol, floa
     if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: albedo_floor must be finite and > 0");
     int64_t n = 0;
     const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
+    if (n_kept) *n_kept = n;
+    return rc;
+}
+
+namespace {
+// ---- include/pt_motion.h: the mark and the reprojection across moved geometry
+// the vertices of the triangles of binding 3 (9 floats each) and centre, stretch, rot, r of the ellipsoids of binding 7 (10 floats each), from the host copies
+void motionPositions(const pt_ctx* c, std::vector<float>& tri, int* nTri, std::vector<float>& el, int* nEl) {
+    const size_t nt = c->tris.size() / 40;
+    tri.resize(nt * 9);
+    for (size_t t = 0; t < nt; t++)
+        for (int v = 0; v < 3; v++) std::memcpy(&tri[9 * t + 3 * v], &c->tris[40 * t + 4 * v], 12);
+    int ne = c->ellip.empty() ? 0 : (int)c->ellip[0];
+    if (ne < 0 || c->ellip.size() < (size_t)1 + 11 * (size_t)ne) ne = 0;      // (buildScene refuses such a buffer)
+    el.resize((size_t)ne * 10);
+    const float* E = c->ellip.data();
+    for (int i = 0; i < ne; i++) {
+        for (int k = 0; k < 3; k++) { el[10 * i + k] = E[1 + 3 * i + k]; el[10 * i + 3 + k] = E[1 + ne * 3 + 3 * i + k]; el[10 * i + 6 + k] = E[1 + ne * 6 + 3 * i + k]; }
+        el[10 * i + 9] = E[1 + ne * 9 + i];
+    }
+    *nTri = (int)nt; *nEl = ne;
+}
+// ... as the kernel reads them: triangle (A, flag), (B, 0), (C, 0); ellipsoid (c, r), (stretch, flag), (rot, 0).  then == nullptr: the mark's own copy, flags 0;
+// else flag = 0 unmoved (every float compares equal), 1 moved, 2 a moved ellipsoid with a rot component != 0 then or now
+void motionPack(const std::vector<float>& tri, int nTri, const std::vector<float>& el, int nEl, const pt_ctx::Mark* then, std::vector<float4>& outTri,
+                std::vector<float4>& outEl) {
+    auto asf = [](int u) { float f; std::memcpy(&f, &u, 4); return f; };
+    outTri.resize(std::max<size_t>((size_t)nTri * 3, 1)); outEl.resize(std::max<size_t>((size_t)nEl * 3, 1));
+    for (int t = 0; t < nTri; t++) {
+        const float* T = &tri[9 * (size_t)t];
+        int flag = 0;
+        if (then) {
+            flag = t < then->nTri ? 0 : 1;
+            for (int k = 0; k < 9 && !flag; k++) if (!(T[k] == then->tri[9 * (size_t)t + k])) flag = 1;
+        }
+        outTri[3 * (size_t)t] = make_float4(T[0], T[1], T[2], asf(flag)); outTri[3 * (size_t)t + 1] = make_float4(T[3], T[4], T[5], 0.0f);
+        outTri[3 * (size_t)t + 2] = make_float4(T[6], T[7], T[8], 0.0f);
+    }
+    for (int i = 0; i < nEl; i++) {
+        const float* E = &el[10 * (size_t)i];
+        int flag = 0;
+        if (then) {
+            flag = i < then->nEl ? 0 : 1;
+            for (int k = 0; k < 10 && !flag; k++) if (!(E[k] == then->el[10 * (size_t)i + k])) flag = 1;
+            if (flag && i < then->nEl)
+                for (int k = 6; k < 9; k++) if (E[k] != 0.0f || then->el[10 * (size_t)i + k] != 0.0f) flag = 2;
+        }
+        outEl[3 * (size_t)i] = make_float4(E[0], E[1], E[2], E[9]); outEl[3 * (size_t)i + 1] = make_float4(E[3], E[4], E[5], asf(flag));
+        outEl[3 * (size_t)i + 2] = make_float4(E[6], E[7], E[8], 0.0f);
+    }
+}
+
+int motionMark(pt_ctx* c) {
+    int rc;
+    if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_motion_mark"))) return rc;
+    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
+    else if ((rc = pt_synchronize(c))) return rc;                 // all submitted work lands first
+    pt_ctx* on = firstStream(c);
+    const pt_ctx::Cam h = on->cam[on->curImage];
+    if (!h.valid) return fail(PT_ERR_ARG, "pt_motion_mark: the current image has no camera (render or pt_write_frame first)");
+    if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_motion_mark: a scene buffer or texture was uploaded since the image's camera was recorded");
+    if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_motion_mark: the image was rendered with DEBUG != 0");
+    if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
+        return fail(PT_ERR_ARG, "pt_motion_mark: the image's camera has Parameters that do not match the image size");
+    on->mark.valid = false;
+    // (a) Rh, through the cache pt_reproject_frame keeps, into a buffer that later uploads leave alone
+    if (on->featHValid && std::memcmp(&on->featHIn, &h.in, sizeof(FrameIn)) != 0) on->featHValid = false;
+    if ((rc = ensureFeaturesFor(on, h.in, &on->dFeatH, &on->featHValid))) return rc;
+    on->featHIn = h.in;
+    const size_t n = (size_t)c->W * c->H;
+    if (!on->dMarkFeat) HIP_TRY(hipMalloc((void**)&on->dMarkFeat, n * 64));
+    HIP_TRY(hipMemcpyAsync(on->dMarkFeat, on->dFeatH, n * 64, hipMemcpyDeviceToDevice, on->stream));
+    // (b), (c) where the primitives are
+    pt_ctx::Mark& m = on->mark;
+    motionPositions(on, m.tri, &m.nTri, m.el, &m.nEl);
+    std::vector<float4> pt, pe;
+    motionPack(m.tri, m.nTri, m.el, m.nEl, nullptr, pt, pe);
+    if ((rc = uploadVec((void**)&on->dMarkTri, pt.data(), pt.size() * 16, on->stream))) return rc;
+    if ((rc = uploadVec((void**)&on->dMarkEl, pe.data(), pe.size() * 16, on->stream))) return rc;
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    // (d)
+    m.image = on->curImage; m.camWrites = on->camWrites; m.otherGen = on->otherGen;
+    m.valid = true;
+    return PT_OK;
+}
+
+// reprojectImage with Rh and the primitives' old positions from the mark
+int reprojectMovedImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept) {
+    if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: max_history must be >= 1");
+    if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: depth_tol must be > 0");
+    if (!(normalTol >= -1.0f && normalTol <= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: normal_tol must be in [-1, 1]");
+    if (flags & ~PT_REPROJECT_ALL_MATERIALS) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: unknown flags");
+    if (!(floorA == 0.0f || floorOk(floorA))) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: albedo_floor must be 0 or finite and > 0");
+    pt_ctx* on = nullptr; const float4* frame = nullptr;
+    int rc;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_reproject_frame_moved", &on, &frame))) return rc;
+    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
+    else if ((rc = pt_synchronize(c))) return rc;
+    FrameIn cur;
+    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
+    const float* P = on->params.data();
+    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
+    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame_moved: DEBUG != 0 renders the traversal heat map, which has no surfaces to carry");
+    pt_ctx::Mark& m = on->mark;
+    if (!m.valid) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: no mark (pt_motion_mark first; a mark serves one call)");
+    if (m.image != on->curImage) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: the mark belongs to another image");
+    const pt_ctx::Cam h = on->cam[on->curImage];
+    if (!h.valid || m.camWrites != on->camWrites)
+        return fail(PT_ERR_ARG, "pt_reproject_frame_moved: the image's camera is no longer the marked one (a render, pt_write_frame, pt_reset_frame or pt_next_image since the mark)");
+    if (m.otherGen != on->otherGen) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: binding 5, binding 14 or a texture was uploaded since the mark");
+    // Rn in the scene as it is now (builds it when an upload is pending)
+    if ((rc = ensureFeaturesFor(on, cur, &on->dFeat, &on->featValid))) return rc;
+    HIP_TRY(hipSetDevice(on->device));
+    const size_t n = (size_t)c->W * c->H;
+    if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
+    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
+    const float4* stats = nullptr;
+    if ((rc = wholeStats(c, on, &stats))) return rc;
+    if (stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
+    // where the primitives are now, with the moved ones flagged
+    std::vector<float> tri, el; int nTri = 0, nEl = 0;
+    motionPositions(on, tri, &nTri, el, &nEl);
+    std::vector<float4> pt, pe;
+    motionPack(tri, nTri, el, nEl, &m, pt, pe);
+    if ((rc = uploadVec((void**)&on->dMoveTri, pt.data(), pt.size() * 16, on->stream))) return rc;
+    if ((rc = uploadVec((void**)&on->dMoveEl, pe.data(), pe.size() * 16, on->stream))) return rc;
+    // the image's camera as k_frame_setup builds it (of which only camRot, origin, screenSize, focalLength and screenHratio are read)
+    *on->hFrameIn = h.in;
+    HIP_TRY(hipMemcpyAsync(on->dFrameIn, on->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, on->stream));
+    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, on->stream, on->sc, on->dFrameIn, on->dFc, on->dEllip);
+    std::memset(&on->streamIn, 0xff, sizeof(FrameIn));
+    const float curIn[6] = {cur.origin[0], cur.origin[1], cur.origin[2], cur.mouse[0], cur.mouse[1], cur.params[2]};
+    const float rule[3] = {maxHistory, depthTol, normalTol};
+    const float4* const geo[4] = {on->dMoveTri, on->dMarkTri, on->dMoveEl, on->dMarkEl};
+    const int counts[4] = {nTri, m.nTri, nEl, m.nEl};
+    HIP_TRY(reprojectMovedLaunch(on->dFeat, on->dMarkFeat, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
+                                 (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, floorA, geo, counts, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept,
+                                 on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));                    // (pt / pe leave scope: their copies have landed)
+    if ((rc = storeReprojected(c, on, stats != nullptr, nKept))) return rc;
+    m.valid = false;                                              // spent
+    return 0;
+}
+}  // namespace
+
+int pt_motion_mark(pt_ctx* c) {
+    if (!c) return fail(PT_ERR_ARG, "pt_motion_mark: null context");
+    return motionMark(c);
+}
+
+int pt_reproject_frame_moved(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
+    if (n_kept) *n_kept = 0;
+    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: null context");
+    int64_t n = 0;
+    const int rc = reprojectMovedImage(c, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
     if (n_kept) *n_kept = n;
     return rc;
 }

@@ -159,6 +159,10 @@ def lib():
             L.pt_fill_frame_through.argtypes = [vp, tr, cf, cf, cf, cf, vp, C.POINTER(C.c_int64)]
             L.pt_denoise_guided_through.argtypes = [vp, tr, ci, cf, cf, cf, cf, ci, cf, vp]
             L.pt_read_display_denoised_guided_through.argtypes = [vp, tr, ci, cf, cf, cf, cf, ci, cf, ci, vp]
+        if hasattr(L, "pt_motion_mark"):                      # include/pt_motion.h
+            cf = C.c_float
+            L.pt_motion_mark.argtypes = [vp]
+            L.pt_reproject_frame_moved.argtypes = [vp, cf, cf, cf, ci, cf, C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -379,6 +383,21 @@ class Renderer:
             _check(self._L.pt_reproject_frame(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, C.byref(n)))
         else:
             _check(self._L.pt_reproject_frame_demod(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, float(albedo_floor), C.byref(n)))
+        return n.value
+
+    # --- reprojection across moved geometry (include/pt_motion.h) ----------------------------------
+    def motion_mark(self):
+        """Pin the scene the current image was rendered in (pt_motion_mark): call it before uploading moved geometry (bindings 3, 7, 10-13)."""
+        _check(self._L.pt_motion_mark(self._h))
+
+    def reproject_frame_moved(self, max_history=64.0, depth_tol=0.02, normal_tol=0.9, all_materials=False, albedo_floor=0.0):
+        """reproject_frame across the geometry uploaded since motion_mark (pt_reproject_frame_moved): every pixel follows its surface point back
+        to where its primitive was at the mark.  Triangle k and ellipsoid k must be the same piece of surface as at the mark.  albedo_floor 0:
+        the plain carry; > 0: include/pt_demod.h's.  Returns the kept count; the mark is spent.  Defaults: reproject_frame's
+        (scripts/motion_quality.py)."""
+        n = C.c_int64(0)
+        flags = self.REPROJECT_ALL_MATERIALS if all_materials else 0
+        _check(self._L.pt_reproject_frame_moved(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, float(albedo_floor), C.byref(n)))
         return n.value
 
     # --- luminance moments and the variance-guided filter (include/pt_guided.h) ---------------------

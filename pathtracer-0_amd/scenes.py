@@ -431,6 +431,47 @@ def t1_textured(W=96, H=54, sample_res=8, max_bounces=8):
     return wl
 
 
+def m1_moving(step=0, W=96, H=54, sample_res=8, max_bounces=8, subdiv=2, textured=True):
+    """M1, the moving-geometry workload of include/pt_motion.h (not a BASELINE config): the Cornell room without its boxes plus four things whose
+    pose is a function of `step` — a box that translates and turns about y, a smooth-normal icosphere that rotates about its centre, a textured
+    quad that translates, an ellipsoid that translates and grows.  Everything is built in the same order at every step, so triangle k and
+    ellipsoid k are the same piece of surface throughout; step 0 is the rest pose.  Every material is diffuse; textured=False leaves the quad's
+    map_Kd out (the same triangles, no texture table)."""
+    s = float(step)
+    sc = _new_scene()
+    _cornell_materials(sc)
+    sc.addMaterial("poster"); sc.setLastMtl("Kd", (0.9, 0.9, 0.9)); sc.setLastMtl("Pr", 1)
+    if textured:
+        sc.setLastMtl("map_Kd", 1)
+    ball = sc.addMaterial("ball"); sc.setLastMtl("Kd", (0.2, 0.3, 0.7)); sc.setLastMtl("Pr", 1)
+    o = Obj()
+    _cornell_room(o, boxes=False)
+    o.group("box")
+    o.usemtl("white")
+    o.box((0.45 + 0.02 * s, 0.3, 0.15 - 0.01 * s), (0.25, 0.3, 0.25), 0.3 + 0.02 * s)
+    o.group("sphere")
+    o.usemtl("green")
+    c = np.array((-0.45, 0.4, 0.25))
+    verts, normals, faces = icosphere(subdiv, (0.0, 0.0, 0.0), 0.35)
+    a = 0.02 * s
+    R = np.array([[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
+    o.mesh([tuple(c + R @ np.array(p)) for p in verts], [tuple(R @ np.array(n)) for n in normals], faces)
+    o.group("poster")
+    o.usemtl("poster")
+    dx = 0.015 * s
+    o.quad_uv((0.3 + dx, 0.9, 0.6), (-0.3 + dx, 0.9, 0.6), (-0.3 + dx, 1.5, 0.6), (0.3 + dx, 1.5, 0.6), (0, 0, -1))
+    sc.addObjectText(o.text(), 0, parentDirectory="")
+    sc.addEllipsoid((0.0 + 0.01 * s, 0.25 + 0.005 * s, -0.45), 1, 0, 0.2 + 0.005 * s, ball)
+    wl = _finish("M1", sc, W, H, CORNELL_CAM, CORNELL_ROT, (0, 0, 0), sample_res, max_bounces)
+    tex = np.zeros((8, 8, 4), np.uint8)
+    for j in range(8):
+        for i in range(8):
+            tex[j, i, :3] = (230, 200, 60) if (i + j) % 2 else (60, 40, 160)
+    tex[..., 3] = 255
+    wl.textures = {1: tex} if textured else {}
+    return wl
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then
@@ -512,6 +553,8 @@ BUILDERS = {"C1": c1_spheres, "C2": c2_cornell, "C3": c3_glass_metal, "C4": c4_m
 def build(name, W=None, H=None, **kw):
     if name == "T1":
         return t1_textured(W or 96, H or 54, **kw)
+    if name == "M1":
+        return m1_moving(kw.pop("step", 0), W or 96, H or 54, **kw)
     cfg = CONFIGS[name]
     W = cfg["W"] if W is None else W
     H = cfg["H"] if H is None else H
