@@ -11,6 +11,8 @@
 
 #include <cstdint>
 
+#include "pt_image_launch.hpp"
+
 namespace {
 
 constexpr int DN_BX = 64, DN_BY = 4;
@@ -82,8 +84,7 @@ float clampInv(float v) { return v > 3.402823466e38f ? 3.402823466e38f : v; }
 
 }  // namespace
 
-// frame, feat: W*H float4 / W*H*4 float4 (read only); col0, col1: W*H float4 ping-pong; guide: 2*W*H float4; out: W*H float4.
-// sigma = (colour, normal, depth, albedo), already checked by the caller.  Enqueued on `s`; returns the first launch error.
+// pt_image_launch.hpp; sigma already checked by the caller
 hipError_t denoiseLaunch(const float4* frame, const float4* feat, int W, int H, int iterations, const float sigma[4], float4* col0, float4* col1,
                          float4* guide, float4* out, hipStream_t s) {
     const int n = W * H;

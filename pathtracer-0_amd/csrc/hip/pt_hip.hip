@@ -35,6 +35,7 @@
 #include "../../../include/pt_through.h"
 #include "../../../include/pt_motion.h"
 #include "pt_device.hpp"
+#include "pt_image_launch.hpp"
 
 #include <algorithm>
 #include <cstddef>
@@ -2339,38 +2340,6 @@ int resolveTimes(pt_ctx* c) {
 // ------------------------------------------------------------------------------------------------ C ABI
 
 int pt_set_error_(int code, const std::string& msg) { return fail(code, msg); }      // for pt_bvh.hip
-// the a-trous filter of include/pt_denoise.h (pt_denoise.hip): device pointers only, enqueued on `s`
-hipError_t denoiseLaunch(const float4* frame, const float4* feat, int W, int H, int iterations, const float sigma[4], float4* col0, float4* col1,
-                         float4* guide, float4* out, hipStream_t s);
-// the reprojection of include/pt_reproject.h (pt_reproject.hip): device pointers only, enqueued on `s`
-hipError_t reprojectLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
-                           int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float4* outFrame, float4* outStats,
-                           unsigned* kept, hipStream_t s);
-// the variance-guided filter of include/pt_guided.h (pt_guided.hip): device pointers only, enqueued on `s`
-hipError_t guidedLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                        float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s, const float4* alpha = nullptr);
-// ... and include/pt_steer.h's selection over it (pt_guided.hip)
-hipError_t guidedSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                              int maxFrames, const float rule[2], const float ov[3], float4* col0, float4* col1, float4* guide, unsigned char* mask,
-                              unsigned* count, hipStream_t s);
-// include/pt_demod.h: the three above on the illumination (pt_guided.hip, pt_reproject.hip); floorA = albedo_floor
-hipError_t guidedDemodLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                             float floorA, float4* col0, float4* col1, float4* guide, float4* out, hipStream_t s, const float4* alpha = nullptr);
-hipError_t guidedDemodSelectLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4],
-                                   int minFrames, int maxFrames, const float rule[2], const float ov[3], float floorA, float4* col0, float4* col1,
-                                   float4* guide, unsigned char* mask, unsigned* count, hipStream_t s);
-hipError_t reprojectDemodLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
-                                int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float floorA, float4* outFrame,
-                                float4* outStats, unsigned* kept, hipStream_t s);
-// include/pt_motion.h (pt_reproject.hip): geo = triangles now / then, ellipsoids now / then (3 float4 per primitive), counts likewise
-hipError_t reprojectMovedLaunch(const float4* rn, const float4* rh, const float4* frame, const float4* stats, const FrameConst* hist, const unsigned char* matVD,
-                                int nMat, int W, int H, const float cur[6], const float rule[3], int allMaterials, float floorA, const float4* const geo[4],
-                                const int counts[4], float4* outFrame, float4* outStats, unsigned* kept, hipStream_t s);
-// include/pt_fill.h (pt_guided.hip): FRAME' into fill, *count = the holes filled; and the guided filter (floorA == 0) or its demodulated variant on FRAME'
-hipError_t fillLaunch(const float4* frame, const float4* feat, int W, int H, const float sigma[4], float floorA, float4* col0, float4* guide, float4* fill,
-                      unsigned* count, hipStream_t s);
-hipError_t guidedFilledLaunch(const float4* frame, const float4* feat, const float4* stats, int W, int H, int iterations, const float sigma[4], int minFrames,
-                              float floorA, float4* col0, float4* col1, float4* guide, float4* fill, float4* out, unsigned* count, hipStream_t s);
 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
@@ -3178,843 +3147,7 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
     return PT_OK;
 }
 
-// ---- T in pixel order (include/pt_adaptive.h, include/pt_guided.h): a group's streams each hold the slots of their own shard, so T travels through the host
-namespace {
-// T of the whole image into host[W*H*4], pixel order: zeros where no stream holds T; *any = some stream does.  Work in flight is the caller's to complete.
-int statsToHost(pt_ctx* c, float* host, bool* any) {
-    std::fill(host, host + (size_t)c->W * c->H * 4, 0.0f);
-    *any = false;
-    const std::vector<pt_ctx*> kids = c->multi ? c->multi->kids : std::vector<pt_ctx*>{c};
-    for (pt_ctx* k : kids) {
-        if (!k->dStats) continue;
-        *any = true;
-        HIP_TRY(hipSetDevice(k->device));
-        if (int rc = shardToHost(k, k->dStats, host)) return rc;
-    }
-    return 0;
-}
-// The whole image's T in pixel order on the device of `on` (firstStream(c)), or nullptr when no stream holds T: a single context's own T; a group's
-// gathered through the host into on->dStatsWhole.  Work in flight is the caller's to complete.
-int wholeStats(pt_ctx* c, pt_ctx* on, const float4** stats) {
-    *stats = c->multi ? nullptr : c->dStats;
-    if (!c->multi) return 0;
-    const size_t n = (size_t)c->W * c->H;
-    std::vector<float> host(n * 4);
-    bool any = false;
-    if (int rc = statsToHost(c, host.data(), &any)) return rc;
-    if (!any) return 0;
-    HIP_TRY(hipSetDevice(on->device));
-    if (!on->dStatsWhole) HIP_TRY(hipMalloc((void**)&on->dStatsWhole, n * 16));
-    HIP_TRY(hipMemcpyAsync(on->dStatsWhole, host.data(), n * 16, hipMemcpyHostToDevice, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    *stats = on->dStatsWhole;
-    return 0;
-}
-int writeMoments(pt_ctx* c, const float* in) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = flushStream(c)) return rc;
-    if (!c->dStats) HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
-    return hostToShard(c, in, c->dStats);
-}
-}  // namespace
-
-int pt_record_moments(pt_ctx* c, int on) {
-    if (!c) return fail(PT_ERR_ARG, "pt_record_moments: null context");
-    MULTI_ALL(c, pt_record_moments(k, on));
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = flushStream(c)) return rc;                       // batches in flight retire under the previous setting
-    if (on && !c->dStats) {
-        HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
-        HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
-    }
-    c->recordMoments = on != 0;
-    return PT_OK;
-}
-
-int pt_read_moments(pt_ctx* c, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_moments: null argument");
-    int rc;
-    if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_read_moments"))) return rc;
-    if ((rc = pt_synchronize(c))) return rc;
-    bool any = false;
-    return statsToHost(c, out, &any);
-}
-
-int pt_write_moments(pt_ctx* c, const float* in) {
-    if (!c || !in) return fail(PT_ERR_ARG, "pt_write_moments: null argument");
-    if (int rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_write_moments")) return rc;
-    MULTI_ALL(c, writeMoments(k, in));                            // every stream takes the pixels of its own tile shard
-    return writeMoments(c, in);
-}
-
-// ---- first-hit feature records and the denoised image (include/pt_denoise.h).  A group context works on its first stream's context: the scene is replicated.
-namespace {
-// the feature records of the frame inputs `fin` into *buf (W*H x 4 float4, allocated on first use); *valid says they are there
-int ensureFeaturesFor(pt_ctx* c, const FrameIn& fin, float4** buf, bool* valid) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (*valid) return 0;
-    int rc;
-    if ((rc = claimFrameConstants(c))) return rc;
-    const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
-    if (!*buf) HIP_TRY(hipMalloc((void**)buf, n * 64));
-    State st{};
-    Scratch scratch;
-    if ((rc = probePool(scratch, st, np, c->sc.numEllip > 0))) return rc;      // HX: the uv an ellipsoid hit inherits (uvOfHit)
-    if (st.HX) HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);      // auto-focus, camera and ellipsoid rotations
-    hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
-    if ((rc = probeIntersect(c, st, np, fin))) return rc;
-    hipLaunchKernelGGL(k_feature_record, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, *buf);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *valid = true;
-    return 0;
-}
-// the records of the current frame inputs (c->dFeat)
-int ensureFeatures(pt_ctx* c) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->featValid) return 0;
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
-    FrameIn fin;
-    currentInputs(c, fin);
-    return ensureFeaturesFor(c, fin, &c->dFeat, &c->featValid);
-}
-
-// include/pt_through.h's rule, checked
-int checkThrough(const pt_through_rule* r, const char* who) {
-    const std::string w(who);
-    if (!r) return fail(PT_ERR_ARG, w + ": null rule");
-    if (r->max_depth < 0 || r->max_depth > 8) return fail(PT_ERR_ARG, w + ": rule.max_depth must be in [0,8]");
-    if (!(r->min_weight > 0.0f && r->min_weight <= 1.0f)) return fail(PT_ERR_ARG, w + ": rule.min_weight must be in (0,1]");
-    if (r->lobes < 0 || r->lobes > 3) return fail(PT_ERR_ARG, w + ": rule.lobes must be in [0,3]");
-    if (r->flags & ~PT_THROUGH_KEY) return fail(PT_ERR_ARG, w + ": unknown rule.flags");
-    return 0;
-}
-// the seen-through records of the current frame inputs under `rule` (c->dThru) and their last segments (c->dThruRays): ensureFeaturesFor's probe
-// pool and ray kernel, then max_depth + 1 rounds of (intersect, k_through_step) — a fixed count, nothing read back in between: a round whose
-// lanes are all dead costs two launches that return at once
-int ensureThrough(pt_ctx* c, const pt_through_rule& rule, const char* who) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->thruValid && std::memcmp(&c->thruRule, &rule, sizeof(rule)) == 0) return 0;
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
-    FrameIn fin;
-    currentInputs(c, fin);
-    int rc;
-    if ((rc = claimFrameConstants(c))) return rc;
-    if ((rule.flags & PT_THROUGH_KEY) && c->sc.numMat > 4096)
-        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": PT_THROUGH_KEY packs a material index into 12 bits; the scene has more than 4096 materials");
-    c->thruValid = false;
-    const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
-    if (!c->dThru) HIP_TRY(hipMalloc((void**)&c->dThru, n * 64));
-    if (!c->dThruRays) HIP_TRY(hipMalloc((void**)&c->dThruRays, n * 32));
-    State st{};
-    Scratch scratch;
-    if ((rc = probePool(scratch, st, np, c->sc.numEllip > 0))) return rc;
-    float4* X = nullptr;
-    scratch.ptrs.push_back((void**)&X);
-    const int planes = c->niBits == 32 ? 5 : (c->niBits == 8 ? 3 : 2);
-    HIP_TRY(hipMalloc((void**)&X, np * 16 * planes));
-    if (st.HX) HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);
-    hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
-    // RAYTRACING == 0 (directDiffuse, frag.glsl:911-912) takes no step
-    const int depth = (rule.lobes == 0 || fin.params[9] != 1.0f) ? 0 : rule.max_depth;
-    const ThroughRule tr{depth, rule.min_weight, rule.lobes, rule.flags};
-    for (int step = 0; step <= depth; step++) {
-        if ((rc = probeIntersect(c, st, np, fin))) return rc;
-#define THROUGH_STEP(T) hipLaunchKernelGGL(k_through_step<T>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, tr, step, X, (unsigned)np, c->dThru, c->dThruRays)
-        if (c->niBits == 3) THROUGH_STEP(3);
-        else if (c->niBits == 8) THROUGH_STEP(8);
-        else if (c->niBits == 32) THROUGH_STEP(32);
-        else THROUGH_STEP(0);
-#undef THROUGH_STEP
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->thruRule = rule;
-    c->thruValid = true;
-    return 0;
-}
-
-// the denoised image of the context's current FRAME into on->dDnOut (W*H float4 on the device of *on), enqueued on on->stream
-int denoiseImage(pt_ctx* c, int iterations, const float sigma[4], pt_ctx** onOut) {
-    if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise: iterations must be in [0,8]");
-    for (int k = 0; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, "pt_denoise: every sigma must be > 0 (+inf switches its term off)");
-    pt_ctx* on = nullptr; const float4* frame = nullptr;
-    int rc;
-    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise", &on, &frame))) return rc;
-    if ((rc = ensureFeatures(on))) return rc;
-    const size_t n = (size_t)c->W * c->H;
-    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
-    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
-    HIP_TRY(denoiseLaunch(frame, on->dFeat, c->W, c->H, iterations, sigma, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
-    *onOut = on;
-    return 0;
-}
-}  // namespace
-
-int pt_read_features(pt_ctx* c, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features: null argument");
-    pt_ctx* on = firstStream(c);
-    int rc;
-    if ((rc = ensureFeatures(on))) return rc;
-    HIP_TRY(hipMemcpy(out, on->dFeat, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_denoise(pt_ctx* c, int iterations, float sigma_color, float sigma_normal, float sigma_depth, float sigma_albedo, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise: null argument");
-    const float sigma[4] = {sigma_color, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = denoiseImage(c, iterations, sigma, &on))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    return PT_OK;
-}
-
-int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float sigma_normal, float sigma_depth, float sigma_albedo, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised: null argument");
-    const float sigma[4] = {sigma_color, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = denoiseImage(c, iterations, sigma, &on))) return rc;
-    // the denoised image is a mean already: k_display's conversion with a frame count of 1 (x / 1.0f is exact)
-    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
-}
-
-// ---- the variance-guided filter (include/pt_guided.h): pt_denoise's plumbing and scratch, with T in pixel order beside FRAME
-namespace {
-// include/pt_demod.h's albedo_floor: finite and > 0
-bool floorOk(float floorA) { return floorA > 0.0f && __builtin_isfinite(floorA); }
-
-// floorA == 0: the plain filter; > 0: include/pt_demod.h's, with that albedo_floor (checked by the caller)
-int guidedImage(pt_ctx* c, int iterations, const float sigma[4], int minFrames, float floorA, pt_ctx** onOut) {
-    if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise_guided: iterations must be in [0,8]");
-    if (minFrames < 2) return fail(PT_ERR_ARG, "pt_denoise_guided: min_frames must be >= 2");
-    for (int k = 0; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, "pt_denoise_guided: every sigma must be > 0 (+inf switches its term off)");
-    pt_ctx* on = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
-    int rc;
-    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise_guided", &on, &frame))) return rc;
-    if ((rc = wholeStats(c, on, &stats))) return rc;
-    if (!stats) return fail(PT_ERR_ARG, "pt_denoise_guided: the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
-    if ((rc = ensureFeatures(on))) return rc;
-    const size_t n = (size_t)c->W * c->H;
-    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
-    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
-    if (floorA > 0.0f)
-        HIP_TRY(guidedDemodLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, floorA, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut,
-                                  on->stream));
-    else
-        HIP_TRY(guidedLaunch(frame, on->dFeat, stats, c->W, c->H, iterations, sigma, minFrames, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
-    *onOut = on;
-    return 0;
-}
-}  // namespace
-
-int pt_denoise_guided(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided: null argument");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = guidedImage(c, iterations, sigma, min_frames, 0.0f, &on))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    return PT_OK;
-}
-
-int pt_read_display_denoised_guided(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
-                                    int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided: null argument");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = guidedImage(c, iterations, sigma, min_frames, 0.0f, &on))) return rc;
-    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
-}
-
-int pt_denoise_guided_demod(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
-                            float albedo_floor, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_demod: null argument");
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_denoise_guided_demod: albedo_floor must be finite and > 0");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = guidedImage(c, iterations, sigma, min_frames, albedo_floor, &on))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    return PT_OK;
-}
-
-int pt_read_display_denoised_guided_demod(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo,
-                                          int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_demod: null argument");
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_demod: albedo_floor must be finite and > 0");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = guidedImage(c, iterations, sigma, min_frames, albedo_floor, &on))) return rc;
-    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
-}
-
-// ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
-// every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
-namespace {
-// the reprojected image (on->dRpFrame, on->dRpStats when `stats`, on->dRpKept; enqueued on on->stream) into the current image of `c`, whose camera
-// becomes the current inputs
-int storeReprojected(pt_ctx* c, pt_ctx* on, bool stats, int64_t* nKept) {
-    const size_t n = (size_t)c->W * c->H;
-    int rc;
-    unsigned kept = 0;
-    HIP_TRY(hipMemcpyAsync(&kept, on->dRpKept, 4, hipMemcpyDeviceToHost, on->stream));
-    if (!c->multi) {                                              // the result into the current image (a copy: pt_frame_device pointers stay valid)
-        HIP_TRY(hipMemcpyAsync(c->dImage[c->curImage], on->dRpFrame, n * 16, hipMemcpyDeviceToDevice, c->stream));
-        if (stats) HIP_TRY(hipMemcpyAsync(c->dStats, on->dRpStats, n * 16, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        recordCamera(c);
-    } else {
-        std::vector<float> hf(n * 4), hostStats(stats ? n * 4 : 0);
-        HIP_TRY(hipMemcpyAsync(hf.data(), on->dRpFrame, n * 16, hipMemcpyDeviceToHost, on->stream));
-        if (stats) HIP_TRY(hipMemcpyAsync(hostStats.data(), on->dRpStats, n * 16, hipMemcpyDeviceToHost, on->stream));
-        HIP_TRY(hipStreamSynchronize(on->stream));
-        const float* pf = hf.data(); const float* ps = stats ? hostStats.data() : nullptr;
-        if ((rc = multiRun(*c->multi, [pf, ps](pt_ctx* k) { return writeFrame(k, pf, ps); }))) return rc;
-    }
-    *nKept = kept;
-    return 0;
-}
-// floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor (checked by the caller)
-int reprojectImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept) {
-    if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: max_history must be >= 1");
-    if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: depth_tol must be > 0");
-    if (!(normalTol >= -1.0f && normalTol <= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame: normal_tol must be in [-1, 1]");
-    if (flags & ~PT_REPROJECT_ALL_MATERIALS) return fail(PT_ERR_ARG, "pt_reproject_frame: unknown flags");
-    pt_ctx* on = nullptr; const float4* frame = nullptr;
-    int rc;
-    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_reproject_frame", &on, &frame))) return rc;      // a group: gathered on on->stream
-    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
-    else if ((rc = pt_synchronize(c))) return rc;                 // all submitted work lands in FRAME and T first
-    FrameIn cur;
-    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
-    const float* P = on->params.data();
-    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
-    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame: DEBUG != 0 renders the traversal heat map, which has no surfaces to carry");
-    const pt_ctx::Cam h = on->cam[on->curImage];
-    if (!h.valid) return PT_OK;                                   // no camera: nothing to map from
-    if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_reproject_frame: a scene buffer or texture was uploaded since the image's camera was recorded");
-    if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame: the image was rendered with DEBUG != 0");
-    if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
-        return fail(PT_ERR_ARG, "pt_reproject_frame: the image's camera has Parameters that do not match the image size");
-    // Rn and Rh; with the camera unchanged they are the same records
-    if ((rc = ensureFeaturesFor(on, cur, &on->dFeat, &on->featValid))) return rc;
-    const bool same = std::memcmp(&h.in, &cur, sizeof(FrameIn)) == 0;
-    if (!same) {
-        if (on->featHValid && std::memcmp(&on->featHIn, &h.in, sizeof(FrameIn)) != 0) on->featHValid = false;
-        if ((rc = ensureFeaturesFor(on, h.in, &on->dFeatH, &on->featHValid))) return rc;
-        on->featHIn = h.in;
-    }
-    HIP_TRY(hipSetDevice(on->device));
-    const size_t n = (size_t)c->W * c->H;
-    if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
-    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
-    // the image's T in pixel order, when allocated (group: through the host)
-    const float4* stats = nullptr;
-    if ((rc = wholeStats(c, on, &stats))) return rc;
-    if (stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
-    // the image's camera as k_frame_setup builds it (camRot), in the frame constants, which are no stream's afterwards
-    *on->hFrameIn = h.in;
-    HIP_TRY(hipMemcpyAsync(on->dFrameIn, on->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, on->stream));
-    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, on->stream, on->sc, on->dFrameIn, on->dFc, on->dEllip);
-    std::memset(&on->streamIn, 0xff, sizeof(FrameIn));
-    const float curIn[6] = {cur.origin[0], cur.origin[1], cur.origin[2], cur.mouse[0], cur.mouse[1], cur.params[2]};
-    const float rule[3] = {maxHistory, depthTol, normalTol};
-    if (floorA > 0.0f)
-        HIP_TRY(reprojectDemodLaunch(on->dFeat, same ? on->dFeat : on->dFeatH, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
-                                     (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, floorA, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept, on->stream));
-    else
-        HIP_TRY(reprojectLaunch(on->dFeat, same ? on->dFeat : on->dFeatH, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
-                                (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept, on->stream));
-    return storeReprojected(c, on, stats != nullptr, nKept);
-}
-}  // namespace
-
-int pt_reproject_frame(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, int64_t* n_kept) {
-    if (n_kept) *n_kept = 0;
-    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame: null context");
-    int64_t n = 0;
-    const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, 0.0f, &n);
-    if (n_kept) *n_kept = n;
-    return rc;
-}
-
-int pt_reproject_frame_demod(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
-    if (n_kept) *n_kept = 0;
-    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: null context");
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: albedo_floor must be finite and > 0");
-    int64_t n = 0;
-    const int rc = reprojectImage(c, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
-    if (n_kept) *n_kept = n;
-    return rc;
-}
-
-namespace {
-// ---- include/pt_motion.h: the mark and the reprojection across moved geometry
-// the vertices of the triangles of binding 3 (9 floats each) and centre, stretch, rot, r of the ellipsoids of binding 7 (10 floats each), from the host copies
-void motionPositions(const pt_ctx* c, std::vector<float>& tri, int* nTri, std::vector<float>& el, int* nEl) {
-    const size_t nt = c->tris.size() / 40;
-    tri.resize(nt * 9);
-    for (size_t t = 0; t < nt; t++)
-        for (int v = 0; v < 3; v++) std::memcpy(&tri[9 * t + 3 * v], &c->tris[40 * t + 4 * v], 12);
-    int ne = c->ellip.empty() ? 0 : (int)c->ellip[0];
-    if (ne < 0 || c->ellip.size() < (size_t)1 + 11 * (size_t)ne) ne = 0;      // (buildScene refuses such a buffer)
-    el.resize((size_t)ne * 10);
-    const float* E = c->ellip.data();
-    for (int i = 0; i < ne; i++) {
-        for (int k = 0; k < 3; k++) { el[10 * i + k] = E[1 + 3 * i + k]; el[10 * i + 3 + k] = E[1 + ne * 3 + 3 * i + k]; el[10 * i + 6 + k] = E[1 + ne * 6 + 3 * i + k]; }
-        el[10 * i + 9] = E[1 + ne * 9 + i];
-    }
-    *nTri = (int)nt; *nEl = ne;
-}
-// ... as the kernel reads them: triangle (A, flag), (B, 0), (C, 0); ellipsoid (c, r), (stretch, flag), (rot, 0).  then == nullptr: the mark's own copy, flags 0;
-// else flag = 0 unmoved (every float compares equal), 1 moved, 2 a moved ellipsoid with a rot component != 0 then or now
-void motionPack(const std::vector<float>& tri, int nTri, const std::vector<float>& el, int nEl, const pt_ctx::Mark* then, std::vector<float4>& outTri,
-                std::vector<float4>& outEl) {
-    auto asf = [](int u) { float f; std::memcpy(&f, &u, 4); return f; };
-    outTri.resize(std::max<size_t>((size_t)nTri * 3, 1)); outEl.resize(std::max<size_t>((size_t)nEl * 3, 1));
-    for (int t = 0; t < nTri; t++) {
-        const float* T = &tri[9 * (size_t)t];
-        int flag = 0;
-        if (then) {
-            flag = t < then->nTri ? 0 : 1;
-            for (int k = 0; k < 9 && !flag; k++) if (!(T[k] == then->tri[9 * (size_t)t + k])) flag = 1;
-        }
-        outTri[3 * (size_t)t] = make_float4(T[0], T[1], T[2], asf(flag)); outTri[3 * (size_t)t + 1] = make_float4(T[3], T[4], T[5], 0.0f);
-        outTri[3 * (size_t)t + 2] = make_float4(T[6], T[7], T[8], 0.0f);
-    }
-    for (int i = 0; i < nEl; i++) {
-        const float* E = &el[10 * (size_t)i];
-        int flag = 0;
-        if (then) {
-            flag = i < then->nEl ? 0 : 1;
-            for (int k = 0; k < 10 && !flag; k++) if (!(E[k] == then->el[10 * (size_t)i + k])) flag = 1;
-            if (flag && i < then->nEl)
-                for (int k = 6; k < 9; k++) if (E[k] != 0.0f || then->el[10 * (size_t)i + k] != 0.0f) flag = 2;
-        }
-        outEl[3 * (size_t)i] = make_float4(E[0], E[1], E[2], E[9]); outEl[3 * (size_t)i + 1] = make_float4(E[3], E[4], E[5], asf(flag));
-        outEl[3 * (size_t)i + 2] = make_float4(E[6], E[7], E[8], 0.0f);
-    }
-}
-
-int motionMark(pt_ctx* c) {
-    int rc;
-    if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_motion_mark"))) return rc;
-    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
-    else if ((rc = pt_synchronize(c))) return rc;                 // all submitted work lands first
-    pt_ctx* on = firstStream(c);
-    const pt_ctx::Cam h = on->cam[on->curImage];
-    if (!h.valid) return fail(PT_ERR_ARG, "pt_motion_mark: the current image has no camera (render or pt_write_frame first)");
-    if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_motion_mark: a scene buffer or texture was uploaded since the image's camera was recorded");
-    if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_motion_mark: the image was rendered with DEBUG != 0");
-    if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
-        return fail(PT_ERR_ARG, "pt_motion_mark: the image's camera has Parameters that do not match the image size");
-    on->mark.valid = false;
-    // (a) Rh, through the cache pt_reproject_frame keeps, into a buffer that later uploads leave alone
-    if (on->featHValid && std::memcmp(&on->featHIn, &h.in, sizeof(FrameIn)) != 0) on->featHValid = false;
-    if ((rc = ensureFeaturesFor(on, h.in, &on->dFeatH, &on->featHValid))) return rc;
-    on->featHIn = h.in;
-    const size_t n = (size_t)c->W * c->H;
-    if (!on->dMarkFeat) HIP_TRY(hipMalloc((void**)&on->dMarkFeat, n * 64));
-    HIP_TRY(hipMemcpyAsync(on->dMarkFeat, on->dFeatH, n * 64, hipMemcpyDeviceToDevice, on->stream));
-    // (b), (c) where the primitives are
-    pt_ctx::Mark& m = on->mark;
-    motionPositions(on, m.tri, &m.nTri, m.el, &m.nEl);
-    std::vector<float4> pt, pe;
-    motionPack(m.tri, m.nTri, m.el, m.nEl, nullptr, pt, pe);
-    if ((rc = uploadVec((void**)&on->dMarkTri, pt.data(), pt.size() * 16, on->stream))) return rc;
-    if ((rc = uploadVec((void**)&on->dMarkEl, pe.data(), pe.size() * 16, on->stream))) return rc;
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    // (d)
-    m.image = on->curImage; m.camWrites = on->camWrites; m.otherGen = on->otherGen;
-    m.valid = true;
-    return PT_OK;
-}
-
-// reprojectImage with Rh and the primitives' old positions from the mark
-int reprojectMovedImage(pt_ctx* c, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept) {
-    if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: max_history must be >= 1");
-    if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: depth_tol must be > 0");
-    if (!(normalTol >= -1.0f && normalTol <= 1.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: normal_tol must be in [-1, 1]");
-    if (flags & ~PT_REPROJECT_ALL_MATERIALS) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: unknown flags");
-    if (!(floorA == 0.0f || floorOk(floorA))) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: albedo_floor must be 0 or finite and > 0");
-    pt_ctx* on = nullptr; const float4* frame = nullptr;
-    int rc;
-    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_reproject_frame_moved", &on, &frame))) return rc;
-    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
-    else if ((rc = pt_synchronize(c))) return rc;
-    FrameIn cur;
-    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
-    const float* P = on->params.data();
-    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
-    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_reproject_frame_moved: DEBUG != 0 renders the traversal heat map, which has no surfaces to carry");
-    pt_ctx::Mark& m = on->mark;
-    if (!m.valid) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: no mark (pt_motion_mark first; a mark serves one call)");
-    if (m.image != on->curImage) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: the mark belongs to another image");
-    const pt_ctx::Cam h = on->cam[on->curImage];
-    if (!h.valid || m.camWrites != on->camWrites)
-        return fail(PT_ERR_ARG, "pt_reproject_frame_moved: the image's camera is no longer the marked one (a render, pt_write_frame, pt_reset_frame or pt_next_image since the mark)");
-    if (m.otherGen != on->otherGen) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: binding 5, binding 14 or a texture was uploaded since the mark");
-    // Rn in the scene as it is now (builds it when an upload is pending)
-    if ((rc = ensureFeaturesFor(on, cur, &on->dFeat, &on->featValid))) return rc;
-    HIP_TRY(hipSetDevice(on->device));
-    const size_t n = (size_t)c->W * c->H;
-    if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
-    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
-    const float4* stats = nullptr;
-    if ((rc = wholeStats(c, on, &stats))) return rc;
-    if (stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
-    // where the primitives are now, with the moved ones flagged
-    std::vector<float> tri, el; int nTri = 0, nEl = 0;
-    motionPositions(on, tri, &nTri, el, &nEl);
-    std::vector<float4> pt, pe;
-    motionPack(tri, nTri, el, nEl, &m, pt, pe);
-    if ((rc = uploadVec((void**)&on->dMoveTri, pt.data(), pt.size() * 16, on->stream))) return rc;
-    if ((rc = uploadVec((void**)&on->dMoveEl, pe.data(), pe.size() * 16, on->stream))) return rc;
-    // the image's camera as k_frame_setup builds it (of which only camRot, origin, screenSize, focalLength and screenHratio are read)
-    *on->hFrameIn = h.in;
-    HIP_TRY(hipMemcpyAsync(on->dFrameIn, on->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, on->stream));
-    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, on->stream, on->sc, on->dFrameIn, on->dFc, on->dEllip);
-    std::memset(&on->streamIn, 0xff, sizeof(FrameIn));
-    const float curIn[6] = {cur.origin[0], cur.origin[1], cur.origin[2], cur.mouse[0], cur.mouse[1], cur.params[2]};
-    const float rule[3] = {maxHistory, depthTol, normalTol};
-    const float4* const geo[4] = {on->dMoveTri, on->dMarkTri, on->dMoveEl, on->dMarkEl};
-    const int counts[4] = {nTri, m.nTri, nEl, m.nEl};
-    HIP_TRY(reprojectMovedLaunch(on->dFeat, on->dMarkFeat, frame, stats, on->dFc, on->dMatVD, on->sc.numMat, c->W, c->H, curIn, rule,
-                                 (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0, floorA, geo, counts, on->dRpFrame, stats ? on->dRpStats : nullptr, on->dRpKept,
-                                 on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));                    // (pt / pe leave scope: their copies have landed)
-    if ((rc = storeReprojected(c, on, stats != nullptr, nKept))) return rc;
-    m.valid = false;                                              // spent
-    return 0;
-}
-}  // namespace
-
-int pt_motion_mark(pt_ctx* c) {
-    if (!c) return fail(PT_ERR_ARG, "pt_motion_mark: null context");
-    return motionMark(c);
-}
-
-int pt_reproject_frame_moved(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
-    if (n_kept) *n_kept = 0;
-    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: null context");
-    int64_t n = 0;
-    const int rc = reprojectMovedImage(c, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
-    if (n_kept) *n_kept = n;
-    return rc;
-}
-
-
-// ---- adaptive sampling steered by the guided filter (include/pt_steer.h).  The selection needs the whole image (the filter's plumbing: wholeFrame,
-// wholeStats, ensureFeatures on the first stream's context); the render takes each stream's own pixels from the W*H-byte mask.
-namespace {
-size_t maskBytes(const pt_ctx* c) { return ((size_t)c->W * c->H + 3) & ~(size_t)3; }      // the active count follows, 4-byte aligned
-
-int checkRule(const pt_guided_rule& r, const char* who) {
-    const std::string w(who);
-    if (r.iterations < 0 || r.iterations > 8) return fail(PT_ERR_ARG, w + ": rule.iterations must be in [0,8]");
-    for (float v : {r.sigma_lum, r.sigma_normal, r.sigma_depth, r.sigma_albedo})
-        if (!(v > 0.0f)) return fail(PT_ERR_ARG, w + ": every sigma of the rule must be > 0 (+inf switches its term off)");
-    if (r.min_frames < 2) return fail(PT_ERR_ARG, w + ": rule.min_frames must be >= 2");
-    if (!(r.rel_err >= 0.0f) || !(r.abs_err >= 0.0f)) return fail(PT_ERR_ARG, w + ": rule.rel_err and rule.abs_err must be >= 0 and not NaN");
-    if (r.max_frames < 0) return fail(PT_ERR_ARG, w + ": rule.max_frames must be >= 0 (0 = no cap)");
-    return 0;
-}
-
-// The rule over the context's current image into (*onOut)->dSelMask (W*H bytes, pixel order, on the device of firstStream(c)); *nActive = its count.
-// FRAME and T are not modified; T never allocated reads as zeros (the filter's scratch output, zeroed).
-// floorA == 0: include/pt_steer.h's rule; > 0: include/pt_demod.h's step 5, with that albedo_floor (checked by the caller).
-int selectGuided(pt_ctx* c, const pt_guided_rule& r, float floorA, const char* who, pt_ctx** onOut, int64_t* nActive) {
-    pt_ctx* on = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
-    int rc;
-    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &frame))) return rc;
-    if ((rc = wholeStats(c, on, &stats))) return rc;
-    if ((rc = ensureFeatures(on))) return rc;                     // (Parameters, ORIGIN and ROTATION are set from here on)
-    HIP_TRY(hipSetDevice(on->device));
-    const size_t n = (size_t)c->W * c->H;
-    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
-    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
-    if (!on->dSelMask) HIP_TRY(hipMalloc((void**)&on->dSelMask, maskBytes(on) + 4));
-    if (!stats) {
-        HIP_TRY(hipMemsetAsync(on->dDnOut, 0, n * 16, on->stream));
-        stats = on->dDnOut;
-    }
-    unsigned* count = reinterpret_cast<unsigned*>(on->dSelMask + maskBytes(on));
-    const float sigma[4] = {r.sigma_lum, r.sigma_normal, r.sigma_depth, r.sigma_albedo};
-    const float rule[2] = {r.rel_err, r.abs_err};
-    const AdaptRule ovr = withOverlay(on, AdaptRule{});
-    const float ov[3] = {ovr.mouseX, ovr.mouseY, ovr.resolution};
-    if (floorA > 0.0f)
-        HIP_TRY(guidedDemodSelectLaunch(frame, on->dFeat, stats, c->W, c->H, r.iterations, sigma, r.min_frames, r.max_frames, rule, ov, floorA, on->dDnCol[0],
-                                        on->dDnCol[1], on->dDnGuide, on->dSelMask, count, on->stream));
-    else
-        HIP_TRY(guidedSelectLaunch(frame, on->dFeat, stats, c->W, c->H, r.iterations, sigma, r.min_frames, r.max_frames, rule, ov, on->dDnCol[0], on->dDnCol[1],
-                                   on->dDnGuide, on->dSelMask, count, on->stream));
-    unsigned hc = 0;
-    HIP_TRY(hipMemcpyAsync(&hc, count, 4, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    *nActive = hc;
-    *onOut = on;
-    return 0;
-}
-
-// pt_render_mask on one stream: hostMask (W*H bytes) into c->dSelMask, or, when hostMask is null, the mask already there (pt_render_adaptive_guided
-// on a one-stream context); then the frame stream over the list entries it selects
-int renderMask(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const uint8_t* hostMask, const char* who, int64_t* nActive) {
-    return renderSelected(c, firstFrame, nFrames, seeds, who, [c, hostMask](hipStream_t s, int nb) {
-        if (hostMask) {
-            if (!c->dSelMask) HIP_TRY(hipMalloc((void**)&c->dSelMask, maskBytes(c) + 4));
-            HIP_TRY(hipMemcpyAsync(c->dSelMask, hostMask, (size_t)c->W * c->H, hipMemcpyHostToDevice, s));
-        }
-        hipLaunchKernelGGL(k_adaptive_select_mask, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, (const unsigned char*)c->dSelMask,
-                           withOverlay(c, AdaptRule{}), c->dAdaptFlag, c->dAdaptBlk);
-        return 0;
-    }, nActive);
-}
-}  // namespace
-
-int pt_render_mask(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const uint8_t* mask, int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!c || !seeds || !mask) return fail(PT_ERR_ARG, "pt_render_mask: null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_mask: n_frames must be >= 1");
-    return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderMask(k, first_frame, n_frames, seeds, mask, "pt_render_mask", n); }, n_active);
-}
-
-namespace {
-// pt_select_guided (floorA == 0) and pt_select_guided_demod
-int selectInto(pt_ctx* c, const pt_guided_rule* rule, float floorA, const char* who, uint8_t* mask_out, int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!c || !rule || !mask_out) return fail(PT_ERR_ARG, std::string(who) + ": null argument");
-    int rc;
-    if ((rc = checkRule(*rule, who))) return rc;
-    pt_ctx* on = nullptr; int64_t n = 0;
-    if ((rc = selectGuided(c, *rule, floorA, who, &on, &n))) return rc;
-    HIP_TRY(hipMemcpyAsync(mask_out, on->dSelMask, (size_t)c->W * c->H, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    if (n_active) *n_active = n;
-    return PT_OK;
-}
-
-// pt_render_adaptive_guided (floorA == 0) and pt_render_adaptive_guided_demod
-int renderAdaptiveGuided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, float floorA, const char* who,
-                         int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!c || !seeds || !rule) return fail(PT_ERR_ARG, std::string(who) + ": null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, std::string(who) + ": n_frames must be >= 1");
-    int rc;
-    if ((rc = checkRule(*rule, who))) return rc;
-    const pt_ctx* f = firstStream(c);
-    if (f->params.size() >= 12 && f->params[10] != 0.0f)          // before the selection, as renderSelected would after it
-        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
-    pt_ctx* on = nullptr; int64_t n = 0;
-    if ((rc = selectGuided(c, *rule, floorA, who, &on, &n))) return rc;
-    if (!c->multi)                                                // one stream (holds the whole image): on == c, the mask stays in c->dSelMask
-        return onEveryStream(c, [=](pt_ctx* k, int64_t* cnt) { return renderMask(k, first_frame, n_frames, seeds, nullptr, who, cnt); }, n_active);
-    std::vector<uint8_t> host((size_t)c->W * c->H);               // a group: every stream selects from its own copy
-    HIP_TRY(hipMemcpyAsync(host.data(), on->dSelMask, host.size(), hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    const uint8_t* hm = host.data();
-    return onEveryStream(c, [=](pt_ctx* k, int64_t* cnt) { return renderMask(k, first_frame, n_frames, seeds, hm, who, cnt); }, n_active);
-}
-}  // namespace
-
-int pt_select_guided(pt_ctx* c, const pt_guided_rule* rule, uint8_t* mask_out, int64_t* n_active) {
-    return selectInto(c, rule, 0.0f, "pt_select_guided", mask_out, n_active);
-}
-
-int pt_render_adaptive_guided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, int64_t* n_active) {
-    return renderAdaptiveGuided(c, first_frame, n_frames, seeds, rule, 0.0f, "pt_render_adaptive_guided", n_active);
-}
-
-int pt_select_guided_demod(pt_ctx* c, const pt_guided_rule* rule, float albedo_floor, uint8_t* mask_out, int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_select_guided_demod: albedo_floor must be finite and > 0");
-    return selectInto(c, rule, albedo_floor, "pt_select_guided_demod", mask_out, n_active);
-}
-
-int pt_render_adaptive_guided_demod(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, float albedo_floor,
-                                    int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_render_adaptive_guided_demod: albedo_floor must be finite and > 0");
-    return renderAdaptiveGuided(c, first_frame, n_frames, seeds, rule, albedo_floor, "pt_render_adaptive_guided_demod", n_active);
-}
-
-// ---- interleaved rendering (include/pt_fill.h): pt_render_mask over a lattice mask that every stream builds on its own device, and the prefill of
-// the unrendered pixels in front of the guided filter (its plumbing and scratch, with FRAME' and the filled count beside them)
-namespace {
-int renderLattice(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, int stride, int phaseX, int phaseY, int64_t* nActive) {
-    return renderSelected(c, firstFrame, nFrames, seeds, "pt_render_interleaved", [=](hipStream_t s, int nb) {
-        if (!c->dSelMask) HIP_TRY(hipMalloc((void**)&c->dSelMask, maskBytes(c) + 4));
-        const int n = c->W * c->H;
-        hipLaunchKernelGGL(k_lattice_mask, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, c->dSelMask, c->W, n, stride, phaseX, phaseY);
-        hipLaunchKernelGGL(k_adaptive_select_mask, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, (const unsigned char*)c->dSelMask,
-                           withOverlay(c, AdaptRule{}), c->dAdaptFlag, c->dAdaptBlk);
-        return 0;
-    }, nActive);
-}
-
-// include/pt_fill.h's albedo_floor: 0 (the plain rule) or include/pt_demod.h's
-bool fillFloorOk(float floorA) { return floorA == 0.0f || floorOk(floorA); }
-
-// FRAME' of the context's current image into on->dFill and, when `filter`, the guided filter over it into on->dDnOut; the filled count into
-// on->dFillCount.  All enqueued on on->stream.  sigma = (luminance, normal, depth, albedo); the luminance entry, iterations and minFrames count
-// only when `filter`.
-// thru: null = the first-hit records; else include/pt_through.h's records under that rule (checked by the caller) in their place
-int filledImage(pt_ctx* c, bool filter, int iterations, const float sigma[4], int minFrames, float floorA, const char* who, pt_ctx** onOut,
-                const pt_through_rule* thru = nullptr) {
-    const std::string w(who);
-    if (filter && (iterations < 0 || iterations > 8)) return fail(PT_ERR_ARG, w + ": iterations must be in [0,8]");
-    if (filter && minFrames < 2) return fail(PT_ERR_ARG, w + ": min_frames must be >= 2");
-    for (int k = filter ? 0 : 1; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, w + ": every sigma must be > 0 (+inf switches its term off)");
-    pt_ctx* on = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
-    int rc;
-    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &frame))) return rc;
-    if (filter) {
-        if ((rc = wholeStats(c, on, &stats))) return rc;
-        if (!stats) return fail(PT_ERR_ARG, w + ": the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
-    }
-    if ((rc = thru ? ensureThrough(on, *thru, who) : ensureFeatures(on))) return rc;
-    const float4* feat = thru ? on->dThru : on->dFeat;
-    const size_t n = (size_t)c->W * c->H;
-    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut, &on->dFill}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
-    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
-    if (!on->dFillCount) HIP_TRY(hipMalloc((void**)&on->dFillCount, 4));
-    if (filter)
-        HIP_TRY(guidedFilledLaunch(frame, feat, stats, c->W, c->H, iterations, sigma, minFrames, floorA, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dFill,
-                                   on->dDnOut, on->dFillCount, on->stream));
-    else
-        HIP_TRY(fillLaunch(frame, feat, c->W, c->H, sigma, floorA, on->dDnCol[0], on->dDnGuide, on->dFill, on->dFillCount, on->stream));
-    *onOut = on;
-    return 0;
-}
-}  // namespace
-
-int pt_render_interleaved(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, int stride, int phase_x, int phase_y, int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!c || !seeds) return fail(PT_ERR_ARG, "pt_render_interleaved: null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_interleaved: n_frames must be >= 1");
-    if (stride < 1 || stride > 8) return fail(PT_ERR_ARG, "pt_render_interleaved: stride must be in [1,8]");
-    if (phase_x < 0 || phase_x >= stride || phase_y < 0 || phase_y >= stride) return fail(PT_ERR_ARG, "pt_render_interleaved: a phase must be in [0, stride)");
-    return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderLattice(k, first_frame, n_frames, seeds, stride, phase_x, phase_y, n); }, n_active);
-}
-
-int pt_fill_frame(pt_ctx* c, float sigma_normal, float sigma_depth, float sigma_albedo, float albedo_floor, float* rgba_out, int64_t* n_filled) {
-    if (n_filled) *n_filled = 0;
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_fill_frame: null argument");
-    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_fill_frame: albedo_floor must be 0 or finite and > 0");
-    const float sigma[4] = {1.0f, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = filledImage(c, false, 0, sigma, 2, albedo_floor, "pt_fill_frame", &on))) return rc;
-    unsigned filled = 0;
-    HIP_TRY(hipMemcpyAsync(rgba_out, on->dFill, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipMemcpyAsync(&filled, on->dFillCount, 4, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    if (n_filled) *n_filled = filled;
-    return PT_OK;
-}
-
-int pt_denoise_guided_filled(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
-                             float albedo_floor, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_filled: null argument");
-    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_denoise_guided_filled: albedo_floor must be 0 or finite and > 0");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_denoise_guided_filled", &on))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    return PT_OK;
-}
-
-int pt_read_display_denoised_guided_filled(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo,
-                                           int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_filled: null argument");
-    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_filled: albedo_floor must be 0 or finite and > 0");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    int rc;
-    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_read_display_denoised_guided_filled", &on))) return rc;
-    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
-}
-
-// ---- seen-through feature records (include/pt_through.h): the records beside the first-hit ones, and include/pt_fill.h's calls on them
-int pt_read_features_through(pt_ctx* c, const pt_through_rule* rule, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features_through: null argument");
-    int rc;
-    if ((rc = checkThrough(rule, "pt_read_features_through"))) return rc;
-    pt_ctx* on = firstStream(c);
-    if ((rc = ensureThrough(on, *rule, "pt_read_features_through"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->dThru, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_read_through_rays(pt_ctx* c, const pt_through_rule* rule, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_through_rays: null argument");
-    int rc;
-    if ((rc = checkThrough(rule, "pt_read_through_rays"))) return rc;
-    pt_ctx* on = firstStream(c);
-    if ((rc = ensureThrough(on, *rule, "pt_read_through_rays"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->dThruRays, (size_t)c->W * c->H * 32, hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_fill_frame_through(pt_ctx* c, const pt_through_rule* rule, float sigma_normal, float sigma_depth, float sigma_albedo, float albedo_floor,
-                          float* rgba_out, int64_t* n_filled) {
-    if (n_filled) *n_filled = 0;
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_fill_frame_through: null argument");
-    int rc;
-    if ((rc = checkThrough(rule, "pt_fill_frame_through"))) return rc;
-    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_fill_frame_through: albedo_floor must be 0 or finite and > 0");
-    const float sigma[4] = {1.0f, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    if ((rc = filledImage(c, false, 0, sigma, 2, albedo_floor, "pt_fill_frame_through", &on, rule))) return rc;
-    unsigned filled = 0;
-    HIP_TRY(hipMemcpyAsync(rgba_out, on->dFill, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipMemcpyAsync(&filled, on->dFillCount, 4, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    if (n_filled) *n_filled = filled;
-    return PT_OK;
-}
-
-int pt_denoise_guided_through(pt_ctx* c, const pt_through_rule* rule, int iterations, float sigma_lum, float sigma_normal, float sigma_depth,
-                              float sigma_albedo, int min_frames, float albedo_floor, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_through: null argument");
-    int rc;
-    if ((rc = checkThrough(rule, "pt_denoise_guided_through"))) return rc;
-    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_denoise_guided_through: albedo_floor must be 0 or finite and > 0");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_denoise_guided_through", &on, rule))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba_out, on->dDnOut, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, on->stream));
-    HIP_TRY(hipStreamSynchronize(on->stream));
-    return PT_OK;
-}
-
-int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* rule, int iterations, float sigma_lum, float sigma_normal,
-                                            float sigma_depth, float sigma_albedo, int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_through: null argument");
-    int rc;
-    if ((rc = checkThrough(rule, "pt_read_display_denoised_guided_through"))) return rc;
-    if (!fillFloorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_through: albedo_floor must be 0 or finite and > 0");
-    const float sigma[4] = {sigma_lum, sigma_normal, sigma_depth, sigma_albedo};
-    pt_ctx* on = nullptr;
-    if ((rc = filledImage(c, true, iterations, sigma, min_frames, albedo_floor, "pt_read_display_denoised_guided_through", &on, rule))) return rc;
-    return displayInto(on, on->dDnOut, c->W, c->H, false, 1.0f, java_bytes, rgb_out);
-}
+// the image-space passes: T in pixel order, feature records, the filters, reprojection, steering and the prefill
+#include "pt_image.hpp"
 
 }  // extern "C"

@@ -1,0 +1,62 @@
+// pt_image_launch.hpp — the launch interface of the image-space passes: pt_denoise.hip, pt_guided.hip and pt_reproject.hip define these functions,
+// pt_image.hpp (the host half, inside pt_hip.hip) calls them.  Device pointers only; everything is enqueued on the stream given and the first
+// launch error is returned.  A job is a plain struct: the caller checks the values, the launch reads them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace ptd { struct FrameConst; }
+
+// ---- the a-trous filter of include/pt_denoise.h (pt_denoise.hip)
+// frame, feat: W*H float4 / W*H*4 float4 (read only); col0, col1: W*H float4 ping-pong; guide: 2*W*H float4; out: W*H float4.
+// sigma = (colour, normal, depth, albedo)
+hipError_t denoiseLaunch(const float4* frame, const float4* feat, int W, int H, int iterations, const float sigma[4], float4* col0, float4* col1,
+                         float4* guide, float4* out, hipStream_t s);
+
+// ---- the variance-guided filter of include/pt_guided.h, its selection (pt_steer.h), demodulation (pt_demod.h) and prefill (pt_fill.h) (pt_guided.hip)
+struct GuidedJob {
+    // the inputs.  frame, stats: W*H float4 (FRAME and T in pixel order), feat: W*H*4 float4, all read only
+    const float4* frame = nullptr; const float4* feat = nullptr; const float4* stats = nullptr;
+    int W = 0, H = 0, iterations = 0;
+    float sigma[4] = {1.0f, 1.0f, 1.0f, 1.0f};                    // (luminance, normal, depth, albedo)
+    int minFrames = 2;
+    float floorA = 0.0f;                                          // 0: the plain kernels; > 0: the demodulated ones, with that albedo_floor
+    float4* col0 = nullptr; float4* col1 = nullptr;               // scratch: W*H float4 ping-pong
+    float4* guide = nullptr;                                      // scratch: 2*W*H float4
+    // the optional prefill: FRAME' into fill[W*H] and the holes filled into *fillCount (zeroed first); the filter then runs on FRAME' and takes
+    // its output's alpha from the real FRAME
+    float4* fill = nullptr; unsigned* fillCount = nullptr;
+    // the output, one of: the filtered image out[W*H] (null with `fill`: the prefill alone); or mask[W*H] and *count (zeroed first) of pt_steer.h's rule
+    float4* out = nullptr;
+    unsigned char* mask = nullptr; unsigned* count = nullptr;
+    int maxFrames = 0; float relErr = 0.0f, absErr = 0.0f;
+    float overlay[3] = {0.0f, 0.0f, 0.0f};                        // (mouse x, mouse y, resolution) of the overlay test
+};
+// prep, the variance (the filter: when iterations > 0; the selection: always), `iterations` passes, then finish or select
+hipError_t guidedLaunch(const GuidedJob& j, hipStream_t s);
+
+// ---- the reprojection of include/pt_reproject.h, pt_demod.h and pt_motion.h (pt_reproject.hip).  The three structs are kernel arguments as they stand.
+struct ReprojCam {
+    float On[3];                        // the current ORIGIN (the origin of Rn's rays)
+    float mouseX, mouseY, resolution;   // the current mouse overlay
+};
+struct ReprojRule { float maxHistory, depthTol, normalTol; int allMaterials; };
+// Geometry: 3 float4 per primitive, then (the mark) and now (packed by the host once per call).  Triangle: (A, flag), (B, 0), (C, 0); ellipsoid:
+// (c, r), (stretch, flag), (rot, 0).  flag (int bits, "now" only): 0 unmoved, 1 moved, 2 a moved ellipsoid with a rotation (rejected).
+struct ReprojMotion {
+    const float4* triNow; const float4* triThen; int nTriNow, nTriThen;
+    const float4* elNow; const float4* elThen; int nElNow, nElThen;
+};
+struct ReprojectJob {
+    // rn, rh: W*H*4 float4 feature records under the current inputs / the image's camera; frame, stats: the image's FRAME and T (stats may be
+    // null), W*H float4 in pixel order; hist: the frame constants k_frame_setup built from the image's camera; matVD: nMat bytes, 1 = view-dependent
+    const float4* rn = nullptr; const float4* rh = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
+    const ptd::FrameConst* hist = nullptr; const unsigned char* matVD = nullptr;
+    int nMat = 0, W = 0, H = 0;
+    ReprojCam cam{};
+    ReprojRule rule{};
+    float floorA = 0.0f;                                          // 0: pt_reproject.h's step 7; > 0: pt_demod.h's, with that albedo_floor
+    const ReprojMotion* motion = nullptr;                         // given: pt_motion.h's mapping, rh and the "then" geometry from the mark
+    // outFrame (and outStats when stats is given): W*H float4; *kept (zeroed first): the pixels kept
+    float4* outFrame = nullptr; float4* outStats = nullptr; unsigned* kept = nullptr;
+};
+hipError_t reprojectLaunch(const ReprojectJob& j, hipStream_t s);

@@ -216,7 +216,7 @@ def main():
         L.append(f"  {p['step']:4d}  {p['kept']:.4f}   {p['rmse_whole']:.5f}      {d['rmse_whole']:.5f}      {p['rmse_floor']:.5f}      {d['rmse_floor']:.5f}")
     for k in res.get("kernel_stats", []):
         name = k.get("Name", k.get("KernelName", ""))
-        if any(t in name for t in ("k_gd_", "k_dm_", "k_reproject")):
+        if any(t in name for t in ("k_gd_", "k_reproject")):
             L.append(f"(d) {k['run']}: " + ", ".join(f"{c}={k[c]}" for c in k if c in ("Name", "KernelName", "Calls", "TotalDurationNs", "AverageNs", "MinNs", "MaxNs")))
     with open(os.path.join(a.out_dir, "r13_demod_quality.txt"), "w") as f:
         f.write("\n".join(L) + "\n")

@@ -264,7 +264,7 @@ def main():
                              f"{m['plain_filled_only'][0]:.4f} / {m['plain_filled_only'][1]:.4f}")
     for k in res.get("kernel_stats", []):
         kn = k.get("Name", k.get("KernelName", ""))
-        if any(t in kn for t in ("k_gd_", "k_dm_", "k_lattice")):
+        if any(t in kn for t in ("k_gd_", "k_lattice")):
             L.append(f"(e) {k['run']}: " + ", ".join(f"{c}={k[c]}" for c in k if c in ("Name", "KernelName", "Calls", "TotalDurationNs", "AverageNs", "MinNs", "MaxNs")))
     with open(os.path.join(a.out_dir, "r14_interleaved_quality.txt"), "w") as f:
         f.write("\n".join(L) + "\n")
