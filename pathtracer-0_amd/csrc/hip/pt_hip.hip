@@ -34,6 +34,7 @@
 #include "../../../include/pt_fill.h"
 #include "../../../include/pt_through.h"
 #include "../../../include/pt_motion.h"
+#include "../../../include/pt_validate.h"
 #include "pt_device.hpp"
 #include "pt_image_launch.hpp"
 
@@ -1325,6 +1326,10 @@ struct pt_ctx {
     uint64_t otherGen = 0, camWrites = 0;
     struct Mark { bool valid = false; int image = 0; uint64_t camWrites = 0, otherGen = 0; int nTri = 0, nEl = 0; std::vector<float> tri, el; } mark;
     float4* dMarkFeat = nullptr; float4* dMarkTri = nullptr; float4* dMarkEl = nullptr; float4* dMoveTri = nullptr; float4* dMoveEl = nullptr;
+    // include/pt_validate.h.  The hold (on a group's first stream): the held FRAME and T in pixel order (H and V, W*H float4 each), the image they were
+    // taken from, the frame inputs of its camera record and sceneGen then; pt_history_merge's kappa (W*H floats, only when asked for)
+    struct Hold { bool valid = false; int image = 0; FrameIn in{}; uint64_t sceneGen = 0; } hold;
+    float4* dHoldFrame = nullptr; float4* dHoldStats = nullptr; float* dKappa = nullptr;
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
@@ -2480,7 +2485,7 @@ int pt_destroy(pt_ctx* c) {
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
                     c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
                     c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount, c->dThru, c->dThruRays,
-                    c->dMarkFeat, c->dMarkTri, c->dMarkEl, c->dMoveTri, c->dMoveEl};
+                    c->dMarkFeat, c->dMarkTri, c->dMarkEl, c->dMoveTri, c->dMoveEl, c->dHoldFrame, c->dHoldStats, c->dKappa};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);

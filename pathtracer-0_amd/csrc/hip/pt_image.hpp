@@ -1,6 +1,6 @@
 // pt_image.hpp — the host half of the image-space passes behind the C ABI (included by pt_hip.hip inside its extern "C" block, where pt_ctx and
 // its helpers are in scope; not a translation unit).  T in pixel order, the feature and seen-through records, the a-trous and the variance-guided
-// filter, the reprojection across camera moves and moved geometry, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
+// filter, the reprojection across camera moves and moved geometry, the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
 // and pt_reproject.hip's, behind pt_image_launch.hpp; the kernels of the records are pt_hip.hip's.
 
 // ---- T in pixel order (include/pt_adaptive.h, include/pt_guided.h): a group's streams each hold the slots of their own shard, so T travels through the host
@@ -529,6 +529,107 @@ int pt_reproject_frame_moved(pt_ctx* c, float max_history, float depth_tol, floa
     int64_t n = 0;
     const int rc = reprojectImage(c, "pt_reproject_frame_moved", true, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
     if (n_kept) *n_kept = n;
+    return rc;
+}
+
+
+// ---- history validation (include/pt_validate.h): the hold lives on the first stream's context, where the merge runs; a group's image and T travel
+// as they do for the reprojection
+namespace {
+int syncAll(pt_ctx* c) {
+    if (c->multi) return multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); });
+    return pt_synchronize(c);
+}
+
+int historyHold(pt_ctx* c) {
+    int rc;
+    if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_history_hold"))) return rc;
+    if ((rc = syncAll(c))) return rc;                             // all submitted work lands in FRAME and T first
+    pt_ctx* on = nullptr;
+    const float4* frame = nullptr; const float4* stats = nullptr;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_history_hold", &on, &frame))) return rc;
+    if ((rc = wholeStats(c, on, &stats))) return rc;
+    if (!stats) return fail(PT_ERR_ARG, "pt_history_hold: the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
+    const pt_ctx::Cam h = on->cam[on->curImage];
+    if (!h.valid) return fail(PT_ERR_ARG, "pt_history_hold: the current image has no camera (render or pt_write_frame first)");
+    HIP_TRY(hipSetDevice(on->device));
+    const size_t n = (size_t)c->W * c->H;
+    if (!on->dHoldFrame) HIP_TRY(hipMalloc((void**)&on->dHoldFrame, n * 16));
+    if (!on->dHoldStats) HIP_TRY(hipMalloc((void**)&on->dHoldStats, n * 16));
+    on->hold.valid = false;
+    HIP_TRY(hipMemcpyAsync(on->dHoldFrame, frame, n * 16, hipMemcpyDeviceToDevice, on->stream));
+    HIP_TRY(hipMemcpyAsync(on->dHoldStats, stats, n * 16, hipMemcpyDeviceToDevice, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    auto zero = [](pt_ctx* k) {                                   // the image and T alone: the camera records, camWrites and a mark stay
+        HIP_TRY(hipSetDevice(k->device));
+        HIP_TRY(hipMemsetAsync(k->dImage[k->curImage], 0, (size_t)k->nSlotsImg * 16, k->stream));
+        if (k->dStats) HIP_TRY(hipMemsetAsync(k->dStats, 0, (size_t)k->nSlotsImg * 16, k->stream));
+        HIP_TRY(hipStreamSynchronize(k->stream));
+        return 0;
+    };
+    if (c->multi) { if ((rc = multiRun(*c->multi, zero))) return rc; }
+    else if ((rc = zero(c))) return rc;
+    on->hold.image = on->curImage; on->hold.in = h.in; on->hold.sceneGen = on->sceneGen;
+    on->hold.valid = true;
+    return PT_OK;
+}
+
+int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t* nReduced) {
+    if (r.radius < 1 || r.radius > 4) return fail(PT_ERR_ARG, "pt_history_merge: rule.radius must be in [1,4]");
+    if (!__builtin_isfinite(r.z_lo) || !__builtin_isfinite(r.z_hi) || !(r.z_lo >= 0.0f && r.z_lo < r.z_hi))
+        return fail(PT_ERR_ARG, "pt_history_merge: rule.z_lo and rule.z_hi must be finite with 0 <= z_lo < z_hi");
+    if (!(r.normal_tol >= -1.0f && r.normal_tol <= 1.0f)) return fail(PT_ERR_ARG, "pt_history_merge: rule.normal_tol must be in [-1, 1]");
+    int rc;
+    if ((rc = syncAll(c))) return rc;                             // work in flight lands in FRAME and T first
+    pt_ctx* on = firstStream(c);
+    const pt_ctx::Hold& hd = on->hold;
+    if (!hd.valid) return fail(PT_ERR_ARG, "pt_history_merge: no hold (pt_history_hold first; a hold serves one merge)");
+    if (hd.image != on->curImage) return fail(PT_ERR_ARG, "pt_history_merge: the hold belongs to another image");
+    const pt_ctx::Cam h = on->cam[on->curImage];
+    if (!h.valid) return fail(PT_ERR_ARG, "pt_history_merge: the image has no camera (pt_reset_frame since the hold)");
+    if (std::memcmp(&h.in, &hd.in, sizeof(FrameIn)) != 0)
+        return fail(PT_ERR_ARG, "pt_history_merge: the image's camera no longer has the held frame inputs (a render or pt_write_frame under other inputs)");
+    if (hd.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_history_merge: a scene buffer or texture was uploaded since the hold");
+    FrameIn cur;
+    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
+    const float* P = on->params.data();
+    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
+    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_history_merge: DEBUG != 0 renders the traversal heat map, which has no surfaces to compare on");
+    ValidateJob j;
+    if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_history_merge", &on, &j.frame))) return rc;      // a group: gathered on on->stream
+    if ((rc = wholeStats(c, on, &j.stats))) return rc;
+    if (!j.stats) return fail(PT_ERR_ARG, "pt_history_merge: the image has no luminance moments");
+    if ((rc = ensureFeatures(on))) return rc;
+    HIP_TRY(hipSetDevice(on->device));
+    const size_t n = (size_t)c->W * c->H;
+    if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
+    if (!on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
+    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
+    if (kappaOut && !on->dKappa) HIP_TRY(hipMalloc((void**)&on->dKappa, n * 4));
+    j.feat = on->dFeat; j.heldFrame = on->dHoldFrame; j.heldStats = on->dHoldStats;
+    j.W = c->W; j.H = c->H; j.radius = r.radius; j.zLo = r.z_lo; j.zHi = r.z_hi; j.normalTol = r.normal_tol;
+    j.overlay[0] = cur.mouse[0]; j.overlay[1] = cur.mouse[1]; j.overlay[2] = cur.params[2];
+    j.outFrame = on->dRpFrame; j.outStats = on->dRpStats; j.kappa = kappaOut ? on->dKappa : nullptr; j.reduced = on->dRpKept;
+    HIP_TRY(validateLaunch(j, on->stream));
+    if (kappaOut) HIP_TRY(hipMemcpyAsync(kappaOut, on->dKappa, n * 4, hipMemcpyDeviceToHost, on->stream));
+    if ((rc = storeReprojected(c, on, true, nReduced))) return rc;      // (records the same camera again)
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    on->hold.valid = false;                                       // spent
+    return 0;
+}
+}  // namespace
+
+int pt_history_hold(pt_ctx* c) {
+    if (!c) return fail(PT_ERR_ARG, "pt_history_hold: null context");
+    return historyHold(c);
+}
+
+int pt_history_merge(pt_ctx* c, const pt_validate_rule* rule, float* kappa_out, int64_t* n_reduced) {
+    if (n_reduced) *n_reduced = 0;
+    if (!c || !rule) return fail(PT_ERR_ARG, "pt_history_merge: null argument");
+    int64_t n = 0;
+    const int rc = historyMerge(c, *rule, kappa_out, &n);
+    if (n_reduced) *n_reduced = n;
     return rc;
 }
 

@@ -60,3 +60,17 @@ struct ReprojectJob {
     float4* outFrame = nullptr; float4* outStats = nullptr; unsigned* kept = nullptr;
 };
 hipError_t reprojectLaunch(const ReprojectJob& j, hipStream_t s);
+
+// ---- the history validation of include/pt_validate.h (pt_reproject.hip)
+struct ValidateJob {
+    // feat: W*H*4 float4 feature records under the current inputs; frame, stats: FRAME and T now (N, U); heldFrame, heldStats: the held ones (H, V);
+    // all W*H float4 in pixel order, read only
+    const float4* feat = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
+    const float4* heldFrame = nullptr; const float4* heldStats = nullptr;
+    int W = 0, H = 0, radius = 0;                                 // radius: 1 .. 4 (checked by the caller)
+    float zLo = 0.0f, zHi = 0.0f, normalTol = 0.0f;
+    float overlay[3] = {0.0f, 0.0f, 0.0f};                        // (mouse x, mouse y, resolution) of the overlay test
+    // outFrame, outStats: W*H float4; kappa: W*H floats, or null; *reduced (zeroed first): the pixels with H.a > 0 and kappa < 1
+    float4* outFrame = nullptr; float4* outStats = nullptr; float* kappa = nullptr; unsigned* reduced = nullptr;
+};
+hipError_t validateLaunch(const ValidateJob& j, hipStream_t s);

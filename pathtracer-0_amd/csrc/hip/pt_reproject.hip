@@ -1,4 +1,4 @@
-// pt_reproject.hip — the reprojection of include/pt_reproject.h for gfx950.
+// pt_reproject.hip — the reprojection of include/pt_reproject.h and the history validation of include/pt_validate.h for gfx950.
 //
 // Device pointers only: pt_hip.hip owns the buffers, computes both sets of feature records and calls reprojectLaunch on its stream.
 //   k_reproject<MOVED, DEMOD>  one lane per new pixel, a wave = 64 pixels of a row, a block = 16 rows.  Reads 48 B of Rn[p] (F0, F1.w, F2), the same
@@ -8,6 +8,10 @@
 //                <false, false>  include/pt_reproject.h
 //                <false, true>   include/pt_demod.h: step 7 carries illumination
 //                <true, DEMOD>   include/pt_motion.h: the hit's surface point followed back to where its primitive was at the mark
+//   k_history_merge<R>  include/pt_validate.h: one lane per pixel in the same blocks.  The block's tile with its halo of R pixels is staged in LDS
+//                once, as ten planes of floats (the six moments, zeroed where a pixel can be no tap for any centre; the normal; one class /
+//                material word), so that a tap costs ten LDS reads of consecutive words per wave and no global load; then steps 1-4 and the
+//                reduced count, counted as k_reproject counts the kept pixels.
 // Under the bit-exact contract: binary32 * + / sqrt in the header's order, no contraction (the build's -ffp-contract=off, IEEE divides).
 #include <hip/hip_runtime.h>
 
@@ -192,6 +196,93 @@ __global__ void __launch_bounds__(RP_BX * RP_BY) k_reproject(const float4* __res
     if (threadIdx.x == 0 && threadIdx.y == 0 && blockKept) atomicAdd(kept, blockKept);
 }
 
+// max(x, 0) of include/pt_guided.h: a NaN is no estimate
+__device__ __forceinline__ float clampVar(float x) { return x >= 0.0f ? x : (x < 0.0f ? 0.0f : __builtin_inff()); }
+
+// include/pt_validate.h, steps 1-4.  The tile: pixel (tx, ty) of the block's 64 x 16 plus a halo of R on every side, plane by plane.  A pixel that
+// fails what no centre can mend (outside the image, not paired, a sum that is not finite) has its six moments stored as zeros: adding +0 to a sum
+// that started at +0 changes no bit of it, so the tap loop needs no test for these.  The word plane holds the material word of a hit and -1 for a
+// miss — k_feature_record gives a hit the index of its material, never -1 — so that "p's class and, for a hit, p's material" is one compare.
+struct ValidateRule { float zLo, zHi, normalTol, mouseX, mouseY, resolution; };
+template <int R>
+__global__ void __launch_bounds__(RP_BX * RP_BY) k_history_merge(const float4* __restrict__ rec, const float4* __restrict__ frameN, const float4* __restrict__ statsU,
+                                                                const float4* __restrict__ frameH, const float4* __restrict__ statsV, int W, int H, ValidateRule r,
+                                                                float4* __restrict__ outFrame, float4* __restrict__ outStats, float* __restrict__ kappaOut,
+                                                                unsigned* __restrict__ reduced) {
+    constexpr int TW = RP_BX + 2 * R, TH = RP_BY + 2 * R, TN = TW * TH;
+    enum { SY_N, SYY_N, N_N, SY_H, SYY_H, N_H, NX, NY, NZ, WORD, PLANES };
+    __shared__ float tile[PLANES][TN];
+    __shared__ unsigned blockReduced;
+    const int tid = threadIdx.y * RP_BX + threadIdx.x;
+    if (tid == 0) blockReduced = 0;
+    const int x0 = blockIdx.x * RP_BX - R, y0 = blockIdx.y * RP_BY - R;
+    for (int i = tid; i < TN; i += RP_BX * RP_BY) {
+        const int gx = x0 + i % TW, gy = y0 + i / TW;
+        float4 U = make_float4(0.0f, 0.0f, 0.0f, 0.0f), V = U, f0 = U;
+        int word = -1;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t g = (size_t)gy * W + gx;
+            const float4 u = statsU[g], v = statsV[g];
+            if (u.z >= 1.0f && v.z >= 1.0f && __builtin_isfinite(u.x) && __builtin_isfinite(u.y) && __builtin_isfinite(v.x) && __builtin_isfinite(v.y)) { U = u; V = v; }
+            f0 = rec[4 * g];
+            const float* w = reinterpret_cast<const float*>(rec + 4 * g);
+            word = __float_as_int(w[7]) != -1 ? __float_as_int(w[11]) : -1;
+        }
+        tile[SY_N][i] = U.x; tile[SYY_N][i] = U.y; tile[N_N][i] = U.z; tile[SY_H][i] = V.x; tile[SYY_H][i] = V.y; tile[N_H][i] = V.z;
+        tile[NX][i] = f0.y; tile[NY][i] = f0.z; tile[NZ][i] = f0.w; tile[WORD][i] = __int_as_float(word);
+    }
+    __syncthreads();
+    const int x = blockIdx.x * RP_BX + threadIdx.x, y = blockIdx.y * RP_BY + threadIdx.y;
+    const bool in = x < W && y < H;
+    bool less = false;
+    if (in) {
+        float kappa = 1.0f;
+        FrameConst fc;
+        fc.mouse[0] = r.mouseX; fc.mouse[1] = r.mouseY; fc.resolution = r.resolution;
+        if (!inMouseOverlay(fc, x, y)) {                                                   // 1
+            const int c = (threadIdx.y + R) * TW + threadIdx.x + R;
+            const float Nx = tile[NX][c], Ny = tile[NY][c], Nz = tile[NZ][c];
+            const int word = __float_as_int(tile[WORD][c]);
+            float SN = 0.0f, QN = 0.0f, NN = 0.0f, SH = 0.0f, QH = 0.0f, NH = 0.0f;
+#pragma unroll 1
+            for (int dy = -R; dy <= R; dy++) {                                             // 2: a row of taps at a time in registers (all of them spill)
+#pragma unroll
+                for (int dx = -R; dx <= R; dx++) {
+                    const int q = c + dy * TW + dx;
+                    const bool tap = __float_as_int(tile[WORD][q]) == word && (word == -1 || dot3(Nx, Ny, Nz, tile[NX][q], tile[NY][q], tile[NZ][q]) >= r.normalTol);
+                    SN = SN + (tap ? tile[SY_N][q] : 0.0f); QN = QN + (tap ? tile[SYY_N][q] : 0.0f); NN = NN + (tap ? tile[N_N][q] : 0.0f);
+                    SH = SH + (tap ? tile[SY_H][q] : 0.0f); QH = QH + (tap ? tile[SYY_H][q] : 0.0f); NH = NH + (tap ? tile[N_H][q] : 0.0f);
+                }
+            }
+            if (NN >= 2.0f && NH >= 2.0f) {                                                // 3
+                const float mN = SN / NN, s2N = clampVar((QN - SN * mN) / (NN - 1.0f));
+                const float mH = SH / NH, s2H = clampVar((QH - SH * mH) / (NH - 1.0f));
+                const float var = s2N / NN + s2H / NH;
+                const float d = __builtin_fabsf(mN - mH);
+                const float z = sqrtf((d * d) / var);
+                if (z != z || z <= r.zLo) kappa = 1.0f;
+                else if (z >= r.zHi) kappa = 0.0f;
+                else kappa = (r.zHi - z) / (r.zHi - r.zLo);
+            }
+        }
+        const size_t p = (size_t)y * W + x;                                                // 4
+        const float4 N = frameN[p], U = statsU[p], Hh = frameH[p];
+        float4 F = N, T = make_float4(U.x, U.y, U.z, 0.0f);
+        if (kappa != 0.0f) {
+            const float4 V = statsV[p];
+            F = make_float4(N.x + kappa * Hh.x, N.y + kappa * Hh.y, N.z + kappa * Hh.z, N.w + kappa * Hh.w);
+            T = make_float4(U.x + kappa * V.x, U.y + kappa * V.y, U.z + kappa * V.z, 0.0f);
+        }
+        outFrame[p] = F; outStats[p] = T;
+        if (kappaOut) kappaOut[p] = kappa;
+        less = Hh.w > 0.0f && kappa < 1.0f;
+    }
+    const unsigned long long m = __ballot(less);                                           // every lane of the block, in range or not
+    if (threadIdx.x == 0 && m) atomicAdd(&blockReduced, (unsigned)__popcll(m));
+    __syncthreads();
+    if (tid == 0 && blockReduced) atomicAdd(reduced, blockReduced);
+}
+
 }  // namespace
 
 // floorA > 0 alone selects the demodulated step 7, `motion` alone the followed-back step 2
@@ -208,5 +299,20 @@ hipError_t reprojectLaunch(const ReprojectJob& j, hipStream_t s) {
     else hipLaunchKernelGGL((k_reproject<false, false>), grid, block, 0, s, RP_IN, RP_OUT);
 #undef RP_IN
 #undef RP_OUT
+    return hipGetLastError();
+}
+
+hipError_t validateLaunch(const ValidateJob& j, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(j.reduced, 0, 4, s);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)((j.W + RP_BX - 1) / RP_BX), (unsigned)((j.H + RP_BY - 1) / RP_BY)), block(RP_BX, RP_BY);
+    const ValidateRule r{j.zLo, j.zHi, j.normalTol, j.overlay[0], j.overlay[1], j.overlay[2]};
+#define VL_ARGS j.feat, j.frame, j.stats, j.heldFrame, j.heldStats, j.W, j.H, r, j.outFrame, j.outStats, j.kappa, j.reduced
+    if (j.radius == 1) hipLaunchKernelGGL(k_history_merge<1>, grid, block, 0, s, VL_ARGS);
+    else if (j.radius == 2) hipLaunchKernelGGL(k_history_merge<2>, grid, block, 0, s, VL_ARGS);
+    else if (j.radius == 3) hipLaunchKernelGGL(k_history_merge<3>, grid, block, 0, s, VL_ARGS);
+    else if (j.radius == 4) hipLaunchKernelGGL(k_history_merge<4>, grid, block, 0, s, VL_ARGS);
+    else return hipErrorInvalidValue;
+#undef VL_ARGS
     return hipGetLastError();
 }

@@ -163,6 +163,9 @@ def lib():
             cf = C.c_float
             L.pt_motion_mark.argtypes = [vp]
             L.pt_reproject_frame_moved.argtypes = [vp, cf, cf, cf, ci, cf, C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_history_hold"):                     # include/pt_validate.h
+            L.pt_history_hold.argtypes = [vp]
+            L.pt_history_merge.argtypes = [vp, C.POINTER(ValidateRule), vp, C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -176,6 +179,11 @@ class GuidedRule(C.Structure):
 class ThroughRule(C.Structure):
     """pt_through_rule of include/pt_through.h"""
     _fields_ = [("max_depth", C.c_int), ("min_weight", C.c_float), ("lobes", C.c_int), ("flags", C.c_int)]
+
+
+class ValidateRule(C.Structure):
+    """pt_validate_rule of include/pt_validate.h"""
+    _fields_ = [("radius", C.c_int), ("z_lo", C.c_float), ("z_hi", C.c_float), ("normal_tol", C.c_float)]
 
 
 class PtError(RuntimeError):
@@ -399,6 +407,35 @@ class Renderer:
         flags = self.REPROJECT_ALL_MATERIALS if all_materials else 0
         _check(self._L.pt_reproject_frame_moved(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, float(albedo_floor), C.byref(n)))
         return n.value
+
+    # --- history validation (include/pt_validate.h) -------------------------------------------------
+    # defaults of validate_rule: the float32 model on the oracle's frames at 160 x 90 (tests/test_validate_abi.py), 64 frames,
+    # one jump, 4 calls of 4 frames, clamped RMSE against 256 frames.  Light slid by 0.5 (M2): reproject only 0.0894, validated 0.0593 with
+    # z = (3, 5) and 0.0610 with (2, 4), reset 0.1443; M1 pose 0 -> 8 (light fixed): 0.0418 / 0.0414 / 0.0419 / 0.1458.  Radius 2 gave 0.0600
+    # on the light jump against 0.0593 for radius 3.
+    VALIDATE_RADIUS = 3
+    VALIDATE_Z = (3.0, 5.0)
+    VALIDATE_NORMAL_TOL = 0.9
+
+    def validate_rule(self, radius=None, z_lo=None, z_hi=None, normal_tol=None):
+        """the pt_validate_rule of these arguments; None takes the defaults above"""
+        return ValidateRule(int(self.VALIDATE_RADIUS if radius is None else radius), float(self.VALIDATE_Z[0] if z_lo is None else z_lo),
+                            float(self.VALIDATE_Z[1] if z_hi is None else z_hi), float(self.VALIDATE_NORMAL_TOL if normal_tol is None else normal_tol))
+
+    def history_hold(self):
+        """Move FRAME and T of the current image aside and zero both (pt_history_hold): render the new frames next, with record_moments on, then
+        history_merge.  After an upload that moves no surface (materials, textures) nothing is needed before the hold; a camera or geometry move
+        goes through reproject_frame / motion_mark + reproject_frame_moved first."""
+        _check(self._L.pt_history_hold(self._h))
+
+    def history_merge(self, rule=None, want_kappa=False):
+        """Add the held history back, scaled down per pixel where the new frames contradict it (pt_history_merge).  Returns how many pixels with
+        a history had it reduced, or (that count, kappa as (H, W) float32 in FRAME order) with want_kappa.  The hold is spent."""
+        rule = self.validate_rule() if rule is None else rule
+        n = C.c_int64(0)
+        kappa = np.zeros((self.H, self.W), dtype=np.float32) if want_kappa else None
+        _check(self._L.pt_history_merge(self._h, C.byref(rule), kappa.ctypes.data if want_kappa else None, C.byref(n)))
+        return (n.value, kappa) if want_kappa else n.value
 
     # --- luminance moments and the variance-guided filter (include/pt_guided.h) ---------------------
     # defaults of denoise_guided / read_display_denoised_guided: sigma_lum and min_frames from scripts/guided_quality.py's grid on C3 and C6

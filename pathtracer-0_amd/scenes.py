@@ -229,8 +229,8 @@ def _cornell_materials(sc):
     return idx
 
 
-def _cornell_room(o, boxes=True):
-    # room: x in [-1,1], y in [0,2], z in [-1,1]; open towards -z (camera side)
+def _cornell_room(o, boxes=True, light_dx=0.0):
+    # room: x in [-1,1], y in [0,2], z in [-1,1]; open towards -z (camera side); light_dx slides the light quad along x
     o.group("walls")
     o.usemtl("white")
     o.quad((-1, 0, -1), (1, 0, -1), (1, 0, 1), (-1, 0, 1), (0, 1, 0))          # floor
@@ -242,7 +242,7 @@ def _cornell_room(o, boxes=True):
     o.quad((-1, 0, -1), (-1, 0, 1), (-1, 2, 1), (-1, 2, -1), (1, 0, 0))        # -x wall
     o.group("light")
     o.usemtl("light")
-    o.quad((-0.25, 1.98, -0.25), (0.25, 1.98, -0.25), (0.25, 1.98, 0.25), (-0.25, 1.98, 0.25), (0, -1, 0))
+    o.quad((-0.25 + light_dx, 1.98, -0.25), (0.25 + light_dx, 1.98, -0.25), (0.25 + light_dx, 1.98, 0.25), (-0.25 + light_dx, 1.98, 0.25), (0, -1, 0))
     if boxes:
         o.group("tallbox")
         o.usemtl("white")
@@ -431,12 +431,12 @@ def t1_textured(W=96, H=54, sample_res=8, max_bounces=8):
     return wl
 
 
-def m1_moving(step=0, W=96, H=54, sample_res=8, max_bounces=8, subdiv=2, textured=True):
+def m1_moving(step=0, W=96, H=54, sample_res=8, max_bounces=8, subdiv=2, textured=True, light_dx=0.0):
     """M1, the moving-geometry workload of include/pt_motion.h (not a BASELINE config): the Cornell room without its boxes plus four things whose
     pose is a function of `step` — a box that translates and turns about y, a smooth-normal icosphere that rotates about its centre, a textured
     quad that translates, an ellipsoid that translates and grows.  Everything is built in the same order at every step, so triangle k and
     ellipsoid k are the same piece of surface throughout; step 0 is the rest pose.  Every material is diffuse; textured=False leaves the quad's
-    map_Kd out (the same triangles, no texture table)."""
+    map_Kd out (the same triangles, no texture table).  light_dx slides the light quad along x (m2_relit)."""
     s = float(step)
     sc = _new_scene()
     _cornell_materials(sc)
@@ -445,7 +445,7 @@ def m1_moving(step=0, W=96, H=54, sample_res=8, max_bounces=8, subdiv=2, texture
         sc.setLastMtl("map_Kd", 1)
     ball = sc.addMaterial("ball"); sc.setLastMtl("Kd", (0.2, 0.3, 0.7)); sc.setLastMtl("Pr", 1)
     o = Obj()
-    _cornell_room(o, boxes=False)
+    _cornell_room(o, boxes=False, light_dx=light_dx)
     o.group("box")
     o.usemtl("white")
     o.box((0.45 + 0.02 * s, 0.3, 0.15 - 0.01 * s), (0.25, 0.3, 0.25), 0.3 + 0.02 * s)
@@ -469,6 +469,14 @@ def m1_moving(step=0, W=96, H=54, sample_res=8, max_bounces=8, subdiv=2, texture
             tex[j, i, :3] = (230, 200, 60) if (i + j) % 2 else (60, 40, 160)
     tex[..., 3] = 255
     wl.textures = {1: tex} if textured else {}
+    return wl
+
+
+def m2_relit(step=0, W=96, H=54, **kw):
+    """M2, the relit workload of include/pt_validate.h (not a BASELINE config): M1's rest pose with the light quad slid by 0.05 * step along x.
+    No surface but the light moves; the shadows and the lit walls change everywhere else."""
+    wl = m1_moving(0, W, H, light_dx=0.05 * float(step), **kw)
+    wl.name = "M2"
     return wl
 
 
@@ -555,6 +563,8 @@ def build(name, W=None, H=None, **kw):
         return t1_textured(W or 96, H or 54, **kw)
     if name == "M1":
         return m1_moving(kw.pop("step", 0), W or 96, H or 54, **kw)
+    if name == "M2":
+        return m2_relit(kw.pop("step", 0), W or 96, H or 54, **kw)
     cfg = CONFIGS[name]
     W = cfg["W"] if W is None else W
     H = cfg["H"] if H is None else H
