@@ -35,6 +35,7 @@
 #include "../../../include/pt_through.h"
 #include "../../../include/pt_motion.h"
 #include "../../../include/pt_validate.h"
+#include "../../../include/pt_reproject_through.h"
 #include "pt_device.hpp"
 #include "pt_image_launch.hpp"
 
@@ -1319,6 +1320,10 @@ struct pt_ctx {
     float4* dFill = nullptr; unsigned* dFillCount = nullptr;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count, allocated on first use
     // include/pt_through.h: the seen-through records (W*H x 4 float4) and their last segments (W*H x 2 float4) under thruRule, cached like dFeat
     float4* dThru = nullptr; float4* dThruRays = nullptr; bool thruValid = false; pt_through_rule thruRule{};
+    // include/pt_reproject_through.h: the same pair under the current image's camera (cached like dFeatH, for the inputs thruHIn and the rule thruHRule)
+    // and the packed candidates of k_through_pack (W*H x 2 float4); dRpKept holds two counts
+    float4* dThruH = nullptr; float4* dThruRaysH = nullptr; bool thruHValid = false; pt_through_rule thruHRule{}; FrameIn thruHIn{};
+    float4* dRpPack = nullptr;
     // include/pt_motion.h.  otherGen counts the uploads that are not geometry (bindings 5, 14 and textures) beside sceneGen, which counts all;
     // camWrites counts every write of a camera record, so that a mark can tell that its image's record is still the one it saw.  The mark: Rh
     // (dMarkFeat), the primitives' positions then on the device (3 float4 each) and on the host (9 floats per triangle, 10 per ellipsoid); the
@@ -2485,7 +2490,7 @@ int pt_destroy(pt_ctx* c) {
                     c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
                     c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
                     c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount, c->dThru, c->dThruRays,
-                    c->dMarkFeat, c->dMarkTri, c->dMarkEl, c->dMoveTri, c->dMoveEl, c->dHoldFrame, c->dHoldStats, c->dKappa};
+                    c->dMarkFeat, c->dMarkTri, c->dMarkEl, c->dMoveTri, c->dMoveEl, c->dHoldFrame, c->dHoldStats, c->dKappa, c->dThruH, c->dThruRaysH, c->dRpPack};
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
     if (c->hFrameIn) hipHostFree(c->hFrameIn);
@@ -2513,7 +2518,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         return PT_OK;
     }
     if (bytes % 4) return fail(PT_ERR_ARG, "pt_set_buffer: size must be a multiple of 4 bytes");
-    c->featValid = false; c->featHValid = false; c->thruValid = false;                  // any binding may move the camera or the scene under the feature records
+    c->featValid = false; c->featHValid = false; c->thruValid = false; c->thruHValid = false;                  // any binding may move the camera or the scene under the feature records
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
         case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
@@ -2547,7 +2552,7 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
         return PT_OK;
     }
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
-    c->featValid = false; c->featHValid = false; c->thruValid = false;
+    c->featValid = false; c->featHValid = false; c->thruValid = false; c->thruHValid = false;
     c->sceneGen++; c->otherGen++;
     if (index == 0) { c->sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->skyW = w; c->skyH = h; }
     if ((size_t)index >= c->textures.size()) c->textures.resize((size_t)index + 1);

@@ -1,6 +1,6 @@
 // pt_image.hpp — the host half of the image-space passes behind the C ABI (included by pt_hip.hip inside its extern "C" block, where pt_ctx and
 // its helpers are in scope; not a translation unit).  T in pixel order, the feature and seen-through records, the a-trous and the variance-guided
-// filter, the reprojection across camera moves and moved geometry, the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
+// filter, the reprojection across camera moves (also through mirror and glass chains) and moved geometry, the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
 // and pt_reproject.hip's, behind pt_image_launch.hpp; the kernels of the records are pt_hip.hip's.
 
 // ---- T in pixel order (include/pt_adaptive.h, include/pt_guided.h): a group's streams each hold the slots of their own shard, so T travels through the host
@@ -118,24 +118,19 @@ int checkThrough(const pt_through_rule* r, const char* who) {
     if (r->flags & ~PT_THROUGH_KEY) return fail(PT_ERR_ARG, w + ": unknown rule.flags");
     return 0;
 }
-// the seen-through records of the current frame inputs under `rule` (c->dThru) and their last segments (c->dThruRays): ensureFeaturesFor's probe
-// pool and ray kernel, then max_depth + 1 rounds of (intersect, k_through_step) — a fixed count, nothing read back in between: a round whose
-// lanes are all dead costs two launches that return at once
-int ensureThrough(pt_ctx* c, const pt_through_rule& rule, const char* who) {
+// the seen-through records of the frame inputs `fin` under `rule` into *recs (W*H x 4 float4) and their last segments into *rays (W*H x 2 float4),
+// both allocated on first use; *valid says they are there: ensureFeaturesFor's probe pool and ray kernel, then max_depth + 1 rounds of (intersect,
+// k_through_step) — a fixed count, nothing read back in between: a round whose lanes are all dead costs two launches that return at once
+int ensureThroughFor(pt_ctx* c, const FrameIn& fin, const pt_through_rule& rule, const char* who, float4** recs, float4** rays, bool* valid) {
     HIP_TRY(hipSetDevice(c->device));
-    if (c->thruValid && std::memcmp(&c->thruRule, &rule, sizeof(rule)) == 0) return 0;
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
-    FrameIn fin;
-    currentInputs(c, fin);
+    if (*valid) return 0;
     int rc;
     if ((rc = claimFrameConstants(c))) return rc;
     if ((rule.flags & PT_THROUGH_KEY) && c->sc.numMat > 4096)
         return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": PT_THROUGH_KEY packs a material index into 12 bits; the scene has more than 4096 materials");
-    c->thruValid = false;
     const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
-    if (!c->dThru) HIP_TRY(hipMalloc((void**)&c->dThru, n * 64));
-    if (!c->dThruRays) HIP_TRY(hipMalloc((void**)&c->dThruRays, n * 32));
+    if (!*recs) HIP_TRY(hipMalloc((void**)recs, n * 64));
+    if (!*rays) HIP_TRY(hipMalloc((void**)rays, n * 32));
     State st{};
     Scratch scratch;
     if ((rc = probePool(scratch, st, np, c->sc.numEllip > 0))) return rc;
@@ -153,7 +148,7 @@ int ensureThrough(pt_ctx* c, const pt_through_rule& rule, const char* who) {
     const ThroughRule tr{depth, rule.min_weight, rule.lobes, rule.flags};
     for (int step = 0; step <= depth; step++) {
         if ((rc = probeIntersect(c, st, np, fin))) return rc;
-#define THROUGH_STEP(T) hipLaunchKernelGGL(k_through_step<T>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, tr, step, X, (unsigned)np, c->dThru, c->dThruRays)
+#define THROUGH_STEP(T) hipLaunchKernelGGL(k_through_step<T>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, tr, step, X, (unsigned)np, *recs, *rays)
         if (c->niBits == 3) THROUGH_STEP(3);
         else if (c->niBits == 8) THROUGH_STEP(8);
         else if (c->niBits == 32) THROUGH_STEP(32);
@@ -162,8 +157,27 @@ int ensureThrough(pt_ctx* c, const pt_through_rule& rule, const char* who) {
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
+    *valid = true;
+    return 0;
+}
+// the records of the current frame inputs under `rule` (c->dThru, c->dThruRays)
+int ensureThrough(pt_ctx* c, const pt_through_rule& rule, const char* who) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->thruValid && std::memcmp(&c->thruRule, &rule, sizeof(rule)) == 0) return 0;
+    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
+    FrameIn fin;
+    currentInputs(c, fin);
+    c->thruValid = false;
+    if (int rc = ensureThroughFor(c, fin, rule, who, &c->dThru, &c->dThruRays, &c->thruValid)) return rc;
     c->thruRule = rule;
-    c->thruValid = true;
+    return 0;
+}
+// the records of the frame inputs `fin` of the current image's camera under `rule` (c->dThruH, c->dThruRaysH): include/pt_reproject_through.h's Sh, Yh
+int ensureThroughH(pt_ctx* c, const FrameIn& fin, const pt_through_rule& rule, const char* who) {
+    if (c->thruHValid && (std::memcmp(&c->thruHRule, &rule, sizeof(rule)) != 0 || std::memcmp(&c->thruHIn, &fin, sizeof(FrameIn)) != 0)) c->thruHValid = false;
+    if (int rc = ensureThroughFor(c, fin, rule, who, &c->dThruH, &c->dThruRaysH, &c->thruHValid)) return rc;
+    c->thruHRule = rule; c->thruHIn = fin;
     return 0;
 }
 
@@ -376,8 +390,11 @@ void motionPack(const std::vector<float>& tri, int nTri, const std::vector<float
 
 // The image of `c` mapped to the current inputs, stored as its current image; *nKept = the pixels kept.  `moved`: include/pt_motion.h's call, with Rh
 // and the primitives' old positions from the mark (which it spends); else include/pt_reproject.h's, Rh from the image's camera.
-// floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor (the unmoved call's: checked by the caller)
-int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept) {
+// floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor (the unmoved call's: checked by the caller).
+// chain (not moved, floorA 0; checked by the caller): include/pt_reproject_through.h's call, Sn / Yn and Sh / Yh beside Rn and Rh
+struct ChainCarry { const pt_through_rule* thru; float pointTol; int radius; int64_t* nKeptThrough; };
+int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept,
+                   const ChainCarry* chain = nullptr) {
     const std::string w(who);
     if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, w + ": max_history must be >= 1");
     if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, w + ": depth_tol must be > 0");
@@ -413,9 +430,19 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     // Rn, in the scene as it is now (builds it when an upload is pending); Rh from the mark, or of the image's camera (the same records when it is unchanged)
     if ((rc = ensureFeaturesFor(on, cur, &on->dFeat, &on->featValid))) return rc;
     j.rn = on->dFeat;
+    const bool sameCam = std::memcmp(&h.in, &cur, sizeof(FrameIn)) == 0;
+    if (chain) {                                                  // an unchanged camera uses one pair for both
+        if ((rc = ensureThrough(on, *chain->thru, who))) return rc;
+        j.sn = j.sh = on->dThru; j.yn = j.yh = on->dThruRays;
+        if (!sameCam) {
+            if ((rc = ensureThroughH(on, h.in, *chain->thru, who))) return rc;
+            j.sh = on->dThruH; j.yh = on->dThruRaysH;
+        }
+        j.pointTol = chain->pointTol; j.radius = chain->radius;
+    }
     if (moved) {
         j.rh = on->dMarkFeat;
-    } else if (std::memcmp(&h.in, &cur, sizeof(FrameIn)) == 0) {
+    } else if (sameCam) {
         j.rh = on->dFeat;
     } else {
         if (on->featHValid && std::memcmp(&on->featHIn, &h.in, sizeof(FrameIn)) != 0) on->featHValid = false;
@@ -426,7 +453,9 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     HIP_TRY(hipSetDevice(on->device));
     const size_t n = (size_t)c->W * c->H;
     if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
-    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
+    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 8));
+    if (chain && !on->dRpPack) HIP_TRY(hipMalloc((void**)&on->dRpPack, n * 32));
+    j.pack = on->dRpPack;
     // the image's T in pixel order, when allocated (group: through the host)
     if ((rc = wholeStats(c, on, &j.stats))) return rc;
     if (j.stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
@@ -455,6 +484,12 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     j.outFrame = on->dRpFrame; j.outStats = j.stats ? on->dRpStats : nullptr; j.kept = on->dRpKept;
     HIP_TRY(reprojectLaunch(j, on->stream));
     if (moved) HIP_TRY(hipStreamSynchronize(on->stream));         // (pt / pe leave scope: their copies have landed)
+    if (chain) {
+        unsigned keptThrough = 0;
+        HIP_TRY(hipMemcpyAsync(&keptThrough, on->dRpKept + 1, 4, hipMemcpyDeviceToHost, on->stream));
+        HIP_TRY(hipStreamSynchronize(on->stream));
+        *chain->nKeptThrough = keptThrough;
+    }
     if ((rc = storeReprojected(c, on, j.stats != nullptr, nKept))) return rc;
     if (moved) m.valid = false;                                   // spent
     return 0;
@@ -477,6 +512,24 @@ int pt_reproject_frame_demod(pt_ctx* c, float max_history, float depth_tol, floa
     int64_t n = 0;
     const int rc = reprojectImage(c, "pt_reproject_frame", false, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
     if (n_kept) *n_kept = n;
+    return rc;
+}
+
+// ---- include/pt_reproject_through.h
+int pt_reproject_frame_through(pt_ctx* c, const pt_through_rule* thru, const pt_reproject_through_rule* rule, int64_t* n_kept, int64_t* n_kept_through) {
+    if (n_kept) *n_kept = 0;
+    if (n_kept_through) *n_kept_through = 0;
+    if (!c || !rule) return fail(PT_ERR_ARG, "pt_reproject_frame_through: null argument");
+    if (rule->radius < 0 || rule->radius > 4) return fail(PT_ERR_ARG, "pt_reproject_frame_through: rule.radius must be in [0,4]");
+    if (!(rule->point_tol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_through: rule.point_tol must be > 0");
+    if (int rc = checkThrough(thru, "pt_reproject_frame_through")) return rc;
+    if (thru->max_depth > 0 && thru->lobes != 0 && !(thru->flags & PT_THROUGH_KEY))
+        return fail(PT_ERR_ARG, "pt_reproject_frame_through: a rule that follows chains needs PT_THROUGH_KEY (the surface word is what a source is matched on)");
+    int64_t n = 0, nt = 0;
+    const ChainCarry chain{thru, rule->point_tol, rule->radius, &nt};
+    const int rc = reprojectImage(c, "pt_reproject_frame_through", false, rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags, 0.0f, &n, &chain);
+    if (n_kept) *n_kept = n;
+    if (n_kept_through) *n_kept_through = rc ? 0 : nt;
     return rc;
 }
 
@@ -604,7 +657,7 @@ int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t*
     const size_t n = (size_t)c->W * c->H;
     if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
     if (!on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
-    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 4));
+    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 8));
     if (kappaOut && !on->dKappa) HIP_TRY(hipMalloc((void**)&on->dKappa, n * 4));
     j.feat = on->dFeat; j.heldFrame = on->dHoldFrame; j.heldStats = on->dHoldStats;
     j.W = c->W; j.H = c->H; j.radius = r.radius; j.zLo = r.z_lo; j.zHi = r.z_hi; j.normalTol = r.normal_tol;

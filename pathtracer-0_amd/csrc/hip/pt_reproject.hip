@@ -1,4 +1,5 @@
-// pt_reproject.hip — the reprojection of include/pt_reproject.h and the history validation of include/pt_validate.h for gfx950.
+// pt_reproject.hip — the reprojection of include/pt_reproject.h and include/pt_reproject_through.h and the history validation of include/pt_validate.h
+// for gfx950.
 //
 // Device pointers only: pt_hip.hip owns the buffers, computes both sets of feature records and calls reprojectLaunch on its stream.
 //   k_reproject<MOVED, DEMOD>  one lane per new pixel, a wave = 64 pixels of a row, a block = 16 rows.  Reads 48 B of Rn[p] (F0, F1.w, F2), the same
@@ -12,6 +13,8 @@
 //                once, as ten planes of floats (the six moments, zeroed where a pixel can be no tap for any centre; the normal; one class /
 //                material word), so that a tap costs ten LDS reads of consecutive words per wave and no global load; then steps 1-4 and the
 //                reduced count, counted as k_reproject counts the kept pixels.
+//   k_through_pack, k_reproject_chain  include/pt_reproject_through.h: behind k_reproject<false, false>, the pixels with a seen-through chain take the
+//                history of the old pixel whose chain ended on the same surface point, found in a window around the projected virtual point.
 // Under the bit-exact contract: binary32 * + / sqrt in the header's order, no contraction (the build's -ffp-contract=off, IEEE divides).
 #include <hip/hip_runtime.h>
 
@@ -283,11 +286,117 @@ __global__ void __launch_bounds__(RP_BX * RP_BY) k_history_merge(const float4* _
     if (tid == 0 && blockReduced) atomicAdd(reduced, blockReduced);
 }
 
+// include/pt_reproject_through.h, per pixel s of the image's camera: what a candidate test of step 5 reads, 32 B in place of the 80 B of Sh[s], Yh[s] and
+// FRAME[s].  pack[2s] = (X', surface word), pack[2s + 1] = (N', usable as an int: Sh[s] is a hit, X' is finite, FRAME[s].a > 0 with a finite rgb)
+constexpr int TP_B = 256;
+__global__ void __launch_bounds__(TP_B) k_through_pack(const float4* __restrict__ sh, const float4* __restrict__ yh, const float4* __restrict__ frame, int n,
+                                                      float4* __restrict__ pack) {
+    const int s = blockIdx.x * TP_B + threadIdx.x;
+    if (s >= n) return;
+    const float4 s0 = sh[4 * (size_t)s];
+    const float* w = reinterpret_cast<const float*>(sh + 4 * (size_t)s);
+    const float4 y0 = yh[2 * (size_t)s], y1 = yh[2 * (size_t)s + 1], F = frame[s];
+    const float X0 = y0.x + y0.w * y1.x, X1 = y0.y + y0.w * y1.y, X2 = y0.z + y0.w * y1.z;
+    const bool usable = __float_as_int(w[7]) != -1 && finite3(X0, X1, X2) && F.w > 0.0f && finite3(F.x, F.y, F.z);
+    pack[2 * (size_t)s] = make_float4(X0, X1, X2, w[11]);
+    pack[2 * (size_t)s + 1] = make_float4(s0.y, s0.z, s0.w, __int_as_float(usable ? 1 : 0));
+}
+
+// Steps 3-6 of include/pt_reproject_through.h, behind k_reproject<false, false> on the same stream: that launch has given every pixel steps 1-2 (a
+// chain pixel among them the verdict of its first hit, which this kernel replaces), so that the steps the two headers share have one definition
+// and k_reproject stays the code object it was.  One lane per new pixel in k_reproject's blocks; a lane whose k_p is 0 (4 B read) or that lies
+// under the overlay is done.  The window's centre depends on the data, so a block's candidates are no tile: the (2 radius + 1)^2 loop reads the packed
+// pixels of k_through_pack straight from L2, 16 B for a candidate of another surface word, 32 B otherwise; neighbouring lanes have neighbouring
+// centres.  The loops are not unrolled (radius is an argument; 81 unrolled candidates would not fit in registers).  kept[0] takes kept-now minus
+// kept-by-the-first-hit (modulo 2^32), kept[1] the chain pixels kept: k_reproject's scheme, a ballot popcount per wave, an LDS sum, one atomic
+// per block and counter.
+__global__ void __launch_bounds__(RP_BX * RP_BY) k_reproject_chain(const float4* __restrict__ sn, const float4* __restrict__ yn, const float4* __restrict__ pack,
+                                                                  const float4* __restrict__ frame, const float4* __restrict__ stats, const FrameConst* __restrict__ hc,
+                                                                  const unsigned char* __restrict__ matVD, int nMat, int W, int H, ReprojCam cam, ReprojRule r,
+                                                                  float pointTol, int radius, float4* __restrict__ outFrame, float4* __restrict__ outStats,
+                                                                  unsigned* __restrict__ kept) {
+    __shared__ unsigned blockKept, blockWas;
+    if (threadIdx.x == 0 && threadIdx.y == 0) { blockKept = 0; blockWas = 0; }
+    __syncthreads();
+    const int x = blockIdx.x * RP_BX + threadIdx.x, y = blockIdx.y * RP_BY + threadIdx.y;
+    const bool in = x < W && y < H;
+    const size_t p = (size_t)y * W + x;
+    bool keep = false, was = false;
+    FrameConst fc;
+    fc.mouse[0] = cam.mouseX; fc.mouse[1] = cam.mouseY; fc.resolution = cam.resolution;
+    if (in && !inMouseOverlay(fc, x, y) && __float_as_int(reinterpret_cast<const float*>(sn + 4 * p)[14]) >= 1) {      // 1, 2
+        was = outFrame[p].w > 0.0f;                                                        // a kept pixel has a count > 0
+        const float4 s0 = sn[4 * p], s2 = sn[4 * p + 2], y0 = yn[2 * p], y1 = yn[2 * p + 1];
+        const int code = __float_as_int(reinterpret_cast<const float*>(sn + 4 * p)[7]), word = __float_as_int(s2.w), mat = word & 0xfff;
+        const float L = s0.x;
+        bool ok = code != -1 && __builtin_isfinite(L) && L > 0.0f && finite3(s0.y, s0.z, s0.w) && finite3(s2.x, s2.y, s2.z) && finite3(y0.x, y0.y, y0.z) &&
+                  __builtin_isfinite(y0.w) && finite3(y1.x, y1.y, y1.z) && mat < nMat && (r.allMaterials || !matVD[mat]);      // 3
+        const float X0 = y0.x + y0.w * y1.x, X1 = y0.y + y0.w * y1.y, X2 = y0.z + y0.w * y1.z;
+        const float* M = hc->camRot;                                                       // 4: the virtual point in the image's camera
+        const float vx = (cam.On[0] + L * s2.x) - hc->origin[0], vy = (cam.On[1] + L * s2.y) - hc->origin[1], vz = (cam.On[2] + L * s2.z) - hc->origin[2];
+        const float q0 = (vx * M[0] + vy * M[1]) + vz * M[2];
+        const float q1 = (vx * M[3] + vy * M[4]) + vz * M[5];
+        const float q2 = (vx * M[6] + vy * M[7]) + vz * M[8];
+        const float ss = hc->screenSize, fl = hc->focalLength, hr = hc->screenHratio;
+        const float a = (q0 / q2) * fl, b = (q1 / q2) * fl;
+        const float sx = ((1.0f - a / ss) * 0.5f) * (float)W, sy = ((1.0f + b / (hr * ss)) * 0.5f) * (float)H;
+        ok = ok && q2 > 0.0f && sx >= 0.0f && sx < (float)W && sy >= 0.0f && sy < (float)H;
+        if (ok) {                                                                          // 5
+            const int cx = (int)sx, cy = (int)sy;
+            const int xLo = max(cx - radius, 0), xHi = min(cx + radius, W - 1), yLo = max(cy - radius, 0), yHi = min(cy + radius, H - 1);
+            const float tol = pointTol * L, tol2 = tol * tol;
+            float best = 0.0f;
+            long long src = -1;
+#pragma unroll 1
+            for (int yy = yLo; yy <= yHi; yy++) {
+#pragma unroll 1
+                for (int xx = xLo; xx <= xHi; xx++) {
+                    const size_t s = (size_t)yy * W + xx;
+                    const float4 c0 = pack[2 * s];
+                    if (__float_as_int(c0.w) != word) continue;
+                    const float4 c1 = pack[2 * s + 1];
+                    const float e0 = c0.x - X0, e1 = c0.y - X1, e2 = c0.z - X2;
+                    const float d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+                    if (__float_as_int(c1.w) != 0 && d2 <= tol2 && dot3(s0.y, s0.z, s0.w, c1.x, c1.y, c1.z) >= r.normalTol && (src < 0 || d2 < best)) {
+                        best = d2; src = (long long)s;
+                    }
+                }
+            }
+            ok = src >= 0;
+            if (ok) {                                                                      // 6: step 7 of include/pt_reproject.h
+                const float4 F = frame[src];
+                float4 o = F, t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (F.w > r.maxHistory) { const float f = r.maxHistory / F.w; o = make_float4(F.x * f, F.y * f, F.z * f, r.maxHistory); }
+                outFrame[p] = o;
+                if (outStats) {
+                    const float4 T = stats[src];
+                    t = T;
+                    if (T.z > r.maxHistory) { const float gg = r.maxHistory / T.z; t = make_float4(T.x * gg, T.y * gg, r.maxHistory, T.w); }
+                    outStats[p] = t;
+                }
+            }
+        }
+        if (!ok && was) {                                                                  // kept by its first hit (PT_REPROJECT_ALL_MATERIALS), rejected by its chain
+            outFrame[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (outStats) outStats[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        keep = ok;
+    }
+    const unsigned long long m = __ballot(keep), mw = __ballot(was);                       // every lane of the block, in range or not
+    if (threadIdx.x == 0 && m) atomicAdd(&blockKept, (unsigned)__popcll(m));
+    if (threadIdx.x == 0 && mw) atomicAdd(&blockWas, (unsigned)__popcll(mw));
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        if (blockKept != blockWas) atomicAdd(kept, blockKept - blockWas);
+        if (blockKept) atomicAdd(kept + 1, blockKept);
+    }
+}
+
 }  // namespace
 
 // floorA > 0 alone selects the demodulated step 7, `motion` alone the followed-back step 2
 hipError_t reprojectLaunch(const ReprojectJob& j, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(j.kept, 0, 4, s);
+    hipError_t e = hipMemsetAsync(j.kept, 0, j.sn ? 8 : 4, s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((j.W + RP_BX - 1) / RP_BX), (unsigned)((j.H + RP_BY - 1) / RP_BY)), block(RP_BX, RP_BY);
     const bool demod = j.floorA > 0.0f;
@@ -299,6 +408,13 @@ hipError_t reprojectLaunch(const ReprojectJob& j, hipStream_t s) {
     else hipLaunchKernelGGL((k_reproject<false, false>), grid, block, 0, s, RP_IN, RP_OUT);
 #undef RP_IN
 #undef RP_OUT
+    if (j.sn) {                                                                            // include/pt_reproject_through.h: the chain pixels, on top
+        if (j.motion || demod || j.radius < 0 || j.radius > 4) return hipErrorInvalidValue;
+        const int n = j.W * j.H;
+        hipLaunchKernelGGL(k_through_pack, dim3((unsigned)((n + TP_B - 1) / TP_B)), dim3(TP_B), 0, s, j.sh, j.yh, j.frame, n, j.pack);
+        hipLaunchKernelGGL(k_reproject_chain, grid, block, 0, s, j.sn, j.yn, (const float4*)j.pack, j.frame, j.stats, j.hist, j.matVD, j.nMat, j.W, j.H, j.cam,
+                           j.rule, j.pointTol, j.radius, j.outFrame, j.outStats, j.kept);
+    }
     return hipGetLastError();
 }
 

@@ -166,6 +166,8 @@ def lib():
         if hasattr(L, "pt_history_hold"):                     # include/pt_validate.h
             L.pt_history_hold.argtypes = [vp]
             L.pt_history_merge.argtypes = [vp, C.POINTER(ValidateRule), vp, C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_reproject_frame_through"):          # include/pt_reproject_through.h
+            L.pt_reproject_frame_through.argtypes = [vp, C.POINTER(ThroughRule), C.POINTER(ReprojectThroughRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -184,6 +186,12 @@ class ThroughRule(C.Structure):
 class ValidateRule(C.Structure):
     """pt_validate_rule of include/pt_validate.h"""
     _fields_ = [("radius", C.c_int), ("z_lo", C.c_float), ("z_hi", C.c_float), ("normal_tol", C.c_float)]
+
+
+class ReprojectThroughRule(C.Structure):
+    """pt_reproject_through_rule of include/pt_reproject_through.h"""
+    _fields_ = [("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_tol", C.c_float), ("point_tol", C.c_float), ("radius", C.c_int),
+                ("flags", C.c_int)]
 
 
 class PtError(RuntimeError):
@@ -392,6 +400,32 @@ class Renderer:
         else:
             _check(self._L.pt_reproject_frame_demod(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, float(albedo_floor), C.byref(n)))
         return n.value
+
+    # --- reprojection of mirror and glass pixels through their chains (include/pt_reproject_through.h) ---
+    # defaults of reproject_through_rule: the float32 model on the oracle's frames of C3 at 160 x 90 (tests/test_reproject_through_abi.py, DESIGN.md
+    # 2.17): 32 frames, move(forward 0.05, strafe 0.03, yaw 0.02), 4 frames, clamped RMSE over the 1941 chain pixels against 128 frames.  Of the
+    # grid point_tol (0.01, 0.02, 0.05) x radius (0, 1, 2, 4), (0.05, 2) is best: 0.0798 against 0.1580 for pt_reproject_frame, which restarts
+    # there; (0.02, 2) gives 0.1039, (0.05, 0) 0.1142, (0.05, 4) 0.0823.
+    REPROJECT_THROUGH_POINT_TOL = 0.05
+    REPROJECT_THROUGH_RADIUS = 2
+    REPROJECT_THROUGH_CHAINS = (4, 0.5, 3, True)                  # the through_rule it follows: depth 4, both lobes at 0.5, with the key (required)
+
+    def reproject_through_rule(self, max_history=64.0, depth_tol=0.02, normal_tol=0.9, point_tol=None, radius=None, all_materials=False):
+        """the pt_reproject_through_rule of these arguments; None takes the defaults above, the first three are reproject_frame's"""
+        return ReprojectThroughRule(float(max_history), float(depth_tol), float(normal_tol),
+                                    float(self.REPROJECT_THROUGH_POINT_TOL if point_tol is None else point_tol),
+                                    int(self.REPROJECT_THROUGH_RADIUS if radius is None else radius), self.REPROJECT_ALL_MATERIALS if all_materials else 0)
+
+    def reproject_frame_through(self, thru=None, rule=None):
+        """reproject_frame that also carries the pixels of mirrors and glass (pt_reproject_frame_through): a pixel with a seen-through chain under
+        `thru` (a through_rule() with the key) takes the history of the old pixel whose chain ended on the same surface point, searched in a
+        window around the projected virtual point.  Returns (kept, kept_through): the pixels that kept their history, and those among them
+        with a chain.  None takes REPROJECT_THROUGH_CHAINS and reproject_through_rule()."""
+        thru = self.through_rule(*self.REPROJECT_THROUGH_CHAINS) if thru is None else thru
+        rule = self.reproject_through_rule() if rule is None else rule
+        n, nt = C.c_int64(0), C.c_int64(0)
+        _check(self._L.pt_reproject_frame_through(self._h, C.byref(thru), C.byref(rule), C.byref(n), C.byref(nt)))
+        return n.value, nt.value
 
     # --- reprojection across moved geometry (include/pt_motion.h) ----------------------------------
     def motion_mark(self):
