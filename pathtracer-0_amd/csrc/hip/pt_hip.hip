@@ -37,6 +37,7 @@
 #include "../../../include/pt_validate.h"
 #include "../../../include/pt_reproject_through.h"
 #include "pt_device.hpp"
+#include "pt_devmem.hpp"
 #include "pt_image_launch.hpp"
 
 #include <algorithm>
@@ -1233,50 +1234,51 @@ struct pt_ctx {
     std::vector<uint8_t> sky; int skyW = 0, skyH = 0;
     struct HostTex { std::vector<uint8_t> rgba; int w = 0, h = 0; };
     std::vector<HostTex> textures;          // bindless table beyond the sky (index 0 mirrors `sky`)
-    uchar4* dTexels = nullptr; TexRec* dTexTable = nullptr;      // all textures beyond the sky in one allocation + the bindless-style table
+    Dev<uchar4> dTexels; Dev<TexRec> dTexTable;      // all textures beyond the sky in one allocation + the bindless-style table
     bool sceneDirty = true, frameInDirty = true;
-    bool trans = false, anySubsurface = false, ambiguousTriObj = false, anyMaps = false, ellipMaps = false; int* dTriObj = nullptr;
+    bool trans = false, anySubsurface = false, ambiguousTriObj = false, anyMaps = false, ellipMaps = false; Dev<int> dTriObj;
     int stackDepth = 1;
     // device scene
-    float4 *dNodes = nullptr, *dTris = nullptr, *dShade = nullptr; ObjRoot* dRoots = nullptr; EllipRec* dEllip = nullptr; MatRec* dMats = nullptr;
-    uchar4* dSky = nullptr; float* dNiTable = nullptr;
+    Dev<float4> dNodes, dTris, dShade; Dev<ObjRoot> dRoots; Dev<EllipRec> dEllip; Dev<MatRec> dMats;
+    Dev<uchar4> dSky; Dev<float> dNiTable;
     int niBits = 0;                 // index-stack encoding of the path state: 0 no transmissive material (the stack is unobservable), 3 or 8 bits per slot, 32: the floats themselves
-    unsigned char* dDisplay = nullptr;      // scratch of pt_read_display (W*H*3 bytes, allocated on first use)
+    Dev<unsigned char> dDisplay;      // scratch of pt_read_display (W*H*3 bytes, allocated on first use)
     DevScene sc{};
     // shard
-    std::vector<int32_t> pixList; int nLocal = 0, nSlotsImg = 0; int* dPixList = nullptr; unsigned* dPixXY = nullptr; int* dAllMaps = nullptr;
+    std::vector<int32_t> pixList; int nLocal = 0, nSlotsImg = 0; Dev<int> dPixList; Dev<unsigned> dPixXY; Dev<int> dAllMaps;
     static constexpr int IMAGES = 4;
-    float4* dImage[IMAGES] = {nullptr, nullptr, nullptr, nullptr}; int curImage = 0;      // FRAME images (more than one only after pt_next_image)
+    Dev<float4> dImage[IMAGES]; int curImage = 0;      // FRAME images (more than one only after pt_next_image)
     // path pool
     int poolSlots = 0;              // 0 = automatic: jobs/5 clamped to [2^20, 2^22] (enough rays per lane for the in-wave refill, short tail)
     int poolActive = 0; int allocSlots = 0; int allocNiBits = -1; bool allocHX = false;
-    State st{};
-    unsigned* dQueue[2] = {nullptr, nullptr};      // dense slot queues of the batch tail, by iteration parity
-    float4* dColbuf = nullptr; int* dSeeds = nullptr; int ringFrames = 0;      // per-frame rings of the stream (Batch)
+    State st{};                     // the pool as the kernels take it; its groups are owned by dPool (in the order of ensurePool) and dPoolJ
+    Dev<float4> dPool[9]; Dev<uint2> dPoolJ;
+    Dev<unsigned> dQueue[2];        // dense slot queues of the batch tail, by iteration parity
+    Dev<float4> dColbuf; Dev<int> dSeeds; int ringFrames = 0;      // per-frame rings of the stream (Batch)
     // frame-stream scheduler (host view)
     struct Entry { unsigned jobEnd, f0; int nFrames, firstFrame, image; };      // a submitted, not yet accumulated batch
     std::deque<Entry> pending;
     FrameIn streamIn{};             // frame inputs the running stream was started with
     unsigned streamFrames = 0, streamJobs = 0, lastNextJob = 0, lastDelta = 0, launched = 0; int lastCheck = 24, iter = 0; bool draining = false;
     uint64_t lastSubmitJobs = 0, jobsThisImage = 0, jobsPerImage = 0;      // what the last submission added; jobs submitted for the current / the previous FRAME image
-    FrameIn* dFrameIn = nullptr; FrameConst* dFc = nullptr; Control* dCtl = nullptr;
+    Dev<FrameIn> dFrameIn; Dev<FrameConst> dFc; Dev<Control> dCtl;
     // The host looks at the device's scheduler words once per GROUP of iterations: a group = its launches + (a scan of the oldest batches) + k_snapshot, which writes
     // Control into the group's pinned snapshot and then the group's number into the group's pinned STAMP.  Up to two groups are in flight: the host looks at a snapshot when
     // its stamp has arrived, so the stream always holds the next group's launches while one runs, and an asynchronous submission never waits for the iterations it started
     // (pump).
-    struct Group { Control* h = nullptr; volatile unsigned* stamp = nullptr; unsigned seq = 0; int check = 0, iterEnd = 0, nScan = 0; unsigned scanF0 = 0, epoch = 0; int64_t predicted = 0; };
+    struct Group { Pinned<Control, hipHostMallocCoherent> h; Pinned<volatile unsigned, hipHostMallocCoherent> stamp; unsigned seq = 0; int check = 0, iterEnd = 0, nScan = 0; unsigned scanF0 = 0, epoch = 0; int64_t predicted = 0; };
     Group grp[2]; int grpHead = 0, grpCount = 0; bool scanInFlight = false; unsigned submitEpoch = 0, groupSeq = 0;
     int64_t inflightPredicted = 0;  // jobs the groups in flight are expected to hand out (iterations x the rate of the last look): lastNextJob is as old as the oldest of them
-    FrameIn* hFrameIn = nullptr; int32_t* hSeeds = nullptr;   // pinned staging (hSeeds: ring like dSeeds)
+    Pinned<FrameIn> hFrameIn; Pinned<int32_t> hSeeds;   // pinned staging (hSeeds: ring like dSeeds)
     // options / stats
     bool countStats = false, timing = false;
     int ldsBudget = 20 * 1024;
     int extendMode = 2;             // 0: one block per 256 lanes (k_extend), 1: persistent blocks (k_extend_persist), 2: the hand-written form of 1
                                     //    (pt_extend_gfx950.s) for the scenes it takes, 1 for the others
-    float* dNodes80 = nullptr;      // node records of the hand-written kernel: the two references + (min pair, max pair, min pair) per axis (80 B), or + pad + (min pair, max pair) (64 B)
+    Dev<float> dNodes80;            // node records of the hand-written kernel: the two references + (min pair, max pair, min pair) per axis (80 B), or + pad + (min pair, max pair) (64 B)
     int asmNodeStride = 80, asmNodeLayout = -1;      // bytes per record as built; pt_set_option 19: -1 automatic, 0 80-B, 1 64-B
     int asmGroupShift = 0; bool asmNoRootCull = false;      // more than 8 BVHs: log2 of the objects per group box of the per-ray cull; pt_set_option 20 switches the cull off (every group box infinite)
-    void* dAsmDbg = nullptr;
+    Dev<unsigned char> dAsmDbg;     // developer builds of the hand-written kernel (-DPT_ASM_DEBUG): its per-wave records
     std::string asmError;           // a failed load / launch of the hand-written kernel (surfaces as PT_ERR_HIP from the render call)
     uint64_t asmLaunches = 0;
     bool asmEligible = false;       // this scene can run on the hand-written kernel (buildScene)
@@ -1299,59 +1301,41 @@ struct pt_ctx {
     uint64_t hostCnt[PT_CNT_N] = {0};
     // adaptive sampling (include/pt_adaptive.h): per accumulator slot (sY, sYY, n, 0), allocated by the first pt_render_adaptive; the selection's scratch;
     // while adaptOn the running frame stream's pixel list is the active list (streamBatch), its nLocal adaptN
-    float4* dStats = nullptr; unsigned char* dAdaptFlag = nullptr; unsigned* dAdaptBlk = nullptr; unsigned* dAdaptXY = nullptr; int* dAdaptSlot = nullptr;
-    unsigned* hAdaptCount = nullptr; bool adaptOn = false; int adaptN = 0;
+    Dev<float4> dStats; Dev<unsigned char> dAdaptFlag; Dev<unsigned> dAdaptBlk, dAdaptXY; Dev<int> dAdaptSlot;
+    Pinned<unsigned> hAdaptCount; bool adaptOn = false; int adaptN = 0;
     // include/pt_steer.h: the whole image's selection mask (W*H bytes, pixel order), then, 4-byte aligned, k_gd_select's active count
-    unsigned char* dSelMask = nullptr;
+    Dev<unsigned char> dSelMask;
     bool recordMoments = false;     // include/pt_guided.h: the frames of pt_render* also go into T (k_accumulate_moments) when they land in the current image
-    // first-hit feature records (include/pt_denoise.h): W*H x 4 float4, valid until the next pt_set_buffer / pt_set_texture; the denoiser's ping-pong
-    // colour buffers, its packed guide (2 float4 per pixel) and its output, all allocated on first use
-    float4* dFeat = nullptr; bool featValid = false;
-    float4* dDnCol[2] = {nullptr, nullptr}; float4* dDnGuide = nullptr; float4* dDnOut = nullptr;
+    // The feature records (W*H x 4 float4) of one set of frame inputs, kept until they are asked for under other inputs or an upload invalidates them
+    // (invalidateRecords): first-hit records (include/pt_denoise.h), or seen-through records under `rule` with their last segments (`rays`, W*H x
+    // 2 float4; include/pt_through.h).  Of each kind one cache under the current inputs and one under the current image's camera (Rh; Sh, Yh)
+    struct Records { Dev<float4> recs, rays; bool valid = false; FrameIn in{}; pt_through_rule rule{}; };
+    Records feat, featH, thru, thruH;
+    Dev<float4> dDnCol[2], dDnGuide, dDnOut;      // the filters' colour ping-pong, packed guide (2 float4 per pixel) and output
     // reprojection (include/pt_reproject.h): the camera of each ring image (the frame inputs it was rendered or written with, and the scene
-    // generation then: sceneGen counts uploads of scene buffers and textures); the feature records under the current image's camera (Rh, cached
-    // like dFeat, for the inputs featHIn); one flag byte per material (1 = view-dependent, buildScene); the scratch images, the kept count
+    // generation then: sceneGen counts uploads of scene buffers and textures); one flag byte per material (1 = view-dependent, buildScene); the
+    // scratch images, the kept counts (two), the packed candidates of k_through_pack (W*H x 2 float4)
     struct Cam { FrameIn in; uint64_t sceneGen = 0; bool valid = false; } cam[IMAGES];
     uint64_t sceneGen = 0;
-    float4* dFeatH = nullptr; bool featHValid = false; FrameIn featHIn{};
-    unsigned char* dMatVD = nullptr;
-    float4* dRpFrame = nullptr; float4* dRpStats = nullptr; unsigned* dRpKept = nullptr;
-    float4* dStatsWhole = nullptr;  // a group's T gathered in pixel order on its first stream (reprojection, the guided filter)
-    float4* dFill = nullptr; unsigned* dFillCount = nullptr;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count, allocated on first use
-    // include/pt_through.h: the seen-through records (W*H x 4 float4) and their last segments (W*H x 2 float4) under thruRule, cached like dFeat
-    float4* dThru = nullptr; float4* dThruRays = nullptr; bool thruValid = false; pt_through_rule thruRule{};
-    // include/pt_reproject_through.h: the same pair under the current image's camera (cached like dFeatH, for the inputs thruHIn and the rule thruHRule)
-    // and the packed candidates of k_through_pack (W*H x 2 float4); dRpKept holds two counts
-    float4* dThruH = nullptr; float4* dThruRaysH = nullptr; bool thruHValid = false; pt_through_rule thruHRule{}; FrameIn thruHIn{};
-    float4* dRpPack = nullptr;
+    Dev<unsigned char> dMatVD;
+    Dev<float4> dRpFrame, dRpStats, dRpPack; Dev<unsigned> dRpKept;
+    Dev<float4> dStatsWhole;        // a group's T gathered in pixel order on its first stream (reprojection, the guided filter)
+    Dev<float4> dFill; Dev<unsigned> dFillCount;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count
     // include/pt_motion.h.  otherGen counts the uploads that are not geometry (bindings 5, 14 and textures) beside sceneGen, which counts all;
     // camWrites counts every write of a camera record, so that a mark can tell that its image's record is still the one it saw.  The mark: Rh
-    // (dMarkFeat), the primitives' positions then on the device (3 float4 each) and on the host (9 floats per triangle, 10 per ellipsoid); the
+    // (feat), the primitives' positions then on the device (3 float4 each) and on the host (9 floats per triangle, 10 per ellipsoid); the
     // positions now are packed per call into dMoveTri / dMoveEl
     uint64_t otherGen = 0, camWrites = 0;
-    struct Mark { bool valid = false; int image = 0; uint64_t camWrites = 0, otherGen = 0; int nTri = 0, nEl = 0; std::vector<float> tri, el; } mark;
-    float4* dMarkFeat = nullptr; float4* dMarkTri = nullptr; float4* dMarkEl = nullptr; float4* dMoveTri = nullptr; float4* dMoveEl = nullptr;
-    // include/pt_validate.h.  The hold (on a group's first stream): the held FRAME and T in pixel order (H and V, W*H float4 each), the image they were
+    struct Mark { bool valid = false; int image = 0; uint64_t camWrites = 0, otherGen = 0; int nTri = 0, nEl = 0; std::vector<float> tri, el; Dev<float4> feat, dTri, dEl; } mark;
+    Dev<float4> dMoveTri, dMoveEl;
+    // include/pt_validate.h.  The hold (on a group's first stream): the held FRAME and T in pixel order (W*H float4 each), the image they were
     // taken from, the frame inputs of its camera record and sceneGen then; pt_history_merge's kappa (W*H floats, only when asked for)
-    struct Hold { bool valid = false; int image = 0; FrameIn in{}; uint64_t sceneGen = 0; } hold;
-    float4* dHoldFrame = nullptr; float4* dHoldStats = nullptr; float* dKappa = nullptr;
+    struct Hold { bool valid = false; int image = 0; FrameIn in{}; uint64_t sceneGen = 0; Dev<float4> frame, stats; } hold;
+    Dev<float> dKappa;
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
 
 namespace {
-
-struct Scratch {            // device allocations of one call: released whichever way the call returns
-    std::vector<void**> ptrs;
-    ~Scratch() { for (void** p : ptrs) if (*p) { hipFree(*p); *p = nullptr; } }
-};
-
-int uploadVec(void** dptr, const void* src, size_t bytes, hipStream_t s) {
-    if (*dptr) { HIP_TRY(hipFree(*dptr)); *dptr = nullptr; }
-    if (bytes == 0) bytes = 16;
-    HIP_TRY(hipMalloc(dptr, bytes));
-    if (src) HIP_TRY(hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, s));
-    return 0;
-}
 
 // tile-major enumeration of the pixels owned by `rank`
 void shardPixels(int W, int H, int rank, int count, std::vector<int32_t>& out) {
@@ -1611,26 +1595,25 @@ int buildScene(pt_ctx* c) {
     // upload
     hipStream_t s = c->stream;
     HIP_TRY(hipStreamSynchronize(s));
-    int rc;
-    if ((rc = uploadVec((void**)&c->dNodes, nodeRecs.data(), nodeRecs.size() * 16, s))) return rc;
-    if ((rc = uploadVec((void**)&c->dNodes80, nodes80.data(), nodes80.size() * 4, s))) return rc;
-    if ((rc = uploadVec((void**)&c->dTris, triRecs.data(), triRecs.size() * 16, s))) return rc;
-    if ((rc = uploadVec((void**)&c->dShade, shade.data(), shade.size() * 16, s))) return rc;
-    if ((rc = uploadVec((void**)&c->dTriObj, triObj.data(), triObj.size() * 4, s))) return rc;
-    if ((rc = uploadVec((void**)&c->dRoots, roots.data(), roots.size() * sizeof(ObjRoot), s))) return rc;
-    if ((rc = uploadVec((void**)&c->dEllip, er.data(), er.size() * sizeof(EllipRec), s))) return rc;
-    if ((rc = uploadVec((void**)&c->dMats, mats.data(), mats.size() * sizeof(MatRec), s))) return rc;
+    HIP_TRY(c->dNodes.upload(nodeRecs.data(), nodeRecs.size() * 16, s));
+    HIP_TRY(c->dNodes80.upload(nodes80.data(), nodes80.size() * 4, s));
+    HIP_TRY(c->dTris.upload(triRecs.data(), triRecs.size() * 16, s));
+    HIP_TRY(c->dShade.upload(shade.data(), shade.size() * 16, s));
+    HIP_TRY(c->dTriObj.upload(triObj.data(), triObj.size() * 4, s));
+    HIP_TRY(c->dRoots.upload(roots.data(), roots.size() * sizeof(ObjRoot), s));
+    HIP_TRY(c->dEllip.upload(er.data(), er.size() * sizeof(EllipRec), s));
+    HIP_TRY(c->dMats.upload(mats.data(), mats.size() * sizeof(MatRec), s));
     {   // the view-dependent materials of include/pt_reproject.h: a mirror, clearcoat or transmission lobe in chooseRay (frag.glsl:745-809)
         std::vector<unsigned char> vd(mats.size(), 0);
         for (int m = 0; m < nMat; m++) {
             const MatRec& r = mats[m];
             vd[m] = (r.Pr != 1.0f || r.Pc != 0.0f || r.Tr > 0.0f || r.Tf[0] > 0.0f || r.illum == 5 || r.illum == 7 || r.map_Pr >= 0 || r.map_Pc >= 0 || r.map_Tr >= 0) ? 1 : 0;
         }
-        if ((rc = uploadVec((void**)&c->dMatVD, vd.data(), vd.size(), s))) return rc;
+        HIP_TRY(c->dMatVD.upload(vd.data(), vd.size(), s));
     }
     // textures stay the RGBA8 texels the caller uploaded (dispatch.java:349-354: GL_RGBA8); byte / 255.0f happens at fetch (unorm8, pt_device.hpp)
-    if ((rc = uploadVec((void**)&c->dSky, c->sky.data(), (size_t)c->skyW * c->skyH * 4, s))) return rc;
-    if ((rc = uploadVec((void**)&c->dNiTable, niDict.data(), niDict.size() * 4, s))) return rc;
+    HIP_TRY(c->dSky.upload(c->sky.data(), (size_t)c->skyW * c->skyH * 4, s));
+    HIP_TRY(c->dNiTable.upload(niDict.data(), niDict.size() * 4, s));
     // the texture table beyond the sky: ONE allocation and one asynchronous copy for all textures
     std::vector<TexRec> table(std::max<size_t>(c->textures.size(), 1));
     table[0].data = c->dSky; table[0].w = c->skyW; table[0].h = c->skyH;
@@ -1642,9 +1625,9 @@ int buildScene(pt_ctx* c) {
         texOff[ti] = texels.size() / 4;
         texels.insert(texels.end(), T.rgba.begin(), T.rgba.begin() + (size_t)T.w * T.h * 4);
     }
-    if ((rc = uploadVec((void**)&c->dTexels, texels.data(), texels.size(), s))) return rc;
+    HIP_TRY(c->dTexels.upload(texels.data(), texels.size(), s));
     for (size_t ti = 1; ti < c->textures.size(); ti++) if (!c->textures[ti].rgba.empty()) table[ti].data = c->dTexels + texOff[ti];
-    if ((rc = uploadVec((void**)&c->dTexTable, table.data(), table.size() * sizeof(TexRec), s))) return rc;
+    HIP_TRY(c->dTexTable.upload(table.data(), table.size() * sizeof(TexRec), s));
     HIP_TRY(hipStreamSynchronize(s));
     DevScene& sc = c->sc;
     sc.nodes = c->dNodes; sc.nNodes = (int)order.size(); sc.tris = c->dTris; sc.nTriRecs = (int)(triRecs.size() / 3);
@@ -1689,17 +1672,19 @@ int ensurePool(pt_ctx* c, int capacity) {               // capacity >= poolActiv
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->allocSlots = 0;                                            // until every allocation below has succeeded there is no pool
     float4** groups[] = {&c->st.G0, &c->st.G1, &c->st.G2, &c->st.G3, &c->st.G4, &c->st.H, &c->st.G5, &c->st.S0, &c->st.HX};
-    for (auto g : groups) if (*g) { HIP_TRY(hipFree(*g)); *g = nullptr; }
-    if (c->st.J) { HIP_TRY(hipFree(c->st.J)); c->st.J = nullptr; }
-    for (unsigned** q : {&c->dQueue[0], &c->dQueue[1]}) if (*q) { HIP_TRY(hipFree(*q)); *q = nullptr; }
+    for (int k = 0; k < 9; k++) { *groups[k] = nullptr; HIP_TRY(c->dPool[k].release()); }
+    c->st.J = nullptr;
+    HIP_TRY(c->dPoolJ.release());
+    for (auto& q : c->dQueue) HIP_TRY(q.release());
     size_t n = (size_t)capacity;
     for (int k = 0; k < 9; k++) {
         if ((k == 6 && c->niBits == 0) || (k == 7 && c->niBits < 8) || (k == 8 && !c->ellipMaps)) continue;      // G5: transmissive scenes; S0: 8-bit index-stack codes, or three planes of floats; HX: mapped ellipsoids
-        HIP_TRY(hipMalloc((void**)groups[k], n * 16 * ((k == 7 && c->niBits == 32) ? 3 : 1)));
+        HIP_TRY(c->dPool[k].reset(n * 16 * ((k == 7 && c->niBits == 32) ? 3 : 1)));
+        *groups[k] = c->dPool[k];
     }
-    HIP_TRY(hipMalloc((void**)&c->st.J, n * 8));
-    HIP_TRY(hipMalloc((void**)&c->dQueue[0], n * 4));
-    HIP_TRY(hipMalloc((void**)&c->dQueue[1], n * 4));
+    HIP_TRY(c->dPoolJ.reset(n * 8));
+    c->st.J = c->dPoolJ;
+    for (auto& q : c->dQueue) HIP_TRY(q.reset(n * 4));
     c->allocSlots = capacity; c->allocNiBits = c->niBits; c->allocHX = c->ellipMaps; c->st.s0Plane = (unsigned)capacity;
     return 0;
 }
@@ -1836,9 +1821,9 @@ bool launchExtendAsm(pt_ctx* c, const PoolRun& pr) {
     a.nWaves = (unsigned)grid * (unsigned)(TPB / 64);
 #ifdef PT_ASM_DEBUG                  // developer builds only (scripts/build_variant.py -DPT_ASM_DEBUG): the per-wave debug records of the assembly
     {
-        if (!c->dAsmDbg) { if (hipMalloc(&c->dAsmDbg, 8192 * 64) != hipSuccess) return false; }
+        if (c->dAsmDbg.ensure(8192 * 64) != hipSuccess) return false;
         hipMemsetAsync(c->dAsmDbg, 0xff, 8192 * 64, pr.stream);
-        a.dbg = c->dAsmDbg;
+        a.dbg = c->dAsmDbg.p;
     }
 #endif
     {   // x / nWaves == mulhi(x, divM) >> divS for x < 2^31 (nWaves >= 4)
@@ -2187,6 +2172,16 @@ int hostToShard(pt_ctx* k, const float* img, float4* devSlots) {
     return 0;
 }
 
+// T (per accumulator slot), allocated when a call first needs it: zeroed on the context's stream, or left for the caller to fill
+int ensureStats(pt_ctx* c, bool zeroed) {
+    if (c->dStats) return 0;
+    HIP_TRY(c->dStats.ensure((size_t)c->nSlotsImg * 16));
+    if (zeroed) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
+    return 0;
+}
+// any upload may move the camera or the scene under the feature records
+void invalidateRecords(pt_ctx* c) { for (pt_ctx::Records* r : {&c->feat, &c->featH, &c->thru, &c->thruH}) r->valid = false; }
+
 // pt_write_frame of a single context: FRAME from the whole host image; T from `stats` when given, else zeroed (where allocated); the camera recorded
 int writeFrame(pt_ctx* c, const float* frame, const float* stats) {
     HIP_TRY(hipSetDevice(c->device));
@@ -2262,13 +2257,10 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
         if ((rc = ensurePool(c, (async && c->poolSlots == 0) ? (1 << 23) : 0))) return rc;
         if (c->ringFrames < wantRing) {
             HIP_TRY(hipStreamSynchronize(s));
-            if (c->dColbuf) HIP_TRY(hipFree(c->dColbuf));
-            if (c->dSeeds) HIP_TRY(hipFree(c->dSeeds));
-            if (c->hSeeds) HIP_TRY(hipHostFree(c->hSeeds));
-            c->dColbuf = nullptr; c->dSeeds = nullptr; c->hSeeds = nullptr; c->ringFrames = 0;
-            HIP_TRY(hipMalloc((void**)&c->dColbuf, (size_t)wantRing * (size_t)c->nSlotsImg * 16));
-            HIP_TRY(hipMalloc((void**)&c->dSeeds, (size_t)wantRing * 4));
-            HIP_TRY(hipHostMalloc((void**)&c->hSeeds, (size_t)wantRing * 4, hipHostMallocDefault));
+            c->ringFrames = 0;
+            HIP_TRY(c->dColbuf.reset((size_t)wantRing * (size_t)c->nSlotsImg * 16));
+            HIP_TRY(c->dSeeds.reset((size_t)wantRing * 4));
+            HIP_TRY(c->hSeeds.reset((size_t)wantRing * 4));
             c->ringFrames = wantRing;
         }
         c->streamIn = fin; *c->hFrameIn = fin; c->streamFast = c->fastContract;
@@ -2369,26 +2361,26 @@ int initContext(pt_ctx* c, int width, int height, int shard_rank, int shard_coun
     c->nLocal = (int)c->pixList.size();
     c->nSlotsImg = shard_count == 1 ? width * height : (int)shardSlots(width, height, shard_count);
     if (c->nLocal == 0) return fail(PT_ERR_ARG, "this shard owns no pixels (more shards than tiles)");
-    HIP_TRY(hipMalloc((void**)&c->dPixList, (size_t)c->nLocal * 4));
+    HIP_TRY(c->dPixList.ensure((size_t)c->nLocal * 4));
     HIP_TRY(hipMemcpy(c->dPixList, c->pixList.data(), (size_t)c->nLocal * 4, hipMemcpyHostToDevice));
     {
         std::vector<unsigned> xy(c->pixList.size());
         for (size_t k = 0; k < xy.size(); k++) xy[k] = (unsigned)(c->pixList[k] % width) | ((unsigned)(c->pixList[k] / width) << 16);
-        HIP_TRY(hipMalloc((void**)&c->dPixXY, xy.size() * 4));
+        HIP_TRY(c->dPixXY.ensure(xy.size() * 4));
         HIP_TRY(hipMemcpy(c->dPixXY, xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc((void**)&c->dImage[0], (size_t)c->nSlotsImg * 16));
+    HIP_TRY(c->dImage[0].ensure((size_t)c->nSlotsImg * 16));
     HIP_TRY(hipMemset(c->dImage[0], 0, (size_t)c->nSlotsImg * 16));
-    HIP_TRY(hipMalloc((void**)&c->dFrameIn, sizeof(FrameIn)));
-    HIP_TRY(hipMalloc((void**)&c->dFc, sizeof(FrameConst)));
-    HIP_TRY(hipMalloc((void**)&c->dCtl, sizeof(Control)));
+    HIP_TRY(c->dFrameIn.ensure(sizeof(FrameIn)));
+    HIP_TRY(c->dFc.ensure(sizeof(FrameConst)));
+    HIP_TRY(c->dCtl.ensure(sizeof(Control)));
     HIP_TRY(hipMemset(c->dCtl, 0, sizeof(Control)));
     for (auto& g : c->grp) {
-        HIP_TRY(hipHostMalloc((void**)&g.h, sizeof(Control), hipHostMallocCoherent));
-        HIP_TRY(hipHostMalloc((void**)&g.stamp, 64, hipHostMallocCoherent));
+        HIP_TRY(g.h.ensure(sizeof(Control)));
+        HIP_TRY(g.stamp.ensure(64));
         *g.stamp = 0;
     }
-    HIP_TRY(hipHostMalloc((void**)&c->hFrameIn, sizeof(FrameIn), hipHostMallocDefault));
+    HIP_TRY(c->hFrameIn.ensure(sizeof(FrameIn)));
     return 0;
 }
 }  // namespace
@@ -2424,7 +2416,7 @@ int pt_create_multi_part(pt_ctx** out, const int* devices, int n_devices, int wi
     for (int i = 0; i < n_devices; i++) {
         if (!runs.empty() && runs.back().device == devices[i]) { runs.back().count++; continue; }
         for (const auto& r : runs) if (r.device == devices[i]) return fail(PT_ERR_ARG, "pt_create_multi: the entries of one device must be adjacent ({0,0,1,1}, not {0,1,0,1})");
-        runs.push_back(MultiCtx::Run{devices[i], i, 1, nullptr});
+        runs.push_back(MultiCtx::Run{devices[i], i, 1});
     }
     for (const auto& r : runs) if (r.count != runs[0].count) return fail(PT_ERR_ARG, "pt_create_multi: every device must be listed the same number of times");
     // Test mode (tests/test_gpu_multi.py): PT_MULTI_VIRTUAL_DEVICES=k splits the streams of ONE device into k "virtual devices", so that a
@@ -2437,7 +2429,7 @@ int pt_create_multi_part(pt_ctx** out, const int* devices, int n_devices, int wi
             if (runs.size() != 1 || n_devices % virtualDevices) return fail(PT_ERR_ARG, "PT_MULTI_VIRTUAL_DEVICES=k needs ONE device listed a multiple of k times");
             const int per = n_devices / virtualDevices, dev = runs[0].device;
             runs.clear();
-            for (int v = 0; v < virtualDevices; v++) runs.push_back(MultiCtx::Run{dev, v * per, per, nullptr});
+            for (int v = 0; v < virtualDevices; v++) runs.push_back(MultiCtx::Run{dev, v * per, per});
         } else virtualDevices = 0;
     }
     pt_ctx* g = new pt_ctx();
@@ -2445,6 +2437,7 @@ int pt_create_multi_part(pt_ctx** out, const int* devices, int n_devices, int wi
     MultiCtx* M = new MultiCtx();
     g->multi = M;
     M->n = n_devices; M->devices.assign(devices, devices + n_devices); M->runs = runs;
+    M->staging.resize(runs.size());
     M->shardBase = first_shard; M->shardTotal = total_shards;
     const char* force = getenv("PT_MULTI_FORCE_RCCL");          // tests: the RCCL call path of a one-device group on a one-GPU box
     M->useRccl = runs.size() > 1 || (force && force[0] == '1');
@@ -2486,22 +2479,16 @@ int pt_destroy(pt_ctx* c) {
     flushStream(c);
     hipStreamSynchronize(c->stream);
     for (hipModule_t m : c->asmModule) if (m) hipModuleUnload(m);
-    void* ptrs[] = {c->dNiTable, c->st.J, c->dNodes80, c->dTexels, c->dTexTable, c->dTriObj, c->dNodes, c->dTris, c->dShade, c->dRoots, c->dEllip, c->dMats, c->dSky, c->dPixList, c->dPixXY, c->dAllMaps, c->dImage[0], c->dImage[1], c->dImage[2], c->dImage[3], c->st.G0, c->st.G1, c->st.G2,
-                    c->st.G3, c->st.G4, c->st.G5, c->st.S0, c->st.H, c->st.HX, c->dQueue[0], c->dQueue[1], c->dColbuf, c->dSeeds, c->dFrameIn, c->dFc, c->dCtl, c->dDisplay,
-                    c->dStats, c->dAdaptFlag, c->dAdaptBlk, c->dAdaptXY, c->dAdaptSlot, c->dFeat, c->dDnCol[0], c->dDnCol[1], c->dDnGuide, c->dDnOut,
-                    c->dFeatH, c->dMatVD, c->dRpFrame, c->dRpStats, c->dStatsWhole, c->dRpKept, c->dSelMask, c->dFill, c->dFillCount, c->dThru, c->dThruRays,
-                    c->dMarkFeat, c->dMarkTri, c->dMarkEl, c->dMoveTri, c->dMoveEl, c->dHoldFrame, c->dHoldStats, c->dKappa, c->dThruH, c->dThruRaysH, c->dRpPack};
-    for (void* p : ptrs) if (p) hipFree(p);
-    for (auto& g : c->grp) { if (g.h) hipHostFree(g.h); if (g.stamp) hipHostFree((void*)g.stamp); }
-    if (c->hFrameIn) hipHostFree(c->hFrameIn);
-    if (c->hSeeds) hipHostFree(c->hSeeds);
-    if (c->hAdaptCount) hipHostFree(c->hAdaptCount);
     for (auto& k : c->kt) for (auto& e : k.ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    if (c->sExt) { hipStreamSynchronize(c->sExt); giveStream((c->device + 1) * 100 + c->cuPartitionBuilt, c->sExt); }
-    if (c->sShade) { hipStreamSynchronize(c->sShade); giveStream((c->device + 1) * 100 + 50 + c->cuPartitionBuilt, c->sShade); }
     for (hipEvent_t e : {c->evExt, c->evShade, c->evHost}) if (e) hipEventDestroy(e);
-    if (c->ownStream) { hipStreamSynchronize(c->ownStream); giveStream(c->device, c->ownStream); }
+    // the context's memory goes with it (pt_devmem.hpp): while its streams are idle, and before they return to the pool for other contexts to use
+    const int device = c->device, part = c->cuPartitionBuilt;
+    hipStream_t sExt = c->sExt, sShade = c->sShade, own = c->ownStream;
+    for (hipStream_t s : {sExt, sShade, own}) if (s) hipStreamSynchronize(s);
     delete c;
+    if (sExt) giveStream((device + 1) * 100 + part, sExt);
+    if (sShade) giveStream((device + 1) * 100 + 50 + part, sShade);
+    if (own) giveStream(device, own);
     return PT_OK;
 }
 
@@ -2518,7 +2505,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         return PT_OK;
     }
     if (bytes % 4) return fail(PT_ERR_ARG, "pt_set_buffer: size must be a multiple of 4 bytes");
-    c->featValid = false; c->featHValid = false; c->thruValid = false; c->thruHValid = false;                  // any binding may move the camera or the scene under the feature records
+    invalidateRecords(c);
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
         case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
@@ -2552,7 +2539,7 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
         return PT_OK;
     }
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
-    c->featValid = false; c->featHValid = false; c->thruValid = false; c->thruHValid = false;
+    invalidateRecords(c);
     c->sceneGen++; c->otherGen++;
     if (index == 0) { c->sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->skyW = w; c->skyH = h; }
     if ((size_t)index >= c->textures.size()) c->textures.resize((size_t)index + 1);
@@ -2595,7 +2582,7 @@ int pt_next_image(pt_ctx* c) {
     MULTI_ALL(c, pt_next_image(k));
     HIP_TRY(hipSetDevice(c->device));
     const int next = (c->curImage + 1) % pt_ctx::IMAGES;
-    if (!c->dImage[next]) HIP_TRY(hipMalloc((void**)&c->dImage[next], (size_t)c->nSlotsImg * 16));
+    HIP_TRY(c->dImage[next].ensure((size_t)c->nSlotsImg * 16));
     int rc;
     if ((rc = pump(c, PUMP_IMAGE, next))) return rc;              // nothing may still be on its way into the image taken over
     c->curImage = next;
@@ -2701,7 +2688,7 @@ int wholeFrame(pt_ctx* c, int code, const char* who, pt_ctx** on, const float4**
 // (FRAME alpha) when perPixel
 int displayInto(pt_ctx* on, const float4* src, int W, int H, bool perPixel, float count, int java_bytes, uint8_t* rgb_out) {
     const size_t bytes = (size_t)W * H * 3;
-    if (!on->dDisplay) HIP_TRY(hipMalloc((void**)&on->dDisplay, bytes));
+    HIP_TRY(on->dDisplay.ensure(bytes));
     hipLaunchKernelGGL(perPixel ? k_display<true> : k_display<false>, dim3((unsigned)(((size_t)W * H + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, on->stream,
                        src, W, H, count, java_bytes, on->dDisplay);
     HIP_TRY(hipGetLastError());
@@ -2742,17 +2729,12 @@ int renderSelected(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds,
     if ((rc = flushStream(c))) return rc;                         // batches in flight land in FRAME, not in the statistics
     hipStream_t s = c->stream;
     const int nb = (c->nLocal + BLOCK - 1) / BLOCK;
-    if (!c->dStats) {
-        HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
-        HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, s));
-    }
-    if (!c->dAdaptXY) {
-        HIP_TRY(hipMalloc((void**)&c->dAdaptFlag, (size_t)c->nLocal));
-        HIP_TRY(hipMalloc((void**)&c->dAdaptBlk, ((size_t)nb + 1) * 4));
-        if (c->shardCount > 1) HIP_TRY(hipMalloc((void**)&c->dAdaptSlot, (size_t)c->nLocal * 4));
-        HIP_TRY(hipHostMalloc((void**)&c->hAdaptCount, 4, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void**)&c->dAdaptXY, (size_t)c->nLocal * 4));      // (last: its presence says the others exist)
-    }
+    if ((rc = ensureStats(c, true))) return rc;
+    HIP_TRY(c->dAdaptFlag.ensure((size_t)c->nLocal));
+    HIP_TRY(c->dAdaptBlk.ensure(((size_t)nb + 1) * 4));
+    if (c->shardCount > 1) HIP_TRY(c->dAdaptSlot.ensure((size_t)c->nLocal * 4));
+    HIP_TRY(c->hAdaptCount.ensure(4));
+    HIP_TRY(c->dAdaptXY.ensure((size_t)c->nLocal * 4));
     if ((rc = select(s, nb))) return rc;
     hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(BLOCK), 0, s, c->dAdaptBlk, nb, c->dAdaptBlk + nb);
     hipLaunchKernelGGL(k_adaptive_compact, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, (const unsigned char*)c->dAdaptFlag, (const unsigned*)c->dAdaptBlk,
@@ -2919,7 +2901,7 @@ int pt_unshard(pt_ctx* c, const void* gathered_dev, void* full_dev) {
     if (!c->dAllMaps) {
         std::vector<int32_t> maps;
         { const int rc = shardMaps(c->W, c->H, 0, c->shardCount, c->shardCount, (size_t)c->nSlotsImg, maps); if (rc) return rc; }
-        HIP_TRY(hipMalloc((void**)&c->dAllMaps, total * 4));
+        HIP_TRY(c->dAllMaps.ensure(total * 4));
         HIP_TRY(hipMemcpy(c->dAllMaps, maps.data(), total * 4, hipMemcpyHostToDevice));
     }
     hipLaunchKernelGGL(k_unshard, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (const float4*)gathered_dev, c->dAllMaps, c->nSlotsImg, c->shardCount, (float4*)full_dev);
@@ -3066,12 +3048,11 @@ int pt_debug_math(pt_ctx* c, int fn, const float* x, const float* y, float* out,
     if (!c || !x || !out) return fail(PT_ERR_ARG, "pt_debug_math: null argument");
     c = firstStream(c);
     HIP_TRY(hipSetDevice(c->device));
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    Scratch scratch{{(void**)&dx, (void**)&dy, (void**)&dout}};       // freed on every return path
-    HIP_TRY(hipMalloc((void**)&dx, n * 4)); HIP_TRY(hipMalloc((void**)&dy, n * 4)); HIP_TRY(hipMalloc((void**)&dout, n * 4));
+    Dev<float> dx, dy, dout;                                       // freed on every return path
+    HIP_TRY(dx.ensure(n * 4)); HIP_TRY(dy.ensure(n * 4)); HIP_TRY(dout.ensure(n * 4));
     HIP_TRY(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
     if (y) HIP_TRY(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice)); else HIP_TRY(hipMemset(dy, 0, n * 4));
-    hipLaunchKernelGGL(k_debug_math, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, fn, dx, dy, dout, n);
+    hipLaunchKernelGGL(k_debug_math, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, fn, dx.p, dy.p, dout.p, n);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
     return PT_OK;
@@ -3108,15 +3089,15 @@ int claimFrameConstants(pt_ctx* c) {
     return 0;
 }
 
-// G0, G1, H and, with hx, HX of a probe pool of np slots, released with `scratch`; their contents are the caller's
-int probePool(Scratch& scratch, State& st, size_t np, bool hx) {
-    for (float4** p : {&st.G0, &st.G1, &st.H, &st.HX}) {
-        if (p == &st.HX && !hx) break;
-        scratch.ptrs.push_back((void**)p);
-        HIP_TRY(hipMalloc((void**)p, np * 16));
+// a probe pool of np slots: G0, G1, H and, with hx, HX, released with the pool; their contents are the caller's
+struct ProbePool {
+    Dev<float4> mem[4]; State st{};
+    int alloc(size_t np, bool hx) {
+        float4** groups[] = {&st.G0, &st.G1, &st.H, &st.HX};
+        for (int k = 0; k < (hx ? 4 : 3); k++) { HIP_TRY(mem[k].ensure(np * 16)); *groups[k] = mem[k]; }
+        return 0;
     }
-    return 0;
-}
+};
 }  // namespace
 
 int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, size_t n) {
@@ -3131,9 +3112,9 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
         g0[4 * i] = o[3 * i]; g0[4 * i + 1] = o[3 * i + 1]; g0[4 * i + 2] = o[3 * i + 2]; g0[4 * i + 3] = d[3 * i];
         g1[4 * i] = d[3 * i + 1]; g1[4 * i + 1] = d[3 * i + 2]; uint32_t fl = FL_ALIVE; std::memcpy(&g1[4 * i + 3], &fl, 4);
     }
-    State st{};
-    Scratch scratch;
-    if ((rc = probePool(scratch, st, np, false))) return rc;
+    ProbePool pool;
+    if ((rc = pool.alloc(np, false))) return rc;
+    const State& st = pool.st;
     HIP_TRY(hipMemcpy(st.G0, g0.data(), np * 16, hipMemcpyHostToDevice)); HIP_TRY(hipMemcpy(st.G1, g1.data(), np * 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(st.H, 0, np * 16, c->stream));       // ordered before the kernels below (the context's stream does not wait for the null stream)
     // the ellipsoid rotation matrices are produced by k_frame_setup

@@ -21,7 +21,7 @@ int statsToHost(pt_ctx* c, float* host, bool* any) {
 // The whole image's T in pixel order on the device of `on` (firstStream(c)), or nullptr when no stream holds T: a single context's own T; a group's
 // gathered through the host into on->dStatsWhole.  Work in flight is the caller's to complete.
 int wholeStats(pt_ctx* c, pt_ctx* on, const float4** stats) {
-    *stats = c->multi ? nullptr : c->dStats;
+    *stats = c->multi ? nullptr : c->dStats.p;
     if (!c->multi) return 0;
     const size_t n = (size_t)c->W * c->H;
     std::vector<float> host(n * 4);
@@ -29,7 +29,7 @@ int wholeStats(pt_ctx* c, pt_ctx* on, const float4** stats) {
     if (int rc = statsToHost(c, host.data(), &any)) return rc;
     if (!any) return 0;
     HIP_TRY(hipSetDevice(on->device));
-    if (!on->dStatsWhole) HIP_TRY(hipMalloc((void**)&on->dStatsWhole, n * 16));
+    HIP_TRY(on->dStatsWhole.ensure(n * 16));
     HIP_TRY(hipMemcpyAsync(on->dStatsWhole, host.data(), n * 16, hipMemcpyHostToDevice, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     *stats = on->dStatsWhole;
@@ -38,8 +38,20 @@ int wholeStats(pt_ctx* c, pt_ctx* on, const float4** stats) {
 int writeMoments(pt_ctx* c, const float* in) {
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = flushStream(c)) return rc;
-    if (!c->dStats) HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
+    if (int rc = ensureStats(c, false)) return rc;
     return hostToShard(c, in, c->dStats);
+}
+// every stream of the context synchronised: all submitted work has landed in FRAME and T
+int syncAll(pt_ctx* c) {
+    if (c->multi) return multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); });
+    return pt_synchronize(c);
+}
+// runs `call` with a count of its own and stores it, zero when the call fails before counting, into *out (may be NULL)
+int counted(int64_t* out, const std::function<int(int64_t*)>& call) {
+    int64_t n = 0;
+    const int rc = call(&n);
+    if (out) *out = n;
+    return rc;
 }
 }  // namespace
 
@@ -48,10 +60,7 @@ int pt_record_moments(pt_ctx* c, int on) {
     MULTI_ALL(c, pt_record_moments(k, on));
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = flushStream(c)) return rc;                       // batches in flight retire under the previous setting
-    if (on && !c->dStats) {
-        HIP_TRY(hipMalloc((void**)&c->dStats, (size_t)c->nSlotsImg * 16));
-        HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
-    }
+    if (on) { if (int rc = ensureStats(c, true)) return rc; }
     c->recordMoments = on != 0;
     return PT_OK;
 }
@@ -74,38 +83,62 @@ int pt_write_moments(pt_ctx* c, const float* in) {
 
 // ---- first-hit feature records and the denoised image (include/pt_denoise.h).  A group context works on its first stream's context: the scene is replicated.
 namespace {
-// the feature records of the frame inputs `fin` into *buf (W*H x 4 float4, allocated on first use); *valid says they are there
-int ensureFeaturesFor(pt_ctx* c, const FrameIn& fin, float4** buf, bool* valid) {
+// The records of the frame inputs `fin` in the cache R: first-hit records (rule == nullptr), or the seen-through records under `rule` with their last
+// segments.  Returns at once when R holds them; a failed fill leaves R invalid.  A probe pool takes the camera rays (k_feature_rays); then one
+// intersect and k_feature_record, or max_depth + 1 rounds of (intersect, k_through_step) — a fixed count, nothing read back in between: a round
+// whose lanes are all dead costs two launches that return at once
+int ensureRecords(pt_ctx* c, pt_ctx::Records& R, const FrameIn& fin, const pt_through_rule* rule, const char* who) {
     HIP_TRY(hipSetDevice(c->device));
-    if (*valid) return 0;
+    if (R.valid && std::memcmp(&R.in, &fin, sizeof(FrameIn)) == 0 && (!rule || std::memcmp(&R.rule, rule, sizeof(*rule)) == 0)) return 0;
+    R.valid = false;
     int rc;
     if ((rc = claimFrameConstants(c))) return rc;
+    if (rule && (rule->flags & PT_THROUGH_KEY) && c->sc.numMat > 4096)
+        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": PT_THROUGH_KEY packs a material index into 12 bits; the scene has more than 4096 materials");
     const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
-    if (!*buf) HIP_TRY(hipMalloc((void**)buf, n * 64));
-    State st{};
-    Scratch scratch;
-    if ((rc = probePool(scratch, st, np, c->sc.numEllip > 0))) return rc;      // HX: the uv an ellipsoid hit inherits (uvOfHit)
+    HIP_TRY(R.recs.ensure(n * 64));
+    if (rule) HIP_TRY(R.rays.ensure(n * 32));
+    ProbePool pool;
+    if ((rc = pool.alloc(np, c->sc.numEllip > 0))) return rc;      // HX: the uv an ellipsoid hit inherits (uvOfHit)
+    const State& st = pool.st;
+    Dev<float4> X;                                                // the chains' state between the rounds
+    if (rule) HIP_TRY(X.ensure(np * 16 * (c->niBits == 32 ? 5 : (c->niBits == 8 ? 3 : 2))));
     if (st.HX) HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);      // auto-focus, camera and ellipsoid rotations
     hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
-    if ((rc = probeIntersect(c, st, np, fin))) return rc;
-    hipLaunchKernelGGL(k_feature_record, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, *buf);
+    if (!rule) {
+        if ((rc = probeIntersect(c, st, np, fin))) return rc;
+        hipLaunchKernelGGL(k_feature_record, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, R.recs.p);
+    } else {
+        // RAYTRACING == 0 (directDiffuse, frag.glsl:911-912) takes no step
+        const int depth = (rule->lobes == 0 || fin.params[9] != 1.0f) ? 0 : rule->max_depth;
+        const ThroughRule tr{depth, rule->min_weight, rule->lobes, rule->flags};
+        for (int step = 0; step <= depth; step++) {
+            if ((rc = probeIntersect(c, st, np, fin))) return rc;
+#define THROUGH_STEP(T) hipLaunchKernelGGL(k_through_step<T>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, tr, step, X.p, (unsigned)np, R.recs.p, R.rays.p)
+            if (c->niBits == 3) THROUGH_STEP(3);
+            else if (c->niBits == 8) THROUGH_STEP(8);
+            else if (c->niBits == 32) THROUGH_STEP(32);
+            else THROUGH_STEP(0);
+#undef THROUGH_STEP
+        }
+        R.rule = *rule;
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    *valid = true;
+    R.in = fin;
+    R.valid = true;
     return 0;
 }
-// the records of the current frame inputs (c->dFeat)
-int ensureFeatures(pt_ctx* c) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->featValid) return 0;
+// the records of the current frame inputs: c->feat, or c->thru under `rule`
+int currentRecords(pt_ctx* c, const pt_through_rule* rule, const char* who) {
     if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
     if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
     FrameIn fin;
     currentInputs(c, fin);
-    return ensureFeaturesFor(c, fin, &c->dFeat, &c->featValid);
+    return ensureRecords(c, rule ? c->thru : c->feat, fin, rule, who);
 }
 
 // include/pt_through.h's rule, checked
@@ -118,74 +151,11 @@ int checkThrough(const pt_through_rule* r, const char* who) {
     if (r->flags & ~PT_THROUGH_KEY) return fail(PT_ERR_ARG, w + ": unknown rule.flags");
     return 0;
 }
-// the seen-through records of the frame inputs `fin` under `rule` into *recs (W*H x 4 float4) and their last segments into *rays (W*H x 2 float4),
-// both allocated on first use; *valid says they are there: ensureFeaturesFor's probe pool and ray kernel, then max_depth + 1 rounds of (intersect,
-// k_through_step) — a fixed count, nothing read back in between: a round whose lanes are all dead costs two launches that return at once
-int ensureThroughFor(pt_ctx* c, const FrameIn& fin, const pt_through_rule& rule, const char* who, float4** recs, float4** rays, bool* valid) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (*valid) return 0;
-    int rc;
-    if ((rc = claimFrameConstants(c))) return rc;
-    if ((rule.flags & PT_THROUGH_KEY) && c->sc.numMat > 4096)
-        return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": PT_THROUGH_KEY packs a material index into 12 bits; the scene has more than 4096 materials");
-    const size_t n = (size_t)c->W * c->H, np = (n + BLOCK - 1) / BLOCK * BLOCK;
-    if (!*recs) HIP_TRY(hipMalloc((void**)recs, n * 64));
-    if (!*rays) HIP_TRY(hipMalloc((void**)rays, n * 32));
-    State st{};
-    Scratch scratch;
-    if ((rc = probePool(scratch, st, np, c->sc.numEllip > 0))) return rc;
-    float4* X = nullptr;
-    scratch.ptrs.push_back((void**)&X);
-    const int planes = c->niBits == 32 ? 5 : (c->niBits == 8 ? 3 : 2);
-    HIP_TRY(hipMalloc((void**)&X, np * 16 * planes));
-    if (st.HX) HIP_TRY(hipMemsetAsync(st.HX, 0, np * 16, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);
-    hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
-    // RAYTRACING == 0 (directDiffuse, frag.glsl:911-912) takes no step
-    const int depth = (rule.lobes == 0 || fin.params[9] != 1.0f) ? 0 : rule.max_depth;
-    const ThroughRule tr{depth, rule.min_weight, rule.lobes, rule.flags};
-    for (int step = 0; step <= depth; step++) {
-        if ((rc = probeIntersect(c, st, np, fin))) return rc;
-#define THROUGH_STEP(T) hipLaunchKernelGGL(k_through_step<T>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, tr, step, X, (unsigned)np, *recs, *rays)
-        if (c->niBits == 3) THROUGH_STEP(3);
-        else if (c->niBits == 8) THROUGH_STEP(8);
-        else if (c->niBits == 32) THROUGH_STEP(32);
-        else THROUGH_STEP(0);
-#undef THROUGH_STEP
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *valid = true;
-    return 0;
-}
-// the records of the current frame inputs under `rule` (c->dThru, c->dThruRays)
-int ensureThrough(pt_ctx* c, const pt_through_rule& rule, const char* who) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->thruValid && std::memcmp(&c->thruRule, &rule, sizeof(rule)) == 0) return 0;
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
-    FrameIn fin;
-    currentInputs(c, fin);
-    c->thruValid = false;
-    if (int rc = ensureThroughFor(c, fin, rule, who, &c->dThru, &c->dThruRays, &c->thruValid)) return rc;
-    c->thruRule = rule;
-    return 0;
-}
-// the records of the frame inputs `fin` of the current image's camera under `rule` (c->dThruH, c->dThruRaysH): include/pt_reproject_through.h's Sh, Yh
-int ensureThroughH(pt_ctx* c, const FrameIn& fin, const pt_through_rule& rule, const char* who) {
-    if (c->thruHValid && (std::memcmp(&c->thruHRule, &rule, sizeof(rule)) != 0 || std::memcmp(&c->thruHIn, &fin, sizeof(FrameIn)) != 0)) c->thruHValid = false;
-    if (int rc = ensureThroughFor(c, fin, rule, who, &c->dThruH, &c->dThruRaysH, &c->thruHValid)) return rc;
-    c->thruHRule = rule; c->thruHIn = fin;
-    return 0;
-}
-
 // the filters' scratch on the device of `on`: the colour ping-pong and the output (W*H float4 each), the packed guide (2*W*H float4)
 int ensureFilterScratch(pt_ctx* on) {
     const size_t n = (size_t)on->W * on->H;
-    for (float4** p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) if (!*p) HIP_TRY(hipMalloc((void**)p, n * 16));
-    if (!on->dDnGuide) HIP_TRY(hipMalloc((void**)&on->dDnGuide, n * 32));
+    for (Dev<float4>* p : {&on->dDnCol[0], &on->dDnCol[1], &on->dDnOut}) HIP_TRY(p->ensure(n * 16));
+    HIP_TRY(on->dDnGuide.ensure(n * 32));
     return 0;
 }
 // an image a filter left on the device of `on` (W*H float4, written on on->stream) into rgba_out; with dCount, that count into *count
@@ -209,9 +179,9 @@ int denoiseImage(pt_ctx* c, int iterations, const float (&sigma)[4], pt_ctx** on
     pt_ctx* on = nullptr; const float4* frame = nullptr;
     int rc;
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise", &on, &frame))) return rc;
-    if ((rc = ensureFeatures(on))) return rc;
+    if ((rc = currentRecords(on, nullptr, "pt_denoise"))) return rc;
     if ((rc = ensureFilterScratch(on))) return rc;
-    HIP_TRY(denoiseLaunch(frame, on->dFeat, c->W, c->H, iterations, sigma, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
+    HIP_TRY(denoiseLaunch(frame, on->feat.recs, c->W, c->H, iterations, sigma, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
     *onOut = on;
     return 0;
 }
@@ -221,8 +191,8 @@ int pt_read_features(pt_ctx* c, float* out) {
     if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features: null argument");
     pt_ctx* on = firstStream(c);
     int rc;
-    if ((rc = ensureFeatures(on))) return rc;
-    HIP_TRY(hipMemcpy(out, on->dFeat, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
+    if ((rc = currentRecords(on, nullptr, "pt_read_features"))) return rc;
+    HIP_TRY(hipMemcpy(out, on->feat.recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -266,12 +236,12 @@ int filteredImage(pt_ctx* c, bool fill, bool filter, int iterations, const float
         if ((rc = wholeStats(c, on, &j.stats))) return rc;
         if (!j.stats) return fail(PT_ERR_ARG, w + ": the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
     }
-    if ((rc = thru ? ensureThrough(on, *thru, who) : ensureFeatures(on))) return rc;
-    j.feat = thru ? on->dThru : on->dFeat;
+    if ((rc = currentRecords(on, thru, who))) return rc;
+    j.feat = thru ? on->thru.recs : on->feat.recs;
     if ((rc = ensureFilterScratch(on))) return rc;
     if (fill) {
-        if (!on->dFill) HIP_TRY(hipMalloc((void**)&on->dFill, (size_t)c->W * c->H * 16));
-        if (!on->dFillCount) HIP_TRY(hipMalloc((void**)&on->dFillCount, 4));
+        HIP_TRY(on->dFill.ensure((size_t)c->W * c->H * 16));
+        HIP_TRY(on->dFillCount.ensure(4));
         j.fill = on->dFill; j.fillCount = on->dFillCount;
     }
     j.W = c->W; j.H = c->H; j.iterations = iterations; j.minFrames = minFrames; j.floorA = floorA;
@@ -318,6 +288,22 @@ int pt_read_display_denoised_guided_demod(pt_ctx* c, int iterations, float sigma
 // ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
 // every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
 namespace {
+// the current inputs of `on` into cur, refused unless they render surfaces at the image's size; toDo: what the caller wants surfaces for
+int usableInputs(const pt_ctx* c, const pt_ctx* on, const std::string& w, const char* toDo, FrameIn& cur) {
+    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
+    const float* P = on->params.data();
+    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
+    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, w + ": DEBUG != 0 renders the traversal heat map, which has no surfaces to " + toDo);
+    return 0;
+}
+// a valid camera record h of an image of `on`, refused unless feature records under it describe the image: the scene as it was, surfaces, the size
+int usableCamera(const pt_ctx* c, const pt_ctx* on, const pt_ctx::Cam& h, const std::string& w) {
+    if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, w + ": a scene buffer or texture was uploaded since the image's camera was recorded");
+    if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, w + ": the image was rendered with DEBUG != 0");
+    if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
+        return fail(PT_ERR_ARG, w + ": the image's camera has Parameters that do not match the image size");
+    return 0;
+}
 // the reprojected image (on->dRpFrame, on->dRpStats when `stats`, on->dRpKept; enqueued on on->stream) into the current image of `c`, whose camera
 // becomes the current inputs
 int storeReprojected(pt_ctx* c, pt_ctx* on, bool stats, int64_t* nKept) {
@@ -405,13 +391,9 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     ReprojectJob j;
     int rc;
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &j.frame))) return rc;      // a group: gathered on on->stream
-    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
-    else if ((rc = pt_synchronize(c))) return rc;                 // all submitted work lands in FRAME and T first
+    if ((rc = syncAll(c))) return rc;                             // all submitted work lands in FRAME and T first
     FrameIn cur;
-    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
-    const float* P = on->params.data();
-    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
-    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, w + ": DEBUG != 0 renders the traversal heat map, which has no surfaces to carry");
+    if ((rc = usableInputs(c, on, w, "carry", cur))) return rc;
     pt_ctx::Mark& m = on->mark;
     const pt_ctx::Cam h = on->cam[on->curImage];
     if (moved) {
@@ -422,43 +404,35 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
         if (m.otherGen != on->otherGen) return fail(PT_ERR_ARG, w + ": binding 5, binding 14 or a texture was uploaded since the mark");
     } else {
         if (!h.valid) return PT_OK;                               // no camera: nothing to map from
-        if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, w + ": a scene buffer or texture was uploaded since the image's camera was recorded");
-        if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, w + ": the image was rendered with DEBUG != 0");
-        if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
-            return fail(PT_ERR_ARG, w + ": the image's camera has Parameters that do not match the image size");
+        if ((rc = usableCamera(c, on, h, w))) return rc;
     }
     // Rn, in the scene as it is now (builds it when an upload is pending); Rh from the mark, or of the image's camera (the same records when it is unchanged)
-    if ((rc = ensureFeaturesFor(on, cur, &on->dFeat, &on->featValid))) return rc;
-    j.rn = on->dFeat;
+    if ((rc = ensureRecords(on, on->feat, cur, nullptr, who))) return rc;
+    j.rn = on->feat.recs;
     const bool sameCam = std::memcmp(&h.in, &cur, sizeof(FrameIn)) == 0;
     if (chain) {                                                  // an unchanged camera uses one pair for both
-        if ((rc = ensureThrough(on, *chain->thru, who))) return rc;
-        j.sn = j.sh = on->dThru; j.yn = j.yh = on->dThruRays;
-        if (!sameCam) {
-            if ((rc = ensureThroughH(on, h.in, *chain->thru, who))) return rc;
-            j.sh = on->dThruH; j.yh = on->dThruRaysH;
-        }
+        pt_ctx::Records& sh = sameCam ? on->thru : on->thruH;
+        if ((rc = ensureRecords(on, on->thru, cur, chain->thru, who))) return rc;
+        if (!sameCam && (rc = ensureRecords(on, sh, h.in, chain->thru, who))) return rc;
+        j.sn = on->thru.recs; j.yn = on->thru.rays; j.sh = sh.recs; j.yh = sh.rays;
         j.pointTol = chain->pointTol; j.radius = chain->radius;
     }
     if (moved) {
-        j.rh = on->dMarkFeat;
-    } else if (sameCam) {
-        j.rh = on->dFeat;
+        j.rh = on->mark.feat;
     } else {
-        if (on->featHValid && std::memcmp(&on->featHIn, &h.in, sizeof(FrameIn)) != 0) on->featHValid = false;
-        if ((rc = ensureFeaturesFor(on, h.in, &on->dFeatH, &on->featHValid))) return rc;
-        on->featHIn = h.in;
-        j.rh = on->dFeatH;
+        pt_ctx::Records& rh = sameCam ? on->feat : on->featH;
+        if (!sameCam && (rc = ensureRecords(on, rh, h.in, nullptr, who))) return rc;
+        j.rh = rh.recs;
     }
     HIP_TRY(hipSetDevice(on->device));
     const size_t n = (size_t)c->W * c->H;
-    if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
-    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 8));
-    if (chain && !on->dRpPack) HIP_TRY(hipMalloc((void**)&on->dRpPack, n * 32));
+    HIP_TRY(on->dRpFrame.ensure(n * 16));
+    HIP_TRY(on->dRpKept.ensure(8));
+    if (chain) HIP_TRY(on->dRpPack.ensure(n * 32));
     j.pack = on->dRpPack;
     // the image's T in pixel order, when allocated (group: through the host)
     if ((rc = wholeStats(c, on, &j.stats))) return rc;
-    if (j.stats && !on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
+    if (j.stats) HIP_TRY(on->dRpStats.ensure(n * 16));
     // where the primitives are now, with the moved ones flagged
     std::vector<float4> pt, pe;
     ReprojMotion g{};
@@ -466,9 +440,9 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
         std::vector<float> tri, el; int nTri = 0, nEl = 0;
         motionPositions(on, tri, &nTri, el, &nEl);
         motionPack(tri, nTri, el, nEl, &m, pt, pe);
-        if ((rc = uploadVec((void**)&on->dMoveTri, pt.data(), pt.size() * 16, on->stream))) return rc;
-        if ((rc = uploadVec((void**)&on->dMoveEl, pe.data(), pe.size() * 16, on->stream))) return rc;
-        g = ReprojMotion{on->dMoveTri, on->dMarkTri, nTri, m.nTri, on->dMoveEl, on->dMarkEl, nEl, m.nEl};
+        HIP_TRY(on->dMoveTri.upload(pt.data(), pt.size() * 16, on->stream));
+        HIP_TRY(on->dMoveEl.upload(pe.data(), pe.size() * 16, on->stream));
+        g = ReprojMotion{on->dMoveTri, m.dTri, nTri, m.nTri, on->dMoveEl, m.dEl, nEl, m.nEl};
         j.motion = &g;
     }
     // the image's camera as k_frame_setup builds it (of which only camRot, origin, screenSize, focalLength and screenHratio are read), in the frame
@@ -481,7 +455,7 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     j.cam = ReprojCam{{cur.origin[0], cur.origin[1], cur.origin[2]}, cur.mouse[0], cur.mouse[1], cur.params[2]};
     j.rule = ReprojRule{maxHistory, depthTol, normalTol, (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0};
     j.floorA = floorA;
-    j.outFrame = on->dRpFrame; j.outStats = j.stats ? on->dRpStats : nullptr; j.kept = on->dRpKept;
+    j.outFrame = on->dRpFrame; j.outStats = j.stats ? on->dRpStats.p : nullptr; j.kept = on->dRpKept;
     HIP_TRY(reprojectLaunch(j, on->stream));
     if (moved) HIP_TRY(hipStreamSynchronize(on->stream));         // (pt / pe leave scope: their copies have landed)
     if (chain) {
@@ -497,22 +471,18 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
 }  // namespace
 
 int pt_reproject_frame(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, int64_t* n_kept) {
-    if (n_kept) *n_kept = 0;
-    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame: null context");
-    int64_t n = 0;
-    const int rc = reprojectImage(c, "pt_reproject_frame", false, max_history, depth_tol, normal_tol, flags, 0.0f, &n);
-    if (n_kept) *n_kept = n;
-    return rc;
+    return counted(n_kept, [&](int64_t* n) {
+        if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame: null context");
+        return reprojectImage(c, "pt_reproject_frame", false, max_history, depth_tol, normal_tol, flags, 0.0f, n);
+    });
 }
 
 int pt_reproject_frame_demod(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
-    if (n_kept) *n_kept = 0;
-    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: null context");
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: albedo_floor must be finite and > 0");
-    int64_t n = 0;
-    const int rc = reprojectImage(c, "pt_reproject_frame", false, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
-    if (n_kept) *n_kept = n;
-    return rc;
+    return counted(n_kept, [&](int64_t* n) {
+        if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: null context");
+        if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: albedo_floor must be finite and > 0");
+        return reprojectImage(c, "pt_reproject_frame", false, max_history, depth_tol, normal_tol, flags, albedo_floor, n);
+    });
 }
 
 // ---- include/pt_reproject_through.h
@@ -538,30 +508,24 @@ namespace {
 int motionMark(pt_ctx* c) {
     int rc;
     if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_motion_mark"))) return rc;
-    if (c->multi) { if ((rc = multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); }))) return rc; }
-    else if ((rc = pt_synchronize(c))) return rc;                 // all submitted work lands first
+    if ((rc = syncAll(c))) return rc;                             // all submitted work lands first
     pt_ctx* on = firstStream(c);
     const pt_ctx::Cam h = on->cam[on->curImage];
     if (!h.valid) return fail(PT_ERR_ARG, "pt_motion_mark: the current image has no camera (render or pt_write_frame first)");
-    if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_motion_mark: a scene buffer or texture was uploaded since the image's camera was recorded");
-    if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_motion_mark: the image was rendered with DEBUG != 0");
-    if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
-        return fail(PT_ERR_ARG, "pt_motion_mark: the image's camera has Parameters that do not match the image size");
+    if ((rc = usableCamera(c, on, h, "pt_motion_mark"))) return rc;
     on->mark.valid = false;
     // (a) Rh, through the cache pt_reproject_frame keeps, into a buffer that later uploads leave alone
-    if (on->featHValid && std::memcmp(&on->featHIn, &h.in, sizeof(FrameIn)) != 0) on->featHValid = false;
-    if ((rc = ensureFeaturesFor(on, h.in, &on->dFeatH, &on->featHValid))) return rc;
-    on->featHIn = h.in;
+    if ((rc = ensureRecords(on, on->featH, h.in, nullptr, "pt_motion_mark"))) return rc;
     const size_t n = (size_t)c->W * c->H;
-    if (!on->dMarkFeat) HIP_TRY(hipMalloc((void**)&on->dMarkFeat, n * 64));
-    HIP_TRY(hipMemcpyAsync(on->dMarkFeat, on->dFeatH, n * 64, hipMemcpyDeviceToDevice, on->stream));
-    // (b), (c) where the primitives are
     pt_ctx::Mark& m = on->mark;
+    HIP_TRY(m.feat.ensure(n * 64));
+    HIP_TRY(hipMemcpyAsync(m.feat, on->featH.recs, n * 64, hipMemcpyDeviceToDevice, on->stream));
+    // (b), (c) where the primitives are
     motionPositions(on, m.tri, &m.nTri, m.el, &m.nEl);
     std::vector<float4> pt, pe;
     motionPack(m.tri, m.nTri, m.el, m.nEl, nullptr, pt, pe);
-    if ((rc = uploadVec((void**)&on->dMarkTri, pt.data(), pt.size() * 16, on->stream))) return rc;
-    if ((rc = uploadVec((void**)&on->dMarkEl, pe.data(), pe.size() * 16, on->stream))) return rc;
+    HIP_TRY(m.dTri.upload(pt.data(), pt.size() * 16, on->stream));
+    HIP_TRY(m.dEl.upload(pe.data(), pe.size() * 16, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     // (d)
     m.image = on->curImage; m.camWrites = on->camWrites; m.otherGen = on->otherGen;
@@ -577,23 +541,16 @@ int pt_motion_mark(pt_ctx* c) {
 }
 
 int pt_reproject_frame_moved(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
-    if (n_kept) *n_kept = 0;
-    if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: null context");
-    int64_t n = 0;
-    const int rc = reprojectImage(c, "pt_reproject_frame_moved", true, max_history, depth_tol, normal_tol, flags, albedo_floor, &n);
-    if (n_kept) *n_kept = n;
-    return rc;
+    return counted(n_kept, [&](int64_t* n) {
+        if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: null context");
+        return reprojectImage(c, "pt_reproject_frame_moved", true, max_history, depth_tol, normal_tol, flags, albedo_floor, n);
+    });
 }
 
 
 // ---- history validation (include/pt_validate.h): the hold lives on the first stream's context, where the merge runs; a group's image and T travel
 // as they do for the reprojection
 namespace {
-int syncAll(pt_ctx* c) {
-    if (c->multi) return multiRun(*c->multi, [](pt_ctx* k) { return pt_synchronize(k); });
-    return pt_synchronize(c);
-}
-
 int historyHold(pt_ctx* c) {
     int rc;
     if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_history_hold"))) return rc;
@@ -607,11 +564,11 @@ int historyHold(pt_ctx* c) {
     if (!h.valid) return fail(PT_ERR_ARG, "pt_history_hold: the current image has no camera (render or pt_write_frame first)");
     HIP_TRY(hipSetDevice(on->device));
     const size_t n = (size_t)c->W * c->H;
-    if (!on->dHoldFrame) HIP_TRY(hipMalloc((void**)&on->dHoldFrame, n * 16));
-    if (!on->dHoldStats) HIP_TRY(hipMalloc((void**)&on->dHoldStats, n * 16));
+    HIP_TRY(on->hold.frame.ensure(n * 16));
+    HIP_TRY(on->hold.stats.ensure(n * 16));
     on->hold.valid = false;
-    HIP_TRY(hipMemcpyAsync(on->dHoldFrame, frame, n * 16, hipMemcpyDeviceToDevice, on->stream));
-    HIP_TRY(hipMemcpyAsync(on->dHoldStats, stats, n * 16, hipMemcpyDeviceToDevice, on->stream));
+    HIP_TRY(hipMemcpyAsync(on->hold.frame, frame, n * 16, hipMemcpyDeviceToDevice, on->stream));
+    HIP_TRY(hipMemcpyAsync(on->hold.stats, stats, n * 16, hipMemcpyDeviceToDevice, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     auto zero = [](pt_ctx* k) {                                   // the image and T alone: the camera records, camWrites and a mark stay
         HIP_TRY(hipSetDevice(k->device));
@@ -644,25 +601,22 @@ int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t*
         return fail(PT_ERR_ARG, "pt_history_merge: the image's camera no longer has the held frame inputs (a render or pt_write_frame under other inputs)");
     if (hd.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_history_merge: a scene buffer or texture was uploaded since the hold");
     FrameIn cur;
-    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
-    const float* P = on->params.data();
-    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
-    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, "pt_history_merge: DEBUG != 0 renders the traversal heat map, which has no surfaces to compare on");
+    if ((rc = usableInputs(c, on, "pt_history_merge", "compare on", cur))) return rc;
     ValidateJob j;
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_history_merge", &on, &j.frame))) return rc;      // a group: gathered on on->stream
     if ((rc = wholeStats(c, on, &j.stats))) return rc;
     if (!j.stats) return fail(PT_ERR_ARG, "pt_history_merge: the image has no luminance moments");
-    if ((rc = ensureFeatures(on))) return rc;
+    if ((rc = currentRecords(on, nullptr, "pt_history_merge"))) return rc;
     HIP_TRY(hipSetDevice(on->device));
     const size_t n = (size_t)c->W * c->H;
-    if (!on->dRpFrame) HIP_TRY(hipMalloc((void**)&on->dRpFrame, n * 16));
-    if (!on->dRpStats) HIP_TRY(hipMalloc((void**)&on->dRpStats, n * 16));
-    if (!on->dRpKept) HIP_TRY(hipMalloc((void**)&on->dRpKept, 8));
-    if (kappaOut && !on->dKappa) HIP_TRY(hipMalloc((void**)&on->dKappa, n * 4));
-    j.feat = on->dFeat; j.heldFrame = on->dHoldFrame; j.heldStats = on->dHoldStats;
+    HIP_TRY(on->dRpFrame.ensure(n * 16));
+    HIP_TRY(on->dRpStats.ensure(n * 16));
+    HIP_TRY(on->dRpKept.ensure(8));
+    if (kappaOut) HIP_TRY(on->dKappa.ensure(n * 4));
+    j.feat = on->feat.recs; j.heldFrame = on->hold.frame; j.heldStats = on->hold.stats;
     j.W = c->W; j.H = c->H; j.radius = r.radius; j.zLo = r.z_lo; j.zHi = r.z_hi; j.normalTol = r.normal_tol;
     j.overlay[0] = cur.mouse[0]; j.overlay[1] = cur.mouse[1]; j.overlay[2] = cur.params[2];
-    j.outFrame = on->dRpFrame; j.outStats = on->dRpStats; j.kappa = kappaOut ? on->dKappa : nullptr; j.reduced = on->dRpKept;
+    j.outFrame = on->dRpFrame; j.outStats = on->dRpStats; j.kappa = kappaOut ? on->dKappa.p : nullptr; j.reduced = on->dRpKept;
     HIP_TRY(validateLaunch(j, on->stream));
     if (kappaOut) HIP_TRY(hipMemcpyAsync(kappaOut, on->dKappa, n * 4, hipMemcpyDeviceToHost, on->stream));
     if ((rc = storeReprojected(c, on, true, nReduced))) return rc;      // (records the same camera again)
@@ -678,17 +632,15 @@ int pt_history_hold(pt_ctx* c) {
 }
 
 int pt_history_merge(pt_ctx* c, const pt_validate_rule* rule, float* kappa_out, int64_t* n_reduced) {
-    if (n_reduced) *n_reduced = 0;
-    if (!c || !rule) return fail(PT_ERR_ARG, "pt_history_merge: null argument");
-    int64_t n = 0;
-    const int rc = historyMerge(c, *rule, kappa_out, &n);
-    if (n_reduced) *n_reduced = n;
-    return rc;
+    return counted(n_reduced, [&](int64_t* n) {
+        if (!c || !rule) return fail(PT_ERR_ARG, "pt_history_merge: null argument");
+        return historyMerge(c, *rule, kappa_out, n);
+    });
 }
 
 
 // ---- adaptive sampling steered by the guided filter (include/pt_steer.h).  The selection needs the whole image (the filter's plumbing: wholeFrame,
-// wholeStats, ensureFeatures on the first stream's context); the render takes each stream's own pixels from the W*H-byte mask.
+// wholeStats, currentRecords on the first stream's context); the render takes each stream's own pixels from the W*H-byte mask.
 namespace {
 size_t maskBytes(const pt_ctx* c) { return ((size_t)c->W * c->H + 3) & ~(size_t)3; }      // the active count follows, 4-byte aligned
 
@@ -712,17 +664,17 @@ int selectGuided(pt_ctx* c, const pt_guided_rule& r, float floorA, const char* w
     int rc;
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &j.frame))) return rc;
     if ((rc = wholeStats(c, on, &j.stats))) return rc;
-    if ((rc = ensureFeatures(on))) return rc;                     // (Parameters, ORIGIN and ROTATION are set from here on)
+    if ((rc = currentRecords(on, nullptr, who))) return rc;       // (Parameters, ORIGIN and ROTATION are set from here on)
     HIP_TRY(hipSetDevice(on->device));
     if ((rc = ensureFilterScratch(on))) return rc;
-    if (!on->dSelMask) HIP_TRY(hipMalloc((void**)&on->dSelMask, maskBytes(on) + 4));
+    HIP_TRY(on->dSelMask.ensure(maskBytes(on) + 4));
     if (!j.stats) {
         HIP_TRY(hipMemsetAsync(on->dDnOut, 0, (size_t)c->W * c->H * 16, on->stream));
         j.stats = on->dDnOut;
     }
     unsigned* count = reinterpret_cast<unsigned*>(on->dSelMask + maskBytes(on));
     const AdaptRule ovr = withOverlay(on, AdaptRule{});
-    j.feat = on->dFeat; j.W = c->W; j.H = c->H; j.iterations = r.iterations; j.minFrames = r.min_frames; j.floorA = floorA;
+    j.feat = on->feat.recs; j.W = c->W; j.H = c->H; j.iterations = r.iterations; j.minFrames = r.min_frames; j.floorA = floorA;
     j.sigma[0] = r.sigma_lum; j.sigma[1] = r.sigma_normal; j.sigma[2] = r.sigma_depth; j.sigma[3] = r.sigma_albedo;
     j.col0 = on->dDnCol[0]; j.col1 = on->dDnCol[1]; j.guide = on->dDnGuide;
     j.mask = on->dSelMask; j.count = count; j.maxFrames = r.max_frames; j.relErr = r.rel_err; j.absErr = r.abs_err;
@@ -741,7 +693,7 @@ int selectGuided(pt_ctx* c, const pt_guided_rule& r, float floorA, const char* w
 int renderMask(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const uint8_t* hostMask, const char* who, int64_t* nActive) {
     return renderSelected(c, firstFrame, nFrames, seeds, who, [c, hostMask](hipStream_t s, int nb) {
         if (hostMask) {
-            if (!c->dSelMask) HIP_TRY(hipMalloc((void**)&c->dSelMask, maskBytes(c) + 4));
+            HIP_TRY(c->dSelMask.ensure(maskBytes(c) + 4));
             HIP_TRY(hipMemcpyAsync(c->dSelMask, hostMask, (size_t)c->W * c->H, hipMemcpyHostToDevice, s));
         }
         hipLaunchKernelGGL(k_adaptive_select_mask, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, (const unsigned char*)c->dSelMask,
@@ -822,7 +774,7 @@ int pt_render_adaptive_guided_demod(pt_ctx* c, int first_frame, int n_frames, co
 namespace {
 int renderLattice(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, int stride, int phaseX, int phaseY, int64_t* nActive) {
     return renderSelected(c, firstFrame, nFrames, seeds, "pt_render_interleaved", [=](hipStream_t s, int nb) {
-        if (!c->dSelMask) HIP_TRY(hipMalloc((void**)&c->dSelMask, maskBytes(c) + 4));
+        HIP_TRY(c->dSelMask.ensure(maskBytes(c) + 4));
         const int n = c->W * c->H;
         hipLaunchKernelGGL(k_lattice_mask, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, c->dSelMask, c->W, n, stride, phaseX, phaseY);
         hipLaunchKernelGGL(k_adaptive_select_mask, dim3(nb), dim3(BLOCK), 0, s, (const unsigned*)c->dPixXY, c->nLocal, c->W, (const unsigned char*)c->dSelMask,
@@ -884,8 +836,8 @@ int pt_read_features_through(pt_ctx* c, const pt_through_rule* rule, float* out)
     int rc;
     if ((rc = checkThrough(rule, "pt_read_features_through"))) return rc;
     pt_ctx* on = firstStream(c);
-    if ((rc = ensureThrough(on, *rule, "pt_read_features_through"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->dThru, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
+    if ((rc = currentRecords(on, rule, "pt_read_features_through"))) return rc;
+    HIP_TRY(hipMemcpy(out, on->thru.recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -894,8 +846,8 @@ int pt_read_through_rays(pt_ctx* c, const pt_through_rule* rule, float* out) {
     int rc;
     if ((rc = checkThrough(rule, "pt_read_through_rays"))) return rc;
     pt_ctx* on = firstStream(c);
-    if ((rc = ensureThrough(on, *rule, "pt_read_through_rays"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->dThruRays, (size_t)c->W * c->H * 32, hipMemcpyDeviceToHost));
+    if ((rc = currentRecords(on, rule, "pt_read_through_rays"))) return rc;
+    HIP_TRY(hipMemcpy(out, on->thru.rays, (size_t)c->W * c->H * 32, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -88,16 +88,17 @@ struct MultiCtx {
     int shardBase = 0, shardTotal = 0;  // they are shards shardBase .. shardBase+n-1 of shardTotal (== n: the whole image)
     std::vector<int> devices;           // per stream; equal entries adjacent
     std::vector<pt_ctx*> kids;
-    struct Run { int device, first, count; float4* staging; };      // the streams of one device
+    struct Run { int device, first, count; };      // the streams of one device
     std::vector<Run> runs;
+    std::vector<Dev<float4>> staging;   // per run, on its device: its streams' accumulators side by side (several devices only)
     bool useRccl = false;               // more than one distinct device (or PT_MULTI_FORCE_RCCL=1: the RCCL call path on a one-GPU box)
     bool virtualDevices = false;        // test mode PT_MULTI_VIRTUAL_DEVICES: the runs share one GPU, the transport between them is device copies
     std::vector<std::unique_ptr<Worker>> workers;
     std::vector<ncclComm_t> comms;      // one per run
     std::vector<hipEvent_t> ev;         // per stream: "this shard's image is complete"; ev[run.first] doubles as "the copies have read it"
-    float4* dGathered = nullptr;        // on devices[0]: n * nSlots packed accumulators, shard-major (what the gather delivers)
-    float4* dFull = nullptr;            // on devices[0]: W * H, un-tiled (whole-image groups)
-    int* dAllMaps = nullptr;            // on devices[0]: packed slot -> global pixel, -1 = padding
+    Dev<float4> dGathered;              // on devices[0]: n * nSlots packed accumulators, shard-major (what the gather delivers)
+    Dev<float4> dFull;                  // on devices[0]: W * H, un-tiled (whole-image groups)
+    Dev<int> dAllMaps;                  // on devices[0]: packed slot -> global pixel, -1 = padding
     std::vector<int32_t> maps;          // the same on the host (pt_read_frame of a partial group)
     bool gatherReady = false;           // the buffers above exist (allocated by the first gather)
     std::set<int> staleBindings;        // bindings (textures: 1000 + index) whose last upload reached only some of the streams: no render until repeated
@@ -142,9 +143,9 @@ void multiFree(pt_ctx* g) {
     for (auto& w : M->workers) if (w) { { std::lock_guard<std::mutex> lk(w->m); w->quit = true; w->cv.notify_all(); } if (w->th.joinable()) w->th.join(); }
     if (!M->devices.empty()) hipSetDevice(M->devices[0]);
     for (hipEvent_t e : M->ev) if (e) hipEventDestroy(e);
-    for (void* p : {(void*)M->dGathered, (void*)M->dFull, (void*)M->dAllMaps}) if (p) hipFree(p);
-    for (auto& r : M->runs) if (r.staging) { hipSetDevice(r.device); hipFree(r.staging); }
-    delete M;
+    for (size_t r = 0; r < M->staging.size(); r++) { hipSetDevice(M->runs[r].device); M->staging[r].release(); }
+    if (!M->devices.empty()) hipSetDevice(M->devices[0]);
+    delete M;                           // (with the gather buffers on devices[0])
     g->multi = nullptr;
 }
 
@@ -166,13 +167,13 @@ int multiGather(pt_ctx* g, int age, float4** out) {
     }
     HIP_TRY(hipSetDevice(M.devices[0]));
     if (!M.gatherReady) {                  // first gather: its buffers.  A failure half-way leaves gatherReady false: the next call starts over
-        for (float4** p : {&M.dGathered, &M.dFull}) if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; }
-        if (M.dAllMaps) { HIP_TRY(hipFree(M.dAllMaps)); M.dAllMaps = nullptr; }
-        HIP_TRY(hipMalloc((void**)&M.dGathered, total * 16));
+        HIP_TRY(M.dFull.release());
+        HIP_TRY(M.dAllMaps.release());
+        HIP_TRY(M.dGathered.reset(total * 16));
         if ((rc = shardMaps(g->W, g->H, M.shardBase, M.n, M.shardTotal, nSlots, M.maps))) return rc;
         if (M.shardTotal == M.n) {
-            HIP_TRY(hipMalloc((void**)&M.dFull, (size_t)g->W * g->H * 16));
-            HIP_TRY(hipMalloc((void**)&M.dAllMaps, total * 4));
+            HIP_TRY(M.dFull.reset((size_t)g->W * g->H * 16));
+            HIP_TRY(M.dAllMaps.reset(total * 4));
             HIP_TRY(hipMemcpy(M.dAllMaps, M.maps.data(), total * 4, hipMemcpyHostToDevice));
         }
         if (M.ev.empty()) M.ev.assign(M.n, nullptr);
@@ -182,12 +183,13 @@ int multiGather(pt_ctx* g, int age, float4** out) {
     }
     // 1. per device: its streams' accumulators side by side, on the device's first stream (one stream: nothing to copy).  Without RCCL
     //    (one device) the block IS the gathered buffer.
-    for (auto& run : M.runs) {
+    for (size_t ri = 0; ri < M.runs.size(); ri++) {
+        const auto& run = M.runs[ri];
         if (run.count == 1 && M.useRccl) continue;
         HIP_TRY(hipSetDevice(run.device));
         pt_ctx* lead = M.kids[run.first];
-        float4* dst = M.useRccl ? run.staging : M.dGathered + (size_t)run.first * nSlots;
-        if (M.useRccl && !dst) { HIP_TRY(hipMalloc((void**)&run.staging, (size_t)run.count * nSlots * 16)); dst = run.staging; }
+        if (M.useRccl) HIP_TRY(M.staging[ri].ensure((size_t)run.count * nSlots * 16));
+        float4* dst = M.useRccl ? M.staging[ri].p : M.dGathered + (size_t)run.first * nSlots;
         for (int j = 0; j < run.count; j++) {
             const int i = run.first + j;
             if (j > 0) { HIP_TRY(hipEventRecord(M.ev[i], M.kids[i]->stream)); HIP_TRY(hipStreamWaitEvent(lead->stream, M.ev[i], 0)); }
@@ -214,7 +216,7 @@ int multiGather(pt_ctx* g, int age, float4** out) {
             const auto& run = M.runs[r];
             // every exit from inside the group closes it: an open group would swallow the next call's collectives
             { const hipError_t he = hipSetDevice(run.device); if (he != hipSuccess) { if (!M.virtualDevices) g_rccl.GroupEnd(); return fail(PT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(he)); } }
-            const float4* send = run.count == 1 ? img[run.first] : run.staging;
+            const float4* send = run.count == 1 ? img[run.first] : M.staging[r].p;
             // recvbuff matters on the root only; the other ranks pass a valid local pointer that is never written
             void* const recv = r == 0 ? (void*)M.dGathered : (void*)send;
             const size_t floats = (size_t)run.count * nSlots * 4;
@@ -222,7 +224,7 @@ int multiGather(pt_ctx* g, int age, float4** out) {
             if (M.virtualDevices) {
                 // what ncclGather does with these arguments, by device copies: rank r's block lands at r * count in the root's receive buffer,
                 // and the root's stream continues once every block has arrived
-                hipError_t he = hipMemcpyAsync((float*)M.dGathered + r * floats, send, floats * 4, hipMemcpyDeviceToDevice, strm);
+                hipError_t he = hipMemcpyAsync((float*)M.dGathered.p + r * floats, send, floats * 4, hipMemcpyDeviceToDevice, strm);
                 if (he == hipSuccess && r > 0) { he = hipEventRecord(M.ev[run.first], strm); if (he == hipSuccess) he = hipStreamWaitEvent(root->stream, M.ev[run.first], 0); }
                 if (he != hipSuccess) return fail(PT_ERR_HIP, std::string("virtual-device gather: ") + hipGetErrorString(he));
                 (void)recv;
