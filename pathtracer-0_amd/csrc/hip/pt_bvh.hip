@@ -22,6 +22,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "../../../include/pt_api.h"
+#include "pt_devmem.hpp"
 
 #include <cstdint>
 #include <cstring>
@@ -287,8 +288,11 @@ __global__ void k_emit(const Node* nodes, int nNodes, const int* leafScan, doubl
 #define BVH_TRY(x)                                                                                     \
     do {                                                                                               \
         hipError_t e_ = (x);                                                                           \
-        if (e_ != hipSuccess) { rc = pt_set_error_(PT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); goto done; } \
+        if (e_ != hipSuccess) return pt_set_error_(PT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// the build's own stream; declared before the device memory, so destroyed after that is freed
+struct StreamOwner { hipStream_t s = nullptr; ~StreamOwner() { if (s) hipStreamDestroy(s); } };
 
 }  // namespace
 
@@ -296,35 +300,33 @@ extern "C" int pt_build_bvh(int device, const double* tri9, int64_t n_tris, int3
                             int32_t* node_leaf, int32_t* leaf_tris, int32_t* max_depth) {
     if (!tri9 || !n_nodes || !node_bounds || !node_links || !node_leaf || !leaf_tris || n_tris < 1 || n_tris > (1ll << 30))
         return pt_set_error_(PT_ERR_ARG, "pt_build_bvh: bad argument");
-    int rc = PT_OK;
     const int n = (int)n_tris;
     const int maxNodes = 2 * n;                 // a full binary tree over at most n leaves
     const int maxLarge = n / SMALL + 2, maxChunks = n / CHUNK + maxLarge + 2;
-    double* dTri = nullptr; int *dIdx[2] = {nullptr, nullptr}, *dNodeOf[2] = {nullptr, nullptr}, *dFlags = nullptr, *dScan = nullptr, *dLeafStart = nullptr;
-    Node* dNodes = nullptr; u64 *dBins = nullptr, *dRootKeys = nullptr; Lists* dL = nullptr; int *dLarge[2] = {nullptr, nullptr}, *dSmall = nullptr, *dCounts = nullptr;
-    int2* dChunk[2] = {nullptr, nullptr};
-    void* dTemp = nullptr; size_t tempBytes = 0;
-    double* dOutB = nullptr; int32_t *dOutLinks = nullptr, *dOutLeaf = nullptr;
-    hipStream_t s = nullptr;
+    StreamOwner stream;
+    Dev<double> dTri, dOutB; Dev<int> dIdx[2], dNodeOf[2], dFlags, dScan, dLeafStart, dLarge[2], dSmall, dCounts;      // (the pairs: ping-pong by level)
+    Dev<Node> dNodes; Dev<u64> dBins, dRootKeys; Dev<Lists> dL; Dev<int2> dChunk[2]; Dev<unsigned char> dTemp; Dev<int32_t> dOutLinks, dOutLeaf;
+    size_t tempBytes = 0;
     Lists h; int counts[2]; int cur = 0, level = 0, nLarge = 0, nChunk = 0;
     const int gridN = (n + 255) / 256;
     u64 rk[6] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull};
 
     BVH_TRY(hipSetDevice(device));
-    BVH_TRY(hipStreamCreate(&s));
-    BVH_TRY(hipMalloc((void**)&dTri, (size_t)n * 72));
+    BVH_TRY(hipStreamCreate(&stream.s));
+    const hipStream_t s = stream.s;
+    BVH_TRY(dTri.reset((size_t)n * 72));
     for (int k = 0; k < 2; k++) {
-        BVH_TRY(hipMalloc((void**)&dIdx[k], (size_t)n * 4)); BVH_TRY(hipMalloc((void**)&dNodeOf[k], (size_t)n * 4));
-        BVH_TRY(hipMalloc((void**)&dLarge[k], (size_t)maxLarge * 4)); BVH_TRY(hipMalloc((void**)&dChunk[k], (size_t)maxChunks * 8));
+        BVH_TRY(dIdx[k].reset((size_t)n * 4)); BVH_TRY(dNodeOf[k].reset((size_t)n * 4));
+        BVH_TRY(dLarge[k].reset((size_t)maxLarge * 4)); BVH_TRY(dChunk[k].reset((size_t)maxChunks * 8));
     }
-    BVH_TRY(hipMalloc((void**)&dFlags, (size_t)(n + 1) * 4)); BVH_TRY(hipMalloc((void**)&dScan, (size_t)(n + 1) * 4));
-    BVH_TRY(hipMalloc((void**)&dLeafStart, (size_t)(n + 1) * 4));
-    BVH_TRY(hipMalloc((void**)&dNodes, (size_t)maxNodes * sizeof(Node)));
-    BVH_TRY(hipMalloc((void**)&dBins, (size_t)maxLarge * 126 * 8));
-    BVH_TRY(hipMalloc((void**)&dRootKeys, 48)); BVH_TRY(hipMalloc((void**)&dL, sizeof(Lists))); BVH_TRY(hipMalloc((void**)&dSmall, (size_t)(n + 2) * 4));
-    BVH_TRY(hipMalloc((void**)&dCounts, 8));
-    BVH_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tempBytes, dFlags, dScan, n + 1, s));
-    BVH_TRY(hipMalloc(&dTemp, tempBytes));
+    BVH_TRY(dFlags.reset((size_t)(n + 1) * 4)); BVH_TRY(dScan.reset((size_t)(n + 1) * 4));
+    BVH_TRY(dLeafStart.reset((size_t)(n + 1) * 4));
+    BVH_TRY(dNodes.reset((size_t)maxNodes * sizeof(Node)));
+    BVH_TRY(dBins.reset((size_t)maxLarge * 126 * 8));
+    BVH_TRY(dRootKeys.reset(48)); BVH_TRY(dL.reset(sizeof(Lists))); BVH_TRY(dSmall.reset((size_t)(n + 2) * 4));
+    BVH_TRY(dCounts.reset(8));
+    BVH_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tempBytes, dFlags.p, dScan.p, n + 1, s));
+    BVH_TRY(dTemp.reset(tempBytes));
     BVH_TRY(hipMemcpyAsync(dTri, tri9, (size_t)n * 72, hipMemcpyHostToDevice, s));
     BVH_TRY(hipMemcpyAsync(dRootKeys, rk, 48, hipMemcpyHostToDevice, s));
     BVH_TRY(hipMemsetAsync(dL, 0, sizeof(Lists), s));
@@ -334,17 +336,17 @@ extern "C" int pt_build_bvh(int device, const double* tri9, int64_t n_tris, int3
     BVH_TRY(hipMemcpyAsync(counts, dCounts, 8, hipMemcpyDeviceToHost, s));
     BVH_TRY(hipMemcpyAsync(&h, dL, sizeof(Lists), hipMemcpyDeviceToHost, s));
     BVH_TRY(hipStreamSynchronize(s));
-    if (h.hasNaN) { rc = pt_set_error_(PT_ERR_SCENE, "pt_build_bvh: NaN coordinate (build this object with the CPU builder)"); goto done; }
+    if (h.hasNaN) return pt_set_error_(PT_ERR_SCENE, "pt_build_bvh: NaN coordinate (build this object with the CPU builder)");
     nLarge = counts[0]; nChunk = counts[1];
     // ---- level loop over the nodes that are still larger than SMALL (one host look per level)
     while (nLarge > 0) {
-        if (level > MAX_BVH_BRANCHES + 2) { rc = pt_set_error_(PT_ERR_HIP, "pt_build_bvh: level loop did not terminate (internal error)"); goto done; }
+        if (level > MAX_BVH_BRANCHES + 2) return pt_set_error_(PT_ERR_HIP, "pt_build_bvh: level loop did not terminate (internal error)");
         hipLaunchKernelGGL(k_clear_bins, dim3((nLarge * 126 + 255) / 256), dim3(256), 0, s, dBins, nLarge);
         hipLaunchKernelGGL(k_bin_large, dim3(nChunk), dim3(256), 0, s, dTri, dIdx[cur], dNodes, dLarge[cur], dChunk[cur], dBins);
         hipLaunchKernelGGL(k_eval_large, dim3((nLarge + 63) / 64), dim3(64), 0, s, dNodes, dLarge[cur], nLarge, dBins, level, dL, dLarge[cur ^ 1], dChunk[cur ^ 1],
                            dSmall, dLeafStart);
         hipLaunchKernelGGL(k_flags, dim3(gridN), dim3(256), 0, s, dTri, dIdx[cur], dNodeOf[cur], dNodes, n, level, dFlags);
-        BVH_TRY(hipcub::DeviceScan::ExclusiveSum(dTemp, tempBytes, dFlags, dScan, n + 1, s));
+        BVH_TRY(hipcub::DeviceScan::ExclusiveSum(dTemp.p, tempBytes, dFlags.p, dScan.p, n + 1, s));
         hipLaunchKernelGGL(k_scatter, dim3(gridN), dim3(256), 0, s, dIdx[cur], dNodeOf[cur], dNodes, n, level, dFlags, dScan, dIdx[cur ^ 1], dNodeOf[cur ^ 1]);
         BVH_TRY(hipMemcpyAsync(&h, dL, sizeof(Lists), hipMemcpyDeviceToHost, s));
         BVH_TRY(hipStreamSynchronize(s));
@@ -358,13 +360,11 @@ extern "C" int pt_build_bvh(int device, const double* tri9, int64_t n_tris, int3
         BVH_TRY(hipMemcpyAsync(&h, dL, sizeof(Lists), hipMemcpyDeviceToHost, s));
         BVH_TRY(hipStreamSynchronize(s));
     }
-    if (h.rootFailed) {
-        rc = pt_set_error_(PT_ERR_SCENE, "BVH root could not be split by any candidate plane (reference: IndexOutOfBoundsException at dispatch.java:1644, SURVEY Q-16)");
-        goto done;
-    }
+    if (h.rootFailed)
+        return pt_set_error_(PT_ERR_SCENE, "BVH root could not be split by any candidate plane (reference: IndexOutOfBoundsException at dispatch.java:1644, SURVEY Q-16)");
     // ---- DFS pre-order ids from the leaf prefix sum; outputs
-    BVH_TRY(hipcub::DeviceScan::ExclusiveSum(dTemp, tempBytes, dLeafStart, dScan, n + 1, s));
-    BVH_TRY(hipMalloc((void**)&dOutB, (size_t)h.nodeCount * 48)); BVH_TRY(hipMalloc((void**)&dOutLinks, (size_t)h.nodeCount * 8)); BVH_TRY(hipMalloc((void**)&dOutLeaf, (size_t)h.nodeCount * 8));
+    BVH_TRY(hipcub::DeviceScan::ExclusiveSum(dTemp.p, tempBytes, dLeafStart.p, dScan.p, n + 1, s));
+    BVH_TRY(dOutB.reset((size_t)h.nodeCount * 48)); BVH_TRY(dOutLinks.reset((size_t)h.nodeCount * 8)); BVH_TRY(dOutLeaf.reset((size_t)h.nodeCount * 8));
     hipLaunchKernelGGL(k_emit, dim3((h.nodeCount + 255) / 256), dim3(256), 0, s, dNodes, h.nodeCount, dScan, dOutB, dOutLinks, dOutLeaf);
     BVH_TRY(hipMemcpyAsync(node_bounds, dOutB, (size_t)h.nodeCount * 48, hipMemcpyDeviceToHost, s));
     BVH_TRY(hipMemcpyAsync(node_links, dOutLinks, (size_t)h.nodeCount * 8, hipMemcpyDeviceToHost, s));
@@ -374,12 +374,5 @@ extern "C" int pt_build_bvh(int device, const double* tri9, int64_t n_tris, int3
     BVH_TRY(hipGetLastError());
     *n_nodes = h.nodeCount;
     if (max_depth) *max_depth = h.maxDepth;
-done:
-    {
-        void* ptrs[] = {dTri, dIdx[0], dIdx[1], dNodeOf[0], dNodeOf[1], dLarge[0], dLarge[1], dChunk[0], dChunk[1], dFlags, dScan, dLeafStart, dNodes, dBins,
-                        dRootKeys, dL, dSmall, dCounts, dTemp, dOutB, dOutLinks, dOutLeaf};
-        for (void* p : ptrs) if (p) hipFree(p);
-        if (s) hipStreamDestroy(s);
-    }
-    return rc;
+    return PT_OK;
 }

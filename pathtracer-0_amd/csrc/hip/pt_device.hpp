@@ -7,6 +7,7 @@
 //   sample set-up in main :894-910, bgCol :235-242, index stack :136-158.
 #pragma once
 #include "pt_math.hpp"
+#include "pt_scene_records.hpp"
 
 namespace ptd {
 using namespace pm;
@@ -29,22 +30,7 @@ using namespace pm;
 //  shading rec = 4 x float4 (64 B) indexed by triangle id: n1, n2, vt1, vt2, vt3, material
 //                (the part of the 160-B reference triangle that only the winning hit needs).
 // ------------------------------------------------------------------------------------------------
-constexpr int REF_EMPTY = (int)0x80000000;
-constexpr int PRIM_NONE = -1;
-constexpr int PRIM_ELLIPSOID = 0x40000000;
-
-struct ObjRoot { float bmin[3]; float bmax[3]; int ref; int pad; };           // 32 B
-struct EllipRec {                                                                // frag.glsl:606-631
-    float c[3], st[3], r; int mat; int rotated; float rot[3]; float R[9]; float RB[9]; float pad[2];
-};
-struct MatRec {                                                                  // the mtl fields trace()/chooseRay()/directDiffuse() read
-    float Kd[3], Ks[3], Ke[3], Tf[3]; float Tr, Ni, Density, Pm, Pr, Pc, Pcr, subsurface; int illum;
-    float Ka[3], ssColor[3], ssRadius[3];                                        // only directDiffuse (frag.glsl:661-675)
-    int hasMaps;                                                                 // any of the map_* below > -1
-    int map_Ka, map_Kd, map_Ks, map_Ke, map_Tr, map_Pm, map_Pr, map_Pc, map_norm; // texture indices (mapMtl :210-225, :827); -1 = none
-    int niCode;                                                                  // Ni as an entry of the scene's refraction-index dictionary (DevScene::ni8 / niTable)
-};                                                                               // 41 dwords = 164 B
-struct TexRec { const uchar4* data; int w, h; };                                 // one entry of the bindless table (binding 15), RGBA8 texels as uploaded
+// REF_EMPTY, PRIM_*, ObjRoot, EllipRec, MatRec, TexRec: pt_scene_records.hpp (the host-only layout step builds them too)
 
 struct FrameConst {            // uniform per batch; written by k_frame_setup
     float screenSize, focalLength, resolution, screenHratio, SAMPLE_RES, MAX_BOUNCES, BLUR, FOCAL_DISTANCE, AUTO_FOCUS;

@@ -38,6 +38,7 @@
 #include "../../../include/pt_reproject_through.h"
 #include "pt_device.hpp"
 #include "pt_devmem.hpp"
+#include "pt_scene_layout.hpp"
 #include "pt_image_launch.hpp"
 
 #include <algorithm>
@@ -53,6 +54,7 @@
 #include <vector>
 
 using namespace ptd;
+using namespace ptl;
 
 namespace {
 
@@ -65,16 +67,12 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
     } while (0)
 
 constexpr int BLOCK = 256;
+static_assert(BLOCK == EXTEND_BLOCK, "the layout sizes the LDS tile beside one traversal stack per lane of a block");
 #ifndef SHADE_BLOCK_SIZE
 #define SHADE_BLOCK_SIZE 256
 #endif
 constexpr int SHADE_BLOCK = SHADE_BLOCK_SIZE;     // threads per block of the shading kernel: one scheduler atomic per block per launch
 constexpr int TILE_W = 32, TILE_H = 8;
-// a BVH whose inner-node records exceed this many bytes (in the 80-B form) makes the hand-written intersect kernel use the 64-B form: what an XCD's 4 MB
-// L2 holds beside the triangles and the path state streaming through it (measured: profiles/r04_d_node_record_layout.txt)
-#ifndef ASM_NODES_80B_LIMIT
-#define ASM_NODES_80B_LIMIT (2 << 20)
-#endif
 
 // Path-state accesses stream through the caches once per launch — hundreds of MB per launch through 4 MB of L2 per XCD — while the OTHER stream's intersect
 // kernel lives on the BVH's node and triangle lines staying there: every access of a state group (and of the per-frame colour rows) carries the non-temporal
@@ -1228,12 +1226,7 @@ struct pt_ctx {
     // spatial partition (pt_set_option 21, an experiment: profiles/r06_c_cu_partition.txt): the intersect launches on a stream whose CU mask holds cuPartition eighths of
     // every XCD's CUs, the shading launches on the complement; events order extend(i) -> shade(i) -> extend(i+1), everything else stays on `stream`
     int cuPartition = 0, cuPartitionBuilt = 0; hipStream_t sExt = nullptr, sShade = nullptr; hipEvent_t evExt = nullptr, evShade = nullptr, evHost = nullptr;
-    // raw SSBO contents (host copies, glBufferData semantics)
-    std::vector<float> origin, rotation, mouse, tris, params, imp, ellip, bvhdata, mtl;
-    std::vector<int32_t> bvhtree, leaftris, objidx;
-    std::vector<uint8_t> sky; int skyW = 0, skyH = 0;
-    struct HostTex { std::vector<uint8_t> rgba; int w = 0, h = 0; };
-    std::vector<HostTex> textures;          // bindless table beyond the sky (index 0 mirrors `sky`)
+    SceneBuffers buf;               // raw SSBO contents and textures (host copies, glBufferData semantics): what layoutScene reads
     Dev<uchar4> dTexels; Dev<TexRec> dTexTable;      // all textures beyond the sky in one allocation + the bindless-style table
     bool sceneDirty = true, frameInDirty = true;
     bool trans = false, anySubsurface = false, ambiguousTriObj = false, anyMaps = false, ellipMaps = false; Dev<int> dTriObj;
@@ -1353,315 +1346,48 @@ size_t shardSlots(int W, int H, int count) {
     return (mx + BLOCK - 1) / BLOCK * BLOCK;
 }
 
-// Validates the reference's buffers and builds the device-private layout (see pt_device.hpp).
+// The scene build's device half: lays the buffers out on the host (layoutScene, pt_scene_layout.hpp), uploads the arrays, wires DevScene, and only then
+// takes the layout's flags and modes into the context: a refused scene leaves the context as it was (sceneDirty stays set).
 int buildScene(pt_ctx* c) {
-    size_t nTris = c->tris.size() / 40, nNodes = c->bvhtree.size() / 3;
-    if (c->params.size() < 12) return fail(PT_ERR_SCENE, "Parameters buffer (binding 4) must hold 12 floats");
-    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_SCENE, "ORIGIN/ROTATION (bindings 0,1) not set");
-    if (c->mouse.size() < 3) return fail(PT_ERR_SCENE, "MOUSE_POS (binding 2) not set");
-    if (c->mtl.empty()) return fail(PT_ERR_SCENE, "mtlData (binding 14) not set");
-    if (c->objidx.empty()) return fail(PT_ERR_SCENE, "objIndices (binding 13) not set");
-    // Implicit surfaces: the reference loops over them (frag.glsl:578-605) and rayImplicit returns 1e30 before anything else (:385-386), so `t < closest_t` never passes —
-    // they are never hit and leave no trace in the image.  The buffer is accepted as the reference's scene code sends it (dispatch.java:429-456) and otherwise unread.
-    if (c->imp.empty() || !(c->imp[0] >= 0.0f)) return fail(PT_ERR_SCENE, "ImpData (binding 5) not set: [count, fn x n, shift x 3n, scale x 3n, rot x 3n, mat x n]; send [0] for none");
-    if (c->ellip.empty()) return fail(PT_ERR_SCENE, "EllipData (binding 7) not set");
-    if (c->sky.empty()) return fail(PT_ERR_SCENE, "texture 0 (sky) not set");
-    if (c->bvhdata.size() < 8 * nNodes) return fail(PT_ERR_SCENE, "BVHdata shorter than 8 floats per BVHtree node");
-    // materials
-    int me = (int)c->mtl[0];
-    if (me < 48) return fail(PT_ERR_SCENE, "mtlData[0] (floats per material) must be >= 48");
-    int nMat = (int)((c->mtl.size() - 1) / me);
-    std::vector<MatRec> mats(std::max(nMat, 1));
-    c->trans = false; c->anySubsurface = false; c->anyMaps = false;
-    for (int m = 0; m < nMat; m++) {
-        const float* F = c->mtl.data() + (size_t)me * m;      // F[k] == mtlData[me*m + k]
-        MatRec& r = mats[m];
-        // map_* slots of the 48-float record (dispatch.java:295-315): Ka 22, Kd 23, Ks 24, Pm 32, Pr 33, Pc 35, bump/norm 37, Tr 39, Ke 41
-        // (map_Ps 34, map_Pcr 36, map_d 38, map_Ns 40 only change fields the render path never reads)
-        r.map_Ka = (int)F[22]; r.map_Kd = (int)F[23]; r.map_Ks = (int)F[24]; r.map_Pm = (int)F[32]; r.map_Pr = (int)F[33]; r.map_Pc = (int)F[35];
-        r.map_norm = (int)F[37]; r.map_Tr = (int)F[39]; r.map_Ke = (int)F[41];
-        r.hasMaps = 0;
-        for (int idx : {r.map_Ka, r.map_Kd, r.map_Ks, r.map_Ke, r.map_Tr, r.map_Pm, r.map_Pr, r.map_Pc, r.map_norm}) {
-            if (idx <= -1) continue;
-            r.hasMaps = 1;
-            if ((size_t)idx >= c->textures.size() || c->textures[idx].rgba.empty())
-                return fail(PT_ERR_SCENE, "a material names a texture index that was never uploaded with pt_set_texture");
-        }
-        for (int k = 0; k < 3; k++) { r.Kd[k] = F[4 + k]; r.Ks[k] = F[7 + k]; r.Tf[k] = F[13 + k]; r.Ke[k] = F[17 + k]; }
-        r.Tr = F[12]; r.Ni = F[16]; r.Density = F[20]; r.illum = (int)F[21]; r.Pm = F[25]; r.Pr = F[26]; r.Pc = F[28]; r.Pcr = F[29]; r.subsurface = F[42];
-        for (int k = 0; k < 3; k++) { r.Ka[k] = F[1 + k]; r.ssColor[k] = F[43 + k]; r.ssRadius[k] = F[46 + k]; }
-        if (r.Tr > 0.0f || r.Tf[0] > 0.0f || r.illum == 5 || r.illum == 7 || r.map_Tr > -1) c->trans = true;   // (a Tr map can switch transmission on)
-        if (r.subsurface > 0.0f) c->anySubsurface = true;
-        if (r.hasMaps) c->anyMaps = true;
-    }
-    // the refraction-index dictionary (pt_device.hpp, DevScene::ni8): 0.0f, 1.0029f, then every distinct Ni bit pattern among the materials
-    std::vector<float> niDict = {0.0f, 1.0029f};
-    for (int m = 0; m < nMat; m++) {
-        uint32_t bits; std::memcpy(&bits, &mats[m].Ni, 4);
-        int code = -1;
-        for (size_t k = 0; k < niDict.size(); k++) { uint32_t kb; std::memcpy(&kb, &niDict[k], 4); if (kb == bits) { code = (int)k; break; } }
-        if (code < 0) { code = (int)niDict.size(); niDict.push_back(mats[m].Ni); }
-        mats[m].niCode = code;
-    }
-    // (more values than the 8-bit dictionary holds, 0.0 and 1.0029 included: the path state carries the ten floats of the shader's stack themselves, frag.glsl:136-158)
-    c->niBits = !c->trans ? 0 : (niDict.size() > 256 || c->forceNiBits8 == 2) ? 32 : ((niDict.size() <= 8 && !c->forceNiBits8) ? 3 : 8);
-    if (niDict.size() > 256) { niDict.resize(256); for (auto& m : mats) if (m.niCode > 255) m.niCode = 0; }      // (the codes are not read in that form)
-    niDict.resize(std::max<size_t>(niDict.size(), 8), 0.0f);
-    // objects / BVH
-    int numObj = c->objidx[0];
-    if (numObj < 0 || (size_t)numObj + 1 > c->objidx.size()) return fail(PT_ERR_SCENE, "objIndices[0] exceeds the buffer");
-    auto childOf = [&](int n, int side) { return c->bvhtree[3 * (size_t)n + 1 + side]; };
-    std::vector<int> newIdx(nNodes, -1), depth(nNodes, 0), objOf(nNodes, -1);
-    std::vector<int> order;                                     // inner nodes in multi-root BFS order
-    std::vector<char> seen(nNodes, 0);
-    std::vector<int> frontier;
-    auto isLeaf = [&](int n) { return (childOf(n, 0) | childOf(n, 1)) == -1; };   // bitwise OR, frag.glsl:478
-    for (int o = 0; o < numObj; o++) {
-        int r = c->objidx[1 + o];
-        if (r < 0 || (size_t)r >= nNodes) return fail(PT_ERR_SCENE, "objIndices root out of range");
-        if (seen[r]) return fail(PT_ERR_SCENE, "BVH node reachable twice (not a tree)");
-        seen[r] = 1; frontier.push_back(r); objOf[r] = o;
-    }
-    int maxInnerDepth = -1;
-    {
-        std::vector<int> cur = frontier, nxt;
-        int d = 0;
-        while (!cur.empty()) {
-            nxt.clear();
-            for (int n : cur) {
-                depth[n] = d;
-                if (isLeaf(n)) continue;
-                maxInnerDepth = std::max(maxInnerDepth, d);
-                newIdx[n] = (int)order.size(); order.push_back(n);
-                for (int s = 0; s < 2; s++) {
-                    int ch = childOf(n, s);
-                    if (ch < 0 || (size_t)ch >= nNodes) return fail(PT_ERR_SCENE, "BVHtree child index out of range");
-                    if (seen[ch]) return fail(PT_ERR_SCENE, "BVH node reachable twice (not a tree)");
-                    seen[ch] = 1; nxt.push_back(ch); objOf[ch] = objOf[n];
-                }
-            }
-            cur.swap(nxt); d++;
-        }
-    }
-    // Below the top levels (the LDS tile and what every XCD's L2 keeps hot anyway) the records are laid out in depth-first order
-    // instead: a node and its left child are then neighbours, and a subtree's last levels share a few cache lines — a big tree's
-    // deep fetches are what misses L2.  Only the addresses change; which nodes a ray visits, and in which order, does not.
-    if ((size_t)c->bfsNodes < order.size()) {
-        int cut = -1; size_t upTo = 0;                          // deepest level that is still completely inside the BFS prefix
-        for (size_t k = 0; k < order.size(); k++) {
-            if (k + 1 == order.size() || depth[order[k + 1]] != depth[order[k]]) {
-                if (k + 1 <= (size_t)c->bfsNodes) { cut = depth[order[k]]; upTo = k + 1; } else break;
-            }
-        }
-        std::vector<int> reordered(order.begin(), order.begin() + upTo), stack;
-        for (size_t k = upTo; k < order.size() && depth[order[k]] == cut + 1; k++) {
-            stack.assign(1, order[k]);
-            while (!stack.empty()) {
-                int n = stack.back(); stack.pop_back();
-                reordered.push_back(n);
-                int L = childOf(n, 0), R = childOf(n, 1);
-                if (!isLeaf(R)) stack.push_back(R);
-                if (!isLeaf(L)) stack.push_back(L);
-            }
-        }
-        if (reordered.size() != order.size()) return fail(PT_ERR_SCENE, "internal: depth-first relayout lost nodes");
-        order.swap(reordered);
-        for (size_t k = 0; k < order.size(); k++) newIdx[order[k]] = (int)k;
-    }
-    int need = maxInnerDepth + 2;                               // worst-case entries on rayBVH's stack
-    if (need > 64) return fail(PT_ERR_SCENE, "BVH too deep for the reference's `int stack[64]` (frag.glsl:465)");
-    c->stackDepth = std::max(need, 1);
-    // leaf-ordered triangle records
-    std::vector<float4> triRecs; std::vector<int> leafRef(nNodes, REF_EMPTY);
-    std::vector<int> triObj(std::max<size_t>(nTris, 1), -1);      // triangle -> object whose BVH holds it (hit.parentID of frag.glsl:573)
-    c->ambiguousTriObj = false;
-    auto f4 = [](float a, float b, float cc, float d) { return make_float4(a, b, cc, d); };
-    auto asf = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-    for (size_t n = 0; n < nNodes; n++) {
-        if (!seen[n] || !isLeaf((int)n)) continue;
-        int s = (int)c->bvhdata[8 * n + 6], e = (int)c->bvhdata[8 * n + 7];
-        if (e <= s) continue;                                   // empty leaf
-        if (s < 0 || (size_t)e > c->leaftris.size()) return fail(PT_ERR_SCENE, "leaf index range outside leafTriIndices");
-        leafRef[n] = -((int)(triRecs.size() / 3) + 1);
-        for (int i = s; i < e; i++) {
-            int t = c->leaftris[i];
-            if (t < 0 || (size_t)t >= nTris) return fail(PT_ERR_SCENE, "leafTriIndices entry outside the triangle buffer");
-            const float* T = c->tris.data() + 40 * (size_t)t;
-            int mat = (int)T[36];
-            if (mat < 0 || mat >= nMat) return fail(PT_ERR_SCENE, "triangle material index out of range (SURVEY.md Q-14: OBJ faces before any o/g line get -1)");
-            if (triObj[t] == -1) triObj[t] = objOf[n]; else if (triObj[t] != objOf[n]) { triObj[t] = -2; c->ambiguousTriObj = true; }
-            float e1x = T[4] - T[0], e1y = T[5] - T[1], e1z = T[6] - T[2], e2x = T[8] - T[0], e2y = T[9] - T[1], e2z = T[10] - T[2];
-            uint32_t idl = (uint32_t)t | (i == e - 1 ? 0x80000000u : 0u);
-            triRecs.push_back(f4(T[0], T[1], T[2], e1x)); triRecs.push_back(f4(e1y, e1z, e2x, e2y)); triRecs.push_back(f4(e2z, asf(idl), 0, 0));
-        }
-    }
-    auto refOf = [&](int n) { return isLeaf(n) ? leafRef[n] : newIdx[n]; };
-    std::vector<float4> nodeRecs;
-    for (int n : order) {
-        int L = childOf(n, 0), R = childOf(n, 1);
-        const float* A = c->bvhdata.data() + 8 * (size_t)L; const float* B = c->bvhdata.data() + 8 * (size_t)R;
-        nodeRecs.push_back(f4(A[0], B[0], A[1], B[1])); nodeRecs.push_back(f4(A[2], B[2], A[3], B[3])); nodeRecs.push_back(f4(A[4], B[4], A[5], B[5]));
-        nodeRecs.push_back(f4(asf((uint32_t)refOf(L)), asf((uint32_t)refOf(R)), 0, 0));
-    }
-    // The hand-written intersect kernel (pt_extend_gfx950.s) reads its own node records.  80 B: the two references, then per axis (Lmin, Rmin | Lmax,
-    // Rmax | Lmin, Rmin), so that a lane whose direction component is negative starts 8 B further in and receives (near pair, far pair) without a
-    // min / max.  Trees that do not fit the caches pay for those bytes on every node visit (C4: 552 B per segment, the chip at 0.61 of its HBM peak):
-    // they get 64-B records — references, pad, (Lmin, Rmin | Lmax, Rmax) per axis — and the kernel's min/max step (pt_set_option 19 overrides).
-    const size_t nInner = order.size();
-    // (what decides is whether the records the rays walk through fit an XCD's L2 beside the state stream: C4's single 100 k-node tree gains 5 % from the small
-    //  records — and so do C6's 64 trees of 1.5 k nodes, 7.8 MB in all, +6.2 %, since the per-ray cull of the object loop took the 64 root tests per ray out of its
-    //  vector instructions; round 4, before the cull, measured -2 % there and chose by the largest tree: profiles/r04_d_node_record_layout.txt, r05_f_*)
-    const int asmStride = c->asmNodeLayout == 0 ? 80 : c->asmNodeLayout == 1 ? 64 : (nInner * 80 > (size_t)ASM_NODES_80B_LIMIT ? 64 : 80);
-    const int W_ = asmStride / 4;
-    std::vector<float> nodes80(std::max<size_t>(nInner, 1) * W_ + 40, 0.0f);      // (+ 160 B: developer builds of the kernel read behind a record, -DFETCH_EXTRA)
-    bool boxesOrdered = true, anyEmpty = false;
-    for (size_t k = 0; k < nInner; k++) {
-        const int n = order[k], L = childOf(n, 0), R = childOf(n, 1);
-        const float* A = c->bvhdata.data() + 8 * (size_t)L; const float* B = c->bvhdata.data() + 8 * (size_t)R;
-        float* o = nodes80.data() + (size_t)W_ * k;
-        for (int ax = 0; ax < 3; ax++) {
-            float* g = asmStride == 80 ? o + 2 + 6 * ax : o + 4 + 4 * ax;
-            g[0] = A[ax]; g[1] = B[ax]; g[2] = A[3 + ax]; g[3] = B[3 + ax];
-            if (asmStride == 80) { g[4] = A[ax]; g[5] = B[ax]; }
-            if (!(A[ax] <= A[3 + ax]) || !(B[ax] <= B[3 + ax])) boxesOrdered = false;      // min > max or a NaN: only the min/max form of rayBox is right
-        }
-        const int lr = refOf(L), rr = refOf(R);
-        std::memcpy(&o[0], &lr, 4); std::memcpy(&o[1], &rr, 4);
-        if (lr == REF_EMPTY || rr == REF_EMPTY) anyEmpty = true;
-    }
-    c->asmNodeStride = asmStride;
-    std::vector<ObjRoot> roots(std::max(numObj, 8));           // (the hand-written kernel fetches root records in batches of four: at least eight exist)
-    for (int o = 0; o < numObj; o++) {
-        int r = c->objidx[1 + o]; const float* A = c->bvhdata.data() + 8 * (size_t)r;
-        for (int k = 0; k < 3; k++) { roots[o].bmin[k] = A[k]; roots[o].bmax[k] = A[3 + k]; }
-        roots[o].ref = refOf(r); roots[o].pad = 0;
-        // an empty root leaf would be "visited" by the reference and find nothing: it can simply never be pushed
-    }
-    // More than 8 BVHs: the hand-written kernel culls the object loop (frag.glsl:563-577) per ray with ONE pass over at most 64 GROUP boxes at refill
-    // (pt_extend_gfx950.s, .Lmask_loop): group g = objects [g << s, (g + 1) << s), its box the union of their root boxes, appended to the root records.  A ray
-    // that misses a group's box misses every root box in it (boxes of subsets; IEEE subtraction and multiplication are monotone, the ray regular: finite origin,
-    // finite non-zero reciprocal direction), and a BVH whose root box the ray misses contributes nothing: rayBVH would pop the root, find neither child box hit
-    // (children lie inside the root box) and return (:468-472, :521-531) — PROVIDED the root is an inner node whose child boxes lie inside an ordered root box.
-    // A group holding a root that does not promise this (a leaf root: its triangles are tested whatever the box says, :478-520; foreign buffers whose children
-    // stick out) gets the box (-inf, +inf): never culled.  Irregular rays skip the cull in the kernel.
-    c->asmGroupShift = 0;
-    if (numObj > 8) {
-        int sft = 0;
-        while (((numObj + (1 << sft) - 1) >> sft) > 64) sft++;
-        c->asmGroupShift = sft;
-        const int nGroups = (numObj + (1 << sft) - 1) >> sft;
-        const float inf = std::numeric_limits<float>::infinity();
-        std::vector<ObjRoot> groups(64);
-        for (int g = 0; g < 64; g++) { for (int k = 0; k < 3; k++) { groups[g].bmin[k] = inf; groups[g].bmax[k] = -inf; } groups[g].ref = 0; groups[g].pad = 0; }
-        for (int o = 0; o < numObj; o++) {
-            const int r = c->objidx[1 + o]; const float* A = c->bvhdata.data() + 8 * (size_t)r;
-            bool cullable = !isLeaf(r) && !c->asmNoRootCull;
-            for (int k = 0; k < 3 && cullable; k++) {
-                if (!(A[k] <= A[3 + k])) cullable = false;                                      // ordered, no NaN
-                for (int side = 0; side < 2 && cullable; side++) {
-                    const float* Ch = c->bvhdata.data() + 8 * (size_t)childOf(r, side);
-                    // BOTH planes of the child inside the root's range: rayBox takes min / max of the two plane distances (:412-413), so an inverted child
-                    // (min > max) whose `max` lies below the root's min would stick out of the root although its `min` and `max` each pass a one-sided test (NaN: not)
-                    if (!(Ch[k] >= A[k] && Ch[k] <= A[3 + k] && Ch[3 + k] >= A[k] && Ch[3 + k] <= A[3 + k])) cullable = false;
-                }
-            }
-            ObjRoot& G = groups[o >> sft];
-            if (!cullable) G.pad = 1;
-            for (int k = 0; k < 3; k++) { G.bmin[k] = std::min(G.bmin[k], A[k]); G.bmax[k] = std::max(G.bmax[k], A[3 + k]); }
-        }
-        for (int g = 0; g < nGroups; g++) if (groups[g].pad) { for (int k = 0; k < 3; k++) { groups[g].bmin[k] = -inf; groups[g].bmax[k] = inf; } }
-        roots.insert(roots.end(), groups.begin(), groups.end());          // at roots[numObj .. numObj + 64)
-    }
-    std::vector<float4> shade(std::max<size_t>(nTris, 1) * 4);
-    for (size_t t = 0; t < nTris; t++) {
-        const float* T = c->tris.data() + 40 * t;
-        shade[4 * t] = f4(T[12], T[13], T[14], T[16]); shade[4 * t + 1] = f4(T[17], T[18], T[24], T[25]);
-        shade[4 * t + 2] = f4(T[28], T[29], T[32], asf((uint32_t)(int)T[36])); shade[4 * t + 3] = f4(T[33], 0, 0, 0);
-    }
-    // ellipsoids (frag.glsl:606-611 layout)
-    int nE = (int)c->ellip[0];
-    if (nE < 0 || c->ellip.size() < (size_t)1 + 11 * (size_t)nE) return fail(PT_ERR_SCENE, "EllipData shorter than its count says");
-    std::vector<EllipRec> er(std::max(nE, 1));
-    bool ellipMaps = false;
-    for (int i = 0; i < nE; i++) {
-        const float* E = c->ellip.data();
-        EllipRec& r = er[i]; std::memset(&r, 0, sizeof(r));
-        for (int k = 0; k < 3; k++) { r.c[k] = E[1 + 3 * i + k]; r.st[k] = E[1 + nE * 3 + 3 * i + k]; r.rot[k] = E[1 + nE * 6 + 3 * i + k]; }
-        r.r = E[1 + nE * 9 + i]; r.mat = (int)E[1 + nE * 10 + i];
-        if (r.mat < 0 || r.mat >= nMat) return fail(PT_ERR_SCENE, "ellipsoid material index out of range");
-        if (mats[r.mat].hasMaps) ellipMaps = true;               // sampled at the uv of the closest triangle found before the ellipsoid (frag.glsl:574 vs :619-630): State::HX
-    }
-    c->ellipMaps = ellipMaps;
-    // upload
+    LayoutOptions opt;
+    opt.bfsNodes = c->bfsNodes; opt.asmNodeLayout = c->asmNodeLayout; opt.asmNoRootCull = c->asmNoRootCull; opt.forceNiBits8 = c->forceNiBits8;
+    opt.ldsBudget = c->ldsBudget; opt.extendCacheBytes = c->extendCacheBytes; opt.stackModeForce = c->stackModeForce;
+    SceneLayout L; std::string err;
+    if (const int rc = layoutScene(c->buf, opt, L, err)) return fail(rc, err);
+    const SceneBuffers& b = c->buf;
     hipStream_t s = c->stream;
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(c->dNodes.upload(nodeRecs.data(), nodeRecs.size() * 16, s));
-    HIP_TRY(c->dNodes80.upload(nodes80.data(), nodes80.size() * 4, s));
-    HIP_TRY(c->dTris.upload(triRecs.data(), triRecs.size() * 16, s));
-    HIP_TRY(c->dShade.upload(shade.data(), shade.size() * 16, s));
-    HIP_TRY(c->dTriObj.upload(triObj.data(), triObj.size() * 4, s));
-    HIP_TRY(c->dRoots.upload(roots.data(), roots.size() * sizeof(ObjRoot), s));
-    HIP_TRY(c->dEllip.upload(er.data(), er.size() * sizeof(EllipRec), s));
-    HIP_TRY(c->dMats.upload(mats.data(), mats.size() * sizeof(MatRec), s));
-    {   // the view-dependent materials of include/pt_reproject.h: a mirror, clearcoat or transmission lobe in chooseRay (frag.glsl:745-809)
-        std::vector<unsigned char> vd(mats.size(), 0);
-        for (int m = 0; m < nMat; m++) {
-            const MatRec& r = mats[m];
-            vd[m] = (r.Pr != 1.0f || r.Pc != 0.0f || r.Tr > 0.0f || r.Tf[0] > 0.0f || r.illum == 5 || r.illum == 7 || r.map_Pr >= 0 || r.map_Pc >= 0 || r.map_Tr >= 0) ? 1 : 0;
-        }
-        HIP_TRY(c->dMatVD.upload(vd.data(), vd.size(), s));
+    HIP_TRY(c->dNodes.upload(L.nodes.data(), L.nodes.size() * 16, s));
+    HIP_TRY(c->dNodes80.upload(L.nodes80.data(), L.nodes80.size() * 4, s));
+    HIP_TRY(c->dTris.upload(L.tris.data(), L.tris.size() * 16, s));
+    HIP_TRY(c->dShade.upload(L.shade.data(), L.shade.size() * 16, s));
+    HIP_TRY(c->dTriObj.upload(L.triObj.data(), L.triObj.size() * 4, s));
+    HIP_TRY(c->dRoots.upload(L.roots.data(), L.roots.size() * sizeof(ObjRoot), s));
+    HIP_TRY(c->dEllip.upload(L.ellip.data(), L.ellip.size() * sizeof(EllipRec), s));
+    HIP_TRY(c->dMats.upload(L.mats.data(), L.mats.size() * sizeof(MatRec), s));
+    HIP_TRY(c->dMatVD.upload(L.matVD.data(), L.matVD.size(), s));
+    HIP_TRY(c->dSky.upload(b.sky.data(), (size_t)b.skyW * b.skyH * 4, s));
+    HIP_TRY(c->dNiTable.upload(L.niDict.data(), L.niDict.size() * 4, s));
+    // the texture table beyond the sky: ONE allocation and one asynchronous copy for all textures; the table gets its device pointers once dTexels exists
+    HIP_TRY(c->dTexels.upload(L.texels.data(), L.texels.size(), s));
+    std::vector<TexRec> table(L.texOff.size());
+    for (size_t ti = 0; ti < table.size(); ti++) {
+        const bool present = ti > 0 && !b.textures[ti].rgba.empty();
+        table[ti].data = ti == 0 ? (const uchar4*)c->dSky : present ? c->dTexels + L.texOff[ti] : nullptr; table[ti].w = L.texW[ti]; table[ti].h = L.texH[ti];
     }
-    // textures stay the RGBA8 texels the caller uploaded (dispatch.java:349-354: GL_RGBA8); byte / 255.0f happens at fetch (unorm8, pt_device.hpp)
-    HIP_TRY(c->dSky.upload(c->sky.data(), (size_t)c->skyW * c->skyH * 4, s));
-    HIP_TRY(c->dNiTable.upload(niDict.data(), niDict.size() * 4, s));
-    // the texture table beyond the sky: ONE allocation and one asynchronous copy for all textures
-    std::vector<TexRec> table(std::max<size_t>(c->textures.size(), 1));
-    table[0].data = c->dSky; table[0].w = c->skyW; table[0].h = c->skyH;
-    std::vector<uint8_t> texels; std::vector<size_t> texOff(table.size(), 0);
-    for (size_t ti = 1; ti < c->textures.size(); ti++) {
-        const pt_ctx::HostTex& T = c->textures[ti];
-        table[ti].data = nullptr; table[ti].w = T.w; table[ti].h = T.h;
-        if (T.rgba.empty()) continue;
-        texOff[ti] = texels.size() / 4;
-        texels.insert(texels.end(), T.rgba.begin(), T.rgba.begin() + (size_t)T.w * T.h * 4);
-    }
-    HIP_TRY(c->dTexels.upload(texels.data(), texels.size(), s));
-    for (size_t ti = 1; ti < c->textures.size(); ti++) if (!c->textures[ti].rgba.empty()) table[ti].data = c->dTexels + texOff[ti];
     HIP_TRY(c->dTexTable.upload(table.data(), table.size() * sizeof(TexRec), s));
     HIP_TRY(hipStreamSynchronize(s));
     DevScene& sc = c->sc;
-    sc.nodes = c->dNodes; sc.nNodes = (int)order.size(); sc.tris = c->dTris; sc.nTriRecs = (int)(triRecs.size() / 3);
-    sc.shade = c->dShade; sc.nTris = (int)nTris; sc.triObj = c->dTriObj; sc.roots = c->dRoots; sc.numObj = numObj; sc.ellip = c->dEllip; sc.numEllip = nE;
-    for (int k = 0; k < 8; k++) sc.ni8[k] = niDict[k];
+    sc.nodes = c->dNodes; sc.nNodes = L.nInner; sc.tris = c->dTris; sc.nTriRecs = L.nTriRecs;
+    sc.shade = c->dShade; sc.nTris = L.nTris; sc.triObj = c->dTriObj; sc.roots = c->dRoots; sc.numObj = L.numObj; sc.ellip = c->dEllip; sc.numEllip = L.numEllip;
+    for (int k = 0; k < 8; k++) sc.ni8[k] = L.ni8[k];
     sc.niTable = c->dNiTable;
-    sc.mats = c->dMats; sc.numMat = nMat; sc.sky = c->dSky; sc.skyW = c->skyW; sc.skyH = c->skyH; sc.tex = c->dTexTable; sc.numTex = (int)table.size();
-    // LDS tile: as many leading (top-of-tree) node records and triangle records as the budget allows
-    int budget = c->ldsBudget - c->stackDepth * BLOCK * 4;
-    int ln = 0, lt = 0;
-    if (budget > 0) {
-        ln = std::min(sc.nNodes, budget / 64);
-        int rest = budget - ln * 64;
-        lt = std::min(sc.nTriRecs, rest / 48);
-        if (ln < sc.nNodes) lt = std::min(lt, 0);               // triangles only once every node fits
-    }
-    sc.ldsNodes = ln; sc.ldsTris = lt;
-    // persistent kernel: one staged tile per resident block
-    c->stackMode = (sc.nNodes < 32767 && sc.nTriRecs < 32767) ? 0 : (sc.nNodes <= 131071 && sc.nTriRecs <= 131071 && c->stackDepth <= 32) ? 1 : 2;
-    if (c->stackModeForce >= 0) c->stackMode = std::max(c->stackMode, c->stackModeForce);      // only ever towards wider entries
-    {
-        int cb = c->extendCacheBytes;
-        int pn = std::min(sc.nNodes, cb / 64);
-        int pt_ = (pn == sc.nNodes) ? std::min(sc.nTriRecs, (cb - pn * 64) / 48) : 0;
-        c->pLdsNodes = pn; c->pLdsTris = pt_;
-    }
-    // which scenes the hand-written kernel takes (the others run on the compiled k_extend_persist, same results)
-    for (int o = 0; o < numObj; o++) if (roots[o].ref == REF_EMPTY) anyEmpty = true;
-    c->asmWhyNot.clear();
-    if (numObj < 1 || numObj > 1024) c->asmWhyNot = "no BVH or more than 1024";
-    else if (anyEmpty) c->asmWhyNot = "a leaf without triangles";
-    else if (!boxesOrdered && asmStride == 80) c->asmWhyNot = "a node box with min > max or a NaN";      // (the 64-B records' min/max step is rayBox as written)
-    else if (triRecs.size() / 3 >= (1u << 23) - 1 || order.size() >= (1u << 23) - 1) c->asmWhyNot = "more than 2^23 - 2 inner nodes or triangle records (24-bit stack entries)";
-    c->asmEligible = c->asmWhyNot.empty();
+    sc.mats = c->dMats; sc.numMat = L.numMat; sc.sky = c->dSky; sc.skyW = b.skyW; sc.skyH = b.skyH; sc.tex = c->dTexTable; sc.numTex = (int)table.size();
+    sc.ldsNodes = L.ldsNodes; sc.ldsTris = L.ldsTris;
+    c->trans = L.trans; c->anySubsurface = L.anySubsurface; c->anyMaps = L.anyMaps; c->ellipMaps = L.ellipMaps; c->ambiguousTriObj = L.ambiguousTriObj;
+    c->niBits = L.niBits; c->stackDepth = L.stackDepth; c->asmNodeStride = L.asmNodeStride; c->asmGroupShift = L.asmGroupShift;
+    c->stackMode = L.stackMode; c->pLdsNodes = L.pLdsNodes; c->pLdsTris = L.pLdsTris;
+    c->asmEligible = L.asmEligible; c->asmWhyNot = L.asmWhyNot;
     c->sceneDirty = false;
     return 0;
 }
@@ -2139,9 +1865,9 @@ int flushStream(pt_ctx* c) {
 
 // the frame inputs current at the call; false while Parameters, ORIGIN or ROTATION are not set
 bool currentInputs(const pt_ctx* c, FrameIn& fin) {
-    if (c->params.size() < 12 || c->origin.size() < 3 || c->rotation.size() < 3 || c->mouse.size() < 3) return false;
-    std::memcpy(fin.params, c->params.data(), 48); std::memcpy(fin.origin, c->origin.data(), 12); std::memcpy(fin.rotation, c->rotation.data(), 12);
-    std::memcpy(fin.mouse, c->mouse.data(), 12);
+    if (c->buf.params.size() < 12 || c->buf.origin.size() < 3 || c->buf.rotation.size() < 3 || c->buf.mouse.size() < 3) return false;
+    std::memcpy(fin.params, c->buf.params.data(), 48); std::memcpy(fin.origin, c->buf.origin.data(), 12); std::memcpy(fin.rotation, c->buf.rotation.data(), 12);
+    std::memcpy(fin.mouse, c->buf.mouse.data(), 12);
     return true;
 }
 // pt_write_frame, pt_reproject_frame: the current image's camera is the inputs current at the call (include/pt_reproject.h)
@@ -2201,8 +1927,8 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     hipStream_t s = c->stream;
     int rc;
     // parameter checks (scope: SURVEY.md §2)
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    const float* P = c->params.data();
+    if (c->buf.params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    const float* P = c->buf.params.data();
     const bool direct = P[9] != 1.0f;                            // RAYTRACING == 0: directDiffuse (frag.glsl:655-681, :911-912)
     if (P[10] != 0.0f) {                                          // DEBUG: no paths at all, one small kernel (frag.glsl:916-918)
         if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
@@ -2210,7 +1936,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
         if (c->sceneDirty && (rc = buildScene(c))) return rc;
         if (c->stackDepth > 64) return fail(PT_ERR_SCENE, "DEBUG heat-map: BVH deeper than the 64-entry traversal stack");
         FrameIn fin;
-        std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->origin.data(), 12); std::memcpy(fin.rotation, c->rotation.data(), 12); std::memcpy(fin.mouse, c->mouse.data(), 12);
+        std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->buf.origin.data(), 12); std::memcpy(fin.rotation, c->buf.rotation.data(), 12); std::memcpy(fin.mouse, c->buf.mouse.data(), 12);
         *c->hFrameIn = fin;
         HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
@@ -2229,7 +1955,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     size_t nJobs64 = (size_t)(c->adaptOn ? c->adaptN : c->nLocal) * (size_t)nFrames;
     if (nJobs64 >= (1ull << 31)) return fail(PT_ERR_ARG, "batch too large: pixels * frames must stay below 2^31 (split the batch)");
     FrameIn fin;
-    std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->origin.data(), 12); std::memcpy(fin.rotation, c->rotation.data(), 12); std::memcpy(fin.mouse, c->mouse.data(), 12);
+    std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->buf.origin.data(), 12); std::memcpy(fin.rotation, c->buf.rotation.data(), 12); std::memcpy(fin.mouse, c->buf.mouse.data(), 12);
     // the running stream can take this batch if nothing the kernels were launched with changes
     // overlapped: room for the batches of as many images as can be pending, and for callers that submit frame by frame to run
     // ahead (at least 64 rows while they stay below 8 GB)
@@ -2397,8 +2123,8 @@ int pt_create(pt_ctx** out, int device, int width, int height, int shard_rank, i
     pt_ctx* c = new pt_ctx();
     c->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     c->device = device; c->W = width; c->H = height; c->shardRank = shard_rank; c->shardCount = shard_count;
-    c->imp = {0.0f}; c->ellip = {0.0f}; c->objidx = {0};
-    c->mouse = {-1.0e6f, -1.0e6f, 0.0f};
+    c->buf.imp = {0.0f}; c->buf.ellip = {0.0f}; c->buf.objidx = {0};
+    c->buf.mouse = {-1.0e6f, -1.0e6f, 0.0f};
     const int rc = initContext(c, width, height, shard_rank, shard_count);
     if (rc) { const std::string msg = g_err; pt_destroy(c); return fail(rc, msg); }      // nothing of a half-built context is left behind
     *out = c;
@@ -2508,18 +2234,18 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
     invalidateRecords(c);
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
-        case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
-        case PT_BIND_ROTATION: if (n < 3) return fail(PT_ERR_ARG, "ROTATION needs 3 floats"); c->rotation.assign(f, f + 3); return PT_OK;
-        case PT_BIND_MOUSE: if (n < 3) return fail(PT_ERR_ARG, "MOUSE_POS needs 3 floats"); c->mouse.assign(f, f + 3); return PT_OK;
-        case PT_BIND_PARAMS: if (n < 12) return fail(PT_ERR_ARG, "Parameters needs 12 floats"); c->params.assign(f, f + 12); return PT_OK;
-        case PT_BIND_TRIANGLES: if (n % 40) return fail(PT_ERR_ARG, "triangle buffer must be 40 floats per triangle"); c->tris.assign(f, f + n); break;
-        case PT_BIND_IMPLICITS: c->imp.assign(f, f + n); break;
-        case PT_BIND_ELLIPSOIDS: c->ellip.assign(f, f + n); break;
-        case PT_BIND_BVHDATA: c->bvhdata.assign(f, f + n); break;
-        case PT_BIND_BVHTREE: if (n % 3) return fail(PT_ERR_ARG, "BVHtree must be 3 ints per node"); c->bvhtree.assign(i, i + n); break;
-        case PT_BIND_LEAFTRIS: c->leaftris.assign(i, i + n); break;
-        case PT_BIND_OBJINDICES: c->objidx.assign(i, i + n); break;
-        case PT_BIND_MATERIALS: c->mtl.assign(f, f + n); break;
+        case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->buf.origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
+        case PT_BIND_ROTATION: if (n < 3) return fail(PT_ERR_ARG, "ROTATION needs 3 floats"); c->buf.rotation.assign(f, f + 3); return PT_OK;
+        case PT_BIND_MOUSE: if (n < 3) return fail(PT_ERR_ARG, "MOUSE_POS needs 3 floats"); c->buf.mouse.assign(f, f + 3); return PT_OK;
+        case PT_BIND_PARAMS: if (n < 12) return fail(PT_ERR_ARG, "Parameters needs 12 floats"); c->buf.params.assign(f, f + 12); return PT_OK;
+        case PT_BIND_TRIANGLES: if (n % 40) return fail(PT_ERR_ARG, "triangle buffer must be 40 floats per triangle"); c->buf.tris.assign(f, f + n); break;
+        case PT_BIND_IMPLICITS: c->buf.imp.assign(f, f + n); break;
+        case PT_BIND_ELLIPSOIDS: c->buf.ellip.assign(f, f + n); break;
+        case PT_BIND_BVHDATA: c->buf.bvhdata.assign(f, f + n); break;
+        case PT_BIND_BVHTREE: if (n % 3) return fail(PT_ERR_ARG, "BVHtree must be 3 ints per node"); c->buf.bvhtree.assign(i, i + n); break;
+        case PT_BIND_LEAFTRIS: c->buf.leaftris.assign(i, i + n); break;
+        case PT_BIND_OBJINDICES: c->buf.objidx.assign(i, i + n); break;
+        case PT_BIND_MATERIALS: c->buf.mtl.assign(f, f + n); break;
         default: return fail(PT_ERR_ARG, "pt_set_buffer: binding point not consumed by the render path (frag.glsl declares 0-5,7,10-15)");
     }
     c->sceneDirty = true;
@@ -2541,9 +2267,9 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
     invalidateRecords(c);
     c->sceneGen++; c->otherGen++;
-    if (index == 0) { c->sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->skyW = w; c->skyH = h; }
-    if ((size_t)index >= c->textures.size()) c->textures.resize((size_t)index + 1);
-    c->textures[index].rgba.assign(rgba8, rgba8 + (size_t)w * h * 4); c->textures[index].w = w; c->textures[index].h = h;
+    if (index == 0) { c->buf.sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->buf.skyW = w; c->buf.skyH = h; }
+    if ((size_t)index >= c->buf.textures.size()) c->buf.textures.resize((size_t)index + 1);
+    c->buf.textures[index].rgba.assign(rgba8, rgba8 + (size_t)w * h * 4); c->buf.textures[index].w = w; c->buf.textures[index].h = h;
     c->sceneDirty = true;
     return PT_OK;
 }
@@ -2723,8 +2449,8 @@ namespace {
 int renderSelected(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const char* who, const std::function<int(hipStream_t, int)>& select,
                    int64_t* nActive) {
     HIP_TRY(hipSetDevice(c->device));
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
+    if (c->buf.params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    if (c->buf.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
     int rc;
     if ((rc = flushStream(c))) return rc;                         // batches in flight land in FRAME, not in the statistics
     hipStream_t s = c->stream;
@@ -2756,8 +2482,8 @@ int renderSelected(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds,
 }
 // the overlay fields of the selection kernels: the context's current MOUSE_POS and resolution (Parameters are checked by renderSelected first)
 AdaptRule withOverlay(const pt_ctx* c, AdaptRule r) {
-    if (c->mouse.size() >= 2) { r.mouseX = c->mouse[0]; r.mouseY = c->mouse[1]; }
-    r.resolution = c->params.size() >= 12 ? c->params[2] : 0.0f;
+    if (c->buf.mouse.size() >= 2) { r.mouseX = c->buf.mouse[0]; r.mouseY = c->buf.mouse[1]; }
+    r.resolution = c->buf.params.size() >= 12 ? c->buf.params[2] : 0.0f;
     return r;
 }
 int renderAdaptive(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, const AdaptRule& r, int64_t* nActive) {
@@ -3119,7 +2845,7 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
     HIP_TRY(hipMemsetAsync(st.H, 0, np * 16, c->stream));       // ordered before the kernels below (the context's stream does not wait for the null stream)
     // the ellipsoid rotation matrices are produced by k_frame_setup
     FrameIn fin; std::memset(&fin, 0, sizeof(fin));
-    if (c->params.size() >= 12) std::memcpy(fin.params, c->params.data(), 48);
+    if (c->buf.params.size() >= 12) std::memcpy(fin.params, c->buf.params.data(), 48);
     fin.params[11] = 0.0f;
     HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);

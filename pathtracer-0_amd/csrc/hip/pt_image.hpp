@@ -134,8 +134,8 @@ int ensureRecords(pt_ctx* c, pt_ctx::Records& R, const FrameIn& fin, const pt_th
 }
 // the records of the current frame inputs: c->feat, or c->thru under `rule`
 int currentRecords(pt_ctx* c, const pt_through_rule* rule, const char* who) {
-    if (c->params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
-    if (c->origin.size() < 3 || c->rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
+    if (c->buf.params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+    if (c->buf.origin.size() < 3 || c->buf.rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
     FrameIn fin;
     currentInputs(c, fin);
     return ensureRecords(c, rule ? c->thru : c->feat, fin, rule, who);
@@ -291,7 +291,7 @@ namespace {
 // the current inputs of `on` into cur, refused unless they render surfaces at the image's size; toDo: what the caller wants surfaces for
 int usableInputs(const pt_ctx* c, const pt_ctx* on, const std::string& w, const char* toDo, FrameIn& cur) {
     if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
-    const float* P = on->params.data();
+    const float* P = on->buf.params.data();
     if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
     if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, w + ": DEBUG != 0 renders the traversal heat map, which has no surfaces to " + toDo);
     return 0;
@@ -330,14 +330,14 @@ int storeReprojected(pt_ctx* c, pt_ctx* on, bool stats, int64_t* nKept) {
 // ---- include/pt_motion.h: where the primitives are, for the mark and for the reprojection across moved geometry
 // the vertices of the triangles of binding 3 (9 floats each) and centre, stretch, rot, r of the ellipsoids of binding 7 (10 floats each), from the host copies
 void motionPositions(const pt_ctx* c, std::vector<float>& tri, int* nTri, std::vector<float>& el, int* nEl) {
-    const size_t nt = c->tris.size() / 40;
+    const size_t nt = c->buf.tris.size() / 40;
     tri.resize(nt * 9);
     for (size_t t = 0; t < nt; t++)
-        for (int v = 0; v < 3; v++) std::memcpy(&tri[9 * t + 3 * v], &c->tris[40 * t + 4 * v], 12);
-    int ne = c->ellip.empty() ? 0 : (int)c->ellip[0];
-    if (ne < 0 || c->ellip.size() < (size_t)1 + 11 * (size_t)ne) ne = 0;      // (buildScene refuses such a buffer)
+        for (int v = 0; v < 3; v++) std::memcpy(&tri[9 * t + 3 * v], &c->buf.tris[40 * t + 4 * v], 12);
+    int ne = c->buf.ellip.empty() ? 0 : toInt(c->buf.ellip[0]);
+    if (ne < 0 || c->buf.ellip.size() < (size_t)1 + 11 * (size_t)ne) ne = 0;      // (buildScene refuses such a buffer)
     el.resize((size_t)ne * 10);
-    const float* E = c->ellip.data();
+    const float* E = c->buf.ellip.data();
     for (int i = 0; i < ne; i++) {
         for (int k = 0; k < 3; k++) { el[10 * i + k] = E[1 + 3 * i + k]; el[10 * i + 3 + k] = E[1 + ne * 3 + 3 * i + k]; el[10 * i + 6 + k] = E[1 + ne * 6 + 3 * i + k]; }
         el[10 * i + 9] = E[1 + ne * 9 + i];
@@ -734,7 +734,7 @@ int renderAdaptiveGuided(pt_ctx* c, int first_frame, int n_frames, const int32_t
     int rc;
     if ((rc = checkRule(*rule, who))) return rc;
     const pt_ctx* f = firstStream(c);
-    if (f->params.size() >= 12 && f->params[10] != 0.0f)          // before the selection, as renderSelected would after it
+    if (f->buf.params.size() >= 12 && f->buf.params[10] != 0.0f)          // before the selection, as renderSelected would after it
         return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
     pt_ctx* on = nullptr; int64_t n = 0;
     if ((rc = selectGuided(c, *rule, floorA, who, &on, &n))) return rc;
