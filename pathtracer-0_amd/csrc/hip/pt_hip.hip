@@ -39,6 +39,7 @@
 #include "pt_device.hpp"
 #include "pt_devmem.hpp"
 #include "pt_scene_layout.hpp"
+#include "pt_launch_plan.hpp"
 #include "pt_image_launch.hpp"
 
 #include <algorithm>
@@ -68,6 +69,7 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 constexpr int BLOCK = 256;
 static_assert(BLOCK == EXTEND_BLOCK, "the layout sizes the LDS tile beside one traversal stack per lane of a block");
+static_assert(BLOCK == ptp::PLAN_BLOCK, "the launch plan sizes k_extend's grid and LDS, and rounds the pool, by its blocks");
 #ifndef SHADE_BLOCK_SIZE
 #define SHADE_BLOCK_SIZE 256
 #endif
@@ -1278,8 +1280,7 @@ struct pt_ctx {
     std::string asmWhyNot;          // ... or why not (pt_debug: reported by option 12)
     // per block size (256, 1024, 512 threads) six code objects: 16-bit stack entries, Packed18, the same two with v_rcp_f32 (relaxed contract), 24-bit entries exact / relaxed
     hipModule_t asmModule[18] = {}; hipFunction_t asmFn[18] = {}; std::string asmLoadError[18];
-    int asmTpb = 0;                 // threads per block of the hand-written kernel: 0 automatic (launchExtendAsm), 256, 1024
-    bool debugExactExtend = false;  // pt_debug_intersect always probes the exact kernels
+    int asmTpb = 0;                 // threads per block of the hand-written kernel: 0 automatic (planExtendAsm, pt_launch_plan.hpp), 256, 1024
     int extendTpb = 256, extendCacheBytes = 8 * 1024, refillMin = 24, numCUs = 256;
     int noneMin = 8;                // lanes waiting for their next object / retirement that make that phase worth a trip
     bool noneMinSet = false;        // pt_set_option 3 was used
@@ -1435,18 +1436,10 @@ int nextEventPair(pt_ctx::KT& k) {
 struct PoolRun {            // host view of the path pool while a batch runs
     hipStream_t stream; State st; unsigned launched; int iter;      // launched: the host's upper bound on the slots an iteration visits
 };
-template <bool COUNT, typename StackT, int TPB>
-void launchEP(pt_ctx* c, const PoolRun& pr, const DevScene& sc, size_t lds, int grid) {
-    int nObjLds = std::min(sc.numObj, 8);
-    // the two rare features of the kernel are compiled into a variant of their own (their registers cost the common one spills):
-    // thickness probes (RAYTRACING == 0 of the running stream, not of a later upload) and the side record of mapped ellipsoids
-    if (c->streamIn.params[9] != 1.0f || c->ellipMaps) {
-        hipLaunchKernelGGL((k_extend_persist<COUNT, StackT, TPB, true>), dim3(grid), dim3(TPB), lds, pr.stream, sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl, c->refillMin,
-                           c->innerKeepEighths, nObjLds, c->noneMin);
-        return;
-    }
-    hipLaunchKernelGGL((k_extend_persist<COUNT, StackT, TPB, false>), dim3(grid), dim3(TPB), lds, pr.stream, sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl, c->refillMin,
-                       c->innerKeepEighths, nObjLds, c->noneMin);
+template <bool COUNT, typename StackT, int TPB, bool RARE>
+void launchEP(pt_ctx* c, const PoolRun& pr, const DevScene& sc, const ptp::ExtendPlan& p) {
+    hipLaunchKernelGGL((k_extend_persist<COUNT, StackT, TPB, RARE>), dim3(p.grid), dim3(TPB), p.lds, pr.stream, sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl, c->refillMin,
+                       c->innerKeepEighths, p.nObjLds, p.noneMin);
 }
 // Kernel arguments of pt_extend_gfx950.s (offsets are written into the assembly)
 struct EpAsmArgs {
@@ -1485,66 +1478,28 @@ int loadAsmKernel(pt_ctx* c, int k) {
     return 0;
 }
 
-// true: launched.  false: this launch is not one the hand-written kernel takes (the caller uses the compiled kernel)
-bool launchExtendAsm(pt_ctx* c, const PoolRun& pr) {
-    // (RAYTRACING == 0, directDiffuse: its rays are ordinary rayScene calls, and the thickness probes of subsurface materials — FL_PROBE: no offset, one BVH, no
-    //  ellipsoids — are set up at the kernel's refill)
-    if (!c->asmEligible || c->countStats || c->extendTpb != 256) return false;
-    const DevScene& sc = c->sc;
-    // Block size.  What bounds this kernel is its CU's instruction issue and vector-memory pipe together (profiles/r03_h_*): node steps served from
-    // the LDS tile cost neither a tag lookup nor a round trip, and the tile is per BLOCK — the same bytes eight times over with 256-thread blocks.
-    // Alone on its GPU the kernel therefore runs 2 blocks of 1024 threads per CU over a 32 KB tile instead of 8 x 256 over 8 KB (C3 +6.6 %, C4 +10 %,
-    // C5 +7 %, C2 +-0).  When the context's streams share the GPU the small blocks win (their slots free one by one for the other stream's
-    // shading blocks: 1024-thread blocks -4...7 %), and so they do for a launch too small to give every CU its two large blocks.
-    const bool part = c->sExt != nullptr && pr.stream == c->sExt;      // spatial partition: the kernel has its CUs to itself, but only those
-    const int cus = part ? c->numCUs * c->cuPartitionBuilt / 8 : c->numCUs;
-    const bool sharedGpu = c->streamsOnDevice > 1 && !part;
-    const bool lazyRoots = sc.numObj > 8;                      // more than 8 BVHs: root records in LDS, tested when a BVH's turn comes (no per-lane distances)
-    const size_t entryBytes = c->stackMode == 2 ? 3 : 2;       // traversal-stack entry in LDS: 16 bits (+ 2 in registers: Packed18), or 16 + 8 (24-bit entries)
-    const size_t perLane = (lazyRoots ? 0 : (size_t)sc.numObj * 4) + (size_t)c->stackDepth * entryBytes;      // root-box distances + traversal stack of one lane
-    const size_t rootBytes = lazyRoots ? ((size_t)sc.numObj + 64) * 32 : 0;      // the root records and the 64 group boxes of the per-ray cull (buildScene)
-    const bool largeFits = 2 * (perLane * 1024 + rootBytes + 48 + 16384) <= (size_t)160 * 1024;      // two large blocks per CU with at least a 16 KB tile each (deep trees: stacks)
-    const int TPB = c->asmTpb ? c->asmTpb : (!sharedGpu && c->streamsOnDevice == 1 && largeFits && pr.launched >= (uint64_t)cus * 2048 ? 1024 : 256);
-    const int BPW = TPB / 256;                                  // how many 256-thread blocks one block stands for
-    const size_t fixed = (lazyRoots ? rootBytes : (size_t)sc.numObj * 4 * TPB) + 48 + (size_t)c->stackDepth * entryBytes * TPB;      // root-box distances (or root records), root references + ray cursor, traversal stacks
-    const size_t ldsPerCU = 160 * 1024;                        // gfx950; one block may take all of it
-    if (fixed + 2048 > ldsPerCU) return false;
-    // Blocks per CU and tile: alone on the GPU the kernel wants every wave slot (8 blocks of 256 threads, 8 KB tile).  When the context's streams
-    // share the GPU (pt_create_multi with a device listed more than once) 6 blocks with a 16 KB tile are worth more: the two slots per SIMD it
-    // leaves let the other stream's shading blocks run beside it instead of behind it (C3 +3.5 %, C4 +3 %, C5 +2.5 % over 8 blocks,
-    // profiles/r03_d_blocks_per_cu_and_tile.txt) — unless the whole scene fits the small tile anyway (C2).
-    const bool wholeSceneInSmallTile = (size_t)sc.nNodes * (size_t)c->asmNodeStride + (size_t)sc.nTriRecs * 48 <= 8192;
-    const bool shareSlots = sharedGpu && !wholeSceneInSmallTile;
-    const int maxBlocks = std::max(1, (c->extendMaxBlocksPerCU > 0 ? std::min(c->extendMaxBlocksPerCU, 8) : (shareSlots ? 6 : 8)) / BPW);
-    const size_t tileWanted = c->extendCacheSet ? (size_t)c->extendCacheBytes : (shareSlots ? 16384 : 8192) * (size_t)BPW;
-    size_t cb = std::min<size_t>(tileWanted, ldsPerCU - fixed);
-    {   // the node tile gives way to residency, as in launchExtendPersist
-        const int want = maxBlocks;
-        const size_t perBlock = ldsPerCU / (size_t)want;
-        if (fixed + cb + 16 > perBlock && perBlock > fixed + 16 + 2048) cb = std::min(cb, (perBlock - fixed - 16) & ~(size_t)15);
-    }
+// The plan of an intersect launch over the pool `pr` (pt_launch_plan.hpp).  probes: the pool carries thickness probes (RAYTRACING == 0); fast: the relaxed
+// reciprocal may be used; handWritten = false: the compiled kernel's plan where pt_set_option 4 would have asked for the hand-written one
+ptp::ExtendPlan planExtendFor(const pt_ctx* c, const PoolRun& pr, bool probes, bool fast, bool handWritten = true) {
+    ptp::PlanScene s; ptp::PlanOptions o; ptp::PlanDevice dv; ptp::PlanCall call;
+    s.nNodes = c->sc.nNodes; s.nTriRecs = c->sc.nTriRecs; s.numObj = c->sc.numObj; s.stackDepth = c->stackDepth; s.stackMode = c->stackMode; s.asmNodeStride = c->asmNodeStride;
+    s.ellipMaps = c->ellipMaps; s.asmEligible = c->asmEligible; s.ldsNodes = c->sc.ldsNodes; s.ldsTris = c->sc.ldsTris;
+    o.extendMode = handWritten ? c->extendMode : 1; o.extendTpb = c->extendTpb; o.extendCacheBytes = c->extendCacheBytes; o.extendCacheSet = c->extendCacheSet;
+    o.extendMaxBlocksPerCU = c->extendMaxBlocksPerCU; o.asmTpb = c->asmTpb; o.asmLoop = c->asmLoop; o.noneMin = c->noneMin; o.noneMinSet = c->noneMinSet; o.countStats = c->countStats;
+    dv.numCUs = c->numCUs; dv.streamsOnDevice = c->streamsOnDevice; dv.part = c->sExt != nullptr && pr.stream == c->sExt; dv.partEighths = c->cuPartitionBuilt;
+    call.launched = pr.launched; call.probes = probes; call.fast = fast;
+    return ptp::planExtend(s, o, dv, call);
+}
+
+// true: launched.  false: the load or the launch failed; c->asmError says why (loud: pump() fails, no silent fallback)
+bool launchExtendAsm(pt_ctx* c, const PoolRun& pr, const ptp::ExtendPlan& p) {
+    if (loadAsmKernel(c, p.variant)) { c->asmError = "hand-written intersect kernel: " + g_err; return false; }
     EpAsmArgs a{};
-    const size_t NS = (size_t)c->asmNodeStride;
-    a.ldsNodes = (int)std::min<size_t>((size_t)sc.nNodes, cb / NS);
-    a.ldsTris = (a.ldsNodes == sc.nNodes) ? (int)std::min<size_t>((size_t)sc.nTriRecs, (cb - (size_t)a.ldsNodes * NS) / 48) : 0;
-    size_t lds = (size_t)a.ldsNodes * NS + (size_t)a.ldsTris * 48 + fixed;
-    lds = (lds + 15) & ~(size_t)15;
-    int perCU = std::max(1, std::min((int)(ldsPerCU / lds), maxBlocks));
-    int grid = cus * perCU;
-    grid = std::max(1, std::min(grid, ((int)pr.launched + TPB - 1) / TPB));
-    const bool fastRcp = c->streamFast && !c->debugExactExtend;
-    const int variant = (c->stackMode == 2 ? (fastRcp ? 5 : 4) : (c->stackMode == 1 ? 1 : 0) + (fastRcp ? 2 : 0)) + (TPB == 1024 ? 6 : TPB == 512 ? 12 : 0);
-    if (loadAsmKernel(c, variant)) { c->asmError = "hand-written intersect kernel: " + g_err; return false; }      // loud: pump() fails, no silent fallback
     a.nodes80 = c->dNodes80; a.tris = c->dTris; a.roots = c->dRoots; a.G0 = pr.st.G0; a.G1 = pr.st.G1; a.H = pr.st.H;
     a.queue = c->dQueue[pr.iter & 1]; a.ctl = c->dCtl;
-    a.ellip = c->dEllip; a.numEllip = sc.numEllip; a.nodeStride = c->asmNodeStride; a.groupShift = c->asmGroupShift; a.stackDepth = c->stackDepth; a.HX = c->ellipMaps ? (void*)pr.st.HX : nullptr;
-    a.numObj = sc.numObj; a.iter = pr.iter; a.nSlots = (int)pr.launched; a.refillMin = c->refillMin; a.keepEighths = c->innerKeepEighths; a.noneMin = c->noneMin;
-    // main loop: the fused trip with fetch-at-decision, unless the whole scene sits in the LDS tile — then no fetch is worth hiding and the
-    // phase-voting loop's fewer instructions per ray win (C2: 3.4 against 3.1 Gsamples/s, profiles/r03_c_*)
-    const bool allInLds = a.ldsNodes == sc.nNodes && a.ldsTris == sc.nTriRecs;
-    a.mode = c->asmLoop >= 0 ? (unsigned)c->asmLoop : (allInLds ? 0u : 1u);
-    if (a.mode && !c->noneMinSet) a.noneMin = 2;      // the fused loop serves lanes that wait for their next BVH sooner (C3 +1.8 %, C5 +1 %, C4 / one stream +-0: profiles/r03_c_main_loops.txt (8))
-    a.nWaves = (unsigned)grid * (unsigned)(TPB / 64);
+    a.ellip = c->dEllip; a.numEllip = c->sc.numEllip; a.nodeStride = c->asmNodeStride; a.groupShift = c->asmGroupShift; a.stackDepth = c->stackDepth; a.HX = c->ellipMaps ? (void*)pr.st.HX : nullptr;
+    a.numObj = c->sc.numObj; a.iter = pr.iter; a.nSlots = (int)pr.launched; a.refillMin = c->refillMin; a.keepEighths = c->innerKeepEighths;
+    a.ldsNodes = p.ldsNodes; a.ldsTris = p.ldsTris; a.noneMin = p.noneMin; a.mode = p.mode; a.nWaves = p.nWaves; a.divM = p.divM; a.divS = p.divS;
 #ifdef PT_ASM_DEBUG                  // developer builds only (scripts/build_variant.py -DPT_ASM_DEBUG): the per-wave debug records of the assembly
     {
         if (c->dAsmDbg.ensure(8192 * 64) != hipSuccess) return false;
@@ -1552,55 +1507,34 @@ bool launchExtendAsm(pt_ctx* c, const PoolRun& pr) {
         a.dbg = c->dAsmDbg.p;
     }
 #endif
-    {   // x / nWaves == mulhi(x, divM) >> divS for x < 2^31 (nWaves >= 4)
-        unsigned d = a.nWaves; int l = 0;
-        while ((1ull << l) < d) l++;
-        a.divM = (unsigned)(((1ull << (31 + l)) + d - 1) / d); a.divS = (unsigned)(l - 1);
-    }
     size_t asz = sizeof(a);
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    const hipError_t e = hipModuleLaunchKernel(c->asmFn[variant], (unsigned)grid, 1, 1, (unsigned)TPB, 1, 1, (unsigned)lds, pr.stream, nullptr, extra);
+    const hipError_t e = hipModuleLaunchKernel(c->asmFn[p.variant], (unsigned)p.grid, 1, 1, (unsigned)p.tpb, 1, 1, (unsigned)p.lds, pr.stream, nullptr, extra);
     if (e != hipSuccess) { c->asmError = std::string("hipModuleLaunchKernel(pt_extend_asm): ") + hipGetErrorString(e); return false; }
     c->asmLaunches++;
     return true;
 }
 
-void launchExtendPersist(pt_ctx* c, const PoolRun& pr) {
-    if (c->extendMode == 2 && launchExtendAsm(c, pr)) return;
-    const int launched = (int)pr.launched;
+void launchExtendPersist(pt_ctx* c, const PoolRun& pr, const ptp::ExtendPlan& p) {
     DevScene sc = c->sc;
-    int tpb = c->extendTpb;
-    // LDS per block: [node tile][triangle tile][root-box distances][traversal stacks]; the tile takes what the fixed parts leave
-    size_t fixed = (size_t)std::min(sc.numObj, 8) * tpb * 4 + (size_t)c->stackDepth * tpb * (c->stackMode == 2 ? 4 : 2) + 64 + 32 * 8 + (size_t)tpb * 4;     // (+ the per-lane slot numbers)     // + the LDS copies of up to 8 object roots
-    size_t avail = fixed < 160 * 1024 ? 160 * 1024 - fixed : 0;
-    size_t cb = std::min<size_t>((size_t)c->extendCacheBytes, avail);
-    {   // a smaller node tile (down to 2 KB; 6 KB under blocks of 512 threads and more) if that lets every wave slot of the CU be used:
-        // occupancy is worth more to this kernel than the last kilobytes of tile (8 instead of 6 waves per SIMD +9 %; tiles of 4, 8 and 16 KB
-        // measure the same, profiles/r02_y_*)
-        const int want = std::min(c->extendMaxBlocksPerCU > 0 ? c->extendMaxBlocksPerCU : 2048 / tpb, 2048 / tpb);
-        const size_t perBlock = (size_t)160 * 1024 / (size_t)std::max(want, 1);
-        const size_t minTile = tpb >= 512 ? 6 * 1024 : 2 * 1024;
-        if (fixed + cb + 16 > perBlock && perBlock > fixed + 16 + minTile) cb = std::min(cb, (perBlock - fixed - 16) & ~(size_t)63);
-    }
-    sc.ldsNodes = (int)std::min<size_t>((size_t)sc.nNodes, cb / 64);
-    sc.ldsTris = (sc.ldsNodes == sc.nNodes) ? (int)std::min<size_t>((size_t)sc.nTriRecs, (cb - (size_t)sc.ldsNodes * 64) / 48) : 0;
-    size_t lds = (size_t)sc.ldsNodes * 64 + (size_t)sc.ldsTris * 48 + fixed;
-    lds = (lds + 15) & ~(size_t)15;
-    // Blocks per CU of the grid = what is resident at once (LDS per block; 2048 threads per CU), capped by pt_set_option 8 (default: no cap).
-    // All waves of the grid start within 1 µs of each other (per-wave stamps of a -DPT_WAVE_STAMPS build, scripts/wave_ends.py).
-    // A grid LARGER than what is resident queues blocks behind the resident ones and is slower (with 512-thread blocks: 5-16 blocks per
-    // CU on C3; C4 and C5, whose deeper traversal stacks then left room for 3 blocks only, lost 5 % and 13 % with 4).
-    int perCU = std::max(1, std::min((int)(160 * 1024 / std::max<size_t>(lds, 1)), 2048 / tpb));
-    if (c->extendMaxBlocksPerCU > 0) perCU = std::min(perCU, c->extendMaxBlocksPerCU);
-    int grid = c->numCUs * perCU;
-    int maxUseful = (launched + tpb - 1) / tpb;                  // never more blocks than 1 lane per ray
-    grid = std::max(1, std::min(grid, maxUseful));
-#define EP(COUNT, T, TPB) launchEP<COUNT, T, TPB>(c, pr, sc, lds, grid)
+    sc.ldsNodes = p.ldsNodes; sc.ldsTris = p.ldsTris;
+    const int tpb = p.tpb;
+#define EP(COUNT, T, TPB) (p.rare ? launchEP<COUNT, T, TPB, true>(c, pr, sc, p) : launchEP<COUNT, T, TPB, false>(c, pr, sc, p))
 #define EP_T(COUNT, T) do { if (tpb == 64) EP(COUNT, T, 64); else if (tpb == 128) EP(COUNT, T, 128); else if (tpb == 256) EP(COUNT, T, 256); else if (tpb == 512) EP(COUNT, T, 512); else EP(COUNT, T, 1024); } while (0)
     if (c->countStats) { if (c->stackMode == 0) EP_T(true, short); else if (c->stackMode == 1) EP_T(true, Packed18); else EP_T(true, int); }
     else { if (c->stackMode == 0) EP_T(false, short); else if (c->stackMode == 1) EP_T(false, Packed18); else EP_T(false, int); }
 #undef EP
 #undef EP_T
+}
+
+// The intersect launch of one iteration over the pool `pr`, as planned; a hand-written kernel that failed to load or launch leaves the compiled one's
+// launch behind it and its error in c->asmError
+void launchExtend(pt_ctx* c, const PoolRun& pr, bool probes, bool fast) {
+    const ptp::ExtendPlan p = planExtendFor(c, pr, probes, fast);
+    if (p.kernel == ptp::K_ASM) { if (!launchExtendAsm(c, pr, p)) launchExtendPersist(c, pr, planExtendFor(c, pr, probes, fast, false)); }
+    else if (p.kernel == ptp::K_PERSIST) launchExtendPersist(c, pr, p);
+    else if (c->countStats) hipLaunchKernelGGL(k_extend<true>, dim3(p.grid), dim3(BLOCK), p.lds, pr.stream, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl);
+    else hipLaunchKernelGGL(k_extend<false>, dim3(p.grid), dim3(BLOCK), p.lds, pr.stream, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl);
 }
 
 // ------------------------------------------------------------------------------------------------ frame-stream scheduler
@@ -1617,12 +1551,8 @@ Batch streamBatch(const pt_ctx* c) {
     b.ringFrames = (unsigned)c->ringFrames; b.seeds = c->dSeeds; b.pixList = c->dPixList; b.pixXY = c->dPixXY; b.colbuf = c->dColbuf;
     // an adaptive stream runs on the compacted subsequence of the list; pixList then holds each entry's accumulator slot (k_accumulate_adaptive)
     if (c->adaptOn) { b.nLocal = c->adaptN; b.pixXY = c->dAdaptXY; b.pixList = c->dAdaptSlot; }
-    if (b.nLocal >= 2) {                                      // ceil(2^(31+l)/d), exact for every job < 2^31
-        unsigned d = (unsigned)b.nLocal; int l = 0;
-        while ((1ull << l) < d) l++;
-        unsigned long long m = ((1ull << (31 + l)) + d - 1) / d;
-        b.divM = (unsigned)m; b.divS = (unsigned)(l - 1);
-    } else { b.divM = 0; b.divS = 0; }
+    if (b.nLocal >= 2) { const ptp::MagicDiv dm = ptp::magicDiv((unsigned)b.nLocal); b.divM = dm.m; b.divS = dm.s; }      // exact for every job < 2^31
+    else { b.divM = 0; b.divS = 0; }
     return b;
 }
 
@@ -1754,7 +1684,6 @@ int pump(pt_ctx* c, PumpUntil until, int arg) {
     const bool fastNow = c->streamFast;                           // the contract the running stream was started with
     const Batch b = streamBatch(c);
     const int N = c->poolActive;
-    size_t ldsBytes = (size_t)c->sc.ldsNodes * 64 + (size_t)c->sc.ldsTris * 48 + (size_t)c->stackDepth * BLOCK * 4;
     auto satisfied = [&]() {
         if (c->pending.empty()) return true;
         switch (until) {
@@ -1788,13 +1717,7 @@ int pump(pt_ctx* c, PumpUntil until, int arg) {
         if (part) { HIP_TRY(hipEventRecord(c->evHost, s)); HIP_TRY(hipStreamWaitEvent(sx, c->evHost, 0)); }      // what `s` holds (submission, revive, accumulate) comes first
         for (int k = 0; k < CHECK; k++) {
             PoolRun pr; pr.stream = sx; pr.st = c->st; pr.launched = c->launched; pr.iter = c->iter;
-            const int grid = std::max(1, (int)((pr.launched + BLOCK - 1) / BLOCK));
-            if (c->extendMode == 0) {
-                if (c->countStats) TIMED_LAUNCH_ON(sx, 0, hipLaunchKernelGGL(k_extend<true>, dim3(grid), dim3(BLOCK), ldsBytes, sx, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl));
-                else TIMED_LAUNCH_ON(sx, 0, hipLaunchKernelGGL(k_extend<false>, dim3(grid), dim3(BLOCK), ldsBytes, sx, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl));
-            } else {
-                TIMED_LAUNCH_ON(sx, 0, launchExtendPersist(c, pr));
-            }
+            TIMED_LAUNCH_ON(sx, 0, launchExtend(c, pr, direct, fastNow));
             if (part) { HIP_TRY(hipEventRecord(c->evExt, sx)); HIP_TRY(hipStreamWaitEvent(ss, c->evExt, 0)); }
 #define SHADE_ARGS dim3(std::max(1, (int)((pr.launched + SHADE_BLOCK - 1) / SHADE_BLOCK))), dim3(SHADE_BLOCK), 0, ss, c->sc, b, c->dFc, pr.st, c->dQueue[pr.iter & 1], c->dQueue[(pr.iter + 1) & 1], pr.iter, (int)pr.launched, c->dCtl
             // kernel variant: transmissive materials present / statistics on / RAYTRACING == 0 / texture-mapped materials present
@@ -1957,13 +1880,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     FrameIn fin;
     std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->buf.origin.data(), 12); std::memcpy(fin.rotation, c->buf.rotation.data(), 12); std::memcpy(fin.mouse, c->buf.mouse.data(), 12);
     // the running stream can take this batch if nothing the kernels were launched with changes
-    // overlapped: room for the batches of as many images as can be pending, and for callers that submit frame by frame to run
-    // ahead (at least 64 rows while they stay below 8 GB)
-    int wantRing = nFrames;
-    if (async) {
-        const size_t rowBytes = (size_t)c->nSlotsImg * 16;
-        wantRing = std::max(pt_ctx::IMAGES * nFrames, (int)std::min<size_t>(64, std::max<size_t>(1, ((size_t)8 << 30) / rowBytes)));
-    }
+    const int wantRing = ptp::ringRows(nFrames, async, (size_t)c->nSlotsImg * 16, pt_ctx::IMAGES);
     bool join = !c->pending.empty() && !c->sceneDirty && std::memcmp(&fin, &c->streamIn, sizeof(FrameIn)) == 0 && c->ringFrames >= wantRing && c->streamFast == c->fastContract &&
                 (uint64_t)c->streamJobs + nJobs64 < (1ull << 31);
     if (!join && (rc = flushStream(c))) return rc;
@@ -1973,14 +1890,8 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
             if (c->sc.numObj > FL_PROBE_OBJ_MAX + 1) return fail(PT_ERR_UNSUPPORTED, "directDiffuse with subsurface materials supports at most 65536 objects (BVHs)");
             if (c->ambiguousTriObj) return fail(PT_ERR_SCENE, "directDiffuse with subsurface materials needs every triangle to belong to one BVH (hit.parentID, frag.glsl:573)");
         }
-        if (c->poolSlots > 0) c->poolActive = c->poolSlots;
-        else {                                                    // automatic pool (measured on C3, profiles/): 5/8 of the batch up to 2^23 when batches overlap
-            // (a batch that drains: one slot per job up to 2^22 — a frame at a time, the reference's own loop, takes 16.0 instead of 19.2 ms per
-            //  1080p frame with 2 M instead of 1 M slots, profiles/r02_m_frame_at_a_time_loop.txt: every job then runs from the first iteration)
-            size_t want = std::min<size_t>(std::max<size_t>(async ? nJobs64 * 5 / 8 : nJobs64, (size_t)1 << 20), (size_t)1 << (async ? 23 : 22));
-            c->poolActive = (int)((std::min<size_t>(want, std::max<size_t>(nJobs64, BLOCK)) + BLOCK - 1) / BLOCK * BLOCK);
-        }
-        if ((rc = ensurePool(c, (async && c->poolSlots == 0) ? (1 << 23) : 0))) return rc;
+        c->poolActive = ptp::newStreamPool(nJobs64, async, c->poolSlots);
+        if ((rc = ensurePool(c, ptp::newStreamCapacity(async, c->poolSlots)))) return rc;
         if (c->ringFrames < wantRing) {
             HIP_TRY(hipStreamSynchronize(s));
             c->ringFrames = 0;
@@ -2005,12 +1916,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     bool grown = false;
     if (join && async && c->poolSlots == 0) {
         const uint64_t outstanding = (uint64_t)std::max<int64_t>(0, (int64_t)c->streamJobs - (int64_t)std::min<uint64_t>(c->lastNextJob, c->streamJobs) - c->inflightPredicted) + nJobs64;
-        size_t target = std::min<size_t>(std::max<size_t>(outstanding * 5 / 8, (size_t)1 << 20), (size_t)1 << 23);
-        // an image is cheapest to finish two images later (pt_finish_image): keep an image's jobs worth several pool turnovers
-        if (c->jobsPerImage) target = std::min<size_t>(target, std::max<size_t>((size_t)(c->jobsPerImage * 5 / 8), (size_t)1 << 20));
-        target = std::min<size_t>((target + BLOCK - 1) / BLOCK * BLOCK, (size_t)c->allocSlots);
-        const size_t cap = std::min<size_t>((size_t)1 << 23, (size_t)c->allocSlots);
-        if (target > (size_t)c->poolActive + (size_t)c->poolActive / 4 || (target >= cap && target > (size_t)c->poolActive)) {      // (the last step to the largest pool may be a small one)
+        if (const size_t target = ptp::grownPool(outstanding, c->jobsPerImage, c->allocSlots, c->poolActive)) {
             HIP_TRY(hipMemsetAsync(c->st.G1 + c->poolActive, 0, (target - (size_t)c->poolActive) * 16, s));      // the new slots are dead
             c->poolActive = (int)target;
             grown = true;
@@ -2788,18 +2694,14 @@ namespace {
 // rayScene for the np slots (a multiple of BLOCK) of a probe pool that is no stream's (pt_debug_intersect, the feature records), on the context's stream behind
 // k_frame_setup: the kernel pt_set_option 2 selects, with the exact numeric contract.  A pool with a side record HX in a scene whose intersect kernels do not
 // write one (no ellipsoid carries a mapped material) runs on k_extend, which writes it whenever it is given.
-int probeIntersect(pt_ctx* c, const State& st, size_t np, const FrameIn& fin) {
-    size_t ldsBytes = (size_t)c->sc.ldsNodes * 64 + (size_t)c->sc.ldsTris * 48 + (size_t)c->stackDepth * BLOCK * 4;
+int probeIntersect(pt_ctx* c, const State& st, size_t np) {
+    const size_t ldsBytes = ptp::kExtendLdsBytes(c->sc.ldsNodes, c->sc.ldsTris, c->stackDepth);
     hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, c->stream, c->dCtl);
     if (c->extendMode == 0 || (st.HX && !c->ellipMaps)) {
         hipLaunchKernelGGL(k_extend<false>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), ldsBytes, c->stream, c->sc, st, (const unsigned*)nullptr, 0, (int)np, c->dCtl);
     } else {                                                      // the production kernels (persistent blocks; hand-written or compiled), as pump() launches them
-        std::memcpy(c->streamIn.params, fin.params, 48); c->streamIn.params[9] = 1.0f;      // no thickness probes in this pool
         PoolRun pr; pr.stream = c->stream; pr.st = st; pr.launched = (unsigned)np; pr.iter = 0;
-        c->debugExactExtend = true;
-        TIMED_LAUNCH_ON(c->stream, 0, launchExtendPersist(c, pr));       // (pt_set_timing: scripts/coherence_probe.py times the production kernel on ray sets of its own)
-        c->debugExactExtend = false;
-        std::memset(&c->streamIn, 0xff, sizeof(FrameIn));
+        TIMED_LAUNCH_ON(c->stream, 0, launchExtend(c, pr, false, false));       // no thickness probes in this pool, the exact reciprocal  (pt_set_timing: scripts/coherence_probe.py times the production kernel on ray sets of its own)
     }
     HIP_TRY(hipGetLastError());
     if (!c->asmError.empty()) { const std::string m = c->asmError; c->asmError.clear(); return fail(PT_ERR_HIP, m); }
@@ -2849,7 +2751,7 @@ int pt_debug_intersect(pt_ctx* c, const float* o, const float* d, float* out, si
     fin.params[11] = 0.0f;
     HIP_TRY(hipMemcpy(c->dFrameIn, &fin, sizeof(fin), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);
-    if ((rc = probeIntersect(c, st, np, fin))) return rc;
+    if ((rc = probeIntersect(c, st, np))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     std::vector<float> h(np * 4);
     HIP_TRY(hipMemcpy(h.data(), st.H, np * 16, hipMemcpyDeviceToHost));

@@ -109,14 +109,14 @@ int ensureRecords(pt_ctx* c, pt_ctx::Records& R, const FrameIn& fin, const pt_th
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, c->stream, c->sc, c->dFrameIn, c->dFc, c->dEllip);      // auto-focus, camera and ellipsoid rotations
     hipLaunchKernelGGL(k_feature_rays, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, (const FrameConst*)c->dFc, c->W, c->H, st, (int)np);
     if (!rule) {
-        if ((rc = probeIntersect(c, st, np, fin))) return rc;
+        if ((rc = probeIntersect(c, st, np))) return rc;
         hipLaunchKernelGGL(k_feature_record, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, R.recs.p);
     } else {
         // RAYTRACING == 0 (directDiffuse, frag.glsl:911-912) takes no step
         const int depth = (rule->lobes == 0 || fin.params[9] != 1.0f) ? 0 : rule->max_depth;
         const ThroughRule tr{depth, rule->min_weight, rule->lobes, rule->flags};
         for (int step = 0; step <= depth; step++) {
-            if ((rc = probeIntersect(c, st, np, fin))) return rc;
+            if ((rc = probeIntersect(c, st, np))) return rc;
 #define THROUGH_STEP(T) hipLaunchKernelGGL(k_through_step<T>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), 0, c->stream, c->sc, st, (int)n, tr, step, X.p, (unsigned)np, R.recs.p, R.rays.p)
             if (c->niBits == 3) THROUGH_STEP(3);
             else if (c->niBits == 8) THROUGH_STEP(8);
