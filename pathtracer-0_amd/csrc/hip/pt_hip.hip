@@ -36,6 +36,7 @@
 #include "../../../include/pt_motion.h"
 #include "../../../include/pt_validate.h"
 #include "../../../include/pt_reproject_through.h"
+#include "../../../include/pt_reproject_bilinear.h"
 #include "pt_device.hpp"
 #include "pt_devmem.hpp"
 #include "pt_scene_layout.hpp"

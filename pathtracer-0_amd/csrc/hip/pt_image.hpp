@@ -1,6 +1,6 @@
 // pt_image.hpp — the host half of the image-space passes behind the C ABI (included by pt_hip.hip inside its extern "C" block, where pt_ctx and
 // its helpers are in scope; not a translation unit).  T in pixel order, the feature and seen-through records, the a-trous and the variance-guided
-// filter, the reprojection across camera moves (also through mirror and glass chains) and moved geometry, the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
+// filter, the reprojection across camera moves (also through mirror and glass chains, and with bilinear taps) and moved geometry, the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
 // and pt_reproject.hip's, behind pt_image_launch.hpp; the kernels of the records are pt_hip.hip's.
 
 // ---- T in pixel order (include/pt_adaptive.h, include/pt_guided.h): a group's streams each hold the slots of their own shard, so T travels through the host
@@ -378,9 +378,11 @@ void motionPack(const std::vector<float>& tri, int nTri, const std::vector<float
 // and the primitives' old positions from the mark (which it spends); else include/pt_reproject.h's, Rh from the image's camera.
 // floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor (the unmoved call's: checked by the caller).
 // chain (not moved, floorA 0; checked by the caller): include/pt_reproject_through.h's call, Sn / Yn and Sh / Yh beside Rn and Rh
+// taps (not moved, no chain; snap and floorA checked by the caller): include/pt_reproject_bilinear.h's call, the four old pixels around the projected point
 struct ChainCarry { const pt_through_rule* thru; float pointTol; int radius; int64_t* nKeptThrough; };
+struct BilinearTaps { float snap; int64_t* nBlended; };
 int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept,
-                   const ChainCarry* chain = nullptr) {
+                   const ChainCarry* chain = nullptr, const BilinearTaps* taps = nullptr) {
     const std::string w(who);
     if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, w + ": max_history must be >= 1");
     if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, w + ": depth_tol must be > 0");
@@ -455,6 +457,7 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     j.cam = ReprojCam{{cur.origin[0], cur.origin[1], cur.origin[2]}, cur.mouse[0], cur.mouse[1], cur.params[2]};
     j.rule = ReprojRule{maxHistory, depthTol, normalTol, (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0};
     j.floorA = floorA;
+    if (taps) { j.bilinear = true; j.snap = taps->snap; }
     j.outFrame = on->dRpFrame; j.outStats = j.stats ? on->dRpStats.p : nullptr; j.kept = on->dRpKept;
     HIP_TRY(reprojectLaunch(j, on->stream));
     if (moved) HIP_TRY(hipStreamSynchronize(on->stream));         // (pt / pe leave scope: their copies have landed)
@@ -463,6 +466,12 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
         HIP_TRY(hipMemcpyAsync(&keptThrough, on->dRpKept + 1, 4, hipMemcpyDeviceToHost, on->stream));
         HIP_TRY(hipStreamSynchronize(on->stream));
         *chain->nKeptThrough = keptThrough;
+    }
+    if (taps) {
+        unsigned blended = 0;
+        HIP_TRY(hipMemcpyAsync(&blended, on->dRpKept + 1, 4, hipMemcpyDeviceToHost, on->stream));
+        HIP_TRY(hipStreamSynchronize(on->stream));
+        *taps->nBlended = blended;
     }
     if ((rc = storeReprojected(c, on, j.stats != nullptr, nKept))) return rc;
     if (moved) m.valid = false;                                   // spent
@@ -500,6 +509,22 @@ int pt_reproject_frame_through(pt_ctx* c, const pt_through_rule* thru, const pt_
     const int rc = reprojectImage(c, "pt_reproject_frame_through", false, rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags, 0.0f, &n, &chain);
     if (n_kept) *n_kept = n;
     if (n_kept_through) *n_kept_through = rc ? 0 : nt;
+    return rc;
+}
+
+// ---- include/pt_reproject_bilinear.h
+int pt_reproject_frame_bilinear(pt_ctx* c, const pt_reproject_bilinear_rule* rule, int64_t* n_kept, int64_t* n_blended) {
+    if (n_kept) *n_kept = 0;
+    if (n_blended) *n_blended = 0;
+    if (!c || !rule) return fail(PT_ERR_ARG, "pt_reproject_frame_bilinear: null argument");
+    if (!(rule->snap >= 0.0f && rule->snap < 0.5f)) return fail(PT_ERR_ARG, "pt_reproject_frame_bilinear: rule.snap must be in [0, 0.5)");
+    if (!fillFloorOk(rule->albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_bilinear: rule.albedo_floor must be 0 or finite and > 0");
+    int64_t n = 0, nb = 0;
+    const BilinearTaps taps{rule->snap, &nb};
+    const int rc = reprojectImage(c, "pt_reproject_frame_bilinear", false, rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags,
+                                  rule->albedo_floor, &n, nullptr, &taps);
+    if (n_kept) *n_kept = n;
+    if (n_blended) *n_blended = rc ? 0 : nb;
     return rc;
 }
 

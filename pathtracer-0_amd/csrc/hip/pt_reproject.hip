@@ -1,5 +1,5 @@
-// pt_reproject.hip — the reprojection of include/pt_reproject.h and include/pt_reproject_through.h and the history validation of include/pt_validate.h
-// for gfx950.
+// pt_reproject.hip — the reprojection of include/pt_reproject.h, include/pt_reproject_through.h and include/pt_reproject_bilinear.h and the history
+// validation of include/pt_validate.h for gfx950.
 //
 // Device pointers only: pt_hip.hip owns the buffers, computes both sets of feature records and calls reprojectLaunch on its stream.
 //   k_reproject<MOVED, DEMOD>  one lane per new pixel, a wave = 64 pixels of a row, a block = 16 rows.  Reads 48 B of Rn[p] (F0, F1.w, F2), the same
@@ -9,6 +9,8 @@
 //                <false, false>  include/pt_reproject.h
 //                <false, true>   include/pt_demod.h: step 7 carries illumination
 //                <true, DEMOD>   include/pt_motion.h: the hit's surface point followed back to where its primitive was at the mark
+//   k_reproject_bilinear<DEMOD>  include/pt_reproject_bilinear.h: the same lanes and blocks; each lane blends up to four old pixels around the projected
+//                point (4 x (24 or 36 B of Rh, FRAME, T), all loaded before the first test) and counts the kept and the blended pixels as k_reproject counts.
 //   k_history_merge<R>  include/pt_validate.h: one lane per pixel in the same blocks.  The block's tile with its halo of R pixels is staged in LDS
 //                once, as ten planes of floats (the six moments, zeroed where a pixel can be no tap for any centre; the normal; one class /
 //                material word), so that a tap costs ten LDS reads of consecutive words per wave and no global load; then steps 1-4 and the
@@ -197,6 +199,162 @@ __global__ void __launch_bounds__(RP_BX * RP_BY) k_reproject(const float4* __res
     if (threadIdx.x == 0 && m) atomicAdd(&blockKept, (unsigned)__popcll(m));
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0 && blockKept) atomicAdd(kept, blockKept);
+}
+
+// include/pt_reproject_bilinear.h, step 5 along one axis: the first tap's coordinate (-1 .. size - 1) and the second tap's weight after snapping
+__device__ __forceinline__ int bilinearAxis(float s, float snap, float& w) {
+    const float f = s - 0.5f;
+    float c0 = floorf(f);
+    w = f - c0;
+    if (w < snap) w = 0.0f;
+    else if (w > 1.0f - snap) { c0 = c0 + 1.0f; w = 0.0f; }
+    return (int)c0;
+}
+// One tap of include/pt_reproject_bilinear.h: what the lane loaded of old pixel s (clamped into the image, so every load is in range) and its weight.
+// Of Rh[s]: h0 = F0 (t', N'), h1 = all of F1 when DEMOD, else the hit code in its w, mat = the material word of F2 — what step 5 and the carried albedo read.
+struct BilinearTap { float4 h0, h1, F, T; int mat; float w; bool in; };
+
+// Steps 1-9 of include/pt_reproject_bilinear.h and both counts.  A new kernel beside k_reproject, which stays the code object it was: steps 1-4 are
+// its unmoved path word for word.  Per lane: Rn[p] once, then of each of the four taps the 24 B of Rh[s] that step 5 reads (36 B with DEMOD: Kd too),
+// FRAME (16 B) and T (16 B), loaded from clamped addresses before the first test and without a branch between them, so that the twenty loads are in
+// flight together; the two x-taps of a row are adjacent 64-B records.  (Loading all 48 B of F0 .. F2 made the compiler reuse the registers of the
+// unread D' while the load was in flight, with a wait in front of every tap.)  A context without T reads FRAME in T's place and ignores it.
+// The taps and the accumulators are scalars (four named structs, no indexed array), so nothing lives on the stack.  kept[0] takes
+// the kept pixels, kept[1] those blended from two or more taps: k_reproject's scheme, a ballot popcount per wave, an LDS sum, one atomic per block
+// and counter.
+template <bool DEMOD>
+__global__ void __launch_bounds__(RP_BX * RP_BY) k_reproject_bilinear(const float4* __restrict__ rn, const float4* __restrict__ rh, const float4* __restrict__ frame,
+                                                                     const float4* __restrict__ stats, const FrameConst* __restrict__ hc,
+                                                                     const unsigned char* __restrict__ matVD, int nMat, int W, int H, ReprojCam cam, ReprojRule r,
+                                                                     float snap, float floorA, float4* __restrict__ outFrame, float4* __restrict__ outStats,
+                                                                     unsigned* __restrict__ kept) {
+    __shared__ unsigned blockKept, blockBlended;
+    if (threadIdx.x == 0 && threadIdx.y == 0) { blockKept = 0; blockBlended = 0; }
+    __syncthreads();
+    const int x = blockIdx.x * RP_BX + threadIdx.x, y = blockIdx.y * RP_BY + threadIdx.y;
+    const bool in = x < W && y < H;
+    const size_t p = (size_t)y * W + x;
+    bool keep = false, blended = false;
+    float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f, f3 = 0.0f, t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f;      // the new FRAME and T
+    const float* M = hc->camRot;                                                           // the image's camera, as k_frame_setup built it
+    const float O0 = hc->origin[0], O1 = hc->origin[1], O2 = hc->origin[2], ss = hc->screenSize, fl = hc->focalLength, hr = hc->screenHratio;
+    FrameConst fc;
+    fc.mouse[0] = cam.mouseX; fc.mouse[1] = cam.mouseY; fc.resolution = cam.resolution;
+    if (in && !inMouseOverlay(fc, x, y)) {                                                 // 1
+        const float4 n0 = rn[4 * p], n2 = rn[4 * p + 2];
+        const float4 n1 = loadF1<DEMOD>(rn + 4 * p);
+        const bool hit = __float_as_int(n1.w) != -1;                                       // 2
+        const int mat = __float_as_int(n2.w);
+        bool ok;
+        float vx, vy, vz;
+        if (hit) {
+            ok = __builtin_isfinite(n0.x) && finite3(n0.y, n0.z, n0.w) && finite3(n2.x, n2.y, n2.z) && (unsigned)mat < (unsigned)nMat &&
+                 (r.allMaterials || !matVD[mat]);
+            vx = (cam.On[0] + n0.x * n2.x) - O0; vy = (cam.On[1] + n0.x * n2.y) - O1; vz = (cam.On[2] + n0.x * n2.z) - O2;
+        } else {
+            ok = true;
+            vx = n2.x; vy = n2.y; vz = n2.z;
+        }
+        const float q0 = (vx * M[0] + vy * M[1]) + vz * M[2];                                  // 3
+        const float q1 = (vx * M[3] + vy * M[4]) + vz * M[5];
+        const float q2 = (vx * M[6] + vy * M[7]) + vz * M[8];
+        const float a = (q0 / q2) * fl, b = (q1 / q2) * fl;                                   // 4
+        const float sx = ((1.0f - a / ss) * 0.5f) * (float)W, sy = ((1.0f + b / (hr * ss)) * 0.5f) * (float)H;
+        ok = ok && q2 > 0.0f && sx >= 0.0f && sx < (float)W && sy >= 0.0f && sy < (float)H;
+        if (ok) {
+            float wx, wy;                                                                  // 5
+            const int ix = bilinearAxis(sx, snap, wx), iy = bilinearAxis(sy, snap, wy);
+            const float ax0 = 1.0f - wx, ay0 = 1.0f - wy;
+            const int cx0 = min(max(ix, 0), W - 1), cx1 = min(max(ix + 1, 0), W - 1), cy0 = min(max(iy, 0), H - 1), cy1 = min(max(iy + 1, 0), H - 1);
+            const bool inx0 = ix >= 0 && ix < W, inx1 = ix + 1 < W, iny0 = iy >= 0 && iy < H, iny1 = iy + 1 < H;      // (ix, iy >= -1)
+            const bool hasT = stats != nullptr;
+            const float4* __restrict__ tsrc = hasT ? stats : frame;
+            auto load = [&](int cx, int cy, float w, bool inside) {
+                const size_t s = (size_t)cy * W + cx;
+                BilinearTap t;
+                t.h0 = rh[4 * s]; t.h1 = loadF1<DEMOD>(rh + 4 * s); t.mat = __float_as_int(reinterpret_cast<const float*>(rh + 4 * s)[11]);
+                t.F = frame[s];
+                t.T = tsrc[s];
+                t.w = w; t.in = inside;
+                return t;
+            };
+            const BilinearTap ta = load(cx0, cy0, ax0 * ay0, inx0 && iny0), tb = load(cx1, cy0, wx * ay0, inx1 && iny0);
+            const BilinearTap tc = load(cx0, cy1, ax0 * wy, inx0 && iny1), td = load(cx1, cy1, wx * wy, inx1 && iny1);
+            const float len = sqrtf((vx * vx + vy * vy) + vz * vz);
+            auto counts = [&](const BilinearTap& t) {
+                const bool hhit = __float_as_int(t.h1.w) != -1;
+                const bool same = hit ? hhit && t.mat == mat && __builtin_isfinite(t.h0.x) && t.h0.x > 0.0f &&
+                                            __builtin_fabsf(len - t.h0.x) <= r.depthTol * t.h0.x && (n0.y * t.h0.y + n0.z * t.h0.z) + n0.w * t.h0.w >= r.normalTol
+                                      : !hhit;
+                return t.w > 0.0f && t.in && same && t.F.w > 0.0f && finite3(t.F.x, t.F.y, t.F.z);
+            };
+            const bool ca = counts(ta), cb = counts(tb), cc = counts(tc), cd = counts(td);
+            const int nc = (int)ca + (int)cb + (int)cc + (int)cd;
+            float3 bn = make_float3(1.0f, 1.0f, 1.0f);
+            if constexpr (DEMOD) bn = carriedAlbedo(n1, floorA);
+            if (nc == 1) {                                                                 // 7: k_reproject's step 7 from the one tap
+                const float4 F = ca ? ta.F : cb ? tb.F : cc ? tc.F : td.F;
+                const float4 T = ca ? ta.T : cb ? tb.T : cc ? tc.T : td.T;
+                if constexpr (DEMOD) {
+                    const float4 h1 = ca ? ta.h1 : cb ? tb.h1 : cc ? tc.h1 : td.h1;
+                    const float3 bh = carriedAlbedo(h1, floorA);
+                    f0 = F.x * (bn.x / bh.x); f1 = F.y * (bn.y / bh.y); f2 = F.z * (bn.z / bh.z); f3 = F.w;
+                    if (F.w > r.maxHistory) { const float f = r.maxHistory / F.w; f0 = f0 * f; f1 = f1 * f; f2 = f2 * f; f3 = r.maxHistory; }
+                    if (hasT) {
+                        const float rho = lum(bn.x, bn.y, bn.z) / lum(bh.x, bh.y, bh.z);
+                        t0 = T.x * rho; t1 = (T.y * rho) * rho; t2 = T.z; t3 = T.w;
+                        if (T.z > r.maxHistory) { const float gg = r.maxHistory / T.z; t0 = t0 * gg; t1 = t1 * gg; t2 = r.maxHistory; }
+                    }
+                } else {
+                    f0 = F.x; f1 = F.y; f2 = F.z; f3 = F.w;
+                    if (F.w > r.maxHistory) { const float f = r.maxHistory / F.w; f0 = F.x * f; f1 = F.y * f; f2 = F.z * f; f3 = r.maxHistory; }
+                    if (hasT) {
+                        t0 = T.x; t1 = T.y; t2 = T.z; t3 = T.w;
+                        if (T.z > r.maxHistory) { const float gg = r.maxHistory / T.z; t0 = T.x * gg; t1 = T.y * gg; t2 = r.maxHistory; }
+                    }
+                }
+            } else if (nc >= 2) {                                                          // 8, 9: a tap that does not count adds +0, which changes no bit of a sum that began at +0
+                float Ws = 0.0f, A = 0.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, WT = 0.0f, NT = 0.0f, Y = 0.0f, YY = 0.0f;
+                auto add = [&](const BilinearTap& t, bool c) {
+                    float m0 = t.F.x / t.F.w, m1 = t.F.y / t.F.w, m2 = t.F.z / t.F.w;
+                    float rho = 1.0f;
+                    if constexpr (DEMOD) {
+                        const float3 bh = carriedAlbedo(t.h1, floorA);
+                        m0 = m0 * (bn.x / bh.x); m1 = m1 * (bn.y / bh.y); m2 = m2 * (bn.z / bh.z);
+                        rho = lum(bn.x, bn.y, bn.z) / lum(bh.x, bh.y, bh.z);
+                    }
+                    Ws = Ws + (c ? t.w : 0.0f); A = A + (c ? t.w * t.F.w : 0.0f);
+                    C0 = C0 + (c ? t.w * m0 : 0.0f); C1 = C1 + (c ? t.w * m1 : 0.0f); C2 = C2 + (c ? t.w * m2 : 0.0f);
+                    const bool ct = hasT && c && t.T.z > 0.0f && __builtin_isfinite(t.T.x) && __builtin_isfinite(t.T.y);
+                    float yv = t.T.x / t.T.z, yy = t.T.y / t.T.z;
+                    if constexpr (DEMOD) { yv = yv * rho; yy = (yy * rho) * rho; }
+                    WT = WT + (ct ? t.w : 0.0f); NT = NT + (ct ? t.w * t.T.z : 0.0f); Y = Y + (ct ? t.w * yv : 0.0f); YY = YY + (ct ? t.w * yy : 0.0f);
+                };
+                add(ta, ca); add(tb, cb); add(tc, cc); add(td, cd);
+                const float n = A / Ws, nn = n > r.maxHistory ? r.maxHistory : n;
+                f0 = (C0 / Ws) * nn; f1 = (C1 / Ws) * nn; f2 = (C2 / Ws) * nn; f3 = nn;
+                if (WT > 0.0f) {
+                    const float nT = NT / WT, nt = nT > r.maxHistory ? r.maxHistory : nT;
+                    t0 = (Y / WT) * nt; t1 = (YY / WT) * nt; t2 = nt; t3 = 0.0f;
+                }
+                blended = true;
+            }
+            ok = nc >= 1;                                                                  // 6
+        }
+        keep = ok;
+    }
+    if (in) {
+        outFrame[p] = keep ? make_float4(f0, f1, f2, f3) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (outStats) outStats[p] = keep ? make_float4(t0, t1, t2, t3) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    const unsigned long long m = __ballot(keep), mb = __ballot(blended);                   // every lane of the block, in range or not
+    if (threadIdx.x == 0 && m) atomicAdd(&blockKept, (unsigned)__popcll(m));
+    if (threadIdx.x == 0 && mb) atomicAdd(&blockBlended, (unsigned)__popcll(mb));
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        if (blockKept) atomicAdd(kept, blockKept);
+        if (blockBlended) atomicAdd(kept + 1, blockBlended);
+    }
 }
 
 // max(x, 0) of include/pt_guided.h: a NaN is no estimate
@@ -396,9 +554,17 @@ __global__ void __launch_bounds__(RP_BX * RP_BY) k_reproject_chain(const float4*
 
 // floorA > 0 alone selects the demodulated step 7, `motion` alone the followed-back step 2
 hipError_t reprojectLaunch(const ReprojectJob& j, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(j.kept, 0, j.sn ? 8 : 4, s);
+    hipError_t e = hipMemsetAsync(j.kept, 0, j.sn || j.bilinear ? 8 : 4, s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((j.W + RP_BX - 1) / RP_BX), (unsigned)((j.H + RP_BY - 1) / RP_BY)), block(RP_BX, RP_BY);
+    if (j.bilinear) {                                                                      // include/pt_reproject_bilinear.h: a mapping of its own, kept[1] = the blended pixels
+        if (j.motion || j.sn) return hipErrorInvalidValue;
+#define RB_ARGS j.rn, j.rh, j.frame, j.stats, j.hist, j.matVD, j.nMat, j.W, j.H, j.cam, j.rule, j.snap, j.floorA, j.outFrame, j.outStats, j.kept
+        if (j.floorA > 0.0f) hipLaunchKernelGGL(k_reproject_bilinear<true>, grid, block, 0, s, RB_ARGS);
+        else hipLaunchKernelGGL(k_reproject_bilinear<false>, grid, block, 0, s, RB_ARGS);
+#undef RB_ARGS
+        return hipGetLastError();
+    }
     const bool demod = j.floorA > 0.0f;
 #define RP_IN j.rn, j.rh, j.frame, j.stats, j.hist, j.matVD, j.nMat, j.W, j.H, j.cam, j.rule
 #define RP_OUT j.outFrame, j.outStats, j.kept

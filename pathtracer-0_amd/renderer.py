@@ -168,6 +168,8 @@ def lib():
             L.pt_history_merge.argtypes = [vp, C.POINTER(ValidateRule), vp, C.POINTER(C.c_int64)]
         if hasattr(L, "pt_reproject_frame_through"):          # include/pt_reproject_through.h
             L.pt_reproject_frame_through.argtypes = [vp, C.POINTER(ThroughRule), C.POINTER(ReprojectThroughRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_reproject_frame_bilinear"):         # include/pt_reproject_bilinear.h
+            L.pt_reproject_frame_bilinear.argtypes = [vp, C.POINTER(ReprojectBilinearRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -191,6 +193,12 @@ class ValidateRule(C.Structure):
 class ReprojectThroughRule(C.Structure):
     """pt_reproject_through_rule of include/pt_reproject_through.h"""
     _fields_ = [("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_tol", C.c_float), ("point_tol", C.c_float), ("radius", C.c_int),
+                ("flags", C.c_int)]
+
+
+class ReprojectBilinearRule(C.Structure):
+    """pt_reproject_bilinear_rule of include/pt_reproject_bilinear.h"""
+    _fields_ = [("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_tol", C.c_float), ("snap", C.c_float), ("albedo_floor", C.c_float),
                 ("flags", C.c_int)]
 
 
@@ -426,6 +434,20 @@ class Renderer:
         n, nt = C.c_int64(0), C.c_int64(0)
         _check(self._L.pt_reproject_frame_through(self._h, C.byref(thru), C.byref(rule), C.byref(n), C.byref(nt)))
         return n.value, nt.value
+
+    # --- reprojection with bilinear taps (include/pt_reproject_bilinear.h) --------------------------
+    def reproject_frame_bilinear(self, max_history=64, depth_tol=0.02, normal_tol=0.9, snap=1 / 64, all_materials=False, albedo_floor=0.0):
+        """reproject_frame that blends the qualifying old pixels around the projected point with bilinear weights (pt_reproject_frame_bilinear)
+        where reproject_frame copies the nearest one: no half-pixel snapping under a slow move, and a pixel restarts only when none of its up
+        to four taps passes.  snap: a projected point closer than this (in pixels) to an old pixel's centre is that pixel, which keeps an
+        unchanged camera the identity; the default stays far above the rounding of the projection.  albedo_floor 0: the plain
+        carry; > 0: include/pt_demod.h's.  Returns (kept, blended): the pixels that kept history, and those among them blended from two or
+        more old pixels.  Counts become fractional, as after history_merge."""
+        rule = ReprojectBilinearRule(float(max_history), float(depth_tol), float(normal_tol), float(snap), float(albedo_floor),
+                                     self.REPROJECT_ALL_MATERIALS if all_materials else 0)
+        n, nb = C.c_int64(0), C.c_int64(0)
+        _check(self._L.pt_reproject_frame_bilinear(self._h, C.byref(rule), C.byref(n), C.byref(nb)))
+        return n.value, nb.value
 
     # --- reprojection across moved geometry (include/pt_motion.h) ----------------------------------
     def motion_mark(self):
