@@ -22,7 +22,8 @@
  * own L) are unchanged, and the albedo edge term still compares the raw Kd (sigma_albedo = +inf switches it off, the natural setting here).
  * The result (I_K, v_K) gives the output rgb = a_p * I_K per component, a = FRAME.a.  Invalid pixels are passed through as include/pt_denoise.h
  * passes them.  iterations 0 gives a_p * (c_p / a_p), two correctly rounded operations: within 2 ulp of the mean, not bit-identical to it.
- * Like pt_denoise_guided not under the bit-exact contract (__expf, sqrtf, the device's summation order); a float32 model agrees to about 1e-4.
+ * Like pt_denoise_guided not under the bit-exact contract (__expf, sqrtf, the device's summation order) but within the bound of
+ * tests/_guided_ref64.py on I_K, times a_p, plus the rounding of the last product; nearly converged pixels as include/pt_guided.h says.
  *
  * Selection.  Steps 1-4 of include/pt_steer.h unchanged, on the raw T.  Step 5: c_K = a_p * I_K, tol = fmaxf(rel_err * fabsf(l(c_K)), abs_err),
  * active iff v_K == +inf or (v_K * L_p) * L_p > tol * tol; a NaN is inactive.  (v_K is a variance of illumination; L_p^2 brings it back to colour.)

@@ -33,8 +33,11 @@
  *     c'_p = sum w c_q / sum w
  *     v'_p = sum w^2 v_q / (sum w)^2, and +inf when a tap that is not skipped has v_q = +inf
  *   Output: (c_K, FRAME.a) per pixel.  iterations 0 is the identity (the mean).
- * Not under the bit-exact contract of the render path, as pt_denoise: the device uses __expf and sqrtf and sums in its own order; a float32
- * model of the text above agrees to about 1e-4 relative.
+ * Not under the bit-exact contract of the render path, as pt_denoise: the device uses __expf and sqrtf and sums in its own order.  What it is
+ * held to instead is the per-pixel bound that tests/_guided_ref64.py derives against a float64 evaluation of the text above: a few hundred
+ * 2^-24 of the colours a pixel's passes reach where the filter is well conditioned.  A nearly converged pixel is not: sqrt(g_p) is small there,
+ * a rounding of l(c) of a few 2^-24 moves e_c by 1e-3 and more, and the error compounds from pass to pass; the bound follows that, up to the
+ * spread of the taps the pixel may take, and is no promise of 1e-4 there.
  */
 #ifndef PT_GUIDED_H
 #define PT_GUIDED_H

@@ -18,8 +18,9 @@
  *   5. otherwise: (c_K, v_K) = the mean and the carried variance of p after K = iterations passes of include/pt_guided.h's filter with the
  *      rule's sigmas and min_frames (K = 0: c_0 = the mean, v_0 = s2 / A); tol = fmaxf(rel_err * fabsf(l(c_K)), abs_err); active iff
  *      v_K == +inf or v_K > tol*tol.  A NaN v_K is inactive.
- * Step 5 inherits the filter's contract: not bit-exact (__expf, sqrtf, the device's summation order), a float32 model of the text agrees to
- * about 1e-4 relative, so a pixel whose v_K lies that close to tol*tol may fall on either side.  Steps 1-4 are exact.
+ * Step 5 inherits the filter's contract: not bit-exact (__expf, sqrtf, the device's summation order) but within the per-pixel bounds on c_K and
+ * v_K that tests/_guided_ref64.py derives (wide on nearly converged pixels, see include/pt_guided.h), so a pixel whose v_K lies within them of
+ * tol*tol may fall on either side.  Steps 1-4 are exact.
  * The rule assumes every frame of the image went into T: pt_render_mask and pt_render_adaptive_guided guarantee it; frames of pt_render /
  * pt_render_batch / pt_render_batch_async do only while moment recording is on (pt_record_moments, include/pt_guided.h).
  */
