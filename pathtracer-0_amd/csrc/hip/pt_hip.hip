@@ -18,7 +18,7 @@
 //   k_scan_inflight is a live slot still on a frame of the oldest unaccumulated batch? (one pass per host poll)
 //   k_accumulate    FRAME accumulation (:924-933) of one batch in u_frameCount order -> bit-identical to
 //                   frame-at-a-time rendering
-// and a host-side frame-stream scheduler (submitBatch / pump / retireFront below): consecutive batches share one running
+// and a host-side frame-stream scheduler (pt_stream_sched.hpp; submitBatch and StreamDev below are its device side): consecutive batches share one running
 // path pool; the host launches iterations in groups and polls the device's scheduler words (Control).
 //
 // Path state is structure-of-arrays in float4 groups (16 B per lane per access = 1 KiB per wave
@@ -41,11 +41,11 @@
 #include "pt_devmem.hpp"
 #include "pt_scene_layout.hpp"
 #include "pt_launch_plan.hpp"
+#include "pt_stream_sched.hpp"
 #include "pt_image_launch.hpp"
 
 #include <algorithm>
 #include <cstddef>
-#include <deque>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -1246,25 +1246,17 @@ struct pt_ctx {
     Dev<float4> dImage[IMAGES]; int curImage = 0;      // FRAME images (more than one only after pt_next_image)
     // path pool
     int poolSlots = 0;              // 0 = automatic: jobs/5 clamped to [2^20, 2^22] (enough rays per lane for the in-wave refill, short tail)
-    int poolActive = 0; int allocSlots = 0; int allocNiBits = -1; bool allocHX = false;
+    int allocSlots = 0; int allocNiBits = -1; bool allocHX = false;
     State st{};                     // the pool as the kernels take it; its groups are owned by dPool (in the order of ensurePool) and dPoolJ
     Dev<float4> dPool[9]; Dev<uint2> dPoolJ;
     Dev<unsigned> dQueue[2];        // dense slot queues of the batch tail, by iteration parity
     Dev<float4> dColbuf; Dev<int> dSeeds; int ringFrames = 0;      // per-frame rings of the stream (Batch)
-    // frame-stream scheduler (host view)
-    struct Entry { unsigned jobEnd, f0; int nFrames, firstFrame, image; };      // a submitted, not yet accumulated batch
-    std::deque<Entry> pending;
+    // frame-stream scheduler: its host view (pt_stream_sched.hpp), and what the device side of it needs
+    ptp::StreamSched sched;
     FrameIn streamIn{};             // frame inputs the running stream was started with
-    unsigned streamFrames = 0, streamJobs = 0, lastNextJob = 0, lastDelta = 0, launched = 0; int lastCheck = 24, iter = 0; bool draining = false;
-    uint64_t lastSubmitJobs = 0, jobsThisImage = 0, jobsPerImage = 0;      // what the last submission added; jobs submitted for the current / the previous FRAME image
     Dev<FrameIn> dFrameIn; Dev<FrameConst> dFc; Dev<Control> dCtl;
-    // The host looks at the device's scheduler words once per GROUP of iterations: a group = its launches + (a scan of the oldest batches) + k_snapshot, which writes
-    // Control into the group's pinned snapshot and then the group's number into the group's pinned STAMP.  Up to two groups are in flight: the host looks at a snapshot when
-    // its stamp has arrived, so the stream always holds the next group's launches while one runs, and an asynchronous submission never waits for the iterations it started
-    // (pump).
-    struct Group { Pinned<Control, hipHostMallocCoherent> h; Pinned<volatile unsigned, hipHostMallocCoherent> stamp; unsigned seq = 0; int check = 0, iterEnd = 0, nScan = 0; unsigned scanF0 = 0, epoch = 0; int64_t predicted = 0; };
-    Group grp[2]; int grpHead = 0, grpCount = 0; bool scanInFlight = false; unsigned submitEpoch = 0, groupSeq = 0;
-    int64_t inflightPredicted = 0;  // jobs the groups in flight are expected to hand out (iterations x the rate of the last look): lastNextJob is as old as the oldest of them
+    // per group in flight (StreamSched::grp, by slot): k_snapshot writes Control into the pinned snapshot and then the group's number into the pinned STAMP
+    struct GroupPins { Pinned<Control, hipHostMallocCoherent> h; Pinned<volatile unsigned, hipHostMallocCoherent> stamp; } grp[2];
     Pinned<FrameIn> hFrameIn; Pinned<int32_t> hSeeds;   // pinned staging (hSeeds: ring like dSeeds)
     // options / stats
     bool countStats = false, timing = false;
@@ -1395,7 +1387,7 @@ int buildScene(pt_ctx* c) {
 }
 
 int ensurePool(pt_ctx* c, int capacity) {               // capacity >= poolActive: room for a pool that grows while a stream runs
-    capacity = std::max(capacity, c->poolActive);
+    capacity = std::max(capacity, c->sched.poolActive);
     if (c->allocSlots >= capacity && c->allocNiBits == c->niBits && c->allocHX == c->ellipMaps) return 0;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->allocSlots = 0;                                            // until every allocation below has succeeded there is no pool
@@ -1459,7 +1451,7 @@ static_assert(sizeof(EllipRec) == 128 && offsetof(EllipRec, rotated) == 32 && of
 #endif
 #include PT_EXTEND_INC              // the assembled code objects (build.py): pt_extend_hsaco_s16[], pt_extend_hsaco_p18[]
 
-// One code object per variant, loaded when a launch first needs it (a stream uses one or two of the eight).  A variant that failed to load stays
+// One code object per variant, loaded when a launch first needs it (a stream uses one or two of the eighteen).  A variant that failed to load stays
 // failed: the error is latched, nothing half-loaded is kept and later launches do not retry.
 int loadAsmKernel(pt_ctx* c, int k) {
     if (c->asmFn[k]) return 0;
@@ -1538,13 +1530,9 @@ void launchExtend(pt_ctx* c, const PoolRun& pr, bool probes, bool fast) {
     else hipLaunchKernelGGL(k_extend<false>, dim3(p.grid), dim3(BLOCK), p.lds, pr.stream, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl);
 }
 
-// ------------------------------------------------------------------------------------------------ frame-stream scheduler
-// A batch is SUBMITTED (its jobs are appended to the running stream, or a new stream starts) and later RETIRED (all its
-// pixel-frame jobs done -> k_accumulate adds its frames to the FRAME image, in u_frameCount order).  Between the two the host
-// only PUMPS: it launches iterations (intersect + shade) in groups and polls the scheduler words after each group.
-//   pt_render_batch        = submit + pump until the batch is retired
-//   pt_render_batch_async  = submit + pump until most of its jobs have been handed out; the rest, and the jobs still in flight,
-//                            are finished underneath the next batch (or by pt_finish_image / any synchronous entry point)
+// ------------------------------------------------------------------------------------------------ frame stream
+// Which batch joins the running stream, the groups of iterations, the looks at the device's scheduler words and the retirements are decided in
+// pt_stream_sched.hpp (pt_ctx::sched); what follows is the device side of it.
 
 Batch streamBatch(const pt_ctx* c) {
     Batch b;
@@ -1555,23 +1543,6 @@ Batch streamBatch(const pt_ctx* c) {
     if (b.nLocal >= 2) { const ptp::MagicDiv dm = ptp::magicDiv((unsigned)b.nLocal); b.divM = dm.m; b.divS = dm.s; }      // exact for every job < 2^31
     else { b.divM = 0; b.divS = 0; }
     return b;
-}
-
-int retireFront(pt_ctx* c) {
-    const pt_ctx::Entry e = c->pending.front();
-    c->pending.pop_front();
-    hipStream_t s = c->stream;
-    Batch b = streamBatch(c);
-    if (c->adaptOn) {
-        TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_adaptive, dim3((c->adaptN + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, b, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    int gridA = (c->nSlotsImg + BLOCK - 1) / BLOCK;
-    if (c->recordMoments && e.image == c->curImage) TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_moments, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
-    else TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], e.f0, e.nFrames, e.firstFrame));
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
 // The streams of destroyed contexts are kept for later contexts of the process instead of being destroyed.  hipStreamDestroy right behind a long asynchronous run —
@@ -1618,106 +1589,24 @@ int ensurePartition(pt_ctx* c) {
     return 0;
 }
 
-enum PumpUntil { PUMP_IDLE, PUMP_ISSUED, PUMP_IMAGE, PUMP_RING };
-// PUMP_IDLE: every batch retired.  PUMP_ISSUED: the jobs not yet handed out fit into roughly one more group of iterations
-// (never waits for the pool to run dry).  PUMP_IMAGE: no unretired batch targets image `arg`.  PUMP_RING: at most `arg` ring
-// rows are still owned by unretired batches.
-// The oldest group in flight: its snapshot of Control, once its stamp has arrived (wait = false: only if it already has).  1 = looked at, 0 = not ready yet, < 0 = PT_ERR_*.
-int processOldestGroup(pt_ctx* c, bool wait, bool discard) {
-    pt_ctx::Group& g = c->grp[(c->grpHead + 2 - c->grpCount) % 2];
-    // has the group's stamp arrived?  (k_snapshot writes it behind a system-scope fence after the snapshot; pinned coherent memory needs no synchronisation to be read)
-    auto landed = [&]() { return *g.stamp == g.seq; };
-    if (!landed()) {
-        if (!wait) return 0;
-        for (int spin = 0; spin < 4000 && !landed(); spin++) __builtin_ia32_pause();
-        for (uint64_t n = 0; !landed(); n++) {
-            std::this_thread::sleep_for(std::chrono::microseconds(n < 100 ? 20 : 100));
-            if ((n & 1023) == 1023) {                              // every ~0.1 s: is the stream still working?  an idle stream without the stamp is a lost launch, an error a fault
-                const hipError_t q = hipStreamQuery(c->stream);
-                if (q != hipSuccess && q != hipErrorNotReady) return fail(PT_ERR_HIP, std::string("the wavefront stream failed: ") + hipGetErrorString(q));
-                if (q == hipSuccess && !landed()) return fail(PT_ERR_HIP, "the wavefront stream is idle but a group's snapshot never arrived (internal error)");
-            }
-        }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    c->grpCount--;
-    if (g.nScan) c->scanInFlight = false;
-    c->inflightPredicted = std::max<int64_t>(0, c->inflightPredicted - g.predicted);
-    if (discard) return 1;
-    const Control& h = *g.h;
-    c->lastDelta = h.nextJob >= c->lastNextJob ? h.nextJob - c->lastNextJob : 0; c->lastCheck = g.check;
-    c->lastNextJob = h.nextJob;
-    bool allDead = false;
-    if (g.epoch == c->submitEpoch) {                               // nothing was submitted since the group was launched: its view of the tail is the stream's
-        if (h.exhausted[(g.iterEnd + 3) & 3]) {                    // the iteration after the group reads the queue: its count is exact (and only falls from there)
-            c->draining = true;
-            c->launched = h.qCount[32 * (g.iterEnd & 1)];
-            allDead = c->launched == 0;
-        } else if (h.nextJob >= c->streamJobs) {
-            c->draining = true;                                    // jobs just ran out; the queue starts within two iterations
-        }
-    }
-    int rc;
-    if (allDead) { while (!c->pending.empty()) if ((rc = retireFront(c))) return rc; }
-    else if (g.nScan && !c->pending.empty() && c->pending.front().f0 == g.scanF0) {
-        for (int k = 0; k < g.nScan && !c->pending.empty() && !h.busy[k]; k++) if ((rc = retireFront(c))) return rc;      // in u_frameCount order, oldest first
-    }
-    return 1;
-}
-int drainGroups(pt_ctx* c, bool discard) {
-    while (c->grpCount > 0) { const int r = processOldestGroup(c, true, discard); if (r < 0) return r; }
-    return 0;
-}
+// The device side of the frame-stream scheduler (pt_stream_sched.hpp): its launches, its waits and what a new stream needs.  The fields behind c are
+// the submission at hand (submitBatch), else unset: its frame inputs, seeds and RAYTRACING == 0, the pool capacity and the ring rows a new stream gets
+struct StreamDev {
+    pt_ctx* c; const FrameIn* in = nullptr; const int32_t* seeds = nullptr; bool directNew = false; int capacity = 0, wantRing = 0;
 
-// PUMP_IDLE: every batch retired.  PUMP_ISSUED: the jobs not yet handed out fit into roughly one more group of iterations
-// (never waits for the pool to run dry, and never for the group it starts).  PUMP_IMAGE: no unretired batch targets image `arg`.  PUMP_RING: at most `arg` ring
-// rows are still owned by unretired batches.
-int pump(pt_ctx* c, PumpUntil until, int arg) {
-    if (c->pending.empty()) return drainGroups(c, true);          // (groups launched before the last batch retired ran over a dead pool: nothing to learn from them)
-    hipStream_t s = c->stream;
-    { int rc = ensurePartition(c); if (rc) return rc; }
-    const bool part = c->sExt != nullptr && s == c->ownStream;
-    hipStream_t sx = part ? c->sExt : s, ss = part ? c->sShade : s;
-    // the Parameters block the running stream was started with: a later pt_set_buffer(PT_BIND_PARAMS) only takes effect with the
-    // next stream (submitBatch finishes this one first), so the remaining iterations keep their kernel variants and bounds
-    const float* P = c->streamIn.params;
-    const bool direct = P[9] != 1.0f;
-    const bool fastNow = c->streamFast;                           // the contract the running stream was started with
-    const Batch b = streamBatch(c);
-    const int N = c->poolActive;
-    auto satisfied = [&]() {
-        if (c->pending.empty()) return true;
-        switch (until) {
-            case PUMP_IDLE: return false;
-            case PUMP_ISSUED: return c->draining || (int64_t)c->streamJobs - (int64_t)c->lastNextJob - c->inflightPredicted <= std::max<int64_t>((int64_t)c->lastDelta, (int64_t)arg);
-            case PUMP_IMAGE: for (const auto& e : c->pending) if (e.image == arg) return false; return true;
-            case PUMP_RING: return (int)(c->streamFrames - c->pending.front().f0) <= arg;
-        }
-        return true;
-    };
-    // every job retires within SAMPLE_RES * ceil(MAX_BOUNCES) iterations of being started, and a slot runs at most
-    // ceil(jobs / slots) jobs back to back: a pump that exceeds this bound (x2) is a scheduler bug, not work
-    const uint64_t outstanding = (uint64_t)c->streamJobs - std::min<uint64_t>(c->lastNextJob, c->streamJobs) + (uint64_t)N;
-    const uint64_t maxIters = 2 * ((outstanding + N - 1) / N + 1) * (uint64_t)(std::ceil(P[4]) * std::ceil(P[5]) + 1) + 64 + 48;
-    uint64_t iters = 0;
-    // One group: its iterations, a scan of the oldest batches once they have been handed out completely, the snapshot of Control with its stamp.
-    // The device runs the schedule by itself: slots pull jobs while there are any; from the iteration after the first empty
-    // pull on, every shading launch packs the surviving slots into a dense queue for the next iteration (Control::exhausted).
-    // The host only looks: while jobs remain the end is at least one whole job (>= SAMPLE_RES iterations) away, so a group is
-    // 24 iterations, in the tail 8; each look shrinks the launch grids to the live count.
-    auto launchGroup = [&](bool kick) -> int {
-        int CHECK = c->draining ? 8 : 24;
-        if (kick && c->lastDelta == 0) CHECK = 4;                  // the first looks of a stream fed in small submissions come early: the pool grows with the backlog they report
-        const int64_t perIter = std::max<int64_t>(1, (int64_t)c->lastDelta / std::max(1, c->lastCheck));      // jobs handed out per iteration at the last look
-        if (until == PUMP_ISSUED && c->lastDelta > 0) {           // approach the end of the job supply without running into it
-            const int64_t backlog = std::max<int64_t>(0, (int64_t)c->streamJobs - (int64_t)c->lastNextJob - c->inflightPredicted);      // as of the last look, less what the groups in flight take
-            const int64_t left = backlog - (int64_t)c->lastDelta / 2 - (int64_t)arg;
-            if (left > 0) CHECK = (int)std::max<int64_t>(1, std::min<int64_t>(CHECK, left / perIter));
-            else if (kick) CHECK = (int)std::max<int64_t>(1, std::min<int64_t>(CHECK, std::max<int64_t>(backlog, (int64_t)c->lastSubmitJobs) / perIter - 2));      // (two iterations' worth stay behind: later submissions sit BEHIND this group in the stream, and a pull that comes back empty sends the pool into its tail)
-        }
+    int launchIterations(int n, unsigned launched, int iter) {
+        hipStream_t s = c->stream;
+        { int rc = ensurePartition(c); if (rc) return rc; }
+        const bool part = c->sExt != nullptr && s == c->ownStream;
+        hipStream_t sx = part ? c->sExt : s, ss = part ? c->sShade : s;
+        // the Parameters block the running stream was started with: a later pt_set_buffer(PT_BIND_PARAMS) only takes effect with the
+        // next stream (the scheduler finishes this one first), so the remaining iterations keep their kernel variants and bounds
+        const bool direct = c->streamIn.params[9] != 1.0f;
+        const bool fastNow = c->streamFast;                           // the contract the running stream was started with
+        const Batch b = streamBatch(c);
         if (part) { HIP_TRY(hipEventRecord(c->evHost, s)); HIP_TRY(hipStreamWaitEvent(sx, c->evHost, 0)); }      // what `s` holds (submission, revive, accumulate) comes first
-        for (int k = 0; k < CHECK; k++) {
-            PoolRun pr; pr.stream = sx; pr.st = c->st; pr.launched = c->launched; pr.iter = c->iter;
+        for (int k = 0; k < n; k++) {
+            PoolRun pr; pr.stream = sx; pr.st = c->st; pr.launched = launched; pr.iter = (iter + k) & 0x3fffffff;
             TIMED_LAUNCH_ON(sx, 0, launchExtend(c, pr, direct, fastNow));
             if (part) { HIP_TRY(hipEventRecord(c->evExt, sx)); HIP_TRY(hipStreamWaitEvent(ss, c->evExt, 0)); }
 #define SHADE_ARGS dim3(std::max(1, (int)((pr.launched + SHADE_BLOCK - 1) / SHADE_BLOCK))), dim3(SHADE_BLOCK), 0, ss, c->sc, b, c->dFc, pr.st, c->dQueue[pr.iter & 1], c->dQueue[(pr.iter + 1) & 1], pr.iter, (int)pr.launched, c->dCtl
@@ -1734,57 +1623,136 @@ int pump(pt_ctx* c, PumpUntil until, int arg) {
             else if (c->niBits == 32) SHADE_X(32, false);
             else SHADE_X(0, false);
             if (part) { HIP_TRY(hipEventRecord(c->evShade, ss)); HIP_TRY(hipStreamWaitEvent(sx, c->evShade, 0)); }
-            c->iter = (c->iter + 1) & 0x3fffffff;
-            iters++;
         }
         if (part) HIP_TRY(hipStreamWaitEvent(s, c->evShade, 0));
         HIP_TRY(hipGetLastError());                                // a failed launch surfaces here, not as "did not drain"
         if (!c->asmError.empty()) { const std::string m = c->asmError; c->asmError.clear(); return fail(PT_ERR_HIP, m); }
-        pt_ctx::Group& g = c->grp[c->grpHead];
-        g.check = CHECK; g.iterEnd = c->iter; g.epoch = c->submitEpoch; g.nScan = 0;
-        g.predicted = c->lastDelta > 0 ? (int64_t)CHECK * perIter : 0; c->inflightPredicted += g.predicted;
-        // have the oldest batches been handed out completely (as of the last look)?  then see which of them are still in flight (one scan in flight at a time)
-        if (!c->scanInFlight) {
-            ScanEnds ends{};
-            for (const auto& e : c->pending) {
-                if (ends.n == 8 || c->lastNextJob < e.jobEnd) break;
-                ends.f[ends.n++] = e.f0 + (unsigned)e.nFrames;
-            }
-            if (ends.n) {
-                HIP_TRY(hipMemsetAsync(c->dCtl->busy, 0, sizeof(c->dCtl->busy), s));
-                hipLaunchKernelGGL(k_scan_inflight, dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, c->st, N, ends, c->dCtl);
-                g.nScan = ends.n; g.scanF0 = c->pending.front().f0; c->scanInFlight = true;
+        return 0;
+    }
+    int launchScan(const ptp::SchedScan& e) {
+        ScanEnds ends{};
+        for (int k = 0; k < 8; k++) ends.f[k] = e.f[k];
+        ends.n = e.n;
+        const int N = c->sched.poolActive;
+        HIP_TRY(hipMemsetAsync(c->dCtl->busy, 0, sizeof(c->dCtl->busy), c->stream));
+        hipLaunchKernelGGL(k_scan_inflight, dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->st, N, ends, c->dCtl);
+        return 0;
+    }
+    int launchSnapshot(int slot, unsigned seq) {
+        pt_ctx::GroupPins& g = c->grp[slot];
+        *g.stamp = 0;
+        hipLaunchKernelGGL(k_snapshot, dim3(1), dim3(64), 0, c->stream, c->dCtl, g.h, g.stamp, seq);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    int landed(int slot, unsigned seq, bool wait, ptp::ControlView& v) {
+        pt_ctx::GroupPins& g = c->grp[slot];
+        // has the group's stamp arrived?  (k_snapshot writes it behind a system-scope fence after the snapshot; pinned coherent memory needs no synchronisation to be read)
+        auto landed = [&]() { return *g.stamp == seq; };
+        if (!landed()) {
+            if (!wait) return 0;
+            for (int spin = 0; spin < 4000 && !landed(); spin++) __builtin_ia32_pause();
+            for (uint64_t n = 0; !landed(); n++) {
+                std::this_thread::sleep_for(std::chrono::microseconds(n < 100 ? 20 : 100));
+                if ((n & 1023) == 1023) {                              // every ~0.1 s: is the stream still working?  an idle stream without the stamp is a lost launch, an error a fault
+                    const hipError_t q = hipStreamQuery(c->stream);
+                    if (q != hipSuccess && q != hipErrorNotReady) return fail(PT_ERR_HIP, std::string("the wavefront stream failed: ") + hipGetErrorString(q));
+                    if (q == hipSuccess && !landed()) return fail(PT_ERR_HIP, "the wavefront stream is idle but a group's snapshot never arrived (internal error)");
+                }
             }
         }
-        if (++c->groupSeq == 0) c->groupSeq = 1;                   // (0 = "nothing has arrived")
-        g.seq = c->groupSeq; *g.stamp = 0;
-        hipLaunchKernelGGL(k_snapshot, dim3(1), dim3(64), 0, s, c->dCtl, g.h, g.stamp, g.seq);
-        HIP_TRY(hipGetLastError());
-        c->grpHead = (c->grpHead + 1) % 2; c->grpCount++;
-        return 0;
-    };
-    int rc;
-    bool kick = until == PUMP_ISSUED;                             // a submission always gets the GPU going: about as many iterations as consume what it added
-    while (c->grpCount > 0 && (rc = processOldestGroup(c, false, false)) != 0) if (rc < 0) return rc;      // whatever has finished since the last call
-    for (;;) {
-        const bool want = kick || !satisfied();
-        if (!want) break;
-        if (iters > maxIters) return fail(PT_ERR_HIP, "wavefront scheduler did not drain (internal error)");
-        const int room = c->draining ? 1 : 2;                     // the tail is run look by look: every look shrinks the grids
-        if (c->grpCount < room) { if ((rc = launchGroup(kick))) return rc; kick = false; continue; }
-        if (kick) { kick = false; continue; }                     // two groups are on their way already: the submission rides behind them
-        if ((rc = processOldestGroup(c, true, false)) < 0) return rc;
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        const Control& h = *g.h;
+        v.nextJob = h.nextJob; v.qCount0 = h.qCount[0]; v.qCount32 = h.qCount[32];
+        for (int k = 0; k < 4; k++) v.exhausted[k] = h.exhausted[k];
+        for (int k = 0; k < 8; k++) v.busy[k] = h.busy[k];
+        return 1;
     }
-    c->hostCnt[PT_CNT_ITERATIONS] += iters;
-    c->hostCnt[PT_CNT_EXTEND_LAUNCHES] += iters;
-    if (until != PUMP_ISSUED) return drainGroups(c, c->pending.empty());      // synchronous callers leave nothing behind them
-    return 0;
-}
+    int retire(const ptp::StreamEntry& e) {
+        hipStream_t s = c->stream;
+        Batch b = streamBatch(c);
+        if (c->adaptOn) {
+            TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_adaptive, dim3((c->adaptN + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, b, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
+        int gridA = (c->nSlotsImg + BLOCK - 1) / BLOCK;
+        if (c->recordMoments && e.image == c->curImage) TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_moments, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
+        else TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], e.f0, e.nFrames, e.firstFrame));
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    // every job retires within SAMPLE_RES * ceil(MAX_BOUNCES) iterations of being started
+    uint64_t itersPerJob() const { const float* P = c->streamIn.params; return (uint64_t)(std::ceil(P[4]) * std::ceil(P[5]) + 1); }
+    int didNotDrain() { return fail(PT_ERR_HIP, "wavefront scheduler did not drain (internal error)"); }
 
+    int sceneReady() {
+        if (c->sceneDirty) { const int rc = buildScene(c); if (rc) return rc; }
+        if (directNew && c->anySubsurface) {
+            if (c->sc.numObj > FL_PROBE_OBJ_MAX + 1) return fail(PT_ERR_UNSUPPORTED, "directDiffuse with subsurface materials supports at most 65536 objects (BVHs)");
+            if (c->ambiguousTriObj) return fail(PT_ERR_SCENE, "directDiffuse with subsurface materials needs every triangle to belong to one BVH (hit.parentID, frag.glsl:573)");
+        }
+        return 0;
+    }
+    int openStream(int pool) {
+        hipStream_t s = c->stream;
+        if (const int rc = ensurePool(c, capacity)) return rc;
+        if (c->ringFrames < wantRing) {
+            HIP_TRY(hipStreamSynchronize(s));
+            c->ringFrames = 0;
+            HIP_TRY(c->dColbuf.reset((size_t)wantRing * (size_t)c->nSlotsImg * 16));
+            HIP_TRY(c->dSeeds.reset((size_t)wantRing * 4));
+            HIP_TRY(c->hSeeds.reset((size_t)wantRing * 4));
+            c->ringFrames = wantRing;
+        }
+        c->streamIn = *in; *c->hFrameIn = *in; c->streamFast = c->fastContract;
+        HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
+        hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, s, c->dCtl);
+        HIP_TRY(hipMemsetAsync(c->st.G1, 0, (size_t)pool * 16, s));       // every slot dead
+        return 0;
+    }
+    int growPool(int from, int to) {
+        HIP_TRY(hipMemsetAsync(c->st.G1 + from, 0, (size_t)(to - from) * 16, c->stream));      // the new slots are dead
+        return 0;
+    }
+    int appendJobs(unsigned f0, int nFrames, unsigned nJobs, int mode, int N) {
+        hipStream_t s = c->stream;
+        for (int f = 0; f < nFrames; f++) c->hSeeds[(f0 + (unsigned)f) % (unsigned)c->ringFrames] = seeds[f];
+        {
+            unsigned r0 = f0 % (unsigned)c->ringFrames, n0 = std::min<unsigned>((unsigned)nFrames, (unsigned)c->ringFrames - r0);
+            HIP_TRY(hipMemcpyAsync(c->dSeeds + r0, c->hSeeds + r0, (size_t)n0 * 4, hipMemcpyHostToDevice, s));
+            if (n0 < (unsigned)nFrames) HIP_TRY(hipMemcpyAsync(c->dSeeds, c->hSeeds, (size_t)(nFrames - n0) * 4, hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(k_submit, dim3(1), dim3(1), 0, s, c->dCtl, nJobs, mode, (unsigned)N);
+        const Batch b = streamBatch(c);
+#define REVIVE(T, F) TIMED_LAUNCH(2, hipLaunchKernelGGL((k_revive<T, F>), dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, b, c->dFc, c->st, N, c->dCtl))
+        const bool fastRevive = c->streamFast && !directNew && !c->countStats;
+        // (directDiffuse never touches the index stack: its k_shade variant is the one without it, and so is its path state — except that the pool of a
+        //  scene with transmissive materials has the groups allocated, which k_revive<niBits> initialises)
+        if (c->niBits == 3) { if (fastRevive) REVIVE(3, true); else REVIVE(3, false); }
+        else if (c->niBits == 8) { if (fastRevive) REVIVE(8, true); else REVIVE(8, false); }
+        else if (c->niBits == 32) { if (fastRevive) REVIVE(32, true); else REVIVE(32, false); }
+        else { if (fastRevive) REVIVE(0, true); else REVIVE(0, false); }
+#undef REVIVE
+        c->cam[c->curImage] = pt_ctx::Cam{*in, c->sceneGen, true}; c->camWrites++;   // the image's camera (include/pt_reproject.h)
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+
+void countIterations(pt_ctx* c, uint64_t iters) { c->hostCnt[PT_CNT_ITERATIONS] += iters; c->hostCnt[PT_CNT_EXTEND_LAUNCHES] += iters; }
+int pump(pt_ctx* c, ptp::PumpUntil until, int arg) {
+    StreamDev dev{c};
+    uint64_t iters = 0;
+    const int rc = c->sched.pump(dev, until, arg, &iters);
+    countIterations(c, iters);
+    return rc;
+}
 int flushStream(pt_ctx* c) {
-    if (c->pending.empty()) return 0;
+    if (c->sched.idle()) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    return pump(c, PUMP_IDLE, 0);
+    return pump(c, ptp::PUMP_IDLE, 0);
 }
 
 // the frame inputs current at the call; false while Parameters, ORIGIN or ROTATION are not set
@@ -1853,14 +1821,13 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     // parameter checks (scope: SURVEY.md §2)
     if (c->buf.params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
     const float* P = c->buf.params.data();
-    const bool direct = P[9] != 1.0f;                            // RAYTRACING == 0: directDiffuse (frag.glsl:655-681, :911-912)
+    FrameIn fin{};
+    currentInputs(c, fin);                                        // (a camera that is not set leaves it zeroed: the scene build refuses before anything reads it)
     if (P[10] != 0.0f) {                                          // DEBUG: no paths at all, one small kernel (frag.glsl:916-918)
         if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
         if ((rc = flushStream(c))) return rc;
         if (c->sceneDirty && (rc = buildScene(c))) return rc;
         if (c->stackDepth > 64) return fail(PT_ERR_SCENE, "DEBUG heat-map: BVH deeper than the 64-entry traversal stack");
-        FrameIn fin;
-        std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->buf.origin.data(), 12); std::memcpy(fin.rotation, c->buf.rotation.data(), 12); std::memcpy(fin.mouse, c->buf.mouse.data(), 12);
         *c->hFrameIn = fin;
         HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
@@ -1878,82 +1845,17 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     if (!(P[5] > 0.0f) || P[5] > 4095.0f) return fail(PT_ERR_ARG, "MAX_BOUNCES must be in (0,4095]");
     size_t nJobs64 = (size_t)(c->adaptOn ? c->adaptN : c->nLocal) * (size_t)nFrames;
     if (nJobs64 >= (1ull << 31)) return fail(PT_ERR_ARG, "batch too large: pixels * frames must stay below 2^31 (split the batch)");
-    FrameIn fin;
-    std::memcpy(fin.params, P, 48); std::memcpy(fin.origin, c->buf.origin.data(), 12); std::memcpy(fin.rotation, c->buf.rotation.data(), 12); std::memcpy(fin.mouse, c->buf.mouse.data(), 12);
-    // the running stream can take this batch if nothing the kernels were launched with changes
-    const int wantRing = ptp::ringRows(nFrames, async, (size_t)c->nSlotsImg * 16, pt_ctx::IMAGES);
-    bool join = !c->pending.empty() && !c->sceneDirty && std::memcmp(&fin, &c->streamIn, sizeof(FrameIn)) == 0 && c->ringFrames >= wantRing && c->streamFast == c->fastContract &&
-                (uint64_t)c->streamJobs + nJobs64 < (1ull << 31);
-    if (!join && (rc = flushStream(c))) return rc;
-    if (!join) {                                                  // ---- a new stream
-        if (c->sceneDirty && (rc = buildScene(c))) return rc;
-        if (direct && c->anySubsurface) {
-            if (c->sc.numObj > FL_PROBE_OBJ_MAX + 1) return fail(PT_ERR_UNSUPPORTED, "directDiffuse with subsurface materials supports at most 65536 objects (BVHs)");
-            if (c->ambiguousTriObj) return fail(PT_ERR_SCENE, "directDiffuse with subsurface materials needs every triangle to belong to one BVH (hit.parentID, frag.glsl:573)");
-        }
-        c->poolActive = ptp::newStreamPool(nJobs64, async, c->poolSlots);
-        if ((rc = ensurePool(c, ptp::newStreamCapacity(async, c->poolSlots)))) return rc;
-        if (c->ringFrames < wantRing) {
-            HIP_TRY(hipStreamSynchronize(s));
-            c->ringFrames = 0;
-            HIP_TRY(c->dColbuf.reset((size_t)wantRing * (size_t)c->nSlotsImg * 16));
-            HIP_TRY(c->dSeeds.reset((size_t)wantRing * 4));
-            HIP_TRY(c->hSeeds.reset((size_t)wantRing * 4));
-            c->ringFrames = wantRing;
-        }
-        c->streamIn = fin; *c->hFrameIn = fin; c->streamFast = c->fastContract;
-        HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
-        hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, s, c->dCtl);
-        HIP_TRY(hipMemsetAsync(c->st.G1, 0, (size_t)c->poolActive * 16, s));       // every slot dead
-        if ((rc = drainGroups(c, true))) return rc;
-        c->inflightPredicted = 0;
-        c->streamFrames = 0; c->streamJobs = 0; c->lastNextJob = 0; c->lastDelta = 0; c->lastCheck = 24; c->iter = 0;
-    } else if ((int)(c->streamFrames - c->pending.front().f0) + nFrames > c->ringFrames) {
-        if ((rc = pump(c, PUMP_RING, c->ringFrames - nFrames))) return rc;        // wait for ring rows
-        if (c->pending.empty()) return submitBatch(c, firstFrame, nFrames, seeds, async);   // the stream ended meanwhile: start over
-    }
-    // a stream fed in small batches (the reference draws ONE frame per call) started with a small pool: let it grow with the backlog
-    bool grown = false;
-    if (join && async && c->poolSlots == 0) {
-        const uint64_t outstanding = (uint64_t)std::max<int64_t>(0, (int64_t)c->streamJobs - (int64_t)std::min<uint64_t>(c->lastNextJob, c->streamJobs) - c->inflightPredicted) + nJobs64;
-        if (const size_t target = ptp::grownPool(outstanding, c->jobsPerImage, c->allocSlots, c->poolActive)) {
-            HIP_TRY(hipMemsetAsync(c->st.G1 + c->poolActive, 0, (target - (size_t)c->poolActive) * 16, s));      // the new slots are dead
-            c->poolActive = (int)target;
-            grown = true;
-        }
-    }
-    // ---- append
-    const unsigned f0 = c->streamFrames;
-    for (int f = 0; f < nFrames; f++) c->hSeeds[(f0 + (unsigned)f) % (unsigned)c->ringFrames] = seeds[f];
-    {
-        unsigned r0 = f0 % (unsigned)c->ringFrames, n0 = std::min<unsigned>((unsigned)nFrames, (unsigned)c->ringFrames - r0);
-        HIP_TRY(hipMemcpyAsync(c->dSeeds + r0, c->hSeeds + r0, (size_t)n0 * 4, hipMemcpyHostToDevice, s));
-        if (n0 < (unsigned)nFrames) HIP_TRY(hipMemcpyAsync(c->dSeeds, c->hSeeds, (size_t)(nFrames - n0) * 4, hipMemcpyHostToDevice, s));
-    }
-    hipLaunchKernelGGL(k_submit, dim3(1), dim3(1), 0, s, c->dCtl, (unsigned)nJobs64, join ? (grown ? 2 : 0) : 1, (unsigned)c->poolActive);
-    const Batch b = streamBatch(c);
-    const int N = c->poolActive;
-#define REVIVE(T, F) TIMED_LAUNCH(2, hipLaunchKernelGGL((k_revive<T, F>), dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, b, c->dFc, c->st, N, c->dCtl))
-    const bool fastRevive = c->streamFast && !direct && !c->countStats;
-    // (directDiffuse never touches the index stack: its k_shade variant is the one without it, and so is its path state — except that the pool of a
-    //  scene with transmissive materials has the groups allocated, which k_revive<niBits> initialises)
-    if (c->niBits == 3) { if (fastRevive) REVIVE(3, true); else REVIVE(3, false); }
-    else if (c->niBits == 8) { if (fastRevive) REVIVE(8, true); else REVIVE(8, false); }
-    else if (c->niBits == 32) { if (fastRevive) REVIVE(32, true); else REVIVE(32, false); }
-    else { if (fastRevive) REVIVE(0, true); else REVIVE(0, false); }
-#undef REVIVE
-    c->streamFrames += (unsigned)nFrames; c->streamJobs += (unsigned)nJobs64;
-    c->lastSubmitJobs = nJobs64; c->jobsThisImage += nJobs64;
-    pt_ctx::Entry e; e.jobEnd = c->streamJobs; e.f0 = f0; e.nFrames = nFrames; e.firstFrame = firstFrame; e.image = c->curImage;
-    c->pending.push_back(e);
-    c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true}; c->camWrites++;   // the image's camera (include/pt_reproject.h)
-    c->draining = false; c->launched = (unsigned)N;              // (if the pool had run dry, k_submit dropped the tail queue)
-    c->submitEpoch++;                                            // the groups in flight were launched for another tail: their view of it no longer counts
-    HIP_TRY(hipGetLastError());
-    // asynchronous: come back while the backlog of jobs not yet handed out is below what keeps the largest pool fed (2^23 * 8/5)
-    if (async) return pump(c, PUMP_ISSUED, c->poolSlots == 0 ? 14000000 : 0);
-    return pump(c, PUMP_IDLE, 0);
+    // whether the running stream takes the batch, the pool, the groups of iterations and the retirements: the scheduler's (pt_stream_sched.hpp)
+    ptp::SubmitReq q;
+    q.firstFrame = firstFrame; q.nFrames = nFrames; q.image = c->curImage; q.nJobs = nJobs64; q.async = async;
+    q.sceneDirty = c->sceneDirty; q.sameInputs = std::memcmp(&fin, &c->streamIn, sizeof(FrameIn)) == 0; q.sameContract = c->streamFast == c->fastContract;
+    q.ringFrames = c->ringFrames; q.wantRing = ptp::ringRows(nFrames, async, (size_t)c->nSlotsImg * 16, pt_ctx::IMAGES);
+    q.poolSlots = c->poolSlots; q.allocSlots = c->allocSlots;
+    StreamDev dev{c, &fin, seeds, P[9] != 1.0f, ptp::newStreamCapacity(async, c->poolSlots), q.wantRing};      // (RAYTRACING == 0: directDiffuse, frag.glsl:655-681, :911-912)
+    uint64_t iters = 0;
+    rc = c->sched.submit(dev, q, &iters);
+    countIterations(c, iters);
+    return rc;
 }
 
 int resolveTimes(pt_ctx* c) {
@@ -2217,11 +2119,10 @@ int pt_next_image(pt_ctx* c) {
     const int next = (c->curImage + 1) % pt_ctx::IMAGES;
     HIP_TRY(c->dImage[next].ensure((size_t)c->nSlotsImg * 16));
     int rc;
-    if ((rc = pump(c, PUMP_IMAGE, next))) return rc;              // nothing may still be on its way into the image taken over
+    if ((rc = pump(c, ptp::PUMP_IMAGE, next))) return rc;              // nothing may still be on its way into the image taken over
     c->curImage = next;
     c->cam[next].valid = false; c->camWrites++;
-    if (c->jobsThisImage) c->jobsPerImage = c->jobsThisImage;
-    c->jobsThisImage = 0;
+    c->sched.imageTurned();
     HIP_TRY(hipMemsetAsync(c->dImage[next], 0, (size_t)c->nSlotsImg * 16, c->stream));
     if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
     return PT_OK;
@@ -2231,7 +2132,7 @@ int pt_finish_image(pt_ctx* c, int age) {
     if (!c || age < 0 || age >= pt_ctx::IMAGES) return fail(PT_ERR_ARG, "pt_finish_image: age must be in [0,3] (0 = current image)");
     MULTI_ALL(c, pt_finish_image(k, age));
     HIP_TRY(hipSetDevice(c->device));
-    return pump(c, PUMP_IMAGE, (c->curImage + pt_ctx::IMAGES - age) % pt_ctx::IMAGES);
+    return pump(c, ptp::PUMP_IMAGE, (c->curImage + pt_ctx::IMAGES - age) % pt_ctx::IMAGES);
 }
 
 int pt_image_device(pt_ctx* c, int age, void** dev_ptr, size_t* n_pixels) {
@@ -2383,7 +2284,7 @@ int renderSelected(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds,
     // next ordinary call starts a fresh stream over the whole list.  The override holds exactly while this batch is in the scheduler.
     c->adaptOn = true; c->adaptN = (int)n;
     rc = submitBatch(c, firstFrame, nFrames, seeds, false);
-    if (rc) c->pending.clear();                                   // a failed stream must not be retired later with the full list
+    if (rc) c->sched.dropPending();                                // a failed stream must not be retired later with the full list
     c->adaptOn = false; c->adaptN = 0;
     return rc;
 }
