@@ -42,6 +42,7 @@
 #include "pt_scene_layout.hpp"
 #include "pt_launch_plan.hpp"
 #include "pt_stream_sched.hpp"
+#include "pt_image_history.hpp"
 #include "pt_image_launch.hpp"
 
 #include <algorithm>
@@ -62,6 +63,7 @@ namespace {
 
 thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
+int fail(const ptp::Refused& r) { return r.code ? fail(r.code, r.msg) : 0; }      // a refusal of the image history (pt_image_history.hpp), or 0
 #define HIP_TRY(x)                                                                                         \
     do {                                                                                                   \
         hipError_t e_ = (x);                                                                               \
@@ -89,7 +91,7 @@ __device__ __forceinline__ void stS(float4* p, float4 v) {
     __builtin_nontemporal_store(w, reinterpret_cast<f32x4*>(p));
 }
 
-struct FrameIn { float params[12]; float origin[3]; float rotation[3]; float mouse[3]; };
+using ptp::FrameIn;               // the frame inputs (pt_image_history.hpp)
 
 struct Control {            // device-resident scheduler words shared by the whole batch
     unsigned nextJob;       // next unassigned job
@@ -1242,8 +1244,8 @@ struct pt_ctx {
     DevScene sc{};
     // shard
     std::vector<int32_t> pixList; int nLocal = 0, nSlotsImg = 0; Dev<int> dPixList; Dev<unsigned> dPixXY; Dev<int> dAllMaps;
-    static constexpr int IMAGES = 4;
-    Dev<float4> dImage[IMAGES]; int curImage = 0;      // FRAME images (more than one only after pt_next_image)
+    static constexpr int IMAGES = ptp::ImageHistory::IMAGES;
+    Dev<float4> dImage[IMAGES];     // FRAME images (more than one only after pt_next_image); hist.image() is the current one
     // path pool
     int poolSlots = 0;              // 0 = automatic: jobs/5 clamped to [2^20, 2^22] (enough rays per lane for the in-wave refill, short tail)
     int allocSlots = 0; int allocNiBits = -1; bool allocHX = false;
@@ -1253,7 +1255,6 @@ struct pt_ctx {
     Dev<float4> dColbuf; Dev<int> dSeeds; int ringFrames = 0;      // per-frame rings of the stream (Batch)
     // frame-stream scheduler: its host view (pt_stream_sched.hpp), and what the device side of it needs
     ptp::StreamSched sched;
-    FrameIn streamIn{};             // frame inputs the running stream was started with
     Dev<FrameIn> dFrameIn; Dev<FrameConst> dFc; Dev<Control> dCtl;
     // per group in flight (StreamSched::grp, by slot): k_snapshot writes Control into the pinned snapshot and then the group's number into the pinned STAMP
     struct GroupPins { Pinned<Control, hipHostMallocCoherent> h; Pinned<volatile unsigned, hipHostMallocCoherent> stamp; } grp[2];
@@ -1293,31 +1294,26 @@ struct pt_ctx {
     // include/pt_steer.h: the whole image's selection mask (W*H bytes, pixel order), then, 4-byte aligned, k_gd_select's active count
     Dev<unsigned char> dSelMask;
     bool recordMoments = false;     // include/pt_guided.h: the frames of pt_render* also go into T (k_accumulate_moments) when they land in the current image
-    // The feature records (W*H x 4 float4) of one set of frame inputs, kept until they are asked for under other inputs or an upload invalidates them
-    // (invalidateRecords): first-hit records (include/pt_denoise.h), or seen-through records under `rule` with their last segments (`rays`, W*H x
-    // 2 float4; include/pt_through.h).  Of each kind one cache under the current inputs and one under the current image's camera (Rh; Sh, Yh)
-    struct Records { Dev<float4> recs, rays; bool valid = false; FrameIn in{}; pt_through_rule rule{}; };
-    Records feat, featH, thru, thruH;
+    // What the current image is a picture of (pt_image_history.hpp): the ring's camera records and the current image, the upload generations, the
+    // validity of the mark and the hold, the keys of the record caches, whose frame constants are on the device.  The buffers below are what it describes
+    ptp::ImageHistory hist;
+    // The feature records (W*H x 4 float4) of one set of frame inputs, by ptp::RecordCache: first-hit records (include/pt_denoise.h), or seen-through
+    // records with their last segments (`rays`, W*H x 2 float4; include/pt_through.h)
+    struct Records { Dev<float4> recs, rays; } rec[ptp::RC_COUNT];
     Dev<float4> dDnCol[2], dDnGuide, dDnOut;      // the filters' colour ping-pong, packed guide (2 float4 per pixel) and output
-    // reprojection (include/pt_reproject.h): the camera of each ring image (the frame inputs it was rendered or written with, and the scene
-    // generation then: sceneGen counts uploads of scene buffers and textures); one flag byte per material (1 = view-dependent, buildScene); the
-    // scratch images, the kept counts (two), the packed candidates of k_through_pack (W*H x 2 float4)
-    struct Cam { FrameIn in; uint64_t sceneGen = 0; bool valid = false; } cam[IMAGES];
-    uint64_t sceneGen = 0;
+    // reprojection (include/pt_reproject.h): one flag byte per material (1 = view-dependent, buildScene); the scratch images, the kept counts
+    // (two), the packed candidates of k_through_pack (W*H x 2 float4)
     Dev<unsigned char> dMatVD;
     Dev<float4> dRpFrame, dRpStats, dRpPack; Dev<unsigned> dRpKept;
     Dev<float4> dStatsWhole;        // a group's T gathered in pixel order on its first stream (reprojection, the guided filter)
     Dev<float4> dFill; Dev<unsigned> dFillCount;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count
-    // include/pt_motion.h.  otherGen counts the uploads that are not geometry (bindings 5, 14 and textures) beside sceneGen, which counts all;
-    // camWrites counts every write of a camera record, so that a mark can tell that its image's record is still the one it saw.  The mark: Rh
-    // (feat), the primitives' positions then on the device (3 float4 each) and on the host (9 floats per triangle, 10 per ellipsoid); the
-    // positions now are packed per call into dMoveTri / dMoveEl
-    uint64_t otherGen = 0, camWrites = 0;
-    struct Mark { bool valid = false; int image = 0; uint64_t camWrites = 0, otherGen = 0; int nTri = 0, nEl = 0; std::vector<float> tri, el; Dev<float4> feat, dTri, dEl; } mark;
+    // include/pt_motion.h.  The mark: Rh (feat), the primitives' positions then on the device (3 float4 each) and on the host (9 floats per
+    // triangle, 10 per ellipsoid); the positions now are packed per call into dMoveTri / dMoveEl
+    struct Mark { int nTri = 0, nEl = 0; std::vector<float> tri, el; Dev<float4> feat, dTri, dEl; } mark;
     Dev<float4> dMoveTri, dMoveEl;
-    // include/pt_validate.h.  The hold (on a group's first stream): the held FRAME and T in pixel order (W*H float4 each), the image they were
-    // taken from, the frame inputs of its camera record and sceneGen then; pt_history_merge's kappa (W*H floats, only when asked for)
-    struct Hold { bool valid = false; int image = 0; FrameIn in{}; uint64_t sceneGen = 0; Dev<float4> frame, stats; } hold;
+    // include/pt_validate.h.  The hold (on a group's first stream): the held FRAME and T in pixel order (W*H float4 each); pt_history_merge's
+    // kappa (W*H floats, only when asked for)
+    struct Hold { Dev<float4> frame, stats; } hold;
     Dev<float> dKappa;
     struct KT { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; int64_t launches = 0; double ms = 0; std::vector<float> each; } kt[4];
 };
@@ -1601,7 +1597,7 @@ struct StreamDev {
         hipStream_t sx = part ? c->sExt : s, ss = part ? c->sShade : s;
         // the Parameters block the running stream was started with: a later pt_set_buffer(PT_BIND_PARAMS) only takes effect with the
         // next stream (the scheduler finishes this one first), so the remaining iterations keep their kernel variants and bounds
-        const bool direct = c->streamIn.params[9] != 1.0f;
+        const bool direct = c->hist.streamInputs().params[9] != 1.0f;
         const bool fastNow = c->streamFast;                           // the contract the running stream was started with
         const Batch b = streamBatch(c);
         if (part) { HIP_TRY(hipEventRecord(c->evHost, s)); HIP_TRY(hipStreamWaitEvent(sx, c->evHost, 0)); }      // what `s` holds (submission, revive, accumulate) comes first
@@ -1677,13 +1673,13 @@ struct StreamDev {
             return 0;
         }
         int gridA = (c->nSlotsImg + BLOCK - 1) / BLOCK;
-        if (c->recordMoments && e.image == c->curImage) TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_moments, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
+        if (c->recordMoments && e.image == c->hist.image()) TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate_moments, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], c->dStats, e.f0, e.nFrames, e.firstFrame));
         else TIMED_LAUNCH(3, hipLaunchKernelGGL(k_accumulate, dim3(gridA), dim3(BLOCK), 0, s, b, c->dFc, c->dImage[e.image], e.f0, e.nFrames, e.firstFrame));
         HIP_TRY(hipGetLastError());
         return 0;
     }
     // every job retires within SAMPLE_RES * ceil(MAX_BOUNCES) iterations of being started
-    uint64_t itersPerJob() const { const float* P = c->streamIn.params; return (uint64_t)(std::ceil(P[4]) * std::ceil(P[5]) + 1); }
+    uint64_t itersPerJob() const { const float* P = c->hist.streamInputs().params; return (uint64_t)(std::ceil(P[4]) * std::ceil(P[5]) + 1); }
     int didNotDrain() { return fail(PT_ERR_HIP, "wavefront scheduler did not drain (internal error)"); }
 
     int sceneReady() {
@@ -1705,7 +1701,7 @@ struct StreamDev {
             HIP_TRY(c->hSeeds.reset((size_t)wantRing * 4));
             c->ringFrames = wantRing;
         }
-        c->streamIn = *in; *c->hFrameIn = *in; c->streamFast = c->fastContract;
+        c->hist.streamStarted(*in); *c->hFrameIn = *in; c->streamFast = c->fastContract;
         HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
         hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, s, c->dCtl);
@@ -1735,7 +1731,7 @@ struct StreamDev {
         else if (c->niBits == 32) { if (fastRevive) REVIVE(32, true); else REVIVE(32, false); }
         else { if (fastRevive) REVIVE(0, true); else REVIVE(0, false); }
 #undef REVIVE
-        c->cam[c->curImage] = pt_ctx::Cam{*in, c->sceneGen, true}; c->camWrites++;   // the image's camera (include/pt_reproject.h)
+        c->hist.rendered(*in);                                    // the image's camera (include/pt_reproject.h)
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -1764,10 +1760,8 @@ bool currentInputs(const pt_ctx* c, FrameIn& fin) {
 }
 // pt_write_frame, pt_reproject_frame: the current image's camera is the inputs current at the call (include/pt_reproject.h)
 void recordCamera(pt_ctx* c) {
-    pt_ctx::Cam& k = c->cam[c->curImage];
-    k.valid = currentInputs(c, k.in);
-    k.sceneGen = c->sceneGen;
-    c->camWrites++;
+    FrameIn cur;
+    c->hist.written(currentInputs(c, cur) ? &cur : nullptr);
 }
 
 // A single context's accumulator slots (FRAME or T) to and from a whole image in host pixel order, on k->stream, synchronised.  A whole-image
@@ -1797,8 +1791,6 @@ int ensureStats(pt_ctx* c, bool zeroed) {
     if (zeroed) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
     return 0;
 }
-// any upload may move the camera or the scene under the feature records
-void invalidateRecords(pt_ctx* c) { for (pt_ctx::Records* r : {&c->feat, &c->featH, &c->thru, &c->thruH}) r->valid = false; }
 
 // pt_write_frame of a single context: FRAME from the whole host image; T from `stats` when given, else zeroed (where allocated); the camera recorded
 int writeFrame(pt_ctx* c, const float* frame, const float* stats) {
@@ -1810,7 +1802,7 @@ int writeFrame(pt_ctx* c, const float* frame, const float* stats) {
         else HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
     }
     recordCamera(c);
-    return hostToShard(c, frame, c->dImage[c->curImage]);
+    return hostToShard(c, frame, c->dImage[c->hist.image()]);
 }
 
 int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bool async) {
@@ -1831,12 +1823,12 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
         *c->hFrameIn = fin;
         HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
-        std::memset(&c->streamIn, 0xff, sizeof(FrameIn));                          // the frame constants on the device are no stream's any more
+        c->hist.frameConstantsTaken();                                             // the frame constants on the device are no stream's any more
         const Batch b = streamBatch(c);
         DevScene dsc = c->sc; dsc.ldsNodes = 0; dsc.ldsTris = 0;                    // no LDS tile in this kernel
-        hipLaunchKernelGGL(k_debug_heatmap, dim3((c->nLocal + 63) / 64), dim3(64), 0, s, dsc, b, c->dFc, c->dImage[c->curImage], firstFrame, nFrames);
+        hipLaunchKernelGGL(k_debug_heatmap, dim3((c->nLocal + 63) / 64), dim3(64), 0, s, dsc, b, c->dFc, c->dImage[c->hist.image()], firstFrame, nFrames);
         HIP_TRY(hipGetLastError());
-        c->cam[c->curImage] = pt_ctx::Cam{fin, c->sceneGen, true}; c->camWrites++;
+        c->hist.rendered(fin);
         return 0;
     }
     if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
@@ -1847,8 +1839,8 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     if (nJobs64 >= (1ull << 31)) return fail(PT_ERR_ARG, "batch too large: pixels * frames must stay below 2^31 (split the batch)");
     // whether the running stream takes the batch, the pool, the groups of iterations and the retirements: the scheduler's (pt_stream_sched.hpp)
     ptp::SubmitReq q;
-    q.firstFrame = firstFrame; q.nFrames = nFrames; q.image = c->curImage; q.nJobs = nJobs64; q.async = async;
-    q.sceneDirty = c->sceneDirty; q.sameInputs = std::memcmp(&fin, &c->streamIn, sizeof(FrameIn)) == 0; q.sameContract = c->streamFast == c->fastContract;
+    q.firstFrame = firstFrame; q.nFrames = nFrames; q.image = c->hist.image(); q.nJobs = nJobs64; q.async = async;
+    q.sceneDirty = c->sceneDirty; q.sameInputs = c->hist.streamHas(fin); q.sameContract = c->streamFast == c->fastContract;
     q.ringFrames = c->ringFrames; q.wantRing = ptp::ringRows(nFrames, async, (size_t)c->nSlotsImg * 16, pt_ctx::IMAGES);
     q.poolSlots = c->poolSlots; q.allocSlots = c->allocSlots;
     StreamDev dev{c, &fin, seeds, P[9] != 1.0f, ptp::newStreamCapacity(async, c->poolSlots), q.wantRing};      // (RAYTRACING == 0: directDiffuse, frag.glsl:655-681, :911-912)
@@ -1932,6 +1924,7 @@ int pt_create(pt_ctx** out, int device, int width, int height, int shard_rank, i
     pt_ctx* c = new pt_ctx();
     c->numCUs = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     c->device = device; c->W = width; c->H = height; c->shardRank = shard_rank; c->shardCount = shard_count;
+    c->hist.create(width, height);
     c->buf.imp = {0.0f}; c->buf.ellip = {0.0f}; c->buf.objidx = {0};
     c->buf.mouse = {-1.0e6f, -1.0e6f, 0.0f};
     const int rc = initContext(c, width, height, shard_rank, shard_count);
@@ -2040,7 +2033,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         return PT_OK;
     }
     if (bytes % 4) return fail(PT_ERR_ARG, "pt_set_buffer: size must be a multiple of 4 bytes");
-    invalidateRecords(c);
+    c->hist.uploadBegins();                                       // (a refused upload has dropped the record caches all the same)
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
         case PT_BIND_ORIGIN: if (n < 3) return fail(PT_ERR_ARG, "ORIGIN needs 3 floats"); c->buf.origin.assign(f, f + 3); return PT_OK;      // per-frame glBufferSubData: no scene rebuild
@@ -2058,8 +2051,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         default: return fail(PT_ERR_ARG, "pt_set_buffer: binding point not consumed by the render path (frag.glsl declares 0-5,7,10-15)");
     }
     c->sceneDirty = true;
-    c->sceneGen++;
-    if (binding == PT_BIND_IMPLICITS || binding == PT_BIND_MATERIALS) c->otherGen++;      // not geometry (include/pt_motion.h)
+    c->hist.sceneBufferAccepted(binding);
     return PT_OK;
 }
 
@@ -2074,8 +2066,7 @@ int pt_set_texture(pt_ctx* c, int index, int w, int h, const uint8_t* rgba8) {
         return PT_OK;
     }
     if (index < 0 || index > 4095) return fail(PT_ERR_ARG, "texture index out of range [0,4095]");
-    invalidateRecords(c);
-    c->sceneGen++; c->otherGen++;
+    c->hist.textureUploaded();
     if (index == 0) { c->buf.sky.assign(rgba8, rgba8 + (size_t)w * h * 4); c->buf.skyW = w; c->buf.skyH = h; }
     if ((size_t)index >= c->buf.textures.size()) c->buf.textures.resize((size_t)index + 1);
     c->buf.textures[index].rgba.assign(rgba8, rgba8 + (size_t)w * h * 4); c->buf.textures[index].w = w; c->buf.textures[index].h = h;
@@ -2089,9 +2080,9 @@ int pt_reset_frame(pt_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = flushStream(c))) return rc;
-    HIP_TRY(hipMemsetAsync(c->dImage[c->curImage], 0, (size_t)c->nSlotsImg * 16, c->stream));
+    HIP_TRY(hipMemsetAsync(c->dImage[c->hist.image()], 0, (size_t)c->nSlotsImg * 16, c->stream));
     if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));      // the statistics describe this image
-    c->cam[c->curImage].valid = false; c->camWrites++;
+    c->hist.reset();
     return PT_OK;
 }
 
@@ -2116,12 +2107,11 @@ int pt_next_image(pt_ctx* c) {
     if (!c) return fail(PT_ERR_ARG, "null context");
     MULTI_ALL(c, pt_next_image(k));
     HIP_TRY(hipSetDevice(c->device));
-    const int next = (c->curImage + 1) % pt_ctx::IMAGES;
+    const int next = c->hist.nextImage();
     HIP_TRY(c->dImage[next].ensure((size_t)c->nSlotsImg * 16));
     int rc;
     if ((rc = pump(c, ptp::PUMP_IMAGE, next))) return rc;              // nothing may still be on its way into the image taken over
-    c->curImage = next;
-    c->cam[next].valid = false; c->camWrites++;
+    c->hist.turnImage();
     c->sched.imageTurned();
     HIP_TRY(hipMemsetAsync(c->dImage[next], 0, (size_t)c->nSlotsImg * 16, c->stream));
     if (c->dStats) HIP_TRY(hipMemsetAsync(c->dStats, 0, (size_t)c->nSlotsImg * 16, c->stream));
@@ -2132,13 +2122,13 @@ int pt_finish_image(pt_ctx* c, int age) {
     if (!c || age < 0 || age >= pt_ctx::IMAGES) return fail(PT_ERR_ARG, "pt_finish_image: age must be in [0,3] (0 = current image)");
     MULTI_ALL(c, pt_finish_image(k, age));
     HIP_TRY(hipSetDevice(c->device));
-    return pump(c, ptp::PUMP_IMAGE, (c->curImage + pt_ctx::IMAGES - age) % pt_ctx::IMAGES);
+    return pump(c, ptp::PUMP_IMAGE, c->hist.imageOfAge(age));
 }
 
 int pt_image_device(pt_ctx* c, int age, void** dev_ptr, size_t* n_pixels) {
     if (!c || !dev_ptr || !n_pixels || age < 0 || age >= pt_ctx::IMAGES) return fail(PT_ERR_ARG, "pt_image_device: bad argument");
     if (c->multi) return fail(PT_ERR_ARG, "pt_image_device: a multi-GPU context has one packed accumulator per device; pt_gather_image delivers the whole image");
-    float4* img = c->dImage[(c->curImage + pt_ctx::IMAGES - age) % pt_ctx::IMAGES];
+    float4* img = c->dImage[c->hist.imageOfAge(age)];
     if (!img) return fail(PT_ERR_ARG, "pt_image_device: no image of that age yet (too few pt_next_image calls)");
     *dev_ptr = img; *n_pixels = (size_t)c->nSlotsImg;
     return PT_OK;
@@ -2184,7 +2174,7 @@ int pt_read_frame(pt_ctx* c, float* out) {
     }
     HIP_TRY(hipSetDevice(c->device));
     { int rc; if ((rc = flushStream(c))) return rc; }
-    return shardToHost(c, c->dImage[c->curImage], out);
+    return shardToHost(c, c->dImage[c->hist.image()], out);
 }
 
 /* The inverse of pt_read_frame: FRAME is the path tracer's only persistent state (frag.glsl:924-933: rgb = running sum, a = count), so a saved image written
@@ -2209,7 +2199,7 @@ int wholeFrame(pt_ctx* c, int code, const char* who, pt_ctx** on, const float4**
     *on = firstStream(c);
     if (!c->multi) {
         HIP_TRY(hipSetDevice(c->device));
-        *frame = c->dImage[c->curImage];
+        *frame = c->dImage[c->hist.image()];
         return flushStream(c);
     }
     float4* full = nullptr;
@@ -2398,7 +2388,7 @@ int pt_gather_image(pt_ctx* c, int age, void** full_dev) {
     if (c->shardCount != 1) return fail(PT_ERR_ARG, "pt_gather_image: this context is one shard of several; the gather belongs to the multi-GPU context (pt_create_multi) or to the host layer");
     int rc = pt_finish_image(c, age);
     if (rc) return rc;
-    *full_dev = c->dImage[(c->curImage + pt_ctx::IMAGES - age) % pt_ctx::IMAGES];
+    *full_dev = c->dImage[c->hist.imageOfAge(age)];
     if (!*full_dev) return fail(PT_ERR_ARG, "pt_gather_image: no image of that age yet (too few pt_next_image calls)");
     return PT_OK;
 }
@@ -2406,7 +2396,7 @@ int pt_gather_image(pt_ctx* c, int age, void** full_dev) {
 int pt_frame_device(pt_ctx* c, void** dev_ptr, size_t* n_pixels) {
     if (!c || !dev_ptr || !n_pixels) return fail(PT_ERR_ARG, "pt_frame_device: null argument");
     if (c->multi) return fail(PT_ERR_ARG, "pt_frame_device: a multi-GPU context has one packed accumulator per device; pt_gather_image delivers the whole image");
-    *dev_ptr = c->dImage[c->curImage]; *n_pixels = (size_t)c->nSlotsImg;
+    *dev_ptr = c->dImage[c->hist.image()]; *n_pixels = (size_t)c->nSlotsImg;
     return PT_OK;
 }
 
@@ -2614,7 +2604,7 @@ int probeIntersect(pt_ctx* c, const State& st, size_t np) {
 int claimFrameConstants(pt_ctx* c) {
     int rc;
     if ((rc = flushStream(c))) return rc;                         // before the frame constants of a running stream are overwritten
-    std::memset(&c->streamIn, 0xff, sizeof(FrameIn));             // ... which are no stream's any more afterwards
+    c->hist.frameConstantsTaken();                                // ... which are no stream's any more afterwards
     if (c->sceneDirty && (rc = buildScene(c))) return rc;
     return 0;
 }

@@ -83,14 +83,15 @@ int pt_write_moments(pt_ctx* c, const float* in) {
 
 // ---- first-hit feature records and the denoised image (include/pt_denoise.h).  A group context works on its first stream's context: the scene is replicated.
 namespace {
-// The records of the frame inputs `fin` in the cache R: first-hit records (rule == nullptr), or the seen-through records under `rule` with their last
-// segments.  Returns at once when R holds them; a failed fill leaves R invalid.  A probe pool takes the camera rays (k_feature_rays); then one
+// The records of the frame inputs `fin` in the cache `which`: first-hit records (rule == nullptr), or the seen-through records under `rule` with their last
+// segments.  Returns at once when it holds them; a failed fill leaves it invalid.  A probe pool takes the camera rays (k_feature_rays); then one
 // intersect and k_feature_record, or max_depth + 1 rounds of (intersect, k_through_step) — a fixed count, nothing read back in between: a round
 // whose lanes are all dead costs two launches that return at once
-int ensureRecords(pt_ctx* c, pt_ctx::Records& R, const FrameIn& fin, const pt_through_rule* rule, const char* who) {
+int ensureRecords(pt_ctx* c, ptp::RecordCache which, const FrameIn& fin, const pt_through_rule* rule, const char* who) {
     HIP_TRY(hipSetDevice(c->device));
-    if (R.valid && std::memcmp(&R.in, &fin, sizeof(FrameIn)) == 0 && (!rule || std::memcmp(&R.rule, rule, sizeof(*rule)) == 0)) return 0;
-    R.valid = false;
+    if (c->hist.cached(which, fin, rule)) return 0;
+    c->hist.beginFill(which);
+    pt_ctx::Records& R = c->rec[which];
     int rc;
     if ((rc = claimFrameConstants(c))) return rc;
     if (rule && (rule->flags & PT_THROUGH_KEY) && c->sc.numMat > 4096)
@@ -124,21 +125,19 @@ int ensureRecords(pt_ctx* c, pt_ctx::Records& R, const FrameIn& fin, const pt_th
             else THROUGH_STEP(0);
 #undef THROUGH_STEP
         }
-        R.rule = *rule;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    R.in = fin;
-    R.valid = true;
+    c->hist.filled(which, fin, rule);
     return 0;
 }
-// the records of the current frame inputs: c->feat, or c->thru under `rule`
+// the records of the current frame inputs: RC_FEAT, or RC_THRU under `rule`
 int currentRecords(pt_ctx* c, const pt_through_rule* rule, const char* who) {
     if (c->buf.params.size() < 12) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
     if (c->buf.origin.size() < 3 || c->buf.rotation.size() < 3) return fail(PT_ERR_ARG, "ORIGIN / ROTATION (bindings 0, 1) not set");
     FrameIn fin;
     currentInputs(c, fin);
-    return ensureRecords(c, rule ? c->thru : c->feat, fin, rule, who);
+    return ensureRecords(c, rule ? ptp::RC_THRU : ptp::RC_FEAT, fin, rule, who);
 }
 
 // include/pt_through.h's rule, checked
@@ -181,7 +180,7 @@ int denoiseImage(pt_ctx* c, int iterations, const float (&sigma)[4], pt_ctx** on
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise", &on, &frame))) return rc;
     if ((rc = currentRecords(on, nullptr, "pt_denoise"))) return rc;
     if ((rc = ensureFilterScratch(on))) return rc;
-    HIP_TRY(denoiseLaunch(frame, on->feat.recs, c->W, c->H, iterations, sigma, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
+    HIP_TRY(denoiseLaunch(frame, on->rec[ptp::RC_FEAT].recs, c->W, c->H, iterations, sigma, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
     *onOut = on;
     return 0;
 }
@@ -192,7 +191,7 @@ int pt_read_features(pt_ctx* c, float* out) {
     pt_ctx* on = firstStream(c);
     int rc;
     if ((rc = currentRecords(on, nullptr, "pt_read_features"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->feat.recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, on->rec[ptp::RC_FEAT].recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -237,7 +236,7 @@ int filteredImage(pt_ctx* c, bool fill, bool filter, int iterations, const float
         if (!j.stats) return fail(PT_ERR_ARG, w + ": the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
     }
     if ((rc = currentRecords(on, thru, who))) return rc;
-    j.feat = thru ? on->thru.recs : on->feat.recs;
+    j.feat = thru ? on->rec[ptp::RC_THRU].recs : on->rec[ptp::RC_FEAT].recs;
     if ((rc = ensureFilterScratch(on))) return rc;
     if (fill) {
         HIP_TRY(on->dFill.ensure((size_t)c->W * c->H * 16));
@@ -289,20 +288,8 @@ int pt_read_display_denoised_guided_demod(pt_ctx* c, int iterations, float sigma
 // every stream its shard back through the host, as pt_write_frame distributes an image; T travels through the host both ways.
 namespace {
 // the current inputs of `on` into cur, refused unless they render surfaces at the image's size; toDo: what the caller wants surfaces for
-int usableInputs(const pt_ctx* c, const pt_ctx* on, const std::string& w, const char* toDo, FrameIn& cur) {
-    if (!currentInputs(on, cur)) return fail(PT_ERR_ARG, "Parameters / ORIGIN / ROTATION (bindings 4, 0, 1) not set");
-    const float* P = on->buf.params.data();
-    if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
-    if (P[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, w + ": DEBUG != 0 renders the traversal heat map, which has no surfaces to " + toDo);
-    return 0;
-}
-// a valid camera record h of an image of `on`, refused unless feature records under it describe the image: the scene as it was, surfaces, the size
-int usableCamera(const pt_ctx* c, const pt_ctx* on, const pt_ctx::Cam& h, const std::string& w) {
-    if (h.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, w + ": a scene buffer or texture was uploaded since the image's camera was recorded");
-    if (h.in.params[10] != 0.0f) return fail(PT_ERR_UNSUPPORTED, w + ": the image was rendered with DEBUG != 0");
-    if ((int)h.in.params[2] != c->W || (int)(h.in.params[2] * h.in.params[3]) != c->H)
-        return fail(PT_ERR_ARG, w + ": the image's camera has Parameters that do not match the image size");
-    return 0;
+int usableInputs(pt_ctx* on, const std::string& w, const char* toDo, FrameIn& cur) {
+    return fail(on->hist.usableInputs(currentInputs(on, cur) ? &cur : nullptr, w, toDo));
 }
 // the reprojected image (on->dRpFrame, on->dRpStats when `stats`, on->dRpKept; enqueued on on->stream) into the current image of `c`, whose camera
 // becomes the current inputs
@@ -312,7 +299,7 @@ int storeReprojected(pt_ctx* c, pt_ctx* on, bool stats, int64_t* nKept) {
     unsigned kept = 0;
     HIP_TRY(hipMemcpyAsync(&kept, on->dRpKept, 4, hipMemcpyDeviceToHost, on->stream));
     if (!c->multi) {                                              // the result into the current image (a copy: pt_frame_device pointers stay valid)
-        HIP_TRY(hipMemcpyAsync(c->dImage[c->curImage], on->dRpFrame, n * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dImage[c->hist.image()], on->dRpFrame, n * 16, hipMemcpyDeviceToDevice, c->stream));
         if (stats) HIP_TRY(hipMemcpyAsync(c->dStats, on->dRpStats, n * 16, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         recordCamera(c);
@@ -395,36 +382,26 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, who, &on, &j.frame))) return rc;      // a group: gathered on on->stream
     if ((rc = syncAll(c))) return rc;                             // all submitted work lands in FRAME and T first
     FrameIn cur;
-    if ((rc = usableInputs(c, on, w, "carry", cur))) return rc;
-    pt_ctx::Mark& m = on->mark;
-    const pt_ctx::Cam h = on->cam[on->curImage];
-    if (moved) {
-        if (!m.valid) return fail(PT_ERR_ARG, w + ": no mark (pt_motion_mark first; a mark serves one call)");
-        if (m.image != on->curImage) return fail(PT_ERR_ARG, w + ": the mark belongs to another image");
-        if (!h.valid || m.camWrites != on->camWrites)
-            return fail(PT_ERR_ARG, w + ": the image's camera is no longer the marked one (a render, pt_write_frame, pt_reset_frame or pt_next_image since the mark)");
-        if (m.otherGen != on->otherGen) return fail(PT_ERR_ARG, w + ": binding 5, binding 14 or a texture was uploaded since the mark");
-    } else {
-        if (!h.valid) return PT_OK;                               // no camera: nothing to map from
-        if ((rc = usableCamera(c, on, h, w))) return rc;
-    }
+    if ((rc = usableInputs(on, w, "carry", cur))) return rc;
+    const pt_ctx::Mark& m = on->mark;
+    const ptp::ReprojectPlan plan = on->hist.planReproject(cur, moved, w);
+    if ((rc = fail(plan.refused))) return rc;
+    if (plan.nothing) return PT_OK;                               // no camera: nothing to map from
+    const FrameIn camIn = on->hist.camera().in;                   // the image's camera
     // Rn, in the scene as it is now (builds it when an upload is pending); Rh from the mark, or of the image's camera (the same records when it is unchanged)
-    if ((rc = ensureRecords(on, on->feat, cur, nullptr, who))) return rc;
-    j.rn = on->feat.recs;
-    const bool sameCam = std::memcmp(&h.in, &cur, sizeof(FrameIn)) == 0;
+    if ((rc = ensureRecords(on, ptp::RC_FEAT, cur, nullptr, who))) return rc;
+    j.rn = on->rec[ptp::RC_FEAT].recs;
     if (chain) {                                                  // an unchanged camera uses one pair for both
-        pt_ctx::Records& sh = sameCam ? on->thru : on->thruH;
-        if ((rc = ensureRecords(on, on->thru, cur, chain->thru, who))) return rc;
-        if (!sameCam && (rc = ensureRecords(on, sh, h.in, chain->thru, who))) return rc;
-        j.sn = on->thru.recs; j.yn = on->thru.rays; j.sh = sh.recs; j.yh = sh.rays;
+        if ((rc = ensureRecords(on, ptp::RC_THRU, cur, chain->thru, who))) return rc;
+        if (!plan.sameCam && (rc = ensureRecords(on, plan.sh, camIn, chain->thru, who))) return rc;
+        j.sn = on->rec[ptp::RC_THRU].recs; j.yn = on->rec[ptp::RC_THRU].rays; j.sh = on->rec[plan.sh].recs; j.yh = on->rec[plan.sh].rays;
         j.pointTol = chain->pointTol; j.radius = chain->radius;
     }
     if (moved) {
         j.rh = on->mark.feat;
     } else {
-        pt_ctx::Records& rh = sameCam ? on->feat : on->featH;
-        if (!sameCam && (rc = ensureRecords(on, rh, h.in, nullptr, who))) return rc;
-        j.rh = rh.recs;
+        if (!plan.sameCam && (rc = ensureRecords(on, plan.rh, camIn, nullptr, who))) return rc;
+        j.rh = on->rec[plan.rh].recs;
     }
     HIP_TRY(hipSetDevice(on->device));
     const size_t n = (size_t)c->W * c->H;
@@ -449,10 +426,10 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     }
     // the image's camera as k_frame_setup builds it (of which only camRot, origin, screenSize, focalLength and screenHratio are read), in the frame
     // constants, which are no stream's afterwards
-    *on->hFrameIn = h.in;
+    *on->hFrameIn = camIn;
     HIP_TRY(hipMemcpyAsync(on->dFrameIn, on->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, on->stream));
     hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, on->stream, on->sc, on->dFrameIn, on->dFc, on->dEllip);
-    std::memset(&on->streamIn, 0xff, sizeof(FrameIn));
+    on->hist.frameConstantsTaken();
     j.hist = on->dFc; j.matVD = on->dMatVD; j.nMat = on->sc.numMat; j.W = c->W; j.H = c->H;
     j.cam = ReprojCam{{cur.origin[0], cur.origin[1], cur.origin[2]}, cur.mouse[0], cur.mouse[1], cur.params[2]};
     j.rule = ReprojRule{maxHistory, depthTol, normalTol, (flags & PT_REPROJECT_ALL_MATERIALS) ? 1 : 0};
@@ -474,7 +451,7 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
         *taps->nBlended = blended;
     }
     if ((rc = storeReprojected(c, on, j.stats != nullptr, nKept))) return rc;
-    if (moved) m.valid = false;                                   // spent
+    if (moved) on->hist.markSpent();
     return 0;
 }
 }  // namespace
@@ -535,16 +512,13 @@ int motionMark(pt_ctx* c) {
     if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_motion_mark"))) return rc;
     if ((rc = syncAll(c))) return rc;                             // all submitted work lands first
     pt_ctx* on = firstStream(c);
-    const pt_ctx::Cam h = on->cam[on->curImage];
-    if (!h.valid) return fail(PT_ERR_ARG, "pt_motion_mark: the current image has no camera (render or pt_write_frame first)");
-    if ((rc = usableCamera(c, on, h, "pt_motion_mark"))) return rc;
-    on->mark.valid = false;
+    if ((rc = fail(on->hist.takeMark()))) return rc;              // (the old mark is gone from here)
     // (a) Rh, through the cache pt_reproject_frame keeps, into a buffer that later uploads leave alone
-    if ((rc = ensureRecords(on, on->featH, h.in, nullptr, "pt_motion_mark"))) return rc;
+    if ((rc = ensureRecords(on, ptp::RC_FEAT_H, FrameIn(on->hist.camera().in), nullptr, "pt_motion_mark"))) return rc;
     const size_t n = (size_t)c->W * c->H;
     pt_ctx::Mark& m = on->mark;
     HIP_TRY(m.feat.ensure(n * 64));
-    HIP_TRY(hipMemcpyAsync(m.feat, on->featH.recs, n * 64, hipMemcpyDeviceToDevice, on->stream));
+    HIP_TRY(hipMemcpyAsync(m.feat, on->rec[ptp::RC_FEAT_H].recs, n * 64, hipMemcpyDeviceToDevice, on->stream));
     // (b), (c) where the primitives are
     motionPositions(on, m.tri, &m.nTri, m.el, &m.nEl);
     std::vector<float4> pt, pe;
@@ -552,9 +526,7 @@ int motionMark(pt_ctx* c) {
     HIP_TRY(m.dTri.upload(pt.data(), pt.size() * 16, on->stream));
     HIP_TRY(m.dEl.upload(pe.data(), pe.size() * 16, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
-    // (d)
-    m.image = on->curImage; m.camWrites = on->camWrites; m.otherGen = on->otherGen;
-    m.valid = true;
+    on->hist.markTaken();                                         // (d)
     return PT_OK;
 }
 
@@ -585,27 +557,25 @@ int historyHold(pt_ctx* c) {
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_history_hold", &on, &frame))) return rc;
     if ((rc = wholeStats(c, on, &stats))) return rc;
     if (!stats) return fail(PT_ERR_ARG, "pt_history_hold: the image has no luminance moments (T was never allocated): call pt_record_moments before rendering");
-    const pt_ctx::Cam h = on->cam[on->curImage];
-    if (!h.valid) return fail(PT_ERR_ARG, "pt_history_hold: the current image has no camera (render or pt_write_frame first)");
+    if ((rc = fail(on->hist.takeHold()))) return rc;
     HIP_TRY(hipSetDevice(on->device));
     const size_t n = (size_t)c->W * c->H;
     HIP_TRY(on->hold.frame.ensure(n * 16));
     HIP_TRY(on->hold.stats.ensure(n * 16));
-    on->hold.valid = false;
+    on->hist.holdBegins();
     HIP_TRY(hipMemcpyAsync(on->hold.frame, frame, n * 16, hipMemcpyDeviceToDevice, on->stream));
     HIP_TRY(hipMemcpyAsync(on->hold.stats, stats, n * 16, hipMemcpyDeviceToDevice, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     auto zero = [](pt_ctx* k) {                                   // the image and T alone: the camera records, camWrites and a mark stay
         HIP_TRY(hipSetDevice(k->device));
-        HIP_TRY(hipMemsetAsync(k->dImage[k->curImage], 0, (size_t)k->nSlotsImg * 16, k->stream));
+        HIP_TRY(hipMemsetAsync(k->dImage[k->hist.image()], 0, (size_t)k->nSlotsImg * 16, k->stream));
         if (k->dStats) HIP_TRY(hipMemsetAsync(k->dStats, 0, (size_t)k->nSlotsImg * 16, k->stream));
         HIP_TRY(hipStreamSynchronize(k->stream));
         return 0;
     };
     if (c->multi) { if ((rc = multiRun(*c->multi, zero))) return rc; }
     else if ((rc = zero(c))) return rc;
-    on->hold.image = on->curImage; on->hold.in = h.in; on->hold.sceneGen = on->sceneGen;
-    on->hold.valid = true;
+    on->hist.holdTaken();
     return PT_OK;
 }
 
@@ -617,16 +587,9 @@ int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t*
     int rc;
     if ((rc = syncAll(c))) return rc;                             // work in flight lands in FRAME and T first
     pt_ctx* on = firstStream(c);
-    const pt_ctx::Hold& hd = on->hold;
-    if (!hd.valid) return fail(PT_ERR_ARG, "pt_history_merge: no hold (pt_history_hold first; a hold serves one merge)");
-    if (hd.image != on->curImage) return fail(PT_ERR_ARG, "pt_history_merge: the hold belongs to another image");
-    const pt_ctx::Cam h = on->cam[on->curImage];
-    if (!h.valid) return fail(PT_ERR_ARG, "pt_history_merge: the image has no camera (pt_reset_frame since the hold)");
-    if (std::memcmp(&h.in, &hd.in, sizeof(FrameIn)) != 0)
-        return fail(PT_ERR_ARG, "pt_history_merge: the image's camera no longer has the held frame inputs (a render or pt_write_frame under other inputs)");
-    if (hd.sceneGen != on->sceneGen) return fail(PT_ERR_ARG, "pt_history_merge: a scene buffer or texture was uploaded since the hold");
+    if ((rc = fail(on->hist.mergeHold()))) return rc;
     FrameIn cur;
-    if ((rc = usableInputs(c, on, "pt_history_merge", "compare on", cur))) return rc;
+    if ((rc = usableInputs(on, "pt_history_merge", "compare on", cur))) return rc;
     ValidateJob j;
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_history_merge", &on, &j.frame))) return rc;      // a group: gathered on on->stream
     if ((rc = wholeStats(c, on, &j.stats))) return rc;
@@ -638,7 +601,7 @@ int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t*
     HIP_TRY(on->dRpStats.ensure(n * 16));
     HIP_TRY(on->dRpKept.ensure(8));
     if (kappaOut) HIP_TRY(on->dKappa.ensure(n * 4));
-    j.feat = on->feat.recs; j.heldFrame = on->hold.frame; j.heldStats = on->hold.stats;
+    j.feat = on->rec[ptp::RC_FEAT].recs; j.heldFrame = on->hold.frame; j.heldStats = on->hold.stats;
     j.W = c->W; j.H = c->H; j.radius = r.radius; j.zLo = r.z_lo; j.zHi = r.z_hi; j.normalTol = r.normal_tol;
     j.overlay[0] = cur.mouse[0]; j.overlay[1] = cur.mouse[1]; j.overlay[2] = cur.params[2];
     j.outFrame = on->dRpFrame; j.outStats = on->dRpStats; j.kappa = kappaOut ? on->dKappa.p : nullptr; j.reduced = on->dRpKept;
@@ -646,7 +609,7 @@ int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t*
     if (kappaOut) HIP_TRY(hipMemcpyAsync(kappaOut, on->dKappa, n * 4, hipMemcpyDeviceToHost, on->stream));
     if ((rc = storeReprojected(c, on, true, nReduced))) return rc;      // (records the same camera again)
     HIP_TRY(hipStreamSynchronize(on->stream));
-    on->hold.valid = false;                                       // spent
+    on->hist.holdSpent();
     return 0;
 }
 }  // namespace
@@ -699,7 +662,7 @@ int selectGuided(pt_ctx* c, const pt_guided_rule& r, float floorA, const char* w
     }
     unsigned* count = reinterpret_cast<unsigned*>(on->dSelMask + maskBytes(on));
     const AdaptRule ovr = withOverlay(on, AdaptRule{});
-    j.feat = on->feat.recs; j.W = c->W; j.H = c->H; j.iterations = r.iterations; j.minFrames = r.min_frames; j.floorA = floorA;
+    j.feat = on->rec[ptp::RC_FEAT].recs; j.W = c->W; j.H = c->H; j.iterations = r.iterations; j.minFrames = r.min_frames; j.floorA = floorA;
     j.sigma[0] = r.sigma_lum; j.sigma[1] = r.sigma_normal; j.sigma[2] = r.sigma_depth; j.sigma[3] = r.sigma_albedo;
     j.col0 = on->dDnCol[0]; j.col1 = on->dDnCol[1]; j.guide = on->dDnGuide;
     j.mask = on->dSelMask; j.count = count; j.maxFrames = r.max_frames; j.relErr = r.rel_err; j.absErr = r.abs_err;
@@ -862,7 +825,7 @@ int pt_read_features_through(pt_ctx* c, const pt_through_rule* rule, float* out)
     if ((rc = checkThrough(rule, "pt_read_features_through"))) return rc;
     pt_ctx* on = firstStream(c);
     if ((rc = currentRecords(on, rule, "pt_read_features_through"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->thru.recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, on->rec[ptp::RC_THRU].recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -872,7 +835,7 @@ int pt_read_through_rays(pt_ctx* c, const pt_through_rule* rule, float* out) {
     if ((rc = checkThrough(rule, "pt_read_through_rays"))) return rc;
     pt_ctx* on = firstStream(c);
     if ((rc = currentRecords(on, rule, "pt_read_through_rays"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->thru.rays, (size_t)c->W * c->H * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, on->rec[ptp::RC_THRU].rays, (size_t)c->W * c->H * 32, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

@@ -162,7 +162,7 @@ int multiGather(pt_ctx* g, int age, float4** out) {
     std::vector<float4*> img(M.n);
     for (int i = 0; i < M.n; i++) {
         pt_ctx* k = M.kids[i];
-        img[i] = k->dImage[(k->curImage + pt_ctx::IMAGES - age) % pt_ctx::IMAGES];
+        img[i] = k->dImage[k->hist.imageOfAge(age)];
         if (!img[i]) return fail(PT_ERR_ARG, "no image of that age yet (too few pt_next_image calls)");
     }
     HIP_TRY(hipSetDevice(M.devices[0]));

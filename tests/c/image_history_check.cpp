@@ -1,0 +1,213 @@
+// image_history_check.cpp — the image history (csrc/hip/pt_image_history.hpp) on the CPU: a stand-alone program that runs scripts of calls against
+// a stand-in for the context (the history, the bound frame inputs and nothing else: no image, no device) and prints what every call answered
+// (tests/test_image_history.py).
+//
+//   image_history_check SCRIPTS       one trace per script on stdout, nothing on stderr, exit 0
+//
+// THE STAND-IN does around the history what pt_hip.hip and pt_image.hpp do around it, in their order, with every HIP call, launch and buffer left
+// out; work in flight, the image's luminance moments and the scene build never refuse here.  A SCRIPT is a block of lines:
+//   script NAME
+//   create W H                        pt_create
+//   inputs K                          the four uploads of Parameters, ORIGIN, ROTATION and MOUSE_POS (each drops the record caches, as every upload
+//                                     does).  K: 0 not set (a context's first state only), 1 a camera, 2 another origin, 3 camera 1 with DEBUG = 1,
+//                                     4 camera 1 with a resolution that is not the image's
+//   upload BINDING ok|refused         pt_set_buffer: camera (an ORIGIN equal to the one bound), geometry (3), implicits (5), materials (14), or
+//                                     other (6, which no upload takes); refused: the upload fails its check (camera: too short; geometry: a size
+//                                     that is no multiple of 40 floats; implicits and materials are never refused)
+//   texture                           pt_set_texture
+//   render | render-debug             pt_render under the bound inputs: a new stream unless the running one has them; render-debug is the same call
+//                                     and says that the script has DEBUG = 1 bound, where it is k_debug_heatmap's branch
+//   write | reset | next-image        pt_write_frame, pt_reset_frame, pt_next_image
+//   records feat|thru cur|image R     the record cache of that kind under the bound inputs (pt_read_features, pt_read_features_through under rule R:
+//                                     1 or 2; R = 0 for feat), or under the image's camera (what pt_motion_mark and a reprojection from a changed
+//                                     camera ask for; nothing without a camera)
+//   mark | moved | hold | merge       pt_motion_mark, pt_reproject_frame_moved, pt_history_hold, pt_history_merge
+//   reproject plain|through|bilinear  pt_reproject_frame, pt_reproject_frame_through (rule 1), pt_reproject_frame_bilinear
+//   claim                             claimFrameConstants (pt_debug_intersect)
+// THE TRACE, per script line after `script`: "cache NAME hit|fill" for every record cache asked, "cache NAME invalidated" for every one that was
+// valid before the call and is not after it, then "rc=CODE scene= other= writes=" (the three counters) "image=" (the current one) "camera= mark= hold="
+// (validity) "stream=" (1: the frame constants on the device are a stream's and that stream has the bound inputs; - when none are bound) and, when
+// refused, "error=" with the message.  After a script: "branches" — the HistoryBranch bits it reached.
+//
+// Every guard of the header can be reached by calls.  (Half of one cannot on its own: the moved reprojection's "camera is no longer the marked one"
+// asks for an invalid camera or another camWrites, and nothing invalidates a camera without counting; the test is kept as the parent has it.)
+#include <cinttypes>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../pathtracer-0_amd/csrc/hip/pt_image_history.hpp"
+
+using namespace ptp;
+
+static const char* const CACHE_NAME[RC_COUNT] = {"feat", "featH", "thru", "thruH"};
+
+struct Ctx {
+    ImageHistory hist;
+    bool bound = false; FrameIn in{};      // pt_ctx::buf's Parameters, ORIGIN, ROTATION, MOUSE_POS
+    std::string err;
+
+    int fail(int code, const std::string& msg) { err = msg; return code; }
+    int fail(const Refused& r) { return r.code ? fail(r.code, r.msg) : 0; }
+    const FrameIn* current() const { return bound ? &in : nullptr; }      // currentInputs
+
+    // ---- pt_hip.hip
+    void recordCamera() { hist.written(current()); }
+    int claimFrameConstants() { hist.frameConstantsTaken(); return 0; }
+    int setBuffer(const std::string& binding, bool ok) {
+        hist.uploadBegins();
+        if (binding == "camera") return ok ? 0 : fail(PT_ERR_ARG, "ORIGIN needs 3 floats");
+        if (binding == "geometry" && !ok) return fail(PT_ERR_ARG, "triangle buffer must be 40 floats per triangle");
+        if (binding == "other") return fail(PT_ERR_ARG, "pt_set_buffer: binding point not consumed by the render path (frag.glsl declares 0-5,7,10-15)");
+        hist.sceneBufferAccepted(binding == "geometry" ? PT_BIND_TRIANGLES : binding == "implicits" ? PT_BIND_IMPLICITS : PT_BIND_MATERIALS);
+        return 0;
+    }
+    int submitBatch() {
+        if (!bound) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+        const float* P = in.params;
+        const bool sized = (int)P[2] == W && (int)(P[2] * P[3]) == H;
+        if (!sized) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
+        if (P[10] != 0.0f) { hist.frameConstantsTaken(); hist.rendered(in); return 0; }      // DEBUG
+        if (!hist.streamHas(in)) hist.streamStarted(in);          // (the scheduler: a new stream)
+        hist.rendered(in);                                        // appendJobs
+        return 0;
+    }
+    // ---- pt_image.hpp
+    int ensureRecords(RecordCache which, const FrameIn& fin, const pt_through_rule* rule) {
+        if (hist.cached(which, fin, rule)) { std::printf("cache %s hit\n", CACHE_NAME[which]); return 0; }
+        hist.beginFill(which);
+        claimFrameConstants();
+        hist.filled(which, fin, rule);
+        std::printf("cache %s fill\n", CACHE_NAME[which]);
+        return 0;
+    }
+    int currentRecords(const pt_through_rule* rule) {
+        if (!bound) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
+        return ensureRecords(rule ? RC_THRU : RC_FEAT, in, rule);
+    }
+    int reprojectImage(const char* who, bool moved, const pt_through_rule* chain) {
+        const std::string w(who);
+        int rc;
+        if ((rc = fail(hist.usableInputs(current(), w, "carry")))) return rc;
+        const ReprojectPlan plan = hist.planReproject(in, moved, w);
+        if ((rc = fail(plan.refused))) return rc;
+        if (plan.nothing) return PT_OK;
+        const FrameIn camIn = hist.camera().in;
+        if ((rc = ensureRecords(RC_FEAT, in, nullptr))) return rc;
+        if (chain) {
+            if ((rc = ensureRecords(RC_THRU, in, chain))) return rc;
+            if (!plan.sameCam && (rc = ensureRecords(plan.sh, camIn, chain))) return rc;
+        }
+        if (!moved && !plan.sameCam && (rc = ensureRecords(plan.rh, camIn, nullptr))) return rc;
+        hist.frameConstantsTaken();
+        recordCamera();                                           // storeReprojected
+        if (moved) hist.markSpent();
+        return 0;
+    }
+    int motionMark() {
+        int rc;
+        if ((rc = fail(hist.takeMark()))) return rc;
+        if ((rc = ensureRecords(RC_FEAT_H, FrameIn(hist.camera().in), nullptr))) return rc;
+        hist.markTaken();
+        return PT_OK;
+    }
+    int historyHold() {
+        if (int rc = fail(hist.takeHold())) return rc;
+        hist.holdBegins();
+        hist.holdTaken();
+        return PT_OK;
+    }
+    int historyMerge() {
+        int rc;
+        if ((rc = fail(hist.mergeHold()))) return rc;
+        if ((rc = fail(hist.usableInputs(current(), "pt_history_merge", "compare on")))) return rc;
+        if ((rc = currentRecords(nullptr))) return rc;
+        recordCamera();                                           // storeReprojected
+        hist.holdSpent();
+        return 0;
+    }
+    int W = 0, H = 0;
+};
+
+static FrameIn inputsOf(int k) {
+    FrameIn f{};
+    const float P[12] = {0.5f, 1.0f, 32.0f, 0.5625f, 2.0f, 4.0f, 0.0f, 0.0f, 3.0f, 1.0f, 0.0f, 0.0f};
+    for (int i = 0; i < 12; i++) f.params[i] = P[i];
+    f.origin[0] = k == 2 ? 1.25f : 0.0f; f.origin[1] = 1.0f; f.origin[2] = -4.0f;
+    f.mouse[0] = -1.0f; f.mouse[1] = -1.0f;
+    if (k == 3) f.params[10] = 1.0f;
+    if (k == 4) f.params[2] = 64.0f;
+    return f;
+}
+
+static int die(const std::string& why) { std::fprintf(stderr, "image_history_check: %s\n", why.c_str()); return 2; }
+
+int main(int argc, char** argv) {
+    if (argc != 2) return die("usage: image_history_check SCRIPTS");
+    std::ifstream f(argv[1]);
+    if (!f) return die("cannot read the scripts");
+    static const pt_through_rule RULES[3] = {{0, 0.0f, 0, 0}, {2, 0.05f, 3, PT_THROUGH_KEY}, {3, 0.05f, 3, PT_THROUGH_KEY}};
+    Ctx* c = nullptr;
+    auto finish = [&]() { if (c) std::printf("branches %" PRIx64 "\n", c->hist.reached()); delete c; c = nullptr; };
+    std::string line;
+    while (std::getline(f, line)) {
+        std::istringstream ss(line);
+        std::string verb, a, b;
+        int k = 0;
+        if (!(ss >> verb)) continue;
+        if (verb == "script") { finish(); ss >> a; std::printf("== %s\n", a.c_str()); continue; }
+        if (verb == "create") { delete c; c = new Ctx; ss >> c->W >> c->H; c->hist.create(c->W, c->H); continue; }
+        if (!c) return die("no context: " + line);
+        bool before[RC_COUNT];
+        for (int i = 0; i < RC_COUNT; i++) before[i] = c->hist.cacheValid((RecordCache)i);
+        c->err.clear();
+        int rc = 0;
+        if (verb == "inputs") {
+            ss >> k;
+            if (k < 0 || k > 4 || (k == 0 && c->bound)) return die("bad inputs: " + line);
+            for (int n = 0; n < 4 && k; n++) c->hist.uploadBegins();
+            if (k) { c->bound = true; c->in = inputsOf(k); }
+        } else if (verb == "upload") {
+            ss >> a >> b;
+            if ((a != "camera" && a != "geometry" && a != "implicits" && a != "materials" && a != "other") || (b != "ok" && b != "refused")) return die("bad upload: " + line);
+            if (b == "refused" && (a == "implicits" || a == "materials")) return die("never refused: " + line);
+            rc = c->setBuffer(a, b == "ok");
+        } else if (verb == "texture") c->hist.textureUploaded();
+        else if (verb == "render" || verb == "render-debug") {
+            if (c->bound && (verb == "render-debug") != (c->in.params[10] != 0.0f)) return die("DEBUG is not what the verb says: " + line);
+            rc = c->submitBatch();
+        } else if (verb == "write") c->recordCamera();
+        else if (verb == "reset") c->hist.reset();
+        else if (verb == "next-image") c->hist.turnImage();
+        else if (verb == "records") {
+            ss >> a >> b >> k;
+            if ((a != "feat" && a != "thru") || (b != "cur" && b != "image") || k < 0 || k > 2 || (a == "thru") != (k != 0)) return die("bad records: " + line);
+            const pt_through_rule* rule = k ? &RULES[k] : nullptr;
+            if (b == "cur") rc = c->currentRecords(rule);
+            else if (c->hist.camera().valid) rc = c->ensureRecords(rule ? RC_THRU_H : RC_FEAT_H, FrameIn(c->hist.camera().in), rule);
+        } else if (verb == "mark") rc = c->motionMark();
+        else if (verb == "moved") rc = c->reprojectImage("pt_reproject_frame_moved", true, nullptr);
+        else if (verb == "hold") rc = c->historyHold();
+        else if (verb == "merge") rc = c->historyMerge();
+        else if (verb == "reproject") {
+            ss >> a;
+            if (a == "plain") rc = c->reprojectImage("pt_reproject_frame", false, nullptr);
+            else if (a == "through") rc = c->reprojectImage("pt_reproject_frame_through", false, &RULES[1]);
+            else if (a == "bilinear") rc = c->reprojectImage("pt_reproject_frame_bilinear", false, nullptr);
+            else return die("bad reproject: " + line);
+        } else if (verb == "claim") rc = c->claimFrameConstants();
+        else return die("unknown verb: " + line);
+        for (int i = 0; i < RC_COUNT; i++)
+            if (before[i] && !c->hist.cacheValid((RecordCache)i)) std::printf("cache %s invalidated\n", CACHE_NAME[i]);
+        const ImageHistory& h = c->hist;
+        std::printf("rc=%d scene=%" PRIu64 " other=%" PRIu64 " writes=%" PRIu64 " image=%d camera=%d mark=%d hold=%d stream=%s", rc, h.sceneUploads(), h.otherUploads(),
+                    h.cameraWrites(), h.image(), (int)h.camera().valid, (int)h.markValid(), (int)h.holdValid(), !c->bound ? "-" : h.streamHas(c->in) ? "1" : "0");
+        if (rc) std::printf(" error=%s", c->err.c_str());
+        std::printf("\n");
+    }
+    finish();
+    return 0;
+}
