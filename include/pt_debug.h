@@ -10,7 +10,8 @@
 extern "C" {
 #endif
 
-/* Tuning knobs: 0 = path slots in flight (default 0 = automatic: one per job of a synchronous batch within [2^20, 2^22]; 5/8 of the
+/* Tuning knobs (the table of csrc/hip/pt_options.hpp is their definition: numbers, accepted values, refusals, defaults; this is its description).
+ * 0 = path slots in flight (default 0 = automatic: one per job of a synchronous batch within [2^20, 2^22]; 5/8 of the
  * backlog up to 2^23 for overlapped batches), 1 = count traversal statistics (0/1), 2 = LDS bytes per block of the simple intersect
  * kernel, 3 = lanes of a wave waiting for their next BVH / retirement that make that phase worth a trip (default 8, 2 in the fused loop of the hand-written kernel; 1 = at once),
  * 4 = intersect kernel (0 simple, one block per 256 rays; 1 persistent blocks, compiled; 2 = default: the hand-written form of 1, csrc/hip/pt_extend_gfx950.s,
@@ -24,7 +25,7 @@ extern "C" {
  * 14 = main loop of the hand-written intersect kernel: -1 automatic (default), 0 phase-voting like the compiled kernel, 1 fused trip (every lane on a node or
  *      a leaf advances each trip; a lane's record is requested the moment its entry is decided).
  * 17 = block size of the hand-written intersect kernel: 0 automatic (default: 1024 threads — 2 blocks per CU over a 32 KB tile of the trees' top — when the
- *      context has its GPU to itself and the launch gives every CU its two blocks, else 256 threads), 256, 1024.
+ *      context has its GPU to itself and the launch gives every CU its two blocks, else 256 threads), 256, 512 or 1024.
  * 16 = numeric contract: 0 (default) exact — every float operation pinned, framebuffers bit-identical to the oracle; 1 relaxed — RNG, draw counts and
  *      branches as written, the continuous functions (Box-Muller's log / cos / sqrt, normalize, 1/d, 1/det, the BSDF weights' divides) on the
  *      hardware's v_log / v_cos / v_sqrt / v_rsq / v_rcp units: results within north_star's per-pixel RMSE <= 1e-3 of the oracle, not bit-identical.

@@ -39,6 +39,7 @@
 #include "../../../include/pt_reproject_bilinear.h"
 #include "pt_device.hpp"
 #include "pt_devmem.hpp"
+#include "pt_options.hpp"
 #include "pt_scene_layout.hpp"
 #include "pt_launch_plan.hpp"
 #include "pt_stream_sched.hpp"
@@ -1228,14 +1229,15 @@ struct pt_ctx {
     MultiCtx* multi = nullptr;      // != nullptr: a multi-GPU group (pt_create_multi, pt_multi.hpp); everything below then lives in its per-device contexts
     int device = 0, W = 0, H = 0, shardRank = 0, shardCount = 1;
     hipStream_t ownStream = nullptr, stream = nullptr;
-    // spatial partition (pt_set_option 21, an experiment: profiles/r06_c_cu_partition.txt): the intersect launches on a stream whose CU mask holds cuPartition eighths of
-    // every XCD's CUs, the shading launches on the complement; events order extend(i) -> shade(i) -> extend(i+1), everything else stays on `stream`
-    int cuPartition = 0, cuPartitionBuilt = 0; hipStream_t sExt = nullptr, sShade = nullptr; hipEvent_t evExt = nullptr, evShade = nullptr, evHost = nullptr;
+    ptp::Options opt;               // what pt_set_option has stored (pt_options.hpp: the table there says what each member means)
+    // spatial partition (opt.cuPartition) as built: the intersect launches on a stream whose CU mask holds that many eighths of every XCD's CUs, the shading
+    // launches on the complement; events order extend(i) -> shade(i) -> extend(i+1), everything else stays on `stream`
+    int cuPartitionBuilt = 0; hipStream_t sExt = nullptr, sShade = nullptr; hipEvent_t evExt = nullptr, evShade = nullptr, evHost = nullptr;
     SceneBuffers buf;               // raw SSBO contents and textures (host copies, glBufferData semantics): what layoutScene reads
     Dev<uchar4> dTexels; Dev<TexRec> dTexTable;      // all textures beyond the sky in one allocation + the bindless-style table
     bool sceneDirty = true, frameInDirty = true;
-    bool trans = false, anySubsurface = false, ambiguousTriObj = false, anyMaps = false, ellipMaps = false; Dev<int> dTriObj;
-    int stackDepth = 1;
+    bool trans = false, anySubsurface = false, ambiguousTriObj = false, anyMaps = false; Dev<int> dTriObj;
+    ptp::PlanScene built;           // the scene as built, as the launch planner reads it (buildScene): stack depth and entry width, record stride, eligibility, ...
     // device scene
     Dev<float4> dNodes, dTris, dShade; Dev<ObjRoot> dRoots; Dev<EllipRec> dEllip; Dev<MatRec> dMats;
     Dev<uchar4> dSky; Dev<float> dNiTable;
@@ -1247,7 +1249,6 @@ struct pt_ctx {
     static constexpr int IMAGES = ptp::ImageHistory::IMAGES;
     Dev<float4> dImage[IMAGES];     // FRAME images (more than one only after pt_next_image); hist.image() is the current one
     // path pool
-    int poolSlots = 0;              // 0 = automatic: jobs/5 clamped to [2^20, 2^22] (enough rays per lane for the in-wave refill, short tail)
     int allocSlots = 0; int allocNiBits = -1; bool allocHX = false;
     State st{};                     // the pool as the kernels take it; its groups are owned by dPool (in the order of ensurePool) and dPoolJ
     Dev<float4> dPool[9]; Dev<uint2> dPoolJ;
@@ -1259,33 +1260,19 @@ struct pt_ctx {
     // per group in flight (StreamSched::grp, by slot): k_snapshot writes Control into the pinned snapshot and then the group's number into the pinned STAMP
     struct GroupPins { Pinned<Control, hipHostMallocCoherent> h; Pinned<volatile unsigned, hipHostMallocCoherent> stamp; } grp[2];
     Pinned<FrameIn> hFrameIn; Pinned<int32_t> hSeeds;   // pinned staging (hSeeds: ring like dSeeds)
-    // options / stats
-    bool countStats = false, timing = false;
-    int ldsBudget = 20 * 1024;
-    int extendMode = 2;             // 0: one block per 256 lanes (k_extend), 1: persistent blocks (k_extend_persist), 2: the hand-written form of 1
-                                    //    (pt_extend_gfx950.s) for the scenes it takes, 1 for the others
+    // stats, and what the hand-written intersect kernel needs
+    bool timing = false;
     Dev<float> dNodes80;            // node records of the hand-written kernel: the two references + (min pair, max pair, min pair) per axis (80 B), or + pad + (min pair, max pair) (64 B)
-    int asmNodeStride = 80, asmNodeLayout = -1;      // bytes per record as built; pt_set_option 19: -1 automatic, 0 80-B, 1 64-B
-    int asmGroupShift = 0; bool asmNoRootCull = false;      // more than 8 BVHs: log2 of the objects per group box of the per-ray cull; pt_set_option 20 switches the cull off (every group box infinite)
+    int asmGroupShift = 0;          // more than 8 BVHs: log2 of the objects per group box of the per-ray cull
     Dev<unsigned char> dAsmDbg;     // developer builds of the hand-written kernel (-DPT_ASM_DEBUG): its per-wave records
     std::string asmError;           // a failed load / launch of the hand-written kernel (surfaces as PT_ERR_HIP from the render call)
     uint64_t asmLaunches = 0;
-    bool asmEligible = false;       // this scene can run on the hand-written kernel (buildScene)
-    std::string asmWhyNot;          // ... or why not (pt_debug: reported by option 12)
+    std::string asmWhyNot;          // why this scene cannot run on the hand-written kernel (built.asmEligible; pt_debug: reported by option 12)
     // per block size (256, 1024, 512 threads) six code objects: 16-bit stack entries, Packed18, the same two with v_rcp_f32 (relaxed contract), 24-bit entries exact / relaxed
     hipModule_t asmModule[18] = {}; hipFunction_t asmFn[18] = {}; std::string asmLoadError[18];
-    int asmTpb = 0;                 // threads per block of the hand-written kernel: 0 automatic (planExtendAsm, pt_launch_plan.hpp), 256, 1024
-    int extendTpb = 256, extendCacheBytes = 8 * 1024, refillMin = 24, numCUs = 256;
-    int noneMin = 8;                // lanes waiting for their next object / retirement that make that phase worth a trip
-    bool noneMinSet = false;        // pt_set_option 3 was used
+    int numCUs = 256;
     int streamsOnDevice = 1;        // streams of the same multi-stream context on this context's GPU (pt_create_multi)
-    bool extendCacheSet = false;    // pt_set_option 6 was used: the tile size is the caller's
-    int forceNiBits8 = 0;           // pt_set_option 18 (tests): 1 = 8-bit index-stack codes even when the scene's dictionary fits 3 bits, 2 = the float stack
-    bool fastContract = false, streamFast = false;      // the relaxed numeric contract (pt_set_option 16) as set / as the running stream was started with
-    int asmLoop = -1;               // hand-written kernel's main loop: -1 automatic, 0 phase-voting, 1 fused trip (pt_set_option 14)
-    int stackMode = 2, stackModeForce = -1;      // 0: short entries, 1: Packed18, 2: int (see k_extend_persist); Force: pt_set_option 11
-    int pLdsNodes = 0, pLdsTris = 0; int extendMaxBlocksPerCU = 0; int innerKeepEighths = 6;
-    int bfsNodes = 0x7fffffff;      // inner-node records kept in breadth-first order (whole levels); the rest follow depth-first (buildScene)
+    bool streamFast = false;        // the relaxed numeric contract (opt.fastContract) as the running stream was started with
     uint64_t hostCnt[PT_CNT_N] = {0};
     // adaptive sampling (include/pt_adaptive.h): per accumulator slot (sY, sYY, n, 0), allocated by the first pt_render_adaptive; the selection's scratch;
     // while adaptOn the running frame stream's pixel list is the active list (streamBatch), its nLocal adaptN
@@ -1339,11 +1326,8 @@ size_t shardSlots(int W, int H, int count) {
 // The scene build's device half: lays the buffers out on the host (layoutScene, pt_scene_layout.hpp), uploads the arrays, wires DevScene, and only then
 // takes the layout's flags and modes into the context: a refused scene leaves the context as it was (sceneDirty stays set).
 int buildScene(pt_ctx* c) {
-    LayoutOptions opt;
-    opt.bfsNodes = c->bfsNodes; opt.asmNodeLayout = c->asmNodeLayout; opt.asmNoRootCull = c->asmNoRootCull; opt.forceNiBits8 = c->forceNiBits8;
-    opt.ldsBudget = c->ldsBudget; opt.extendCacheBytes = c->extendCacheBytes; opt.stackModeForce = c->stackModeForce;
     SceneLayout L; std::string err;
-    if (const int rc = layoutScene(c->buf, opt, L, err)) return fail(rc, err);
+    if (const int rc = layoutScene(c->buf, c->opt, L, err)) return fail(rc, err);
     const SceneBuffers& b = c->buf;
     hipStream_t s = c->stream;
     HIP_TRY(hipStreamSynchronize(s));
@@ -1374,17 +1358,16 @@ int buildScene(pt_ctx* c) {
     sc.niTable = c->dNiTable;
     sc.mats = c->dMats; sc.numMat = L.numMat; sc.sky = c->dSky; sc.skyW = b.skyW; sc.skyH = b.skyH; sc.tex = c->dTexTable; sc.numTex = (int)table.size();
     sc.ldsNodes = L.ldsNodes; sc.ldsTris = L.ldsTris;
-    c->trans = L.trans; c->anySubsurface = L.anySubsurface; c->anyMaps = L.anyMaps; c->ellipMaps = L.ellipMaps; c->ambiguousTriObj = L.ambiguousTriObj;
-    c->niBits = L.niBits; c->stackDepth = L.stackDepth; c->asmNodeStride = L.asmNodeStride; c->asmGroupShift = L.asmGroupShift;
-    c->stackMode = L.stackMode; c->pLdsNodes = L.pLdsNodes; c->pLdsTris = L.pLdsTris;
-    c->asmEligible = L.asmEligible; c->asmWhyNot = L.asmWhyNot;
+    c->trans = L.trans; c->anySubsurface = L.anySubsurface; c->anyMaps = L.anyMaps; c->ambiguousTriObj = L.ambiguousTriObj;
+    c->niBits = L.niBits; c->asmGroupShift = L.asmGroupShift; c->asmWhyNot = L.asmWhyNot;
+    c->built = L.planScene();
     c->sceneDirty = false;
     return 0;
 }
 
 int ensurePool(pt_ctx* c, int capacity) {               // capacity >= poolActive: room for a pool that grows while a stream runs
     capacity = std::max(capacity, c->sched.poolActive);
-    if (c->allocSlots >= capacity && c->allocNiBits == c->niBits && c->allocHX == c->ellipMaps) return 0;
+    if (c->allocSlots >= capacity && c->allocNiBits == c->niBits && c->allocHX == c->built.ellipMaps) return 0;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->allocSlots = 0;                                            // until every allocation below has succeeded there is no pool
     float4** groups[] = {&c->st.G0, &c->st.G1, &c->st.G2, &c->st.G3, &c->st.G4, &c->st.H, &c->st.G5, &c->st.S0, &c->st.HX};
@@ -1394,14 +1377,14 @@ int ensurePool(pt_ctx* c, int capacity) {               // capacity >= poolActiv
     for (auto& q : c->dQueue) HIP_TRY(q.release());
     size_t n = (size_t)capacity;
     for (int k = 0; k < 9; k++) {
-        if ((k == 6 && c->niBits == 0) || (k == 7 && c->niBits < 8) || (k == 8 && !c->ellipMaps)) continue;      // G5: transmissive scenes; S0: 8-bit index-stack codes, or three planes of floats; HX: mapped ellipsoids
+        if ((k == 6 && c->niBits == 0) || (k == 7 && c->niBits < 8) || (k == 8 && !c->built.ellipMaps)) continue;      // G5: transmissive scenes; S0: 8-bit index-stack codes, or three planes of floats; HX: mapped ellipsoids
         HIP_TRY(c->dPool[k].reset(n * 16 * ((k == 7 && c->niBits == 32) ? 3 : 1)));
         *groups[k] = c->dPool[k];
     }
     HIP_TRY(c->dPoolJ.reset(n * 8));
     c->st.J = c->dPoolJ;
     for (auto& q : c->dQueue) HIP_TRY(q.reset(n * 4));
-    c->allocSlots = capacity; c->allocNiBits = c->niBits; c->allocHX = c->ellipMaps; c->st.s0Plane = (unsigned)capacity;
+    c->allocSlots = capacity; c->allocNiBits = c->niBits; c->allocHX = c->built.ellipMaps; c->st.s0Plane = (unsigned)capacity;
     return 0;
 }
 
@@ -1427,8 +1410,8 @@ struct PoolRun {            // host view of the path pool while a batch runs
 };
 template <bool COUNT, typename StackT, int TPB, bool RARE>
 void launchEP(pt_ctx* c, const PoolRun& pr, const DevScene& sc, const ptp::ExtendPlan& p) {
-    hipLaunchKernelGGL((k_extend_persist<COUNT, StackT, TPB, RARE>), dim3(p.grid), dim3(TPB), p.lds, pr.stream, sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl, c->refillMin,
-                       c->innerKeepEighths, p.nObjLds, p.noneMin);
+    hipLaunchKernelGGL((k_extend_persist<COUNT, StackT, TPB, RARE>), dim3(p.grid), dim3(TPB), p.lds, pr.stream, sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl, c->opt.refillMin,
+                       c->opt.innerKeepEighths, p.nObjLds, p.noneMin);
 }
 // Kernel arguments of pt_extend_gfx950.s (offsets are written into the assembly)
 struct EpAsmArgs {
@@ -1467,17 +1450,13 @@ int loadAsmKernel(pt_ctx* c, int k) {
     return 0;
 }
 
-// The plan of an intersect launch over the pool `pr` (pt_launch_plan.hpp).  probes: the pool carries thickness probes (RAYTRACING == 0); fast: the relaxed
-// reciprocal may be used; handWritten = false: the compiled kernel's plan where pt_set_option 4 would have asked for the hand-written one
-ptp::ExtendPlan planExtendFor(const pt_ctx* c, const PoolRun& pr, bool probes, bool fast, bool handWritten = true) {
-    ptp::PlanScene s; ptp::PlanOptions o; ptp::PlanDevice dv; ptp::PlanCall call;
-    s.nNodes = c->sc.nNodes; s.nTriRecs = c->sc.nTriRecs; s.numObj = c->sc.numObj; s.stackDepth = c->stackDepth; s.stackMode = c->stackMode; s.asmNodeStride = c->asmNodeStride;
-    s.ellipMaps = c->ellipMaps; s.asmEligible = c->asmEligible; s.ldsNodes = c->sc.ldsNodes; s.ldsTris = c->sc.ldsTris;
-    o.extendMode = handWritten ? c->extendMode : 1; o.extendTpb = c->extendTpb; o.extendCacheBytes = c->extendCacheBytes; o.extendCacheSet = c->extendCacheSet;
-    o.extendMaxBlocksPerCU = c->extendMaxBlocksPerCU; o.asmTpb = c->asmTpb; o.asmLoop = c->asmLoop; o.noneMin = c->noneMin; o.noneMinSet = c->noneMinSet; o.countStats = c->countStats;
+// The plan of an intersect launch over the pool `pr` (pt_launch_plan.hpp) under the options o.  probes: the pool carries thickness probes (RAYTRACING == 0);
+// fast: the relaxed reciprocal may be used
+ptp::ExtendPlan planExtendFor(const pt_ctx* c, const ptp::Options& o, const PoolRun& pr, bool probes, bool fast) {
+    ptp::PlanDevice dv; ptp::PlanCall call;
     dv.numCUs = c->numCUs; dv.streamsOnDevice = c->streamsOnDevice; dv.part = c->sExt != nullptr && pr.stream == c->sExt; dv.partEighths = c->cuPartitionBuilt;
     call.launched = pr.launched; call.probes = probes; call.fast = fast;
-    return ptp::planExtend(s, o, dv, call);
+    return ptp::planExtend(c->built, o, dv, call);
 }
 
 // true: launched.  false: the load or the launch failed; c->asmError says why (loud: pump() fails, no silent fallback)
@@ -1486,8 +1465,8 @@ bool launchExtendAsm(pt_ctx* c, const PoolRun& pr, const ptp::ExtendPlan& p) {
     EpAsmArgs a{};
     a.nodes80 = c->dNodes80; a.tris = c->dTris; a.roots = c->dRoots; a.G0 = pr.st.G0; a.G1 = pr.st.G1; a.H = pr.st.H;
     a.queue = c->dQueue[pr.iter & 1]; a.ctl = c->dCtl;
-    a.ellip = c->dEllip; a.numEllip = c->sc.numEllip; a.nodeStride = c->asmNodeStride; a.groupShift = c->asmGroupShift; a.stackDepth = c->stackDepth; a.HX = c->ellipMaps ? (void*)pr.st.HX : nullptr;
-    a.numObj = c->sc.numObj; a.iter = pr.iter; a.nSlots = (int)pr.launched; a.refillMin = c->refillMin; a.keepEighths = c->innerKeepEighths;
+    a.ellip = c->dEllip; a.numEllip = c->sc.numEllip; a.nodeStride = c->built.asmNodeStride; a.groupShift = c->asmGroupShift; a.stackDepth = c->built.stackDepth; a.HX = c->built.ellipMaps ? (void*)pr.st.HX : nullptr;
+    a.numObj = c->sc.numObj; a.iter = pr.iter; a.nSlots = (int)pr.launched; a.refillMin = c->opt.refillMin; a.keepEighths = c->opt.innerKeepEighths;
     a.ldsNodes = p.ldsNodes; a.ldsTris = p.ldsTris; a.noneMin = p.noneMin; a.mode = p.mode; a.nWaves = p.nWaves; a.divM = p.divM; a.divS = p.divS;
 #ifdef PT_ASM_DEBUG                  // developer builds only (scripts/build_variant.py -DPT_ASM_DEBUG): the per-wave debug records of the assembly
     {
@@ -1510,8 +1489,8 @@ void launchExtendPersist(pt_ctx* c, const PoolRun& pr, const ptp::ExtendPlan& p)
     const int tpb = p.tpb;
 #define EP(COUNT, T, TPB) (p.rare ? launchEP<COUNT, T, TPB, true>(c, pr, sc, p) : launchEP<COUNT, T, TPB, false>(c, pr, sc, p))
 #define EP_T(COUNT, T) do { if (tpb == 64) EP(COUNT, T, 64); else if (tpb == 128) EP(COUNT, T, 128); else if (tpb == 256) EP(COUNT, T, 256); else if (tpb == 512) EP(COUNT, T, 512); else EP(COUNT, T, 1024); } while (0)
-    if (c->countStats) { if (c->stackMode == 0) EP_T(true, short); else if (c->stackMode == 1) EP_T(true, Packed18); else EP_T(true, int); }
-    else { if (c->stackMode == 0) EP_T(false, short); else if (c->stackMode == 1) EP_T(false, Packed18); else EP_T(false, int); }
+    if (c->opt.countStats) { if (c->built.stackMode == 0) EP_T(true, short); else if (c->built.stackMode == 1) EP_T(true, Packed18); else EP_T(true, int); }
+    else { if (c->built.stackMode == 0) EP_T(false, short); else if (c->built.stackMode == 1) EP_T(false, Packed18); else EP_T(false, int); }
 #undef EP
 #undef EP_T
 }
@@ -1519,10 +1498,15 @@ void launchExtendPersist(pt_ctx* c, const PoolRun& pr, const ptp::ExtendPlan& p)
 // The intersect launch of one iteration over the pool `pr`, as planned; a hand-written kernel that failed to load or launch leaves the compiled one's
 // launch behind it and its error in c->asmError
 void launchExtend(pt_ctx* c, const PoolRun& pr, bool probes, bool fast) {
-    const ptp::ExtendPlan p = planExtendFor(c, pr, probes, fast);
-    if (p.kernel == ptp::K_ASM) { if (!launchExtendAsm(c, pr, p)) launchExtendPersist(c, pr, planExtendFor(c, pr, probes, fast, false)); }
+    const ptp::ExtendPlan p = planExtendFor(c, c->opt, pr, probes, fast);
+    if (p.kernel == ptp::K_ASM) {
+        if (!launchExtendAsm(c, pr, p)) {                         // the compiled kernel's plan where option 4 asked for the hand-written one
+            ptp::Options compiled = c->opt; compiled.extendMode = 1;
+            launchExtendPersist(c, pr, planExtendFor(c, compiled, pr, probes, fast));
+        }
+    }
     else if (p.kernel == ptp::K_PERSIST) launchExtendPersist(c, pr, p);
-    else if (c->countStats) hipLaunchKernelGGL(k_extend<true>, dim3(p.grid), dim3(BLOCK), p.lds, pr.stream, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl);
+    else if (c->opt.countStats) hipLaunchKernelGGL(k_extend<true>, dim3(p.grid), dim3(BLOCK), p.lds, pr.stream, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl);
     else hipLaunchKernelGGL(k_extend<false>, dim3(p.grid), dim3(BLOCK), p.lds, pr.stream, c->sc, pr.st, c->dQueue[pr.iter & 1], pr.iter, (int)pr.launched, c->dCtl);
 }
 
@@ -1565,22 +1549,22 @@ void giveStream(int device, hipStream_t s) { std::lock_guard<std::mutex> lk(g_st
 // CU-masked streams of the spatial partition.  Bit k of a mask is CU k in the driver's order; whether consecutive bits walk the CUs of one XCD or the XCDs round-robin,
 // the pattern ((k / 8) + (k % 8)) % 8 < e puts 4 e of every XCD's 32 CUs on the intersect side.
 int ensurePartition(pt_ctx* c) {
-    if (c->cuPartition == c->cuPartitionBuilt) return 0;
+    if (c->opt.cuPartition == c->cuPartitionBuilt) return 0;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->sExt) { hipStreamSynchronize(c->sExt); giveStream((c->device + 1) * 100 + c->cuPartitionBuilt, c->sExt); c->sExt = nullptr; }
     if (c->sShade) { hipStreamSynchronize(c->sShade); giveStream((c->device + 1) * 100 + 50 + c->cuPartitionBuilt, c->sShade); c->sShade = nullptr; }
     c->cuPartitionBuilt = 0;
-    if (c->cuPartition > 0) {
+    if (c->opt.cuPartition > 0) {
         const int words = (c->numCUs + 31) / 32;
         std::vector<uint32_t> mE((size_t)words, 0u), mS((size_t)words, 0u);
         for (int k = 0; k < c->numCUs; k++) {
-            const bool ext = ((k / 8) + (k % 8)) % 8 < c->cuPartition;
+            const bool ext = ((k / 8) + (k % 8)) % 8 < c->opt.cuPartition;
             (ext ? mE : mS)[(size_t)k / 32] |= 1u << (k % 32);
         }
-        if (!pooledStream((c->device + 1) * 100 + c->cuPartition, &c->sExt)) HIP_TRY(hipExtStreamCreateWithCUMask(&c->sExt, (uint32_t)words, mE.data()));
-        if (!pooledStream((c->device + 1) * 100 + 50 + c->cuPartition, &c->sShade)) HIP_TRY(hipExtStreamCreateWithCUMask(&c->sShade, (uint32_t)words, mS.data()));
+        if (!pooledStream((c->device + 1) * 100 + c->opt.cuPartition, &c->sExt)) HIP_TRY(hipExtStreamCreateWithCUMask(&c->sExt, (uint32_t)words, mE.data()));
+        if (!pooledStream((c->device + 1) * 100 + 50 + c->opt.cuPartition, &c->sShade)) HIP_TRY(hipExtStreamCreateWithCUMask(&c->sShade, (uint32_t)words, mS.data()));
         if (!c->evExt) { HIP_TRY(hipEventCreateWithFlags(&c->evExt, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&c->evShade, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&c->evHost, hipEventDisableTiming)); }
-        c->cuPartitionBuilt = c->cuPartition;
+        c->cuPartitionBuilt = c->opt.cuPartition;
     }
     return 0;
 }
@@ -1611,7 +1595,7 @@ struct StreamDev {
 #define SHADE_V(T, S, D, X) TIMED_LAUNCH_ON(ss, 1, hipLaunchKernelGGL((k_shade<T, S, D, X>), SHADE_ARGS))
 #define SHADE_F(T, X) TIMED_LAUNCH_ON(ss, 1, hipLaunchKernelGGL((k_shade<T, false, false, X, true>), SHADE_ARGS))
             // (the relaxed numeric contract, pt_set_option 16: path tracing without statistics only; everything else keeps the exact kernels)
-#define SHADE_S(T, D, X) do { if (c->countStats) SHADE_V(T, true, D, X); else if (fastNow && !(D)) SHADE_F(T, X); else SHADE_V(T, false, D, X); } while (0)
+#define SHADE_S(T, D, X) do { if (c->opt.countStats) SHADE_V(T, true, D, X); else if (fastNow && !(D)) SHADE_F(T, X); else SHADE_V(T, false, D, X); } while (0)
 #define SHADE_X(T, D) do { if (c->anyMaps) SHADE_S(T, D, true); else SHADE_S(T, D, false); } while (0)
             if (direct) SHADE_X(0, true);
             else if (c->niBits == 3) SHADE_X(3, false);
@@ -1701,7 +1685,7 @@ struct StreamDev {
             HIP_TRY(c->hSeeds.reset((size_t)wantRing * 4));
             c->ringFrames = wantRing;
         }
-        c->hist.streamStarted(*in); *c->hFrameIn = *in; c->streamFast = c->fastContract;
+        c->hist.streamStarted(*in); *c->hFrameIn = *in; c->streamFast = c->opt.fastContract;
         HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
         hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, s, c->dCtl);
@@ -1723,7 +1707,7 @@ struct StreamDev {
         hipLaunchKernelGGL(k_submit, dim3(1), dim3(1), 0, s, c->dCtl, nJobs, mode, (unsigned)N);
         const Batch b = streamBatch(c);
 #define REVIVE(T, F) TIMED_LAUNCH(2, hipLaunchKernelGGL((k_revive<T, F>), dim3((N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, b, c->dFc, c->st, N, c->dCtl))
-        const bool fastRevive = c->streamFast && !directNew && !c->countStats;
+        const bool fastRevive = c->streamFast && !directNew && !c->opt.countStats;
         // (directDiffuse never touches the index stack: its k_shade variant is the one without it, and so is its path state — except that the pool of a
         //  scene with transmissive materials has the groups allocated, which k_revive<niBits> initialises)
         if (c->niBits == 3) { if (fastRevive) REVIVE(3, true); else REVIVE(3, false); }
@@ -1819,7 +1803,7 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
         if ((int)P[2] != c->W || (int)(P[2] * P[3]) != c->H) return fail(PT_ERR_ARG, "Parameters.resolution / screenHratio do not match the FRAME image size given to pt_create");
         if ((rc = flushStream(c))) return rc;
         if (c->sceneDirty && (rc = buildScene(c))) return rc;
-        if (c->stackDepth > 64) return fail(PT_ERR_SCENE, "DEBUG heat-map: BVH deeper than the 64-entry traversal stack");
+        if (c->built.stackDepth > 64) return fail(PT_ERR_SCENE, "DEBUG heat-map: BVH deeper than the 64-entry traversal stack");
         *c->hFrameIn = fin;
         HIP_TRY(hipMemcpyAsync(c->dFrameIn, c->hFrameIn, sizeof(FrameIn), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_frame_setup, dim3(1), dim3(64), 0, s, c->sc, c->dFrameIn, c->dFc, c->dEllip);
@@ -1840,10 +1824,10 @@ int submitBatch(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, bo
     // whether the running stream takes the batch, the pool, the groups of iterations and the retirements: the scheduler's (pt_stream_sched.hpp)
     ptp::SubmitReq q;
     q.firstFrame = firstFrame; q.nFrames = nFrames; q.image = c->hist.image(); q.nJobs = nJobs64; q.async = async;
-    q.sceneDirty = c->sceneDirty; q.sameInputs = c->hist.streamHas(fin); q.sameContract = c->streamFast == c->fastContract;
+    q.sceneDirty = c->sceneDirty; q.sameInputs = c->hist.streamHas(fin); q.sameContract = c->streamFast == c->opt.fastContract;
     q.ringFrames = c->ringFrames; q.wantRing = ptp::ringRows(nFrames, async, (size_t)c->nSlotsImg * 16, pt_ctx::IMAGES);
-    q.poolSlots = c->poolSlots; q.allocSlots = c->allocSlots;
-    StreamDev dev{c, &fin, seeds, P[9] != 1.0f, ptp::newStreamCapacity(async, c->poolSlots), q.wantRing};      // (RAYTRACING == 0: directDiffuse, frag.glsl:655-681, :911-912)
+    q.poolSlots = c->opt.poolSlots; q.allocSlots = c->allocSlots;
+    StreamDev dev{c, &fin, seeds, P[9] != 1.0f, ptp::newStreamCapacity(async, c->opt.poolSlots), q.wantRing};      // (RAYTRACING == 0: directDiffuse, frag.glsl:655-681, :911-912)
     uint64_t iters = 0;
     rc = c->sched.submit(dev, q, &iters);
     countIterations(c, iters);
@@ -2447,33 +2431,15 @@ int pt_set_option(pt_ctx* c, int option, int64_t value) {
     if (!c) return fail(PT_ERR_ARG, "null context");
     MULTI_ALL(c, pt_set_option(k, option, value));
     { int rc; if ((rc = flushStream(c))) return rc; }
-    switch (option) {
-        case 0: if (value != 0 && (value < BLOCK || value > (1 << 26))) return fail(PT_ERR_ARG, "path slots must be 0 (automatic) or in [256, 2^26]"); c->poolSlots = (int)((value + BLOCK - 1) / BLOCK * BLOCK); return PT_OK;
-        case 1: c->countStats = value != 0; return PT_OK;
-        case 2: if (value < 0 || value > 160 * 1024) return fail(PT_ERR_ARG, "LDS budget out of range"); c->ldsBudget = (int)value; c->sceneDirty = true; return PT_OK;
-        case 3: if (value < 1 || value > 64) return fail(PT_ERR_ARG, "next-object threshold must be in [1,64]"); c->noneMin = (int)value; c->noneMinSet = true; return PT_OK;
-        case 4: if (value < 0 || value > 2) return fail(PT_ERR_ARG, "extend mode must be 0, 1 or 2"); c->extendMode = (int)value; return PT_OK;
-        case 16: if (value != 0 && value != 1) return fail(PT_ERR_ARG, "numeric contract: 0 exact (bit-identical to the oracle), 1 relaxed (hardware rcp/rsq/sqrt/log/cos; RMSE <= 1e-3)"); c->fastContract = value != 0; return PT_OK;
-        case 19: if (value < -1 || value > 1) return fail(PT_ERR_ARG, "node records of the hand-written kernel: -1 automatic, 0 80-B sign-ordered, 1 64-B"); c->asmNodeLayout = (int)value; c->sceneDirty = true; return PT_OK;
-        case 18: if (value < 0 || value > 2) return fail(PT_ERR_ARG, "index-stack encoding: 0 automatic, 1 at least 8-bit codes, 2 the floats themselves"); c->forceNiBits8 = (int)value; c->sceneDirty = true; return PT_OK;
-        case 21: if (value < 0 || value > 7) return fail(PT_ERR_ARG, "spatial partition: eighths of every XCD's CUs for the intersect kernel (0 = off: both kernels on all CUs)"); c->cuPartition = (int)value; return PT_OK;
-        case 20: if (value != 0 && value != 1) return fail(PT_ERR_ARG, "per-ray cull of the object loop (more than 8 BVHs): 0 off, 1 on"); c->asmNoRootCull = value == 0; c->sceneDirty = true; return PT_OK;
-        case 17: if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(PT_ERR_ARG, "block size of the hand-written kernel: 0 automatic, 256, 512 or 1024"); c->asmTpb = (int)value; return PT_OK;
-        case 14: if (value < -1 || value > 1) return fail(PT_ERR_ARG, "main loop of the hand-written kernel: -1 automatic, 0 phase-voting, 1 fused trip"); c->asmLoop = (int)value; return PT_OK;
-        case 13: return c->asmLaunches > (uint64_t)value ? PT_OK : fail(PT_ERR_UNSUPPORTED, "the hand-written intersect kernel has been launched " + std::to_string(c->asmLaunches) + " times");      // query (debug)
-        case 12: {                                                // query (debug): 0 = the current scene runs on the hand-written intersect kernel, else PT_ERR_UNSUPPORTED + why not
-            if (c->sceneDirty) { int rc = buildScene(c); if (rc) return rc; }
-            return c->asmEligible ? PT_OK : fail(PT_ERR_UNSUPPORTED, "compiled intersect kernel: " + c->asmWhyNot);
-        }
-        case 5: if (value != 64 && value != 128 && value != 256 && value != 512 && value != 1024) return fail(PT_ERR_ARG, "extend block size must be 64, 128, 256, 512 or 1024"); c->extendTpb = (int)value; return PT_OK;
-        case 6: if (value < 0 || value > 150 * 1024) return fail(PT_ERR_ARG, "extend LDS cache bytes out of range"); c->extendCacheBytes = (int)value; c->extendCacheSet = true; c->sceneDirty = true; return PT_OK;
-        case 7: if (value < 1 || value > 64) return fail(PT_ERR_ARG, "refill threshold must be in [1,64]"); c->refillMin = (int)value; return PT_OK;
-        case 8: if (value < 0 || value > 32) return fail(PT_ERR_ARG, "blocks per CU must be in [0,32]"); c->extendMaxBlocksPerCU = (int)value; return PT_OK;
-        case 9: if (value < 0 || value > 8) return fail(PT_ERR_ARG, "inner-phase persistence must be in [0,8] eighths"); c->innerKeepEighths = (int)value; return PT_OK;
-        case 11: if (value < -1 || value > 2) return fail(PT_ERR_ARG, "stack mode must be -1 (automatic), 0, 1 or 2"); c->stackModeForce = (int)value; c->sceneDirty = true; return PT_OK;
-        case 10: if (value < 0 || value > 0x7fffffff) return fail(PT_ERR_ARG, "breadth-first node count out of range"); c->bfsNodes = (int)value; c->sceneDirty = true; return PT_OK;
+    const ptp::SetResult r = c->opt.set(option, value);          // the table of pt_options.hpp: range, refusal, member, rebuild
+    if (r.query && option == 12) {                                // 0 = the current scene runs on the hand-written intersect kernel, else PT_ERR_UNSUPPORTED + why not
+        if (c->sceneDirty) { int rc = buildScene(c); if (rc) return rc; }
+        return c->built.asmEligible ? PT_OK : fail(PT_ERR_UNSUPPORTED, "compiled intersect kernel: " + c->asmWhyNot);
     }
-    return fail(PT_ERR_ARG, "unknown option");
+    if (r.query) return c->asmLaunches > (uint64_t)value ? PT_OK : fail(PT_ERR_UNSUPPORTED, "the hand-written intersect kernel has been launched " + std::to_string(c->asmLaunches) + " times");      // 13
+    if (r.code) return fail(r.code, r.msg);
+    if (r.dirty) c->sceneDirty = true;
+    return PT_OK;
 }
 
 int pt_get_counters(pt_ctx* c, uint64_t* out, int n) {
@@ -2587,9 +2553,9 @@ namespace {
 // k_frame_setup: the kernel pt_set_option 2 selects, with the exact numeric contract.  A pool with a side record HX in a scene whose intersect kernels do not
 // write one (no ellipsoid carries a mapped material) runs on k_extend, which writes it whenever it is given.
 int probeIntersect(pt_ctx* c, const State& st, size_t np) {
-    const size_t ldsBytes = ptp::kExtendLdsBytes(c->sc.ldsNodes, c->sc.ldsTris, c->stackDepth);
+    const size_t ldsBytes = ptp::kExtendLdsBytes(c->sc.ldsNodes, c->sc.ldsTris, c->built.stackDepth);
     hipLaunchKernelGGL(k_init_control, dim3(1), dim3(1), 0, c->stream, c->dCtl);
-    if (c->extendMode == 0 || (st.HX && !c->ellipMaps)) {
+    if (c->opt.extendMode == 0 || (st.HX && !c->built.ellipMaps)) {
         hipLaunchKernelGGL(k_extend<false>, dim3((unsigned)(np / BLOCK)), dim3(BLOCK), ldsBytes, c->stream, c->sc, st, (const unsigned*)nullptr, 0, (int)np, c->dCtl);
     } else {                                                      // the production kernels (persistent blocks; hand-written or compiled), as pump() launches them
         PoolRun pr; pr.stream = c->stream; pr.st = st; pr.launched = (unsigned)np; pr.iter = 0;

@@ -2,6 +2,8 @@
 // kernel is handed), of the path pool's size and of the frame ring's.  Pure integer arithmetic: no HIP runtime call and no context.  launchExtend and
 // submitBatch (pt_hip.hip) fill the inputs from the context and act on the result; tests/c/launch_plan_check.cpp runs it on the CPU.
 #pragma once
+#include "pt_options.hpp"
+
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
@@ -14,18 +16,14 @@
 namespace ptp {
 
 constexpr int PLAN_BLOCK = 256;                       // lanes of a k_extend block, and what pool sizes are rounded to (BLOCK of pt_hip.hip)
+static_assert(POOL_SLOT_STEP == PLAN_BLOCK, "option 0 rounds the caller's pool to the blocks the planner sizes pools by");
 constexpr size_t LDS_PER_CU = 160 * 1024;             // gfx950; one block may take all of it
 
-// what the planner reads of the scene as built (SceneLayout, pt_scene_layout.hpp)
+// what the planner reads of the scene as built (SceneLayout::planScene, pt_scene_layout.hpp)
 struct PlanScene {
     int nNodes = 0, nTriRecs = 0, numObj = 0, stackDepth = 1, stackMode = 2, asmNodeStride = 80;
     bool ellipMaps = false, asmEligible = false;
     int ldsNodes = 0, ldsTris = 0;                    // the tile of k_extend, which the layout sizes
-};
-// the options of pt_set_option it reads (their meaning: pt_ctx, pt_hip.hip)
-struct PlanOptions {
-    int extendMode = 2, extendTpb = 256, extendCacheBytes = 8 * 1024; bool extendCacheSet = false; int extendMaxBlocksPerCU = 0;
-    int asmTpb = 0, asmLoop = -1, noneMin = 8; bool noneMinSet = false, countStats = false;
 };
 struct PlanDevice {
     int numCUs = 256, streamsOnDevice = 1;
@@ -36,6 +34,8 @@ struct PlanCall {
     bool probes = false;                              // the pool carries thickness probes (RAYTRACING == 0 of the running stream)
     bool fast = false;                                // the relaxed reciprocal may be used (the running stream's numeric contract)
 };
+
+using PlanOptions = Options;                          // the planner reads the options themselves (pt_options.hpp)
 
 enum ExtendKernel { K_EXTEND = 0, K_PERSIST = 1, K_ASM = 2 };      // k_extend, k_extend_persist, pt_extend_asm
 struct ExtendPlan {

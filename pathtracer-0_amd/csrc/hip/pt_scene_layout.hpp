@@ -4,6 +4,7 @@
 #pragma once
 #include "../../../include/pt_api.h"
 #include "pt_scene_records.hpp"
+#include "pt_launch_plan.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -14,15 +15,10 @@
 #include <string>
 #include <vector>
 
-// a BVH whose inner-node records exceed this many bytes (in the 80-B form) makes the hand-written intersect kernel use the 64-B form: what an XCD's 4 MB
-// L2 holds beside the triangles and the path state streaming through it (measured: profiles/r04_d_node_record_layout.txt)
-#ifndef ASM_NODES_80B_LIMIT
-#define ASM_NODES_80B_LIMIT (2 << 20)
-#endif
-
 namespace ptl {
 using namespace ptd;
 
+using LayoutOptions = ptp::Options;          // the layout reads the members whose rows of the option table say they rebuild the scene, and asmNodes80Limit
 constexpr int EXTEND_BLOCK = 256;            // lanes of a k_extend block: one traversal stack each beside the LDS tile (BLOCK of pt_hip.hip)
 
 // raw SSBO contents (host copies, glBufferData semantics)
@@ -32,12 +28,6 @@ struct SceneBuffers {
     std::vector<uint8_t> sky; int skyW = 0, skyH = 0;
     struct HostTex { std::vector<uint8_t> rgba; int w = 0, h = 0; };
     std::vector<HostTex> textures;          // bindless table beyond the sky (index 0 mirrors `sky`)
-};
-
-// the options of pt_set_option that the layout reads (their meaning: pt_ctx, pt_hip.hip)
-struct LayoutOptions {
-    int bfsNodes = 0x7fffffff, asmNodeLayout = -1; bool asmNoRootCull = false; int forceNiBits8 = 0, ldsBudget = 20 * 1024, extendCacheBytes = 8 * 1024, stackModeForce = -1;
-    int asmNodes80Limit = ASM_NODES_80B_LIMIT;
 };
 
 struct SceneLayout {
@@ -55,6 +45,14 @@ struct SceneLayout {
     int niBits = 0; float ni8[8] = {};
     int stackDepth = 1, asmNodeStride = 80, asmGroupShift = 0, ldsNodes = 0, ldsTris = 0, stackMode = 2, pLdsNodes = 0, pLdsTris = 0;
     bool asmEligible = false; std::string asmWhyNot;
+
+    // what the launch planner reads of it (pt_launch_plan.hpp)
+    ptp::PlanScene planScene() const {
+        ptp::PlanScene s;
+        s.nNodes = nInner; s.nTriRecs = nTriRecs; s.numObj = numObj; s.stackDepth = stackDepth; s.stackMode = stackMode; s.asmNodeStride = asmNodeStride;
+        s.ellipMaps = ellipMaps; s.asmEligible = asmEligible; s.ldsNodes = ldsNodes; s.ldsTris = ldsTris;
+        return s;
+    }
 };
 
 // (int)f of caller data with a defined result for every f: what the x86 conversion returns, INT_MIN for a NaN and for values outside int's range
