@@ -44,6 +44,8 @@
 #include "pt_launch_plan.hpp"
 #include "pt_stream_sched.hpp"
 #include "pt_image_history.hpp"
+#include "pt_image_args.hpp"
+#include "pt_motion_pack.hpp"
 #include "pt_image_launch.hpp"
 
 #include <algorithm>
@@ -2299,11 +2301,8 @@ int onEveryStream(pt_ctx* c, const std::function<int(pt_ctx*, int64_t*)>& fn, in
 }  // namespace
 
 int pt_render_adaptive(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, float rel_err, float abs_err, int min_frames, int max_frames, int64_t* n_active) {
-    if (!c || !seeds) return fail(PT_ERR_ARG, "pt_render_adaptive: null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_adaptive: n_frames must be >= 1");
-    if (min_frames < 2) return fail(PT_ERR_ARG, "pt_render_adaptive: min_frames must be >= 2 (a variance needs two frames)");
-    if (max_frames < 0) return fail(PT_ERR_ARG, "pt_render_adaptive: max_frames must be >= 0 (0 = no cap)");
-    if (!(rel_err >= 0.0f) || !(abs_err >= 0.0f)) return fail(PT_ERR_ARG, "pt_render_adaptive: rel_err and abs_err must be >= 0 and not NaN");
+    if (int rc = fail(ptp::checkImageArgs(ptp::IC_RENDER_ADAPTIVE, ptp::ImageArgs::given(c).seeded(seeds, n_frames).adaptive(rel_err, abs_err, min_frames, max_frames))))
+        return rc;
     AdaptRule r{};
     r.relErr = rel_err; r.absErr = abs_err; r.minFrames = min_frames; r.maxFrames = max_frames;
     return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderAdaptive(k, first_frame, n_frames, seeds, r, n); }, n_active);   // every stream selects within its own shard

@@ -53,10 +53,14 @@ int counted(int64_t* out, const std::function<int(int64_t*)>& call) {
     if (out) *out = n;
     return rc;
 }
+// ---- every entry point below asks its row of pt_image_args.hpp first: what it refuses in its arguments, in which order and in which words, is there
+using ptp::ImageArgs;
+using ptp::checkImageArgs;
+const char* nameOf(ptp::ImageCall call) { return ptp::imageCallTable()[call].name; }
 }  // namespace
 
 int pt_record_moments(pt_ctx* c, int on) {
-    if (!c) return fail(PT_ERR_ARG, "pt_record_moments: null context");
+    if (int rc = fail(checkImageArgs(ptp::IC_RECORD_MOMENTS, ImageArgs::given(c)))) return rc;
     MULTI_ALL(c, pt_record_moments(k, on));
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = flushStream(c)) return rc;                       // batches in flight retire under the previous setting
@@ -66,8 +70,8 @@ int pt_record_moments(pt_ctx* c, int on) {
 }
 
 int pt_read_moments(pt_ctx* c, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_moments: null argument");
     int rc;
+    if ((rc = fail(checkImageArgs(ptp::IC_READ_MOMENTS, ImageArgs::given(c, out))))) return rc;
     if ((rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_read_moments"))) return rc;
     if ((rc = pt_synchronize(c))) return rc;
     bool any = false;
@@ -75,7 +79,7 @@ int pt_read_moments(pt_ctx* c, float* out) {
 }
 
 int pt_write_moments(pt_ctx* c, const float* in) {
-    if (!c || !in) return fail(PT_ERR_ARG, "pt_write_moments: null argument");
+    if (int rc = fail(checkImageArgs(ptp::IC_WRITE_MOMENTS, ImageArgs::given(c, in)))) return rc;
     if (int rc = needWholeImage(c, PT_ERR_UNSUPPORTED, "pt_write_moments")) return rc;
     MULTI_ALL(c, writeMoments(k, in));                            // every stream takes the pixels of its own tile shard
     return writeMoments(c, in);
@@ -140,16 +144,6 @@ int currentRecords(pt_ctx* c, const pt_through_rule* rule, const char* who) {
     return ensureRecords(c, rule ? ptp::RC_THRU : ptp::RC_FEAT, fin, rule, who);
 }
 
-// include/pt_through.h's rule, checked
-int checkThrough(const pt_through_rule* r, const char* who) {
-    const std::string w(who);
-    if (!r) return fail(PT_ERR_ARG, w + ": null rule");
-    if (r->max_depth < 0 || r->max_depth > 8) return fail(PT_ERR_ARG, w + ": rule.max_depth must be in [0,8]");
-    if (!(r->min_weight > 0.0f && r->min_weight <= 1.0f)) return fail(PT_ERR_ARG, w + ": rule.min_weight must be in (0,1]");
-    if (r->lobes < 0 || r->lobes > 3) return fail(PT_ERR_ARG, w + ": rule.lobes must be in [0,3]");
-    if (r->flags & ~PT_THROUGH_KEY) return fail(PT_ERR_ARG, w + ": unknown rule.flags");
-    return 0;
-}
 // the filters' scratch on the device of `on`: the colour ping-pong and the output (W*H float4 each), the packed guide (2*W*H float4)
 int ensureFilterScratch(pt_ctx* on) {
     const size_t n = (size_t)on->W * on->H;
@@ -173,8 +167,6 @@ int displayFiltered(pt_ctx* on, int java_bytes, uint8_t* rgb_out) {
 
 // the denoised image of the context's current FRAME into on->dDnOut (W*H float4 on the device of *on), enqueued on on->stream
 int denoiseImage(pt_ctx* c, int iterations, const float (&sigma)[4], pt_ctx** onOut) {
-    if (iterations < 0 || iterations > 8) return fail(PT_ERR_ARG, "pt_denoise: iterations must be in [0,8]");
-    for (int k = 0; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, "pt_denoise: every sigma must be > 0 (+inf switches its term off)");
     pt_ctx* on = nullptr; const float4* frame = nullptr;
     int rc;
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise", &on, &frame))) return rc;
@@ -187,23 +179,24 @@ int denoiseImage(pt_ctx* c, int iterations, const float (&sigma)[4], pt_ctx** on
 }  // namespace
 
 int pt_read_features(pt_ctx* c, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features: null argument");
-    pt_ctx* on = firstStream(c);
     int rc;
+    if ((rc = fail(checkImageArgs(ptp::IC_READ_FEATURES, ImageArgs::given(c, out))))) return rc;
+    pt_ctx* on = firstStream(c);
     if ((rc = currentRecords(on, nullptr, "pt_read_features"))) return rc;
     HIP_TRY(hipMemcpy(out, on->rec[ptp::RC_FEAT].recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
 int pt_denoise(pt_ctx* c, int iterations, float sigma_color, float sigma_normal, float sigma_depth, float sigma_albedo, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise: null argument");
+    if (int rc = fail(checkImageArgs(ptp::IC_DENOISE, ImageArgs::given(c, rgba_out).filter(iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, 0, 0.0f)))) return rc;
     pt_ctx* on = nullptr;
     if (int rc = denoiseImage(c, iterations, {sigma_color, sigma_normal, sigma_depth, sigma_albedo}, &on)) return rc;
     return imageToHost(on, on->dDnOut, rgba_out);
 }
 
 int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float sigma_normal, float sigma_depth, float sigma_albedo, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised: null argument");
+    if (int rc = fail(checkImageArgs(ptp::IC_READ_DISPLAY_DENOISED, ImageArgs::given(c, rgb_out).filter(iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, 0, 0.0f))))
+        return rc;
     pt_ctx* on = nullptr;
     if (int rc = denoiseImage(c, iterations, {sigma_color, sigma_normal, sigma_depth, sigma_albedo}, &on)) return rc;
     return displayFiltered(on, java_bytes, rgb_out);
@@ -212,21 +205,13 @@ int pt_read_display_denoised(pt_ctx* c, int iterations, float sigma_color, float
 // ---- the variance-guided filter (include/pt_guided.h) and, in front of it, the prefill of the unrendered pixels (include/pt_fill.h): pt_denoise's
 // plumbing and scratch, with T in pixel order beside FRAME, and FRAME' and the filled count beside them
 namespace {
-// include/pt_demod.h's albedo_floor: finite and > 0
-bool floorOk(float floorA) { return floorA > 0.0f && __builtin_isfinite(floorA); }
-// include/pt_fill.h's albedo_floor: 0 (the plain rule) or include/pt_demod.h's
-bool fillFloorOk(float floorA) { return floorA == 0.0f || floorOk(floorA); }
-
 // Of the context's current image: when `fill`, FRAME' into on->dFill and the filled count into on->dFillCount; when `filter`, the guided filter over
 // FRAME (or FRAME') into on->dDnOut.  All enqueued on on->stream.  sigma = (luminance, normal, depth, albedo); the luminance entry, iterations and
-// minFrames count only when `filter`.  floorA == 0: the plain kernels; > 0: include/pt_demod.h's, with that albedo_floor (checked by the caller).
-// thru: null = the first-hit records; else include/pt_through.h's records under that rule (checked by the caller) in their place
+// minFrames count only when `filter`.  floorA == 0: the plain kernels; > 0: include/pt_demod.h's, with that albedo_floor.
+// thru: null = the first-hit records; else include/pt_through.h's records under that rule in their place
 int filteredImage(pt_ctx* c, bool fill, bool filter, int iterations, const float (&sigma)[4], int minFrames, float floorA, const char* who, pt_ctx** onOut,
                   const pt_through_rule* thru = nullptr) {
     const std::string w(who);
-    if (filter && (iterations < 0 || iterations > 8)) return fail(PT_ERR_ARG, w + ": iterations must be in [0,8]");
-    if (filter && minFrames < 2) return fail(PT_ERR_ARG, w + ": min_frames must be >= 2");
-    for (int k = filter ? 0 : 1; k < 4; k++) if (!(sigma[k] > 0.0f)) return fail(PT_ERR_ARG, w + ": every sigma must be > 0 (+inf switches its term off)");
     pt_ctx* on = nullptr;
     GuidedJob j;
     int rc;
@@ -251,8 +236,11 @@ int filteredImage(pt_ctx* c, bool fill, bool filter, int iterations, const float
     *onOut = on;
     return 0;
 }
-// the filtered image to the host (rgba_out) or to the display (rgb_out): pt_denoise_guided and its demodulated form, which share its message prefix
-int guidedTo(pt_ctx* c, int iterations, const float (&sigma)[4], int minFrames, float floorA, float* rgba_out, int java_bytes, uint8_t* rgb_out) {
+// pt_denoise_guided, its demodulated form (floorA > 0) and their display forms: the filtered image to the host (rgba_out) or to the display
+// (rgb_out).  All four share the first one's message prefix past their own checks
+int guidedTo(ptp::ImageCall call, pt_ctx* c, int iterations, const float (&sigma)[4], int minFrames, float floorA, float* rgba_out, int java_bytes, uint8_t* rgb_out) {
+    if (int rc = fail(checkImageArgs(call, ImageArgs::given(c, rgba_out ? (const void*)rgba_out : rgb_out).filter(iterations, sigma[0], sigma[1], sigma[2], sigma[3], minFrames, floorA))))
+        return rc;
     pt_ctx* on = nullptr;
     if (int rc = filteredImage(c, false, true, iterations, sigma, minFrames, floorA, "pt_denoise_guided", &on)) return rc;
     return rgba_out ? imageToHost(on, on->dDnOut, rgba_out) : displayFiltered(on, java_bytes, rgb_out);
@@ -260,28 +248,23 @@ int guidedTo(pt_ctx* c, int iterations, const float (&sigma)[4], int minFrames, 
 }  // namespace
 
 int pt_denoise_guided(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided: null argument");
-    return guidedTo(c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, 0.0f, rgba_out, 0, nullptr);
+    return guidedTo(ptp::IC_DENOISE_GUIDED, c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, 0.0f, rgba_out, 0, nullptr);
 }
 
 int pt_read_display_denoised_guided(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
                                     int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided: null argument");
-    return guidedTo(c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, 0.0f, nullptr, java_bytes, rgb_out);
+    return guidedTo(ptp::IC_READ_DISPLAY_DENOISED_GUIDED, c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, 0.0f, nullptr, java_bytes, rgb_out);
 }
 
 int pt_denoise_guided_demod(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
                             float albedo_floor, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_demod: null argument");
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_denoise_guided_demod: albedo_floor must be finite and > 0");
-    return guidedTo(c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, rgba_out, 0, nullptr);
+    return guidedTo(ptp::IC_DENOISE_GUIDED_DEMOD, c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, rgba_out, 0, nullptr);
 }
 
 int pt_read_display_denoised_guided_demod(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo,
                                           int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_demod: null argument");
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_demod: albedo_floor must be finite and > 0");
-    return guidedTo(c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, nullptr, java_bytes, rgb_out);
+    return guidedTo(ptp::IC_READ_DISPLAY_DENOISED_GUIDED_DEMOD, c, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, nullptr,
+                    java_bytes, rgb_out);
 }
 
 // ---- reprojection across a camera move (include/pt_reproject.h).  A group context reprojects its gathered image on its first stream's context and hands
@@ -315,67 +298,18 @@ int storeReprojected(pt_ctx* c, pt_ctx* on, bool stats, int64_t* nKept) {
     return 0;
 }
 // ---- include/pt_motion.h: where the primitives are, for the mark and for the reprojection across moved geometry
-// the vertices of the triangles of binding 3 (9 floats each) and centre, stretch, rot, r of the ellipsoids of binding 7 (10 floats each), from the host copies
-void motionPositions(const pt_ctx* c, std::vector<float>& tri, int* nTri, std::vector<float>& el, int* nEl) {
-    const size_t nt = c->buf.tris.size() / 40;
-    tri.resize(nt * 9);
-    for (size_t t = 0; t < nt; t++)
-        for (int v = 0; v < 3; v++) std::memcpy(&tri[9 * t + 3 * v], &c->buf.tris[40 * t + 4 * v], 12);
-    int ne = c->buf.ellip.empty() ? 0 : toInt(c->buf.ellip[0]);
-    if (ne < 0 || c->buf.ellip.size() < (size_t)1 + 11 * (size_t)ne) ne = 0;      // (buildScene refuses such a buffer)
-    el.resize((size_t)ne * 10);
-    const float* E = c->buf.ellip.data();
-    for (int i = 0; i < ne; i++) {
-        for (int k = 0; k < 3; k++) { el[10 * i + k] = E[1 + 3 * i + k]; el[10 * i + 3 + k] = E[1 + ne * 3 + 3 * i + k]; el[10 * i + 6 + k] = E[1 + ne * 6 + 3 * i + k]; }
-        el[10 * i + 9] = E[1 + ne * 9 + i];
-    }
-    *nTri = (int)nt; *nEl = ne;
-}
-// ... as the kernel reads them: triangle (A, flag), (B, 0), (C, 0); ellipsoid (c, r), (stretch, flag), (rot, 0).  then == nullptr: the mark's own copy, flags 0;
-// else flag = 0 unmoved (every float compares equal), 1 moved, 2 a moved ellipsoid with a rot component != 0 then or now
-void motionPack(const std::vector<float>& tri, int nTri, const std::vector<float>& el, int nEl, const pt_ctx::Mark* then, std::vector<float4>& outTri,
-                std::vector<float4>& outEl) {
-    auto asf = [](int u) { float f; std::memcpy(&f, &u, 4); return f; };
-    outTri.resize(std::max<size_t>((size_t)nTri * 3, 1)); outEl.resize(std::max<size_t>((size_t)nEl * 3, 1));
-    for (int t = 0; t < nTri; t++) {
-        const float* T = &tri[9 * (size_t)t];
-        int flag = 0;
-        if (then) {
-            flag = t < then->nTri ? 0 : 1;
-            for (int k = 0; k < 9 && !flag; k++) if (!(T[k] == then->tri[9 * (size_t)t + k])) flag = 1;
-        }
-        outTri[3 * (size_t)t] = make_float4(T[0], T[1], T[2], asf(flag)); outTri[3 * (size_t)t + 1] = make_float4(T[3], T[4], T[5], 0.0f);
-        outTri[3 * (size_t)t + 2] = make_float4(T[6], T[7], T[8], 0.0f);
-    }
-    for (int i = 0; i < nEl; i++) {
-        const float* E = &el[10 * (size_t)i];
-        int flag = 0;
-        if (then) {
-            flag = i < then->nEl ? 0 : 1;
-            for (int k = 0; k < 10 && !flag; k++) if (!(E[k] == then->el[10 * (size_t)i + k])) flag = 1;
-            if (flag && i < then->nEl)
-                for (int k = 6; k < 9; k++) if (E[k] != 0.0f || then->el[10 * (size_t)i + k] != 0.0f) flag = 2;
-        }
-        outEl[3 * (size_t)i] = make_float4(E[0], E[1], E[2], E[9]); outEl[3 * (size_t)i + 1] = make_float4(E[3], E[4], E[5], asf(flag));
-        outEl[3 * (size_t)i + 2] = make_float4(E[6], E[7], E[8], 0.0f);
-    }
-}
+// (pt_motion_pack.hpp turns the bound buffers and the mark's host copies into the records uploaded here)
 
 // The image of `c` mapped to the current inputs, stored as its current image; *nKept = the pixels kept.  `moved`: include/pt_motion.h's call, with Rh
 // and the primitives' old positions from the mark (which it spends); else include/pt_reproject.h's, Rh from the image's camera.
-// floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor (the unmoved call's: checked by the caller).
-// chain (not moved, floorA 0; checked by the caller): include/pt_reproject_through.h's call, Sn / Yn and Sh / Yh beside Rn and Rh
-// taps (not moved, no chain; snap and floorA checked by the caller): include/pt_reproject_bilinear.h's call, the four old pixels around the projected point
+// floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor.
+// chain (not moved, floorA 0): include/pt_reproject_through.h's call, Sn / Yn and Sh / Yh beside Rn and Rh
+// taps (not moved, no chain): include/pt_reproject_bilinear.h's call, the four old pixels around the projected point
 struct ChainCarry { const pt_through_rule* thru; float pointTol; int radius; int64_t* nKeptThrough; };
 struct BilinearTaps { float snap; int64_t* nBlended; };
 int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept,
                    const ChainCarry* chain = nullptr, const BilinearTaps* taps = nullptr) {
     const std::string w(who);
-    if (!(maxHistory >= 1.0f)) return fail(PT_ERR_ARG, w + ": max_history must be >= 1");
-    if (!(depthTol > 0.0f)) return fail(PT_ERR_ARG, w + ": depth_tol must be > 0");
-    if (!(normalTol >= -1.0f && normalTol <= 1.0f)) return fail(PT_ERR_ARG, w + ": normal_tol must be in [-1, 1]");
-    if (flags & ~PT_REPROJECT_ALL_MATERIALS) return fail(PT_ERR_ARG, w + ": unknown flags");
-    if (moved && !(floorA == 0.0f || floorOk(floorA))) return fail(PT_ERR_ARG, w + ": albedo_floor must be 0 or finite and > 0");
     pt_ctx* on = nullptr;
     ReprojectJob j;
     int rc;
@@ -413,14 +347,15 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     if ((rc = wholeStats(c, on, &j.stats))) return rc;
     if (j.stats) HIP_TRY(on->dRpStats.ensure(n * 16));
     // where the primitives are now, with the moved ones flagged
-    std::vector<float4> pt, pe;
+    std::vector<float> pt, pe;
     ReprojMotion g{};
     if (moved) {
         std::vector<float> tri, el; int nTri = 0, nEl = 0;
-        motionPositions(on, tri, &nTri, el, &nEl);
-        motionPack(tri, nTri, el, nEl, &m, pt, pe);
-        HIP_TRY(on->dMoveTri.upload(pt.data(), pt.size() * 16, on->stream));
-        HIP_TRY(on->dMoveEl.upload(pe.data(), pe.size() * 16, on->stream));
+        ptp::motionPositions(on->buf.tris, on->buf.ellip, tri, &nTri, el, &nEl);
+        const ptp::MotionThen then{m.tri.data(), m.nTri, m.el.data(), m.nEl};
+        ptp::motionPack(tri, nTri, el, nEl, &then, pt, pe);
+        HIP_TRY(on->dMoveTri.upload(pt.data(), pt.size() * 4, on->stream));
+        HIP_TRY(on->dMoveEl.upload(pe.data(), pe.size() * 4, on->stream));
         g = ReprojMotion{on->dMoveTri, m.dTri, nTri, m.nTri, on->dMoveEl, m.dEl, nEl, m.nEl};
         j.motion = &g;
     }
@@ -458,15 +393,14 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
 
 int pt_reproject_frame(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, int64_t* n_kept) {
     return counted(n_kept, [&](int64_t* n) {
-        if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame: null context");
+        if (int rc = fail(checkImageArgs(ptp::IC_REPROJECT_FRAME, ImageArgs::given(c).reproject(max_history, depth_tol, normal_tol, flags, 0.0f)))) return rc;
         return reprojectImage(c, "pt_reproject_frame", false, max_history, depth_tol, normal_tol, flags, 0.0f, n);
     });
 }
 
 int pt_reproject_frame_demod(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
     return counted(n_kept, [&](int64_t* n) {
-        if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: null context");
-        if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_demod: albedo_floor must be finite and > 0");
+        if (int rc = fail(checkImageArgs(ptp::IC_REPROJECT_FRAME_DEMOD, ImageArgs::given(c).reproject(max_history, depth_tol, normal_tol, flags, albedo_floor)))) return rc;
         return reprojectImage(c, "pt_reproject_frame", false, max_history, depth_tol, normal_tol, flags, albedo_floor, n);
     });
 }
@@ -475,12 +409,9 @@ int pt_reproject_frame_demod(pt_ctx* c, float max_history, float depth_tol, floa
 int pt_reproject_frame_through(pt_ctx* c, const pt_through_rule* thru, const pt_reproject_through_rule* rule, int64_t* n_kept, int64_t* n_kept_through) {
     if (n_kept) *n_kept = 0;
     if (n_kept_through) *n_kept_through = 0;
-    if (!c || !rule) return fail(PT_ERR_ARG, "pt_reproject_frame_through: null argument");
-    if (rule->radius < 0 || rule->radius > 4) return fail(PT_ERR_ARG, "pt_reproject_frame_through: rule.radius must be in [0,4]");
-    if (!(rule->point_tol > 0.0f)) return fail(PT_ERR_ARG, "pt_reproject_frame_through: rule.point_tol must be > 0");
-    if (int rc = checkThrough(thru, "pt_reproject_frame_through")) return rc;
-    if (thru->max_depth > 0 && thru->lobes != 0 && !(thru->flags & PT_THROUGH_KEY))
-        return fail(PT_ERR_ARG, "pt_reproject_frame_through: a rule that follows chains needs PT_THROUGH_KEY (the surface word is what a source is matched on)");
+    ImageArgs a = ImageArgs::given(c).has(ptp::AP_RULE, rule).has(thru);
+    if (rule) { a.reproject(rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags, 0.0f); a.radius = rule->radius; a.point_tol = rule->point_tol; }
+    if (int rc = fail(checkImageArgs(ptp::IC_REPROJECT_FRAME_THROUGH, a))) return rc;
     int64_t n = 0, nt = 0;
     const ChainCarry chain{thru, rule->point_tol, rule->radius, &nt};
     const int rc = reprojectImage(c, "pt_reproject_frame_through", false, rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags, 0.0f, &n, &chain);
@@ -493,9 +424,9 @@ int pt_reproject_frame_through(pt_ctx* c, const pt_through_rule* thru, const pt_
 int pt_reproject_frame_bilinear(pt_ctx* c, const pt_reproject_bilinear_rule* rule, int64_t* n_kept, int64_t* n_blended) {
     if (n_kept) *n_kept = 0;
     if (n_blended) *n_blended = 0;
-    if (!c || !rule) return fail(PT_ERR_ARG, "pt_reproject_frame_bilinear: null argument");
-    if (!(rule->snap >= 0.0f && rule->snap < 0.5f)) return fail(PT_ERR_ARG, "pt_reproject_frame_bilinear: rule.snap must be in [0, 0.5)");
-    if (!fillFloorOk(rule->albedo_floor)) return fail(PT_ERR_ARG, "pt_reproject_frame_bilinear: rule.albedo_floor must be 0 or finite and > 0");
+    ImageArgs a = ImageArgs::given(c).has(ptp::AP_RULE, rule);
+    if (rule) { a.reproject(rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags, rule->albedo_floor); a.snap = rule->snap; }
+    if (int rc = fail(checkImageArgs(ptp::IC_REPROJECT_FRAME_BILINEAR, a))) return rc;
     int64_t n = 0, nb = 0;
     const BilinearTaps taps{rule->snap, &nb};
     const int rc = reprojectImage(c, "pt_reproject_frame_bilinear", false, rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags,
@@ -520,11 +451,11 @@ int motionMark(pt_ctx* c) {
     HIP_TRY(m.feat.ensure(n * 64));
     HIP_TRY(hipMemcpyAsync(m.feat, on->rec[ptp::RC_FEAT_H].recs, n * 64, hipMemcpyDeviceToDevice, on->stream));
     // (b), (c) where the primitives are
-    motionPositions(on, m.tri, &m.nTri, m.el, &m.nEl);
-    std::vector<float4> pt, pe;
-    motionPack(m.tri, m.nTri, m.el, m.nEl, nullptr, pt, pe);
-    HIP_TRY(m.dTri.upload(pt.data(), pt.size() * 16, on->stream));
-    HIP_TRY(m.dEl.upload(pe.data(), pe.size() * 16, on->stream));
+    ptp::motionPositions(on->buf.tris, on->buf.ellip, m.tri, &m.nTri, m.el, &m.nEl);
+    std::vector<float> pt, pe;
+    ptp::motionPack(m.tri, m.nTri, m.el, m.nEl, nullptr, pt, pe);
+    HIP_TRY(m.dTri.upload(pt.data(), pt.size() * 4, on->stream));
+    HIP_TRY(m.dEl.upload(pe.data(), pe.size() * 4, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     on->hist.markTaken();                                         // (d)
     return PT_OK;
@@ -533,13 +464,13 @@ int motionMark(pt_ctx* c) {
 }  // namespace
 
 int pt_motion_mark(pt_ctx* c) {
-    if (!c) return fail(PT_ERR_ARG, "pt_motion_mark: null context");
+    if (int rc = fail(checkImageArgs(ptp::IC_MOTION_MARK, ImageArgs::given(c)))) return rc;
     return motionMark(c);
 }
 
 int pt_reproject_frame_moved(pt_ctx* c, float max_history, float depth_tol, float normal_tol, int flags, float albedo_floor, int64_t* n_kept) {
     return counted(n_kept, [&](int64_t* n) {
-        if (!c) return fail(PT_ERR_ARG, "pt_reproject_frame_moved: null context");
+        if (int rc = fail(checkImageArgs(ptp::IC_REPROJECT_FRAME_MOVED, ImageArgs::given(c).reproject(max_history, depth_tol, normal_tol, flags, albedo_floor)))) return rc;
         return reprojectImage(c, "pt_reproject_frame_moved", true, max_history, depth_tol, normal_tol, flags, albedo_floor, n);
     });
 }
@@ -580,10 +511,6 @@ int historyHold(pt_ctx* c) {
 }
 
 int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t* nReduced) {
-    if (r.radius < 1 || r.radius > 4) return fail(PT_ERR_ARG, "pt_history_merge: rule.radius must be in [1,4]");
-    if (!__builtin_isfinite(r.z_lo) || !__builtin_isfinite(r.z_hi) || !(r.z_lo >= 0.0f && r.z_lo < r.z_hi))
-        return fail(PT_ERR_ARG, "pt_history_merge: rule.z_lo and rule.z_hi must be finite with 0 <= z_lo < z_hi");
-    if (!(r.normal_tol >= -1.0f && r.normal_tol <= 1.0f)) return fail(PT_ERR_ARG, "pt_history_merge: rule.normal_tol must be in [-1, 1]");
     int rc;
     if ((rc = syncAll(c))) return rc;                             // work in flight lands in FRAME and T first
     pt_ctx* on = firstStream(c);
@@ -615,13 +542,13 @@ int historyMerge(pt_ctx* c, const pt_validate_rule& r, float* kappaOut, int64_t*
 }  // namespace
 
 int pt_history_hold(pt_ctx* c) {
-    if (!c) return fail(PT_ERR_ARG, "pt_history_hold: null context");
+    if (int rc = fail(checkImageArgs(ptp::IC_HISTORY_HOLD, ImageArgs::given(c)))) return rc;
     return historyHold(c);
 }
 
 int pt_history_merge(pt_ctx* c, const pt_validate_rule* rule, float* kappa_out, int64_t* n_reduced) {
     return counted(n_reduced, [&](int64_t* n) {
-        if (!c || !rule) return fail(PT_ERR_ARG, "pt_history_merge: null argument");
+        if (int rc = fail(checkImageArgs(ptp::IC_HISTORY_MERGE, ImageArgs::given(c).has(rule)))) return rc;
         return historyMerge(c, *rule, kappa_out, n);
     });
 }
@@ -632,20 +559,9 @@ int pt_history_merge(pt_ctx* c, const pt_validate_rule* rule, float* kappa_out, 
 namespace {
 size_t maskBytes(const pt_ctx* c) { return ((size_t)c->W * c->H + 3) & ~(size_t)3; }      // the active count follows, 4-byte aligned
 
-int checkRule(const pt_guided_rule& r, const char* who) {
-    const std::string w(who);
-    if (r.iterations < 0 || r.iterations > 8) return fail(PT_ERR_ARG, w + ": rule.iterations must be in [0,8]");
-    for (float v : {r.sigma_lum, r.sigma_normal, r.sigma_depth, r.sigma_albedo})
-        if (!(v > 0.0f)) return fail(PT_ERR_ARG, w + ": every sigma of the rule must be > 0 (+inf switches its term off)");
-    if (r.min_frames < 2) return fail(PT_ERR_ARG, w + ": rule.min_frames must be >= 2");
-    if (!(r.rel_err >= 0.0f) || !(r.abs_err >= 0.0f)) return fail(PT_ERR_ARG, w + ": rule.rel_err and rule.abs_err must be >= 0 and not NaN");
-    if (r.max_frames < 0) return fail(PT_ERR_ARG, w + ": rule.max_frames must be >= 0 (0 = no cap)");
-    return 0;
-}
-
 // The rule over the context's current image into (*onOut)->dSelMask (W*H bytes, pixel order, on the device of firstStream(c)); *nActive = its count.
 // FRAME and T are not modified; T never allocated reads as zeros (the filter's scratch output, zeroed).
-// floorA == 0: include/pt_steer.h's rule; > 0: include/pt_demod.h's step 5, with that albedo_floor (checked by the caller).
+// floorA == 0: include/pt_steer.h's rule; > 0: include/pt_demod.h's step 5, with that albedo_floor.
 int selectGuided(pt_ctx* c, const pt_guided_rule& r, float floorA, const char* who, pt_ctx** onOut, int64_t* nActive) {
     pt_ctx* on = nullptr;
     GuidedJob j;
@@ -693,20 +609,18 @@ int renderMask(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, con
 
 int pt_render_mask(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const uint8_t* mask, int64_t* n_active) {
     if (n_active) *n_active = 0;
-    if (!c || !seeds || !mask) return fail(PT_ERR_ARG, "pt_render_mask: null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_mask: n_frames must be >= 1");
+    if (int rc = fail(checkImageArgs(ptp::IC_RENDER_MASK, ImageArgs::given(c).has(ptp::AP_MASK, mask).seeded(seeds, n_frames)))) return rc;
     return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderMask(k, first_frame, n_frames, seeds, mask, "pt_render_mask", n); }, n_active);
 }
 
 namespace {
 // pt_select_guided (floorA == 0) and pt_select_guided_demod
-int selectInto(pt_ctx* c, const pt_guided_rule* rule, float floorA, const char* who, uint8_t* mask_out, int64_t* n_active) {
+int selectInto(ptp::ImageCall call, pt_ctx* c, const pt_guided_rule* rule, float floorA, uint8_t* mask_out, int64_t* n_active) {
     if (n_active) *n_active = 0;
-    if (!c || !rule || !mask_out) return fail(PT_ERR_ARG, std::string(who) + ": null argument");
     int rc;
-    if ((rc = checkRule(*rule, who))) return rc;
+    if ((rc = fail(checkImageArgs(call, ImageArgs::given(c, mask_out).has(rule).floor(floorA))))) return rc;
     pt_ctx* on = nullptr; int64_t n = 0;
-    if ((rc = selectGuided(c, *rule, floorA, who, &on, &n))) return rc;
+    if ((rc = selectGuided(c, *rule, floorA, nameOf(call), &on, &n))) return rc;
     HIP_TRY(hipMemcpyAsync(mask_out, on->dSelMask, (size_t)c->W * c->H, hipMemcpyDeviceToHost, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     if (n_active) *n_active = n;
@@ -714,13 +628,12 @@ int selectInto(pt_ctx* c, const pt_guided_rule* rule, float floorA, const char* 
 }
 
 // pt_render_adaptive_guided (floorA == 0) and pt_render_adaptive_guided_demod
-int renderAdaptiveGuided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, float floorA, const char* who,
+int renderAdaptiveGuided(ptp::ImageCall call, pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, float floorA,
                          int64_t* n_active) {
     if (n_active) *n_active = 0;
-    if (!c || !seeds || !rule) return fail(PT_ERR_ARG, std::string(who) + ": null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, std::string(who) + ": n_frames must be >= 1");
     int rc;
-    if ((rc = checkRule(*rule, who))) return rc;
+    if ((rc = fail(checkImageArgs(call, ImageArgs::given(c).has(rule).seeded(seeds, n_frames).floor(floorA))))) return rc;
+    const char* who = nameOf(call);
     const pt_ctx* f = firstStream(c);
     if (f->buf.params.size() >= 12 && f->buf.params[10] != 0.0f)          // before the selection, as renderSelected would after it
         return fail(PT_ERR_UNSUPPORTED, std::string(who) + ": DEBUG != 0 renders the traversal heat map, which has no noise to adapt to");
@@ -737,24 +650,20 @@ int renderAdaptiveGuided(pt_ctx* c, int first_frame, int n_frames, const int32_t
 }  // namespace
 
 int pt_select_guided(pt_ctx* c, const pt_guided_rule* rule, uint8_t* mask_out, int64_t* n_active) {
-    return selectInto(c, rule, 0.0f, "pt_select_guided", mask_out, n_active);
+    return selectInto(ptp::IC_SELECT_GUIDED, c, rule, 0.0f, mask_out, n_active);
 }
 
 int pt_render_adaptive_guided(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, int64_t* n_active) {
-    return renderAdaptiveGuided(c, first_frame, n_frames, seeds, rule, 0.0f, "pt_render_adaptive_guided", n_active);
+    return renderAdaptiveGuided(ptp::IC_RENDER_ADAPTIVE_GUIDED, c, first_frame, n_frames, seeds, rule, 0.0f, n_active);
 }
 
 int pt_select_guided_demod(pt_ctx* c, const pt_guided_rule* rule, float albedo_floor, uint8_t* mask_out, int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_select_guided_demod: albedo_floor must be finite and > 0");
-    return selectInto(c, rule, albedo_floor, "pt_select_guided_demod", mask_out, n_active);
+    return selectInto(ptp::IC_SELECT_GUIDED_DEMOD, c, rule, albedo_floor, mask_out, n_active);
 }
 
 int pt_render_adaptive_guided_demod(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, const pt_guided_rule* rule, float albedo_floor,
                                     int64_t* n_active) {
-    if (n_active) *n_active = 0;
-    if (!floorOk(albedo_floor)) return fail(PT_ERR_ARG, "pt_render_adaptive_guided_demod: albedo_floor must be finite and > 0");
-    return renderAdaptiveGuided(c, first_frame, n_frames, seeds, rule, albedo_floor, "pt_render_adaptive_guided_demod", n_active);
+    return renderAdaptiveGuided(ptp::IC_RENDER_ADAPTIVE_GUIDED_DEMOD, c, first_frame, n_frames, seeds, rule, albedo_floor, n_active);
 }
 
 // ---- interleaved rendering (include/pt_fill.h): pt_render_mask over a lattice mask that every stream builds on its own device, and the prefill of
@@ -772,93 +681,79 @@ int renderLattice(pt_ctx* c, int firstFrame, int nFrames, const int32_t* seeds, 
 }
 
 // pt_fill_frame and pt_fill_frame_through: FRAME' and the count of the holes filled, to the host
-int fillTo(pt_ctx* c, const pt_through_rule* thru, float sigmaNormal, float sigmaDepth, float sigmaAlbedo, float floorA, const char* who, float* rgba_out,
+int fillTo(ptp::ImageCall call, pt_ctx* c, const pt_through_rule* thru, float sigmaNormal, float sigmaDepth, float sigmaAlbedo, float floorA, float* rgba_out,
            int64_t* n_filled) {
-    if (!fillFloorOk(floorA)) return fail(PT_ERR_ARG, std::string(who) + ": albedo_floor must be 0 or finite and > 0");
+    if (n_filled) *n_filled = 0;
+    if (int rc = fail(checkImageArgs(call, ImageArgs::given(c, rgba_out).has(thru).filter(0, 1.0f, sigmaNormal, sigmaDepth, sigmaAlbedo, 2, floorA)))) return rc;
     pt_ctx* on = nullptr;
-    if (int rc = filteredImage(c, true, false, 0, {1.0f, sigmaNormal, sigmaDepth, sigmaAlbedo}, 2, floorA, who, &on, thru)) return rc;
+    if (int rc = filteredImage(c, true, false, 0, {1.0f, sigmaNormal, sigmaDepth, sigmaAlbedo}, 2, floorA, nameOf(call), &on, thru)) return rc;
     return imageToHost(on, on->dFill, rgba_out, on->dFillCount, n_filled);
 }
 // pt_denoise_guided_filled, pt_denoise_guided_through and their display forms: the filter over FRAME', to the host (rgba_out) or to the display (rgb_out)
-int filledTo(pt_ctx* c, const pt_through_rule* thru, int iterations, const float (&sigma)[4], int minFrames, float floorA, const char* who, float* rgba_out,
+int filledTo(ptp::ImageCall call, pt_ctx* c, const pt_through_rule* thru, int iterations, const float (&sigma)[4], int minFrames, float floorA, float* rgba_out,
              int java_bytes, uint8_t* rgb_out) {
-    if (!fillFloorOk(floorA)) return fail(PT_ERR_ARG, std::string(who) + ": albedo_floor must be 0 or finite and > 0");
+    const void* out = rgba_out ? (const void*)rgba_out : rgb_out;
+    if (int rc = fail(checkImageArgs(call, ImageArgs::given(c, out).has(thru).filter(iterations, sigma[0], sigma[1], sigma[2], sigma[3], minFrames, floorA)))) return rc;
     pt_ctx* on = nullptr;
-    if (int rc = filteredImage(c, true, true, iterations, sigma, minFrames, floorA, who, &on, thru)) return rc;
+    if (int rc = filteredImage(c, true, true, iterations, sigma, minFrames, floorA, nameOf(call), &on, thru)) return rc;
     return rgba_out ? imageToHost(on, on->dDnOut, rgba_out) : displayFiltered(on, java_bytes, rgb_out);
+}
+// pt_read_features_through (the records) and pt_read_through_rays (their last segments, `rays`), to the host
+int throughToHost(ptp::ImageCall call, pt_ctx* c, const pt_through_rule* rule, bool rays, float* out) {
+    int rc;
+    if ((rc = fail(checkImageArgs(call, ImageArgs::given(c, out).has(rule))))) return rc;
+    pt_ctx* on = firstStream(c);
+    if ((rc = currentRecords(on, rule, nameOf(call)))) return rc;
+    const pt_ctx::Records& R = on->rec[ptp::RC_THRU];
+    HIP_TRY(hipMemcpy(out, rays ? (const void*)R.rays.p : (const void*)R.recs.p, (size_t)c->W * c->H * (rays ? 32 : 64), hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 }  // namespace
 
 int pt_render_interleaved(pt_ctx* c, int first_frame, int n_frames, const int32_t* seeds, int stride, int phase_x, int phase_y, int64_t* n_active) {
     if (n_active) *n_active = 0;
-    if (!c || !seeds) return fail(PT_ERR_ARG, "pt_render_interleaved: null argument");
-    if (n_frames < 1) return fail(PT_ERR_ARG, "pt_render_interleaved: n_frames must be >= 1");
-    if (stride < 1 || stride > 8) return fail(PT_ERR_ARG, "pt_render_interleaved: stride must be in [1,8]");
-    if (phase_x < 0 || phase_x >= stride || phase_y < 0 || phase_y >= stride) return fail(PT_ERR_ARG, "pt_render_interleaved: a phase must be in [0, stride)");
+    if (int rc = fail(checkImageArgs(ptp::IC_RENDER_INTERLEAVED, ImageArgs::given(c).seeded(seeds, n_frames).lattice(stride, phase_x, phase_y)))) return rc;
     return onEveryStream(c, [=](pt_ctx* k, int64_t* n) { return renderLattice(k, first_frame, n_frames, seeds, stride, phase_x, phase_y, n); }, n_active);
 }
 
 int pt_fill_frame(pt_ctx* c, float sigma_normal, float sigma_depth, float sigma_albedo, float albedo_floor, float* rgba_out, int64_t* n_filled) {
-    if (n_filled) *n_filled = 0;
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_fill_frame: null argument");
-    return fillTo(c, nullptr, sigma_normal, sigma_depth, sigma_albedo, albedo_floor, "pt_fill_frame", rgba_out, n_filled);
+    return fillTo(ptp::IC_FILL_FRAME, c, nullptr, sigma_normal, sigma_depth, sigma_albedo, albedo_floor, rgba_out, n_filled);
 }
 
 int pt_denoise_guided_filled(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo, int min_frames,
                              float albedo_floor, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_filled: null argument");
-    return filledTo(c, nullptr, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, "pt_denoise_guided_filled", rgba_out, 0,
+    return filledTo(ptp::IC_DENOISE_GUIDED_FILLED, c, nullptr, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, rgba_out, 0,
                     nullptr);
 }
 
 int pt_read_display_denoised_guided_filled(pt_ctx* c, int iterations, float sigma_lum, float sigma_normal, float sigma_depth, float sigma_albedo,
                                            int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_filled: null argument");
-    return filledTo(c, nullptr, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor,
-                    "pt_read_display_denoised_guided_filled", nullptr, java_bytes, rgb_out);
+    return filledTo(ptp::IC_READ_DISPLAY_DENOISED_GUIDED_FILLED, c, nullptr, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor,
+                    nullptr, java_bytes, rgb_out);
 }
 
 // ---- seen-through feature records (include/pt_through.h): the records beside the first-hit ones, and include/pt_fill.h's calls on them
 int pt_read_features_through(pt_ctx* c, const pt_through_rule* rule, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_features_through: null argument");
-    int rc;
-    if ((rc = checkThrough(rule, "pt_read_features_through"))) return rc;
-    pt_ctx* on = firstStream(c);
-    if ((rc = currentRecords(on, rule, "pt_read_features_through"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->rec[ptp::RC_THRU].recs, (size_t)c->W * c->H * 64, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return throughToHost(ptp::IC_READ_FEATURES_THROUGH, c, rule, false, out);
 }
 
 int pt_read_through_rays(pt_ctx* c, const pt_through_rule* rule, float* out) {
-    if (!c || !out) return fail(PT_ERR_ARG, "pt_read_through_rays: null argument");
-    int rc;
-    if ((rc = checkThrough(rule, "pt_read_through_rays"))) return rc;
-    pt_ctx* on = firstStream(c);
-    if ((rc = currentRecords(on, rule, "pt_read_through_rays"))) return rc;
-    HIP_TRY(hipMemcpy(out, on->rec[ptp::RC_THRU].rays, (size_t)c->W * c->H * 32, hipMemcpyDeviceToHost));
-    return PT_OK;
+    return throughToHost(ptp::IC_READ_THROUGH_RAYS, c, rule, true, out);
 }
 
 int pt_fill_frame_through(pt_ctx* c, const pt_through_rule* rule, float sigma_normal, float sigma_depth, float sigma_albedo, float albedo_floor,
                           float* rgba_out, int64_t* n_filled) {
-    if (n_filled) *n_filled = 0;
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_fill_frame_through: null argument");
-    if (int rc = checkThrough(rule, "pt_fill_frame_through")) return rc;
-    return fillTo(c, rule, sigma_normal, sigma_depth, sigma_albedo, albedo_floor, "pt_fill_frame_through", rgba_out, n_filled);
+    return fillTo(ptp::IC_FILL_FRAME_THROUGH, c, rule, sigma_normal, sigma_depth, sigma_albedo, albedo_floor, rgba_out, n_filled);
 }
 
 int pt_denoise_guided_through(pt_ctx* c, const pt_through_rule* rule, int iterations, float sigma_lum, float sigma_normal, float sigma_depth,
                               float sigma_albedo, int min_frames, float albedo_floor, float* rgba_out) {
-    if (!c || !rgba_out) return fail(PT_ERR_ARG, "pt_denoise_guided_through: null argument");
-    if (int rc = checkThrough(rule, "pt_denoise_guided_through")) return rc;
-    return filledTo(c, rule, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, "pt_denoise_guided_through", rgba_out, 0,
+    return filledTo(ptp::IC_DENOISE_GUIDED_THROUGH, c, rule, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor, rgba_out, 0,
                     nullptr);
 }
 
 int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* rule, int iterations, float sigma_lum, float sigma_normal,
                                             float sigma_depth, float sigma_albedo, int min_frames, float albedo_floor, int java_bytes, uint8_t* rgb_out) {
-    if (!c || !rgb_out) return fail(PT_ERR_ARG, "pt_read_display_denoised_guided_through: null argument");
-    if (int rc = checkThrough(rule, "pt_read_display_denoised_guided_through")) return rc;
-    return filledTo(c, rule, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor,
-                    "pt_read_display_denoised_guided_through", nullptr, java_bytes, rgb_out);
+    return filledTo(ptp::IC_READ_DISPLAY_DENOISED_GUIDED_THROUGH, c, rule, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor,
+                    nullptr, java_bytes, rgb_out);
 }
