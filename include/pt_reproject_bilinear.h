@@ -33,7 +33,7 @@
  * Caller notes.  As include/pt_reproject.h's: continue with frame numbers other than 1, and show the image with pt_read_display_mean
  * (include/pt_adaptive.h), not pt_read_display.  The counts FRAME.a and T.n of a blended pixel are weighted means of its taps' counts and so
  * no longer whole numbers, as after the history merge of include/pt_validate.h; every call that reads them takes them as floats.
- * Out of scope: bilinear taps for pt_reproject_frame_moved and pt_reproject_frame_through, a wider search when no tap counts, higher-order kernels.
+ * Out of scope: bilinear taps for pt_reproject_frame_through, a wider search when no tap counts, higher-order kernels.
  */
 #ifndef PT_REPROJECT_BILINEAR_H
 #define PT_REPROJECT_BILINEAR_H

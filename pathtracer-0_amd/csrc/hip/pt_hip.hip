@@ -37,6 +37,7 @@
 #include "../../../include/pt_validate.h"
 #include "../../../include/pt_reproject_through.h"
 #include "../../../include/pt_reproject_bilinear.h"
+#include "../../../include/pt_motion_bilinear.h"
 #include "pt_device.hpp"
 #include "pt_devmem.hpp"
 #include "pt_options.hpp"

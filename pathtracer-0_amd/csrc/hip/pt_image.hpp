@@ -1,6 +1,6 @@
 // pt_image.hpp — the host half of the image-space passes behind the C ABI (included by pt_hip.hip inside its extern "C" block, where pt_ctx and
 // its helpers are in scope; not a translation unit).  T in pixel order, the feature and seen-through records, the a-trous and the variance-guided
-// filter, the reprojection across camera moves (also through mirror and glass chains, and with bilinear taps) and moved geometry, the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
+// filter, the reprojection across camera moves (also through mirror and glass chains, and with bilinear taps) and moved geometry (also with bilinear taps), the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
 // and pt_reproject.hip's, behind pt_image_launch.hpp; the kernels of the records are pt_hip.hip's.
 
 // ---- T in pixel order (include/pt_adaptive.h, include/pt_guided.h): a group's streams each hold the slots of their own shard, so T travels through the host
@@ -304,7 +304,7 @@ int storeReprojected(pt_ctx* c, pt_ctx* on, bool stats, int64_t* nKept) {
 // and the primitives' old positions from the mark (which it spends); else include/pt_reproject.h's, Rh from the image's camera.
 // floorA == 0: include/pt_reproject.h's step 7; > 0: include/pt_demod.h's, with that albedo_floor.
 // chain (not moved, floorA 0): include/pt_reproject_through.h's call, Sn / Yn and Sh / Yh beside Rn and Rh
-// taps (not moved, no chain): include/pt_reproject_bilinear.h's call, the four old pixels around the projected point
+// taps (no chain): include/pt_reproject_bilinear.h's call, the four old pixels around the projected point; with `moved`, include/pt_motion_bilinear.h's
 struct ChainCarry { const pt_through_rule* thru; float pointTol; int radius; int64_t* nKeptThrough; };
 struct BilinearTaps { float snap; int64_t* nBlended; };
 int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, float depthTol, float normalTol, int flags, float floorA, int64_t* nKept,
@@ -318,6 +318,9 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     FrameIn cur;
     if ((rc = usableInputs(on, w, "carry", cur))) return rc;
     const pt_ctx::Mark& m = on->mark;
+    // include/pt_motion_bilinear.h leaves an image without a camera alone as the bilinear call does, when there is no mark either (planReproject has
+    // no "nothing" among its moved outcomes: pt_reproject_frame_moved answers "no mark" there).  With a mark, its refusals are the moved call's
+    if (moved && taps && !on->hist.camera().valid && !on->hist.markValid()) return PT_OK;
     const ptp::ReprojectPlan plan = on->hist.planReproject(cur, moved, w);
     if ((rc = fail(plan.refused))) return rc;
     if (plan.nothing) return PT_OK;                               // no camera: nothing to map from
@@ -475,6 +478,21 @@ int pt_reproject_frame_moved(pt_ctx* c, float max_history, float depth_tol, floa
     });
 }
 
+// ---- include/pt_motion_bilinear.h: the bilinear call's argument checks under this call's name, the moved call's path with the taps
+int pt_reproject_frame_moved_bilinear(pt_ctx* c, const pt_reproject_bilinear_rule* rule, int64_t* n_kept, int64_t* n_blended) {
+    if (n_kept) *n_kept = 0;
+    if (n_blended) *n_blended = 0;
+    ImageArgs a = ImageArgs::given(c).has(ptp::AP_RULE, rule);
+    if (rule) { a.reproject(rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags, rule->albedo_floor); a.snap = rule->snap; }
+    if (int rc = fail(checkImageArgs(ptp::IC_REPROJECT_FRAME_BILINEAR, a, "pt_reproject_frame_moved_bilinear"))) return rc;
+    int64_t n = 0, nb = 0;
+    const BilinearTaps taps{rule->snap, &nb};
+    const int rc = reprojectImage(c, "pt_reproject_frame_moved_bilinear", true, rule->max_history, rule->depth_tol, rule->normal_tol, rule->flags,
+                                  rule->albedo_floor, &n, nullptr, &taps);
+    if (n_kept) *n_kept = rc ? 0 : n;
+    if (n_blended) *n_blended = rc ? 0 : nb;
+    return rc;
+}
 
 // ---- history validation (include/pt_validate.h): the hold lives on the first stream's context, where the merge runs; a group's image and T travel
 // as they do for the reprojection

@@ -1,6 +1,6 @@
 // pt_image_args.hpp — what every image-space call of the C ABI refuses in its arguments, before its first HIP call: one enumerator per entry point,
 // one struct for whatever they can be given, each predicate and its refusal text once, and one table row per entry point with the checks it makes
-// in the order it makes them.  Plain C++: no HIP runtime call and no context.  pt_image.hpp's wrappers (and pt_render_adaptive in pt_hip.hip) fill
+// in the order it makes them (an entry point that makes another's checks under its own name asks with that row and its name).  Plain C++: no HIP runtime call and no context.  pt_image.hpp's wrappers (and pt_render_adaptive in pt_hip.hip) fill
 // the struct and ask checkImageArgs; tests/c/image_args_check.cpp asks the same from scripts, so every refusal can be run on a CPU.
 //
 // The refusals that read the context (a whole image, moments never allocated, Parameters or ORIGIN not set, DEBUG != 0, more than 4096 materials
@@ -276,11 +276,13 @@ inline const std::vector<ImageCallRow>& imageCallTable() {
     return T;
 }
 
-// the first check of the call's row that does not hold, as the refusal the call answers; or none
-inline Refused checkImageArgs(ImageCall call, const ImageArgs& a) {
+// the first check of the call's row that does not hold, as the refusal the call answers; or none.  `as`: an entry point that makes another's
+// checks in the same order and has no row of its own (pt_reproject_frame_moved_bilinear: the bilinear call's) — its name, in place of the row's
+// name and prefix
+inline Refused checkImageArgs(ImageCall call, const ImageArgs& a, const char* as = nullptr) {
     const ImageCallRow& row = imageCallTable()[call];
     for (const ArgCheck& k : row.checks)
-        if (!holds(k, a)) return Refused{PT_ERR_ARG, std::string(k.own ? row.name : row.prefix) + ": " + refusalText(k)};
+        if (!holds(k, a)) return Refused{PT_ERR_ARG, std::string(as ? as : (k.own ? row.name : row.prefix)) + ": " + refusalText(k)};
     return {};
 }
 

@@ -34,7 +34,7 @@ struct GuidedJob {
 // prep, the variance (the filter: when iterations > 0; the selection: always), `iterations` passes, then finish or select
 hipError_t guidedLaunch(const GuidedJob& j, hipStream_t s);
 
-// ---- the reprojection of include/pt_reproject.h, pt_demod.h, pt_motion.h, pt_reproject_through.h and pt_reproject_bilinear.h (pt_reproject.hip).  The three structs are kernel arguments as they stand.
+// ---- the reprojection of include/pt_reproject.h, pt_demod.h, pt_motion.h, pt_reproject_through.h, pt_reproject_bilinear.h and pt_motion_bilinear.h (pt_reproject.hip).  The three structs are kernel arguments as they stand.
 struct ReprojCam {
     float On[3];                        // the current ORIGIN (the origin of Rn's rays)
     float mouseX, mouseY, resolution;   // the current mouse overlay
@@ -56,7 +56,7 @@ struct ReprojectJob {
     ReprojRule rule{};
     float floorA = 0.0f;                                          // 0: pt_reproject.h's step 7; > 0: pt_demod.h's, with that albedo_floor
     const ReprojMotion* motion = nullptr;                         // given: pt_motion.h's mapping, rh and the "then" geometry from the mark
-    bool bilinear = false; float snap = 0.0f;                     // include/pt_reproject_bilinear.h's taps (no motion, no sn); kept[1]: the blended pixels
+    bool bilinear = false; float snap = 0.0f;                     // include/pt_reproject_bilinear.h's taps (no sn; with motion: include/pt_motion_bilinear.h's); kept[1]: the blended pixels
     // include/pt_reproject_through.h, when sn is given (no motion, floorA 0): sn, yn / sh, yh: the seen-through records (W*H*4 float4) and their last
     // segments (W*H*2 float4) under the current inputs / the image's camera; pack: scratch, W*H*2 float4; radius: 0 .. 4 (checked by the caller)
     const float4* sn = nullptr; const float4* yn = nullptr; const float4* sh = nullptr; const float4* yh = nullptr;

@@ -1,5 +1,5 @@
-// pt_reproject.hip — the reprojection of include/pt_reproject.h, include/pt_reproject_through.h and include/pt_reproject_bilinear.h and the history
-// validation of include/pt_validate.h for gfx950.
+// pt_reproject.hip — the reprojection of include/pt_reproject.h, include/pt_reproject_through.h, include/pt_reproject_bilinear.h and
+// include/pt_motion_bilinear.h and the history validation of include/pt_validate.h for gfx950.
 //
 // Device pointers only: pt_hip.hip owns the buffers, computes both sets of feature records and calls reprojectLaunch on its stream.
 //   k_reproject<MOVED, DEMOD>  one lane per new pixel, a wave = 64 pixels of a row, a block = 16 rows.  Reads 48 B of Rn[p] (F0, F1.w, F2), the same
@@ -11,6 +11,8 @@
 //                <true, DEMOD>   include/pt_motion.h: the hit's surface point followed back to where its primitive was at the mark
 //   k_reproject_bilinear<DEMOD>  include/pt_reproject_bilinear.h: the same lanes and blocks; each lane blends up to four old pixels around the projected
 //                point (4 x (24 or 36 B of Rh, FRAME, T), all loaded before the first test) and counts the kept and the blended pixels as k_reproject counts.
+//   k_reproject_moved_bilinear<DEMOD>  include/pt_motion_bilinear.h: k_reproject<true, DEMOD>'s step 2 (P', N~ from the mark's and the current positions), then
+//                k_reproject_bilinear's taps tested against them; the motion loads decide the taps' addresses and so precede them.
 //   k_history_merge<R>  include/pt_validate.h: one lane per pixel in the same blocks.  The block's tile with its halo of R pixels is staged in LDS
 //                once, as ten planes of floats (the six moments, zeroed where a pixel can be no tap for any centre; the normal; one class /
 //                material word), so that a tap costs ten LDS reads of consecutive words per wave and no global load; then steps 1-4 and the
@@ -357,6 +359,200 @@ __global__ void __launch_bounds__(RP_BX * RP_BY) k_reproject_bilinear(const floa
     }
 }
 
+// Steps 1-9 of include/pt_motion_bilinear.h and both counts: k_reproject<true, DEMOD>'s steps 1-4 (the hit's surface point followed back to where its
+// primitive was at the mark: P', N~) and then k_reproject_bilinear's taps, tested against |v| of P' and against N~.  A kernel of its own with its own
+// copy of both texts: k_reproject and k_reproject_bilinear stay the code objects they were.  Per lane: Rn[p] once; one 16-B flag record of an unmoved
+// primitive, 96 B of a moved triangle, 64 B of a moved ellipsoid — these loads decide sx and sy, so they precede the taps, and nothing of them but
+// P', N~ and the verdict lives on into the taps —; then the four taps as k_reproject_bilinear loads them: clamped addresses, the "in the image" flag
+// beside each, all twenty loads before the first test and without a branch between them, FRAME in T's place in a context without T.  Four named
+// structs and scalar accumulators: nothing on the stack.  kept[0], kept[1]: k_reproject_bilinear's two counts, by its scheme.
+template <bool DEMOD>
+__global__ void __launch_bounds__(RP_BX * RP_BY) k_reproject_moved_bilinear(const float4* __restrict__ rn, const float4* __restrict__ rh, const float4* __restrict__ frame,
+                                                                           const float4* __restrict__ stats, const FrameConst* __restrict__ hc,
+                                                                           const unsigned char* __restrict__ matVD, int nMat, int W, int H, ReprojCam cam, ReprojRule r,
+                                                                           float snap, float floorA, ReprojMotion g, float4* __restrict__ outFrame,
+                                                                           float4* __restrict__ outStats, unsigned* __restrict__ kept) {
+    __shared__ unsigned blockKept, blockBlended;
+    if (threadIdx.x == 0 && threadIdx.y == 0) { blockKept = 0; blockBlended = 0; }
+    __syncthreads();
+    const int x = blockIdx.x * RP_BX + threadIdx.x, y = blockIdx.y * RP_BY + threadIdx.y;
+    const bool in = x < W && y < H;
+    const size_t p = (size_t)y * W + x;
+    bool keep = false, blended = false;
+    float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f, f3 = 0.0f, t0 = 0.0f, t1 = 0.0f, t2 = 0.0f, t3 = 0.0f;      // the new FRAME and T
+    const float* M = hc->camRot;                                                           // the image's camera, as k_frame_setup built it
+    const float O0 = hc->origin[0], O1 = hc->origin[1], O2 = hc->origin[2], ss = hc->screenSize, fl = hc->focalLength, hr = hc->screenHratio;
+    FrameConst fc;
+    fc.mouse[0] = cam.mouseX; fc.mouse[1] = cam.mouseY; fc.resolution = cam.resolution;
+    if (in && !inMouseOverlay(fc, x, y)) {                                                 // 1
+        const float4 n0 = rn[4 * p], n2 = rn[4 * p + 2];
+        const float4 n1 = loadF1<DEMOD>(rn + 4 * p);
+        const int code = __float_as_int(n1.w);
+        const bool hit = code != -1;                                                       // 2
+        const int mat = __float_as_int(n2.w);
+        bool ok;
+        float vx, vy, vz;
+        float Nx = n0.y, Ny = n0.z, Nz = n0.w;                                             // N~: the normal the surface point had at the mark
+        if (hit) {
+            ok = __builtin_isfinite(n0.x) && finite3(n0.y, n0.z, n0.w) && finite3(n2.x, n2.y, n2.z) && (unsigned)mat < (unsigned)nMat &&
+                 (r.allMaterials || !matVD[mat]);
+            float Px = cam.On[0] + n0.x * n2.x, Py = cam.On[1] + n0.x * n2.y, Pz = cam.On[2] + n0.x * n2.z;      // P, then P'
+            const unsigned type = (unsigned)code >> 24;
+            const int id = code & 0xffffff;
+            if (!ok) {
+            } else if (type == 1u) {
+                if (id < g.nTriNow && id < g.nTriThen) {
+                    const float4 A = g.triNow[3 * (size_t)id];
+                    if (__float_as_int(A.w) != 0) {                                        // moved: through the barycentrics of P in (A, B, C)
+                        const float4 B = g.triNow[3 * (size_t)id + 1], C = g.triNow[3 * (size_t)id + 2];
+                        const float4 Ah = g.triThen[3 * (size_t)id], Bh = g.triThen[3 * (size_t)id + 1], Ch = g.triThen[3 * (size_t)id + 2];
+                        const float e1x = B.x - A.x, e1y = B.y - A.y, e1z = B.z - A.z, e2x = C.x - A.x, e2y = C.y - A.y, e2z = C.z - A.z;
+                        const float wx = Px - A.x, wy = Py - A.y, wz = Pz - A.z;
+                        const float h1x = Bh.x - Ah.x, h1y = Bh.y - Ah.y, h1z = Bh.z - Ah.z, h2x = Ch.x - Ah.x, h2y = Ch.y - Ah.y, h2z = Ch.z - Ah.z;
+                        const float d11 = dot3(e1x, e1y, e1z, e1x, e1y, e1z), d12 = dot3(e1x, e1y, e1z, e2x, e2y, e2z), d22 = dot3(e2x, e2y, e2z, e2x, e2y, e2z);
+                        const float den = d11 * d22 - d12 * d12;
+                        const float w1 = dot3(wx, wy, wz, e1x, e1y, e1z), w2 = dot3(wx, wy, wz, e2x, e2y, e2z);
+                        const float beta = (d22 * w1 - d12 * w2) / den, gamma = (d11 * w2 - d12 * w1) / den;
+                        Px = (Ah.x + beta * h1x) + gamma * h2x; Py = (Ah.y + beta * h1y) + gamma * h2y; Pz = (Ah.z + beta * h1z) + gamma * h2z;
+                        const float gx = e1y * e2z - e1z * e2y, gy = e1z * e2x - e1x * e2z, gz = e1x * e2y - e1y * e2x;
+                        const float kx = h1y * h2z - h1z * h2y, ky = h1z * h2x - h1x * h2z, kz = h1x * h2y - h1y * h2x;
+                        const float m1 = dot3(Nx, Ny, Nz, e1x, e1y, e1z), m2 = dot3(Nx, Ny, Nz, e2x, e2y, e2z);
+                        const float a = (d22 * m1 - d12 * m2) / den, b = (d11 * m2 - d12 * m1) / den;
+                        const float c = dot3(Nx, Ny, Nz, gx, gy, gz) / dot3(gx, gy, gz, gx, gy, gz);
+                        const float Mx = (a * h1x + b * h2x) + c * kx, My = (a * h1y + b * h2y) + c * ky, Mz = (a * h1z + b * h2z) + c * kz;
+                        const float ml = sqrtf(dot3(Mx, My, Mz, Mx, My, Mz));
+                        Nx = Mx / ml; Ny = My / ml; Nz = Mz / ml;
+                        ok = __builtin_isfinite(den) && den > 0.0f && finite3(Px, Py, Pz) && finite3(Nx, Ny, Nz);
+                    }
+                } else {
+                    ok = false;
+                }
+            } else if (type == 3u) {
+                if (id < g.nElNow && id < g.nElThen) {
+                    const float4 S = g.elNow[3 * (size_t)id + 1];
+                    const int flag = __float_as_int(S.w);
+                    if (flag == 1) {                                                       // moved, no rotation: the point keeps its place on the unit sphere
+                        const float4 Cn = g.elNow[3 * (size_t)id], Ch = g.elThen[3 * (size_t)id], Sh = g.elThen[3 * (size_t)id + 1];
+                        const float rr = Ch.w / Cn.w;
+                        const float k0 = sqrtf(S.x / Sh.x) * rr, k1 = sqrtf(S.y / Sh.y) * rr, k2 = sqrtf(S.z / Sh.z) * rr;
+                        Px = Ch.x + (Px - Cn.x) * k0; Py = Ch.y + (Py - Cn.y) * k1; Pz = Ch.z + (Pz - Cn.z) * k2;
+                        ok = finite3(Px, Py, Pz);
+                    } else if (flag != 0) {
+                        ok = false;
+                    }
+                } else {
+                    ok = false;
+                }
+            } else {
+                ok = false;
+            }
+            vx = Px - O0; vy = Py - O1; vz = Pz - O2;
+        } else {
+            ok = true;
+            vx = n2.x; vy = n2.y; vz = n2.z;
+        }
+        const float q0 = (vx * M[0] + vy * M[1]) + vz * M[2];                                  // 3
+        const float q1 = (vx * M[3] + vy * M[4]) + vz * M[5];
+        const float q2 = (vx * M[6] + vy * M[7]) + vz * M[8];
+        const float a = (q0 / q2) * fl, b = (q1 / q2) * fl;                                   // 4
+        const float sx = ((1.0f - a / ss) * 0.5f) * (float)W, sy = ((1.0f + b / (hr * ss)) * 0.5f) * (float)H;
+        ok = ok && q2 > 0.0f && sx >= 0.0f && sx < (float)W && sy >= 0.0f && sy < (float)H;
+        if (ok) {
+            float wx, wy;                                                                  // 5
+            const int ix = bilinearAxis(sx, snap, wx), iy = bilinearAxis(sy, snap, wy);
+            const float ax0 = 1.0f - wx, ay0 = 1.0f - wy;
+            const int cx0 = min(max(ix, 0), W - 1), cx1 = min(max(ix + 1, 0), W - 1), cy0 = min(max(iy, 0), H - 1), cy1 = min(max(iy + 1, 0), H - 1);
+            const bool inx0 = ix >= 0 && ix < W, inx1 = ix + 1 < W, iny0 = iy >= 0 && iy < H, iny1 = iy + 1 < H;      // (ix, iy >= -1)
+            const bool hasT = stats != nullptr;
+            const float4* __restrict__ tsrc = hasT ? stats : frame;
+            auto load = [&](int cx, int cy, float w, bool inside) {
+                const size_t s = (size_t)cy * W + cx;
+                BilinearTap t;
+                t.h0 = rh[4 * s]; t.h1 = loadF1<DEMOD>(rh + 4 * s); t.mat = __float_as_int(reinterpret_cast<const float*>(rh + 4 * s)[11]);
+                t.F = frame[s];
+                t.T = tsrc[s];
+                t.w = w; t.in = inside;
+                return t;
+            };
+            const BilinearTap ta = load(cx0, cy0, ax0 * ay0, inx0 && iny0), tb = load(cx1, cy0, wx * ay0, inx1 && iny0);
+            const BilinearTap tc = load(cx0, cy1, ax0 * wy, inx0 && iny1), td = load(cx1, cy1, wx * wy, inx1 && iny1);
+            const float len = sqrtf((vx * vx + vy * vy) + vz * vz);
+            auto counts = [&](const BilinearTap& t) {
+                const bool hhit = __float_as_int(t.h1.w) != -1;
+                const bool same = hit ? hhit && t.mat == mat && __builtin_isfinite(t.h0.x) && t.h0.x > 0.0f &&
+                                            __builtin_fabsf(len - t.h0.x) <= r.depthTol * t.h0.x && (Nx * t.h0.y + Ny * t.h0.z) + Nz * t.h0.w >= r.normalTol
+                                      : !hhit;
+                return t.w > 0.0f && t.in && same && t.F.w > 0.0f && finite3(t.F.x, t.F.y, t.F.z);
+            };
+            const bool ca = counts(ta), cb = counts(tb), cc = counts(tc), cd = counts(td);
+            const int nc = (int)ca + (int)cb + (int)cc + (int)cd;
+            float3 bn = make_float3(1.0f, 1.0f, 1.0f);
+            if constexpr (DEMOD) bn = carriedAlbedo(n1, floorA);
+            if (nc == 1) {                                                                 // 7: k_reproject's step 7 from the one tap
+                const float4 F = ca ? ta.F : cb ? tb.F : cc ? tc.F : td.F;
+                const float4 T = ca ? ta.T : cb ? tb.T : cc ? tc.T : td.T;
+                if constexpr (DEMOD) {
+                    const float4 h1 = ca ? ta.h1 : cb ? tb.h1 : cc ? tc.h1 : td.h1;
+                    const float3 bh = carriedAlbedo(h1, floorA);
+                    f0 = F.x * (bn.x / bh.x); f1 = F.y * (bn.y / bh.y); f2 = F.z * (bn.z / bh.z); f3 = F.w;
+                    if (F.w > r.maxHistory) { const float f = r.maxHistory / F.w; f0 = f0 * f; f1 = f1 * f; f2 = f2 * f; f3 = r.maxHistory; }
+                    if (hasT) {
+                        const float rho = lum(bn.x, bn.y, bn.z) / lum(bh.x, bh.y, bh.z);
+                        t0 = T.x * rho; t1 = (T.y * rho) * rho; t2 = T.z; t3 = T.w;
+                        if (T.z > r.maxHistory) { const float gg = r.maxHistory / T.z; t0 = t0 * gg; t1 = t1 * gg; t2 = r.maxHistory; }
+                    }
+                } else {
+                    f0 = F.x; f1 = F.y; f2 = F.z; f3 = F.w;
+                    if (F.w > r.maxHistory) { const float f = r.maxHistory / F.w; f0 = F.x * f; f1 = F.y * f; f2 = F.z * f; f3 = r.maxHistory; }
+                    if (hasT) {
+                        t0 = T.x; t1 = T.y; t2 = T.z; t3 = T.w;
+                        if (T.z > r.maxHistory) { const float gg = r.maxHistory / T.z; t0 = T.x * gg; t1 = T.y * gg; t2 = r.maxHistory; }
+                    }
+                }
+            } else if (nc >= 2) {                                                          // 8, 9: a tap that does not count adds +0, which changes no bit of a sum that began at +0
+                float Ws = 0.0f, A = 0.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, WT = 0.0f, NT = 0.0f, Y = 0.0f, YY = 0.0f;
+                auto add = [&](const BilinearTap& t, bool c) {
+                    float m0 = t.F.x / t.F.w, m1 = t.F.y / t.F.w, m2 = t.F.z / t.F.w;
+                    float rho = 1.0f;
+                    if constexpr (DEMOD) {
+                        const float3 bh = carriedAlbedo(t.h1, floorA);
+                        m0 = m0 * (bn.x / bh.x); m1 = m1 * (bn.y / bh.y); m2 = m2 * (bn.z / bh.z);
+                        rho = lum(bn.x, bn.y, bn.z) / lum(bh.x, bh.y, bh.z);
+                    }
+                    Ws = Ws + (c ? t.w : 0.0f); A = A + (c ? t.w * t.F.w : 0.0f);
+                    C0 = C0 + (c ? t.w * m0 : 0.0f); C1 = C1 + (c ? t.w * m1 : 0.0f); C2 = C2 + (c ? t.w * m2 : 0.0f);
+                    const bool ct = hasT && c && t.T.z > 0.0f && __builtin_isfinite(t.T.x) && __builtin_isfinite(t.T.y);
+                    float yv = t.T.x / t.T.z, yy = t.T.y / t.T.z;
+                    if constexpr (DEMOD) { yv = yv * rho; yy = (yy * rho) * rho; }
+                    WT = WT + (ct ? t.w : 0.0f); NT = NT + (ct ? t.w * t.T.z : 0.0f); Y = Y + (ct ? t.w * yv : 0.0f); YY = YY + (ct ? t.w * yy : 0.0f);
+                };
+                add(ta, ca); add(tb, cb); add(tc, cc); add(td, cd);
+                const float n = A / Ws, nn = n > r.maxHistory ? r.maxHistory : n;
+                f0 = (C0 / Ws) * nn; f1 = (C1 / Ws) * nn; f2 = (C2 / Ws) * nn; f3 = nn;
+                if (WT > 0.0f) {
+                    const float nT = NT / WT, nt = nT > r.maxHistory ? r.maxHistory : nT;
+                    t0 = (Y / WT) * nt; t1 = (YY / WT) * nt; t2 = nt; t3 = 0.0f;
+                }
+                blended = true;
+            }
+            ok = nc >= 1;                                                                  // 6
+        }
+        keep = ok;
+    }
+    if (in) {
+        outFrame[p] = keep ? make_float4(f0, f1, f2, f3) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (outStats) outStats[p] = keep ? make_float4(t0, t1, t2, t3) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    const unsigned long long m = __ballot(keep), mb = __ballot(blended);                   // every lane of the block, in range or not
+    if (threadIdx.x == 0 && m) atomicAdd(&blockKept, (unsigned)__popcll(m));
+    if (threadIdx.x == 0 && mb) atomicAdd(&blockBlended, (unsigned)__popcll(mb));
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        if (blockKept) atomicAdd(kept, blockKept);
+        if (blockBlended) atomicAdd(kept + 1, blockBlended);
+    }
+}
+
 // max(x, 0) of include/pt_guided.h: a NaN is no estimate
 __device__ __forceinline__ float clampVar(float x) { return x >= 0.0f ? x : (x < 0.0f ? 0.0f : __builtin_inff()); }
 
@@ -558,11 +754,15 @@ hipError_t reprojectLaunch(const ReprojectJob& j, hipStream_t s) {
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((j.W + RP_BX - 1) / RP_BX), (unsigned)((j.H + RP_BY - 1) / RP_BY)), block(RP_BX, RP_BY);
     if (j.bilinear) {                                                                      // include/pt_reproject_bilinear.h: a mapping of its own, kept[1] = the blended pixels
-        if (j.motion || j.sn) return hipErrorInvalidValue;
-#define RB_ARGS j.rn, j.rh, j.frame, j.stats, j.hist, j.matVD, j.nMat, j.W, j.H, j.cam, j.rule, j.snap, j.floorA, j.outFrame, j.outStats, j.kept
-        if (j.floorA > 0.0f) hipLaunchKernelGGL(k_reproject_bilinear<true>, grid, block, 0, s, RB_ARGS);
-        else hipLaunchKernelGGL(k_reproject_bilinear<false>, grid, block, 0, s, RB_ARGS);
-#undef RB_ARGS
+        if (j.sn) return hipErrorInvalidValue;
+#define RB_IN j.rn, j.rh, j.frame, j.stats, j.hist, j.matVD, j.nMat, j.W, j.H, j.cam, j.rule, j.snap, j.floorA
+#define RB_OUT j.outFrame, j.outStats, j.kept
+        if (j.motion && j.floorA > 0.0f) hipLaunchKernelGGL(k_reproject_moved_bilinear<true>, grid, block, 0, s, RB_IN, *j.motion, RB_OUT);      // include/pt_motion_bilinear.h
+        else if (j.motion) hipLaunchKernelGGL(k_reproject_moved_bilinear<false>, grid, block, 0, s, RB_IN, *j.motion, RB_OUT);
+        else if (j.floorA > 0.0f) hipLaunchKernelGGL(k_reproject_bilinear<true>, grid, block, 0, s, RB_IN, RB_OUT);
+        else hipLaunchKernelGGL(k_reproject_bilinear<false>, grid, block, 0, s, RB_IN, RB_OUT);
+#undef RB_IN
+#undef RB_OUT
         return hipGetLastError();
     }
     const bool demod = j.floorA > 0.0f;

@@ -170,6 +170,8 @@ def lib():
             L.pt_reproject_frame_through.argtypes = [vp, C.POINTER(ThroughRule), C.POINTER(ReprojectThroughRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         if hasattr(L, "pt_reproject_frame_bilinear"):         # include/pt_reproject_bilinear.h
             L.pt_reproject_frame_bilinear.argtypes = [vp, C.POINTER(ReprojectBilinearRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_reproject_frame_moved_bilinear"):   # include/pt_motion_bilinear.h
+            L.pt_reproject_frame_moved_bilinear.argtypes = [vp, C.POINTER(ReprojectBilinearRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -463,6 +465,18 @@ class Renderer:
         flags = self.REPROJECT_ALL_MATERIALS if all_materials else 0
         _check(self._L.pt_reproject_frame_moved(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, float(albedo_floor), C.byref(n)))
         return n.value
+
+    # --- reprojection across moved geometry with bilinear taps (include/pt_motion_bilinear.h) ------
+    def reproject_frame_moved_bilinear(self, max_history=64, depth_tol=0.02, normal_tol=0.9, snap=1 / 64, all_materials=False, albedo_floor=0.0):
+        """reproject_frame_moved that blends the qualifying old pixels around the point a surface point projected to at the mark
+        (pt_reproject_frame_moved_bilinear) where reproject_frame_moved copies the nearest one: a primitive that moves by a fraction of a pixel
+        per step keeps its history in place.  The mark and the caller contract are reproject_frame_moved's, snap and albedo_floor
+        reproject_frame_bilinear's.  Returns (kept, blended); the mark is spent.  Counts become fractional."""
+        rule = ReprojectBilinearRule(float(max_history), float(depth_tol), float(normal_tol), float(snap), float(albedo_floor),
+                                     self.REPROJECT_ALL_MATERIALS if all_materials else 0)
+        n, nb = C.c_int64(0), C.c_int64(0)
+        _check(self._L.pt_reproject_frame_moved_bilinear(self._h, C.byref(rule), C.byref(n), C.byref(nb)))
+        return n.value, nb.value
 
     # --- history validation (include/pt_validate.h) -------------------------------------------------
     # defaults of validate_rule: the float32 model on the oracle's frames at 160 x 90 (tests/test_validate_abi.py, DESIGN.md 2.16), 64 frames,
