@@ -172,6 +172,11 @@ def lib():
             L.pt_reproject_frame_bilinear.argtypes = [vp, C.POINTER(ReprojectBilinearRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         if hasattr(L, "pt_reproject_frame_moved_bilinear"):   # include/pt_motion_bilinear.h
             L.pt_reproject_frame_moved_bilinear.argtypes = [vp, C.POINTER(ReprojectBilinearRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_refit_create"):                     # include/pt_refit.h
+            L.pt_refit_create.argtypes = [ci, vp, sz, vp, sz, vp, sz, vp, sz, C.c_int64, C.POINTER(vp)]
+            L.pt_refit_run.argtypes = [vp, vp, sz, vp, vp]
+            L.pt_refit_destroy.argtypes = [vp]
+            L.pt_refit_destroy.restype = None
         _LIB = L
     return _LIB
 
@@ -228,6 +233,45 @@ def shard_map(W, H, rank, count):
     out = np.empty(n, dtype=np.int32)
     _check(lib().pt_shard_map(W, H, rank, count, out.ctypes.data, n))
     return out
+
+
+class RefitPlan:
+    """A BVH refit plan (include/pt_refit.h): the topology of `buffers` (bindings 10, 11, 12, 13 of a scene; binding 3, when present, gives the
+    triangle count) validated, ordered by height and kept on `device`.  run(tris) recomputes binding 10 for a new binding 3 in which triangle k
+    is still the same piece of surface (the rule of include/pt_motion.h).  No render context is involved."""
+
+    def __init__(self, buffers, device=0, n_tris=None):
+        self._L = lib()
+        self._h = C.c_void_p()
+        if not hasattr(self._L, "pt_refit_create"):
+            raise RuntimeError("this libpt_hip.so has no pt_refit_create (include/pt_refit.h): no fallback")
+        data, tree, leaf, roots = (np.ascontiguousarray(buffers[10], dtype=np.float32), np.ascontiguousarray(buffers[11], dtype=np.int32),
+                                   np.ascontiguousarray(buffers[12], dtype=np.int32), np.ascontiguousarray(buffers[13], dtype=np.int32))
+        self.n_tris = int(n_tris if n_tris is not None else np.asarray(buffers[3]).size // 40)
+        self.n_floats, self.n_roots = data.size, int(roots[0]) if roots.size else 0
+        _check(self._L.pt_refit_create(int(device), data.ctypes.data, data.nbytes, tree.ctypes.data, tree.nbytes, leaf.ctypes.data, leaf.nbytes,
+                                       roots.ctypes.data, roots.nbytes, self.n_tris, C.byref(self._h)))
+
+    def run(self, tris, out=None):
+        """-> (binding 10 for these triangles, root_cost: one float64 per root, in binding 13's order).  PtError -4 when a referenced triangle
+        holds a NaN; `out`, when given, is then untouched."""
+        t = np.ascontiguousarray(tris, dtype=np.float32)
+        data = np.empty(self.n_floats, np.float32) if out is None else out
+        assert data.dtype == np.float32 and data.size == self.n_floats and data.flags.c_contiguous
+        cost = np.zeros(self.n_roots, np.float64)
+        _check(self._L.pt_refit_run(self._h, t.ctypes.data, t.nbytes, data.ctypes.data, cost.ctypes.data))
+        return data, cost
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pt_refit_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Renderer:
@@ -465,6 +509,16 @@ class Renderer:
         flags = self.REPROJECT_ALL_MATERIALS if all_materials else 0
         _check(self._L.pt_reproject_frame_moved(self._h, float(max_history), float(depth_tol), float(normal_tol), flags, float(albedo_floor), C.byref(n)))
         return n.value
+
+    # --- BVH refit for moved triangles (include/pt_refit.h) -----------------------------------------
+    def move_triangles(self, plan, tris):
+        """Upload a moved binding 3 and the binding 10 that `plan` (a RefitPlan over this scene's bindings 10-13) refits to it; bindings 11-13 stay
+        as uploaded.  Between motion_mark and reproject_frame_moved this replaces the rebuild of every tree; moved ellipsoids (binding 7) are the
+        caller's to upload.  Returns (binding 10, root_cost): the cost against the rest pose's says when a rebuild pays."""
+        data, cost = plan.run(tris)
+        self.set_buffer(3, np.ascontiguousarray(tris, dtype=np.float32))
+        self.set_buffer(10, data)
+        return data, cost
 
     # --- reprojection across moved geometry with bilinear taps (include/pt_motion_bilinear.h) ------
     def reproject_frame_moved_bilinear(self, max_history=64, depth_tol=0.02, normal_tol=0.9, snap=1 / 64, all_materials=False, albedo_floor=0.0):

@@ -472,6 +472,18 @@ def m1_moving(step=0, W=96, H=54, sample_res=8, max_bounces=8, subdiv=2, texture
     return wl
 
 
+def m1_refit(step=0, W=96, H=54, **kw):
+    """M1 at `step` over the rest pose's trees, the input of a BVH refit (include/pt_refit.h): bindings 3 and 7 (and everything else) of
+    m1_moving(step), bindings 10-13 of m1_moving(0).  Binding 10 is the REST pose's and stale for step != 0: the caller fills it in with its plan,
+    `wl.buffers[10], cost = renderer.RefitPlan(wl.buffers).run(wl.buffers[3])`."""
+    rest, wl = m1_moving(0, W, H, **kw), m1_moving(step, W, H, **kw)
+    assert rest.buffers[3].size == wl.buffers[3].size
+    b = dict(wl.buffers)
+    for k in (10, 11, 12, 13):
+        b[k] = rest.buffers[k].copy()
+    return Workload("M1", W, H, b, wl.sky, wl.sample_res, wl.max_bounces, dict(rest.info), wl.textures)
+
+
 def m2_relit(step=0, W=96, H=54, **kw):
     """M2, the relit workload of include/pt_validate.h (not a BASELINE config): M1's rest pose with the light quad slid by 0.05 * step along x.
     No surface but the light moves; the shadows and the lit walls change everywhere else."""
