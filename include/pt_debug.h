@@ -63,6 +63,13 @@ int pt_kernel_time_median(pt_ctx* ctx, int kernel, double* median_ms);
 int pt_debug_math(pt_ctx* ctx, int fn, const float* x, const float* y, float* out, size_t n);
 /* Single rays through the intersect kernel option 4 selects (the production kernels included): o,d are n*3 f32 (host); out is n*4 f32 (t,u,v) + prim as int bits */
 int pt_debug_intersect(pt_ctx* ctx, const float* o, const float* d, float* out, size_t n);
+/* One device record array of the built scene, read back as it lies on the device (tests of include/pt_move.h): which = 0 the 64-byte node records,
+ * 1 the hand-written kernel's node records (with their 160 trailing bytes), 2 the 48-byte triangle records, 3 the 64-byte shading records,
+ * 4 the root records and, beyond 8 BVHs, the 64 group boxes, 5 the ellipsoid records (rotation matrices as the last frame setup left them),
+ * 6 the triangle-to-object table.  *bytes receives the array's size; cap == 0 only queries it, else out must hold it.  Completes submitted
+ * batches.  PT_ERR_ARG: a null argument, an unknown array, a buffer too small, a multi-stream context, a scene that is not built (an upload or a
+ * rebuilding option since the last render). */
+int pt_debug_scene_records(pt_ctx* ctx, int which, void* out, size_t cap, size_t* bytes);
 
 #ifdef __cplusplus
 }

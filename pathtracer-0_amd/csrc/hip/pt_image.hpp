@@ -775,3 +775,6 @@ int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* ru
     return filledTo(ptp::IC_READ_DISPLAY_DENOISED_GUIDED_THROUGH, c, rule, iterations, {sigma_lum, sigma_normal, sigma_depth, sigma_albedo}, min_frames, albedo_floor,
                     nullptr, java_bytes, rgb_out);
 }
+
+// the in-place move of a scene's triangles (include/pt_move.h) and the read-back of the scene's record arrays
+#include "pt_move_host.hpp"

@@ -12,9 +12,7 @@
 // the file is compiled with -ffp-contract=off like the rest of the library.  Every index a kernel follows was range-checked by planRefit.
 #include <hip/hip_runtime.h>
 
-#include "../../../include/pt_refit.h"
-#include "pt_devmem.hpp"
-#include "pt_refit_plan.hpp"
+#include "pt_refit_state.hpp"
 
 #include <cstdint>
 #include <mutex>
@@ -23,26 +21,6 @@
 #include <vector>
 
 int pt_set_error_(int code, const std::string& msg);     // pt_hip.hip
-
-struct pt_refit_plan {
-    int device = 0;
-    ptr::RefitSchedule s;                                // (host copy: the launch sizes, the roots)
-    size_t dataBytes = 0; int64_t nTris = 0;
-    hipStream_t stream = nullptr;
-    Dev<float> dData;                                    // binding 10 as created; every run rewrites floats 0-5 of the reachable rows
-    Dev<float> dTris;                                    // binding 3 of the current run
-    Dev<int32_t> dTree, dLeaf, dOrder, dLevelStart, dRoots;
-    Dev<double> dS, dRootCost;
-    Dev<int> dFlag;
-    ~pt_refit_plan() {
-        if (!stream) return;                             // refused before anything was allocated
-        // the device memory goes before the stream, on the plan's device
-        hipSetDevice(device);
-        dData.release(); dTris.release(); dTree.release(); dLeaf.release(); dOrder.release(); dLevelStart.release(); dRoots.release();
-        dS.release(); dRootCost.release(); dFlag.release();
-        if (stream) hipStreamDestroy(stream);
-    }
-};
 
 namespace {
 
@@ -185,6 +163,7 @@ extern "C" int pt_refit_create(int device, const float* bvh_data, size_t data_by
         return pt_set_error_(PT_ERR_NO_DEVICE, "pt_refit_create: the device is not a usable gfx950 (this library is built for gfx950 only)");
     }
     P->device = device; P->dataBytes = data_bytes; P->nTris = n_tris;
+    P->digest = ptr::topologyDigest(bvh_tree, tree_bytes / 4, leaf_tris, leaf_bytes / 4, obj_roots, roots_bytes / 4, bvh_data, data_bytes / 4);
     rc = uploadPlan(*P, in);
     if (rc) { delete P; return rc; }
     { std::lock_guard<std::mutex> g(g_plansMutex); g_plans.insert(P); }
@@ -192,13 +171,12 @@ extern "C" int pt_refit_create(int device, const float* bvh_data, size_t data_by
     return PT_OK;
 }
 
-extern "C" int pt_refit_run(pt_refit_plan* P, const float* tris, size_t tri_bytes, float* bvh_data_out, double* root_cost) {
-    {
-        std::lock_guard<std::mutex> g(g_plansMutex);
-        if (!P || !g_plans.count(P)) return pt_set_error_(PT_ERR_ARG, "pt_refit_run: null or destroyed plan");
-    }
-    if (!tris || !bvh_data_out) return pt_set_error_(PT_ERR_ARG, "pt_refit_run: null pointer");
-    if (tri_bytes != (size_t)P->nTris * 160) return pt_set_error_(PT_ERR_ARG, "pt_refit_run: tri_bytes != n_tris * 160");
+bool pt_refit_live_(pt_refit_plan* P) {
+    std::lock_guard<std::mutex> g(g_plansMutex);
+    return P && g_plans.count(P);
+}
+
+int pt_refit_device_(pt_refit_plan* P, const float* tris, size_t tri_bytes, const char* who) {
     const ptr::RefitSchedule& s = P->s;
     const hipStream_t st = P->stream;
     REFIT_TRY(hipSetDevice(P->device));
@@ -220,7 +198,17 @@ extern "C" int pt_refit_run(pt_refit_plan* P, const float* tris, size_t tri_byte
     int flag = 0;
     REFIT_TRY(hipMemcpyAsync(&flag, P->dFlag, 4, hipMemcpyDeviceToHost, st));
     REFIT_TRY(hipStreamSynchronize(st));
-    if (flag) return pt_set_error_(PT_ERR_SCENE, "pt_refit_run: NaN coordinate in a referenced triangle");
+    if (flag) return pt_set_error_(PT_ERR_SCENE, std::string(who) + ": NaN coordinate in a referenced triangle");
+    return PT_OK;
+}
+
+extern "C" int pt_refit_run(pt_refit_plan* P, const float* tris, size_t tri_bytes, float* bvh_data_out, double* root_cost) {
+    if (!pt_refit_live_(P)) return pt_set_error_(PT_ERR_ARG, "pt_refit_run: null or destroyed plan");
+    if (!tris || !bvh_data_out) return pt_set_error_(PT_ERR_ARG, "pt_refit_run: null pointer");
+    if (tri_bytes != (size_t)P->nTris * 160) return pt_set_error_(PT_ERR_ARG, "pt_refit_run: tri_bytes != n_tris * 160");
+    if (const int rc = pt_refit_device_(P, tris, tri_bytes, "pt_refit_run")) return rc;
+    const ptr::RefitSchedule& s = P->s;
+    const hipStream_t st = P->stream;
     if (P->dataBytes) REFIT_TRY(hipMemcpyAsync(bvh_data_out, P->dData, P->dataBytes, hipMemcpyDeviceToHost, st));
     if (root_cost && s.nRoots > 0) REFIT_TRY(hipMemcpyAsync(root_cost, P->dRootCost, (size_t)s.nRoots * 8, hipMemcpyDeviceToHost, st));
     REFIT_TRY(hipStreamSynchronize(st));

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -40,6 +41,35 @@ struct RefitSchedule {
         return h;
     }
 };
+
+// What a plan was made from, as 64 bits: bindings 11, 12 and 13 whole, floats 6 and 7 (the leaf ranges) of every row of binding 10, and the lengths
+// of all four.  pt_refit_create keeps it; pt_move_geometry (include/pt_move.h) compares it with the same digest of a context's host copies.  Four
+// multiplicative lanes over the 32-bit words, so that the multiplies of neighbouring words overlap; the values' bit patterns, never their order.
+struct TopologyDigest {
+    uint64_t h[4] = {0xcbf29ce484222325ull, 0x9e3779b97f4a7c15ull, 0xc2b2ae3d27d4eb4full, 0x165667b19e3779f9ull};
+    size_t n = 0;
+    void word(uint32_t w) { uint64_t& x = h[n++ & 3]; x = (x ^ w) * 0x100000001b3ull; }
+    void words(const void* p, size_t count) {
+        const unsigned char* q = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < count; i++) { uint32_t w; std::memcpy(&w, q + 4 * i, 4); word(w); }
+    }
+    void length(size_t v) { n = 0; word((uint32_t)v); word((uint32_t)((uint64_t)v >> 32)); }
+    uint64_t value() const {
+        uint64_t r = 0;
+        for (int k = 0; k < 4; k++) { r = (r ^ h[k]) * 0x100000001b3ull; r ^= r >> 29; }
+        return r;
+    }
+};
+inline uint64_t topologyDigest(const int32_t* tree, size_t nTree, const int32_t* leaf, size_t nLeaf, const int32_t* roots, size_t nRoots, const float* data,
+                               size_t nData) {
+    TopologyDigest d;
+    d.length(nTree); d.words(tree, nTree);
+    d.length(nLeaf); d.words(leaf, nLeaf);
+    d.length(nRoots); d.words(roots, nRoots);
+    d.length(nData);
+    for (size_t row = 0; row + 1 <= nData / 8; row++) d.words(data + 8 * row + 6, 2);
+    return d.value();
+}
 
 inline int refitFail(std::string& err, int code, const char* msg) { err = std::string("pt_refit_create: ") + msg; return code; }
 

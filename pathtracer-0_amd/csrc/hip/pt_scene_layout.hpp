@@ -60,6 +60,72 @@ inline int toInt(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? 
 inline float4 f4(float a, float b, float c, float d) { return make_float4(a, b, c, d); }
 inline float asf(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
+// ---- the per-record expressions that depend on the coordinates of binding 3 and the boxes of binding 10: the layout below and the in-place move
+// (pt_scene_move.hpp, whose kernels in pt_move.hip evaluate the same binary32 expressions) both call them
+// floats 0-8 of a triangle record (v1, e1, e2) from the 40 floats T of a triangle: r[0], r[1] and the first float of r[2]
+inline void triRecordGeometry(const float* T, float4* r) {
+    float e1x = T[4] - T[0], e1y = T[5] - T[1], e1z = T[6] - T[2], e2x = T[8] - T[0], e2y = T[9] - T[1], e2z = T[10] - T[2];
+    r[0] = f4(T[0], T[1], T[2], e1x); r[1] = f4(e1y, e1z, e2x, e2y); r[2].x = e2z;
+}
+inline void shadeRecord(const float* T, float4* r) {
+    r[0] = f4(T[12], T[13], T[14], T[16]); r[1] = f4(T[17], T[18], T[24], T[25]);
+    r[2] = f4(T[28], T[29], T[32], asf((uint32_t)toInt(T[36]))); r[3] = f4(T[33], 0, 0, 0);
+}
+// the three box float4 of a 64-byte inner record from its children's rows A (left) and B (right) of binding 10
+inline void nodeRecordBoxes(const float* A, const float* B, float4* r) {
+    r[0] = f4(A[0], B[0], A[1], B[1]); r[1] = f4(A[2], B[2], A[3], B[3]); r[2] = f4(A[4], B[4], A[5], B[5]);
+}
+// the box floats of a record of the hand-written kernel (o: its first float, stride 80 or 64 bytes); false: a box with min > max or a NaN
+inline bool node80RecordBoxes(const float* A, const float* B, float* o, int asmStride) {
+    bool ordered = true;
+    for (int ax = 0; ax < 3; ax++) {
+        float* g = asmStride == 80 ? o + 2 + 6 * ax : o + 4 + 4 * ax;
+        g[0] = A[ax]; g[1] = B[ax]; g[2] = A[3 + ax]; g[3] = B[3 + ax];
+        if (asmStride == 80) { g[4] = A[ax]; g[5] = B[ax]; }
+        if (!(A[ax] <= A[3 + ax]) || !(B[ax] <= B[3 + ax])) ordered = false;      // min > max or a NaN: only the min/max form of rayBox is right
+    }
+    return ordered;
+}
+inline void rootRecordBox(const float* A, ObjRoot& r) { for (int k = 0; k < 3; k++) { r.bmin[k] = A[k]; r.bmax[k] = A[3 + k]; } }
+inline int cullGroupShift(int numObj) {
+    int sft = 0;
+    if (numObj > 8) while (((numObj + (1 << sft) - 1) >> sft) > 64) sft++;
+    return sft;
+}
+// The 64 group boxes of more than 8 BVHs (rootsAndCullGroups below says what they promise).  root(o): the root node's row of binding 10; rootIsLeaf(o);
+// child(o, side): the row of an inner root's child
+template <class Root, class IsLeaf, class Child>
+inline void cullGroups(int numObj, bool noRootCull, Root root, IsLeaf rootIsLeaf, Child child, std::vector<ObjRoot>& groups) {
+    const int sft = cullGroupShift(numObj);
+    const int nGroups = (numObj + (1 << sft) - 1) >> sft;
+    const float inf = std::numeric_limits<float>::infinity();
+    groups.assign(64, ObjRoot{});
+    for (int g = 0; g < 64; g++) { for (int k = 0; k < 3; k++) { groups[g].bmin[k] = inf; groups[g].bmax[k] = -inf; } groups[g].ref = 0; groups[g].pad = 0; }
+    for (int o = 0; o < numObj; o++) {
+        const float* A = root(o);
+        bool cullable = !rootIsLeaf(o) && !noRootCull;
+        for (int k = 0; k < 3 && cullable; k++) {
+            if (!(A[k] <= A[3 + k])) cullable = false;                                      // ordered, no NaN
+            for (int side = 0; side < 2 && cullable; side++) {
+                const float* Ch = child(o, side);
+                // BOTH planes of the child inside the root's range: rayBox takes min / max of the two plane distances (:412-413), so an inverted child
+                // (min > max) whose `max` lies below the root's min would stick out of the root although its `min` and `max` each pass a one-sided test (NaN: not)
+                if (!(Ch[k] >= A[k] && Ch[k] <= A[3 + k] && Ch[3 + k] >= A[k] && Ch[3 + k] <= A[3 + k])) cullable = false;
+            }
+        }
+        ObjRoot& G = groups[o >> sft];
+        if (!cullable) G.pad = 1;
+        for (int k = 0; k < 3; k++) { G.bmin[k] = std::min(G.bmin[k], A[k]); G.bmax[k] = std::max(G.bmax[k], A[3 + k]); }
+    }
+    for (int g = 0; g < nGroups; g++) if (groups[g].pad) { for (int k = 0; k < 3; k++) { groups[g].bmin[k] = -inf; groups[g].bmax[k] = inf; } }
+}
+// record i of the N ellipsoids of binding 7 (frag.glsl:606-611 layout); the material index is the caller's to check
+inline void ellipRecord(const float* E, size_t N, size_t i, EllipRec& r) {
+    std::memset(&r, 0, sizeof(r));
+    for (int k = 0; k < 3; k++) { r.c[k] = E[1 + 3 * i + k]; r.st[k] = E[1 + N * 3 + 3 * i + k]; r.rot[k] = E[1 + N * 6 + 3 * i + k]; }
+    r.r = E[1 + N * 9 + i]; r.mat = toInt(E[1 + N * 10 + i]);
+}
+
 // One run of layoutScene: the buffers, the result, and what the steps hand each other.  Each step returns 0 or fails with PT_ERR_SCENE and its text.
 struct LayoutRun {
     const SceneBuffers& b; const LayoutOptions& opt; SceneLayout& L; std::string& err;
@@ -228,9 +294,10 @@ struct LayoutRun {
                 int mat = toInt(T[36]);
                 if (mat < 0 || mat >= nMat) return fail("triangle material index out of range (SURVEY.md Q-14: OBJ faces before any o/g line get -1)");
                 if (triObj[t] == -1) triObj[t] = objOf[n]; else if (triObj[t] != objOf[n]) { triObj[t] = -2; L.ambiguousTriObj = true; }
-                float e1x = T[4] - T[0], e1y = T[5] - T[1], e1z = T[6] - T[2], e2x = T[8] - T[0], e2y = T[9] - T[1], e2z = T[10] - T[2];
                 uint32_t idl = (uint32_t)t | (i == e - 1 ? 0x80000000u : 0u);
-                triRecs.push_back(f4(T[0], T[1], T[2], e1x)); triRecs.push_back(f4(e1y, e1z, e2x, e2y)); triRecs.push_back(f4(e2z, asf(idl), 0, 0));
+                float4 rec[3]; rec[2] = f4(0, asf(idl), 0, 0);
+                triRecordGeometry(T, rec);
+                triRecs.insert(triRecs.end(), rec, rec + 3);
             }
         }
         L.nTriRecs = (int)(triRecs.size() / 3); L.nTris = (int)nTris;
@@ -241,8 +308,9 @@ struct LayoutRun {
         for (int n : order) {
             int Lc = childOf(n, 0), Rc = childOf(n, 1);
             const float* A = boxOf(Lc); const float* B = boxOf(Rc);
-            L.nodes.push_back(f4(A[0], B[0], A[1], B[1])); L.nodes.push_back(f4(A[2], B[2], A[3], B[3])); L.nodes.push_back(f4(A[4], B[4], A[5], B[5]));
-            L.nodes.push_back(f4(asf((uint32_t)refOf(Lc)), asf((uint32_t)refOf(Rc)), 0, 0));
+            float4 rec[4]; rec[3] = f4(asf((uint32_t)refOf(Lc)), asf((uint32_t)refOf(Rc)), 0, 0);
+            nodeRecordBoxes(A, B, rec);
+            L.nodes.insert(L.nodes.end(), rec, rec + 4);
         }
         // The hand-written intersect kernel (pt_extend_gfx950.s) reads its own node records.  80 B: the two references, then per axis (Lmin, Rmin | Lmax,
         // Rmax | Lmin, Rmin), so that a lane whose direction component is negative starts 8 B further in and receives (near pair, far pair) without a
@@ -259,12 +327,7 @@ struct LayoutRun {
             const int n = order[k], Lc = childOf(n, 0), Rc = childOf(n, 1);
             const float* A = boxOf(Lc); const float* B = boxOf(Rc);
             float* o = L.nodes80.data() + (size_t)W_ * k;
-            for (int ax = 0; ax < 3; ax++) {
-                float* g = asmStride == 80 ? o + 2 + 6 * ax : o + 4 + 4 * ax;
-                g[0] = A[ax]; g[1] = B[ax]; g[2] = A[3 + ax]; g[3] = B[3 + ax];
-                if (asmStride == 80) { g[4] = A[ax]; g[5] = B[ax]; }
-                if (!(A[ax] <= A[3 + ax]) || !(B[ax] <= B[3 + ax])) boxesOrdered = false;      // min > max or a NaN: only the min/max form of rayBox is right
-            }
+            if (!node80RecordBoxes(A, B, o, asmStride)) boxesOrdered = false;
             const int lr = refOf(Lc), rr = refOf(Rc);
             std::memcpy(&o[0], &lr, 4); std::memcpy(&o[1], &rr, 4);
             if (lr == REF_EMPTY || rr == REF_EMPTY) anyEmpty = true;
@@ -277,7 +340,7 @@ struct LayoutRun {
         roots.assign(std::max(numObj, 8), ObjRoot{});           // (the hand-written kernel fetches root records in batches of four: at least eight exist)
         for (int o = 0; o < numObj; o++) {
             int r = b.objidx[1 + o]; const float* A = boxOf(r);
-            for (int k = 0; k < 3; k++) { roots[o].bmin[k] = A[k]; roots[o].bmax[k] = A[3 + k]; }
+            rootRecordBox(A, roots[o]);
             roots[o].ref = refOf(r); roots[o].pad = 0;
             // an empty root leaf would be "visited" by the reference and find nothing: it can simply never be pushed
         }
@@ -288,32 +351,11 @@ struct LayoutRun {
         // (children lie inside the root box) and return (:468-472, :521-531) — PROVIDED the root is an inner node whose child boxes lie inside an ordered root box.
         // A group holding a root that does not promise this (a leaf root: its triangles are tested whatever the box says, :478-520; foreign buffers whose children
         // stick out) gets the box (-inf, +inf): never culled.  Irregular rays skip the cull in the kernel.
-        L.asmGroupShift = 0;
+        L.asmGroupShift = cullGroupShift(numObj);
         if (numObj > 8) {
-            int sft = 0;
-            while (((numObj + (1 << sft) - 1) >> sft) > 64) sft++;
-            L.asmGroupShift = sft;
-            const int nGroups = (numObj + (1 << sft) - 1) >> sft;
-            const float inf = std::numeric_limits<float>::infinity();
-            std::vector<ObjRoot> groups(64);
-            for (int g = 0; g < 64; g++) { for (int k = 0; k < 3; k++) { groups[g].bmin[k] = inf; groups[g].bmax[k] = -inf; } groups[g].ref = 0; groups[g].pad = 0; }
-            for (int o = 0; o < numObj; o++) {
-                const int r = b.objidx[1 + o]; const float* A = boxOf(r);
-                bool cullable = !isLeaf(r) && !opt.asmNoRootCull;
-                for (int k = 0; k < 3 && cullable; k++) {
-                    if (!(A[k] <= A[3 + k])) cullable = false;                                      // ordered, no NaN
-                    for (int side = 0; side < 2 && cullable; side++) {
-                        const float* Ch = boxOf(childOf(r, side));
-                        // BOTH planes of the child inside the root's range: rayBox takes min / max of the two plane distances (:412-413), so an inverted child
-                        // (min > max) whose `max` lies below the root's min would stick out of the root although its `min` and `max` each pass a one-sided test (NaN: not)
-                        if (!(Ch[k] >= A[k] && Ch[k] <= A[3 + k] && Ch[3 + k] >= A[k] && Ch[3 + k] <= A[3 + k])) cullable = false;
-                    }
-                }
-                ObjRoot& G = groups[o >> sft];
-                if (!cullable) G.pad = 1;
-                for (int k = 0; k < 3; k++) { G.bmin[k] = std::min(G.bmin[k], A[k]); G.bmax[k] = std::max(G.bmax[k], A[3 + k]); }
-            }
-            for (int g = 0; g < nGroups; g++) if (groups[g].pad) { for (int k = 0; k < 3; k++) { groups[g].bmin[k] = -inf; groups[g].bmax[k] = inf; } }
+            std::vector<ObjRoot> groups;
+            cullGroups(numObj, opt.asmNoRootCull, [&](int o) { return boxOf(b.objidx[1 + o]); }, [&](int o) { return isLeaf(b.objidx[1 + o]); },
+                       [&](int o, int side) { return boxOf(childOf(b.objidx[1 + o], side)); }, groups);
             roots.insert(roots.end(), groups.begin(), groups.end());          // at roots[numObj .. numObj + 64)
         }
     }
@@ -322,9 +364,7 @@ struct LayoutRun {
         std::vector<float4>& shade = L.shade;
         shade.assign(std::max<size_t>(nTris, 1) * 4, float4{});
         for (size_t t = 0; t < nTris; t++) {
-            const float* T = b.tris.data() + 40 * t;
-            shade[4 * t] = f4(T[12], T[13], T[14], T[16]); shade[4 * t + 1] = f4(T[17], T[18], T[24], T[25]);
-            shade[4 * t + 2] = f4(T[28], T[29], T[32], asf((uint32_t)toInt(T[36]))); shade[4 * t + 3] = f4(T[33], 0, 0, 0);
+            shadeRecord(b.tris.data() + 40 * t, &shade[4 * t]);
         }
     }
 
@@ -335,10 +375,8 @@ struct LayoutRun {
         L.ellip.resize(std::max(nE, 1));
         const size_t N = (size_t)nE;
         for (size_t i = 0; i < N; i++) {
-            const float* E = b.ellip.data();
-            EllipRec& r = L.ellip[i]; std::memset(&r, 0, sizeof(r));
-            for (int k = 0; k < 3; k++) { r.c[k] = E[1 + 3 * i + k]; r.st[k] = E[1 + N * 3 + 3 * i + k]; r.rot[k] = E[1 + N * 6 + 3 * i + k]; }
-            r.r = E[1 + N * 9 + i]; r.mat = toInt(E[1 + N * 10 + i]);
+            EllipRec& r = L.ellip[i];
+            ellipRecord(b.ellip.data(), N, i, r);
             if (r.mat < 0 || r.mat >= nMat) return fail("ellipsoid material index out of range");
             if (L.mats[r.mat].hasMaps) L.ellipMaps = true;           // sampled at the uv of the closest triangle found before the ellipsoid (frag.glsl:574 vs :619-630): State::HX
         }
@@ -393,10 +431,8 @@ struct LayoutRun {
 };
 
 // Validates the reference's buffers and builds the device-private layout (see pt_device.hpp).  0, or PT_ERR_SCENE with the reason in err; out is
-// meaningful only after 0.
-inline int layoutScene(const SceneBuffers& in, const LayoutOptions& opt, SceneLayout& out, std::string& err) {
-    out = SceneLayout{};
-    LayoutRun r(in, opt, out, err);
+// meaningful only after 0.  runLayout: the steps on a run the caller keeps (pt_scene_move.hpp reads the order it decided)
+inline int runLayout(LayoutRun& r) {
     int rc;
     if ((rc = r.presence()) || (rc = r.materials()) || (rc = r.treeOrder()) || (rc = r.triangleRecords())) return rc;
     r.nodeRecords();
@@ -406,6 +442,11 @@ inline int layoutScene(const SceneBuffers& in, const LayoutOptions& opt, SceneLa
     r.textures();
     r.modes();
     return 0;
+}
+inline int layoutScene(const SceneBuffers& in, const LayoutOptions& opt, SceneLayout& out, std::string& err) {
+    out = SceneLayout{};
+    LayoutRun r(in, opt, out, err);
+    return runLayout(r);
 }
 
 }  // namespace ptl

@@ -21,6 +21,10 @@ OPTIONS = {"path_slots": 0, "count_stats": 1, "lds_budget": 2, "none_min": 3, "e
            "refill_min": 7, "extend_blocks_per_cu": 8, "inner_keep_eighths": 9, "bfs_nodes": 10, "stack_mode": 11,
            "query_asm_eligible": 12, "query_asm_launches_above": 13, "asm_loop": 14, "numeric_contract": 16, "asm_tpb": 17, "index_stack_8bit": 18, "asm_node_layout": 19, "asm_root_cull": 20, "cu_partition": 21}
 
+# the device record arrays pt_debug_scene_records reads back (include/pt_debug.h), with the element type each comes back as
+SCENE_RECORDS = {"nodes": (0, np.float32), "nodes80": (1, np.float32), "tris": (2, np.float32), "shade": (3, np.float32), "roots": (4, np.float32),
+                 "ellip": (5, np.float32), "triObj": (6, np.int32)}
+
 # the albedo_floor to pass for the demodulated calls of include/pt_demod.h (albedo_floor=ALBEDO_FLOOR; the keyword's own default None makes the
 # plain call): scripts/demod_quality.py's grid on T1, C3 and C6 (profiles/r13_demod_quality.txt)
 ALBEDO_FLOOR = 0.2
@@ -177,6 +181,9 @@ def lib():
             L.pt_refit_run.argtypes = [vp, vp, sz, vp, vp]
             L.pt_refit_destroy.argtypes = [vp]
             L.pt_refit_destroy.restype = None
+        if hasattr(L, "pt_move_geometry"):                    # include/pt_move.h, and its read-back in include/pt_debug.h
+            L.pt_move_geometry.argtypes = [vp, vp, vp, sz, vp, sz, vp, C.POINTER(ci)]
+            L.pt_debug_scene_records.argtypes = [vp, ci, vp, sz, C.POINTER(sz)]
         _LIB = L
     return _LIB
 
@@ -519,6 +526,33 @@ class Renderer:
         self.set_buffer(3, np.ascontiguousarray(tris, dtype=np.float32))
         self.set_buffer(10, data)
         return data, cost
+
+    # --- triangles moved in place (include/pt_move.h) ------------------------------------------------
+    def move_geometry(self, plan, tris, ellip=None):
+        """move_triangles (and set_buffer(7, ellip) when `ellip` is given) with the context's device records patched in place
+        (pt_move_geometry): the refit runs, and what of the built scene depends on the triangles' coordinates and the trees' boxes is rewritten on
+        the device from the plan's copies, so the next render neither lays the scene out again nor uploads its record arrays.  The context ends
+        in the state move_triangles and the next render's scene build would leave it in.  Returns (root_cost, in_place): in_place is False when
+        the call had to build the scene after all (a multi-stream context, foreign unordered boxes, a binding 7 that changes a count or a
+        material)."""
+        if not hasattr(self._L, "pt_move_geometry"):
+            raise RuntimeError("this libpt_hip.so has no pt_move_geometry (include/pt_move.h): no fallback")
+        t = np.ascontiguousarray(tris, dtype=np.float32)
+        e = None if ellip is None else np.ascontiguousarray(ellip, dtype=np.float32)
+        cost = np.zeros(plan.n_roots, np.float64)
+        in_place = C.c_int(-1)
+        _check(self._L.pt_move_geometry(self._h, plan._h, t.ctypes.data, t.nbytes, None if e is None else e.ctypes.data, 0 if e is None else e.nbytes,
+                                        cost.ctypes.data, C.byref(in_place)))
+        return cost, bool(in_place.value)
+
+    def debug_scene_records(self, which):
+        """One device record array of the built scene as it lies on the device (pt_debug_scene_records): `which` is a key of SCENE_RECORDS."""
+        idx, dtype = SCENE_RECORDS[which]
+        n = C.c_size_t()
+        _check(self._L.pt_debug_scene_records(self._h, idx, None, 0, C.byref(n)))
+        out = np.empty(n.value // 4, dtype)
+        _check(self._L.pt_debug_scene_records(self._h, idx, out.ctypes.data, out.nbytes, C.byref(n)))
+        return out
 
     # --- reprojection across moved geometry with bilinear taps (include/pt_motion_bilinear.h) ------
     def reproject_frame_moved_bilinear(self, max_history=64, depth_tol=0.02, normal_tol=0.9, snap=1 / 64, all_materials=False, albedo_floor=0.0):
