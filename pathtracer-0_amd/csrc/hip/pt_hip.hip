@@ -125,6 +125,7 @@ struct State {              // SoA path pool, float4 groups (see header comment)
     unsigned s0Plane;       // STK == 32 (the index stack as ten floats): S0 holds three planes of this many slots — stack slots 0-3, 4-7, 8-9
     uint2* J;               // (frame slot of the stream, accumulator slot) of the slot's job: written when the job starts, read when it ends
     float4* HX;             // (u, v, id) of the closest triangle behind an ellipsoid hit; only for scenes whose ellipsoids carry texture-mapped materials
+    const float4* Z;        // 64 zero bytes, zeroed when the context allocates them and never written again: what a lane of k_shade reads in place of a group it does not need
 };
 
 // The frame stream: consecutive batches with the same frame inputs (Parameters, ORIGIN, ROTATION, MOUSE_POS) form ONE job
@@ -214,12 +215,13 @@ __device__ __forceinline__ void startJob(const Batch& b, const FrameConst& fc, u
     unsigned fi = b.divM ? (__umulhi(job, b.divM) >> b.divS) : job;      // job / nLocal without an integer division
     unsigned k = job - fi * (unsigned)b.nLocal;
     unsigned xy = b.pixXY[k];
+    const int seed = b.seeds[fi % b.ringFrames];                         // (both words of the job are asked for before either is used: one round trip)
     int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
     uint32_t index;
     pixelIndex(fc, b.W, b.H, px, py, index);
     p.pix = xy; p.fi = fi;
     p.ls = (b.shardCount == 1) ? (unsigned)(py * b.W + px) : k;
-    p.rng = index + (uint32_t)b.seeds[fi % b.ringFrames];
+    p.rng = index + (uint32_t)seed;
     p.sum = v3(0.0f);
     p.sample = 0;
     p.applyAbs = false; p.inObj = false;
@@ -595,8 +597,8 @@ __global__ void __launch_bounds__(SHADE_BLOCK, (TEX && !STATS && STK != 32) ? 5 
     const unsigned jobEnd = ctl->jobEnd;
     if (writeQueue && blockIdx.x == 0 && threadIdx.x == 0) ctl->exhausted[(iter + 1) & 3] = 1u;     // sticky, also through an empty launch
     if (blockIdx.x * SHADE_BLOCK >= n) return;                           // the grid is sized by the host's last known bound
-    // ---- 1. the slot and its state: every load of the segment is issued here, in one batch — the kernel's critical path is
-    // memory round trips, not bytes.  Only the groups few lanes need wait for the flags: incLight (G3) and the medium-entry group (G5).
+    // ---- 1. the slot and its state, in two round trips — the kernel's critical path is memory round trips, not bytes: (G2 G1 G0 H, the index stack),
+    // then, once the flags and the hit record have said what the segment ends, (G3 G5 G4 J), which is still in flight under the job pull's barrier.
     const unsigned q = blockIdx.x * SHADE_BLOCK + threadIdx.x;
     const bool valid = q < n;
     const unsigned i = valid ? (queue ? queue[q] : q) : 0u;
@@ -605,8 +607,17 @@ __global__ void __launch_bounds__(SHADE_BLOCK, (TEX && !STATS && STK != 32) ? 5 
     // the sum over the job's samples (G4, 16 B) and the job words (J) are then fetched by the lanes whose sample / job ends only — a segment in four — and the job
     // pull runs while those loads and the shading records are on their way.  directDiffuse learns it from the material (a subsurface hit goes on as a probe): old order.
     constexpr bool EARLY = !DIRECT;
+    // ONE_TRIP: the groups that only some lanes need — incLight (G3) while FL_INCNZ, the medium-entry group (G5), the sum (G4) at a sample's end, the job
+    // words (J) at a job's end — are loaded by EVERY live lane in one batch, without a branch: a lane that does not need a group reads the context's
+    // zero block (st.Z) in its place.  A load under `if (flag)` meets the register's initial value in a phi at the end of the `if`, and the compiler
+    // waits for the load there: four flags were four round trips in a row, before the job pull's barrier, for every wave with one such lane (nearly
+    // all).  With the address selected instead there is nothing to merge, and the wait moves to the first use: G3 and G5 rely on the block's zeros
+    // (their initial value), G4 and J are used and stored under sampleDone / jobDone only.  The instantiations held to 96 registers by the launch
+    // bounds (texture maps) have none to spare for four loads in flight — they spill — and keep the predicated loads.
+    constexpr bool ONE_TRIP = EARLY && !(TEX && !STATS && STK != 32);
     if (valid) {
-        g1 = ldS(st.G1 + i); g0 = ldS(st.G0 + i); h = ldS(st.H + i); g2 = ldS(st.G2 + i);
+        // (G2 first: in the order G1 G0 H G2 the compiler issues G2 behind the wait for G1 — the flags' copy out of the `if` — a round trip later)
+        g2 = ldS(st.G2 + i); g1 = ldS(st.G1 + i); g0 = ldS(st.G0 + i); h = ldS(st.H + i);
         if (!EARLY) g4 = ldS(st.G4 + i);
         if (STK == 8 || STK == 32) s0 = ldS(st.S0 + i);
         if (STK == 32) { s1 = ldS(st.S0 + st.s0Plane + i); s2 = ldS(st.S0 + 2 * (size_t)st.s0Plane + i); }
@@ -627,25 +638,32 @@ __global__ void __launch_bounds__(SHADE_BLOCK, (TEX && !STATS && STK != 32) ? 5 
         // incLight of the running sample: +0.0 in every component unless the path has met an emitter and gone on (FL_INCNZ): only those lanes fetch it.
         // (directDiffuse parks its probe state in the group: that mode reads and writes it for every lane.)
         incInMemory = DIRECT || p.incNZ;
-        if (!DIRECT && p.incNZ) g3 = ldS(st.G3 + i);
+        if (!ONE_TRIP && !DIRECT && p.incNZ) g3 = ldS(st.G3 + i);
         if (TRANS) {
             // RAY_ENTER_LOCATION / DISTANCE_TRAVELED are read only while the path is inside a medium or owes an absorption term;
-            // a transmission event on any other path fetches them late (shadeSegment), which is rare
-            p.g5loaded = p.inObj || p.applyAbs;
-            if (p.g5loaded) g5 = ldS(st.G5 + i);
+            // a transmission event on any other path fetches them late (shadeSegment), which is rare per lane but a round trip for its wave:
+            // where the load rides in the batch below it costs none, and every live lane fetches them
+            p.g5loaded = ONE_TRIP || p.inObj || p.applyAbs;
+            if (!ONE_TRIP && p.g5loaded) g5 = ldS(st.G5 + i);
         }
         p.O = v3(g0.x, g0.y, g0.z); p.D = v3(g0.w, g1.x, g1.y); p.rng = __float_as_uint(g1.z);
         p.col = v3(g2.x, g2.y, g2.z);
         if (EARLY) {
             sampleDone = segmentEndsSample<FAST>(fc, p, h.x, __float_as_int(h.w));
             if (sampleDone) {
-                g4 = ldS(st.G4 + i);
+                if (!ONE_TRIP) g4 = ldS(st.G4 + i);
                 nSamp = 1;
                 if ((float)(p.sample + 1) < fc.SAMPLE_RES) needStart = true;      // loop condition :898
-                else { jobDone = true; jobWords = st.J[i]; }
+                else { jobDone = true; if (!ONE_TRIP) jobWords = st.J[i]; }
+            }
+            if (ONE_TRIP) {
+                g3 = ldS(p.incNZ ? st.G3 + i : st.Z);
+                if (TRANS) g5 = ldS(st.G5 + i);
+                g4 = ldS(sampleDone ? st.G4 + i : st.Z);
+                jobWords = *(jobDone ? st.J + i : reinterpret_cast<const uint2*>(st.Z));
             }
         }
-        p.inc = incInMemory ? v3(g3.x, g3.y, g3.z) : v3(0.0f);
+        p.inc = (ONE_TRIP || incInMemory) ? v3(g3.x, g3.y, g3.z) : v3(0.0f);      // (ONE_TRIP: the zero block's +0.0)
         p.sum = v3(g4.x, g4.y, g4.z); p.pix = __float_as_uint(g4.w);      // (path tracing: of the lanes whose sample ends; the others neither read nor write them)
         p.fi = 0u; p.ls = 0u;                                       // the job's (frame slot, accumulator slot) wait in J until the job ends
         p.enter = v3(g5.x, g5.y, g5.z); p.dist = g5.w; p.g5dirty = false;
@@ -1255,6 +1273,7 @@ struct pt_ctx {
     int allocSlots = 0; int allocNiBits = -1; bool allocHX = false;
     State st{};                     // the pool as the kernels take it; its groups are owned by dPool (in the order of ensurePool) and dPoolJ
     Dev<float4> dPool[9]; Dev<uint2> dPoolJ;
+    Dev<float4> dZero;              // st.Z: zeroed when allocated (ensurePool), then read only; it outlives every pool
     Dev<unsigned> dQueue[2];        // dense slot queues of the batch tail, by iteration parity
     Dev<float4> dColbuf; Dev<int> dSeeds; int ringFrames = 0;      // per-frame rings of the stream (Batch)
     // frame-stream scheduler: its host view (pt_stream_sched.hpp), and what the device side of it needs
@@ -1386,6 +1405,12 @@ int ensurePool(pt_ctx* c, int capacity) {               // capacity >= poolActiv
     }
     HIP_TRY(c->dPoolJ.reset(n * 8));
     c->st.J = c->dPoolJ;
+    if (!c->dZero) {
+        HIP_TRY(c->dZero.reset(64));
+        HIP_TRY(hipMemsetAsync(c->dZero, 0, 64, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));                 // the shading launches run on other streams as well
+    }
+    c->st.Z = c->dZero;
     for (auto& q : c->dQueue) HIP_TRY(q.reset(n * 4));
     c->allocSlots = capacity; c->allocNiBits = c->niBits; c->allocHX = c->built.ellipMaps; c->st.s0Plane = (unsigned)capacity;
     return 0;
