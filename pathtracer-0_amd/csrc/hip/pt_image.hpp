@@ -778,3 +778,6 @@ int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* ru
 
 // the in-place move of a scene's triangles (include/pt_move.h) and the read-back of the scene's record arrays
 #include "pt_move_host.hpp"
+
+// the outlier rejection (include/pt_despeckle.h): both calls on historyMerge's path
+#include "pt_despeckle_host.hpp"

@@ -79,3 +79,17 @@ struct ValidateJob {
     float4* outFrame = nullptr; float4* outStats = nullptr; float* kappa = nullptr; unsigned* reduced = nullptr;
 };
 hipError_t validateLaunch(const ValidateJob& j, hipStream_t s);
+
+// ---- the outlier rejection of include/pt_despeckle.h (pt_despeckle.hip)
+struct DespeckleJob {
+    // feat: W*H*4 float4 feature records under the current inputs; frame, stats: FRAME and T in pixel order (stats may be null: step 5 is off then),
+    // W*H float4, read only
+    const float4* feat = nullptr; const float4* frame = nullptr; const float4* stats = nullptr;
+    int W = 0, H = 0, radius = 0, minTaps = 0;                    // radius: 1 .. 3 (checked by the caller)
+    float sigmas = 0.0f, ownZ = 0.0f, normalTol = 0.0f, minLum = 0.0f;
+    float overlay[3] = {0.0f, 0.0f, 0.0f};                        // (mouse x, mouse y, resolution) of the overlay test
+    bool mean = false;                                            // outFrame takes (the rule applied to the mean, FRAME.a) in place of FRAME'
+    // outFrame: W*H float4; outStats: T', W*H float4, or null (needs stats); scale: W*H floats, or null; *clamped (zeroed first): the pixels clamped
+    float4* outFrame = nullptr; float4* outStats = nullptr; float* scale = nullptr; unsigned* clamped = nullptr;
+};
+hipError_t despeckleLaunch(const DespeckleJob& j, hipStream_t s);
