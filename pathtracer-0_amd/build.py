@@ -22,7 +22,11 @@
                  the CPU statement of the patch, tests/c/scene_move_check.cpp) and its host half csrc/hip/pt_move_host.hpp (included by pt_image.hpp).
                  The outlier rejection (include/pt_despeckle.h) is csrc/hip/pt_despeckle.hip, an image-space kernel file like pt_reproject.hip, behind
                  csrc/hip/pt_image_launch.hpp; its host-only argument check csrc/hip/pt_despeckle_rule.hpp (tests/c/despeckle_rule_check.cpp) and its
-                 host half csrc/hip/pt_despeckle_host.hpp (included by pt_image.hpp)
+                 host half csrc/hip/pt_despeckle_host.hpp (included by pt_image.hpp).
+                 The display image (include/pt_tonemap.h: metered exposure, tone curve, sRGB transfer) is csrc/hip/pt_tonemap.hip, an image-space
+                 kernel file as well, behind csrc/hip/pt_image_launch.hpp; its host-only step csrc/hip/pt_tonemap_rule.hpp (the argument check, the
+                 metered exposure and the sRGB threshold table that scripts/tonemap_srgb_table.py generates; tests/c/tonemap_rule_check.cpp) and
+                 its host half csrc/hip/pt_tonemap_host.hpp (included by pt_image.hpp)
 """
 import os
 import subprocess
@@ -83,12 +87,12 @@ def assemble_extend(out_inc=None, defines=()):
 
 def build_hip(force=False, extra=(), asm_defines=()):
     d = os.path.join(HERE, "csrc", "hip")
-    srcs = [os.path.join(d, f) for f in ("pt_hip.hip", "pt_bvh.hip", "pt_denoise.hip", "pt_reproject.hip", "pt_guided.hip", "pt_refit.hip", "pt_move.hip", "pt_despeckle.hip", "pt_device.hpp", "pt_math.hpp", "pt_multi.hpp", "pt_image.hpp", "pt_image_launch.hpp", "pt_devmem.hpp", "pt_scene_records.hpp", "pt_scene_layout.hpp", "pt_options.hpp", "pt_launch_plan.hpp", "pt_stream_sched.hpp", "pt_image_history.hpp", "pt_image_args.hpp", "pt_motion_pack.hpp", "pt_refit_plan.hpp", "pt_refit_state.hpp", "pt_scene_move.hpp", "pt_move_host.hpp", "pt_move_launch.hpp", "pt_despeckle_rule.hpp", "pt_despeckle_host.hpp", "pt_extend_gfx950.s")] + [os.path.join(HERE, "..", "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_adaptive.h", "pt_denoise.h", "pt_reproject.h", "pt_guided.h", "pt_steer.h", "pt_demod.h", "pt_fill.h", "pt_through.h", "pt_motion.h", "pt_validate.h", "pt_reproject_through.h", "pt_reproject_bilinear.h", "pt_motion_bilinear.h", "pt_refit.h", "pt_move.h", "pt_despeckle.h")]
+    srcs = [os.path.join(d, f) for f in ("pt_hip.hip", "pt_bvh.hip", "pt_denoise.hip", "pt_reproject.hip", "pt_guided.hip", "pt_refit.hip", "pt_move.hip", "pt_despeckle.hip", "pt_tonemap.hip", "pt_device.hpp", "pt_math.hpp", "pt_multi.hpp", "pt_image.hpp", "pt_image_launch.hpp", "pt_devmem.hpp", "pt_scene_records.hpp", "pt_scene_layout.hpp", "pt_options.hpp", "pt_launch_plan.hpp", "pt_stream_sched.hpp", "pt_image_history.hpp", "pt_image_args.hpp", "pt_motion_pack.hpp", "pt_refit_plan.hpp", "pt_refit_state.hpp", "pt_scene_move.hpp", "pt_move_host.hpp", "pt_move_launch.hpp", "pt_despeckle_rule.hpp", "pt_despeckle_host.hpp", "pt_tonemap_rule.hpp", "pt_tonemap_host.hpp", "pt_extend_gfx950.s")] + [os.path.join(HERE, "..", "include", h) for h in ("pt_api.h", "pt_debug.h", "pt_adaptive.h", "pt_denoise.h", "pt_reproject.h", "pt_guided.h", "pt_steer.h", "pt_demod.h", "pt_fill.h", "pt_through.h", "pt_motion.h", "pt_validate.h", "pt_reproject_through.h", "pt_reproject_bilinear.h", "pt_motion_bilinear.h", "pt_refit.h", "pt_move.h", "pt_despeckle.h", "pt_tonemap.h")]
     out = os.path.join(HERE, "libpt_hip.so")
     if force or _stale(out, srcs):
         assemble_extend(defines=asm_defines)
         hipcc = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"
-        subprocess.check_call([hipcc] + HIP_FLAGS + list(extra) + ["-o", out] + srcs[:8])
+        subprocess.check_call([hipcc] + HIP_FLAGS + list(extra) + ["-o", out] + srcs[:9])
     return out
 
 
@@ -97,7 +101,7 @@ def kernel_source_hash():
     and bench.py flags them stale when the kernels have changed underneath.  (pt_multi.hpp — host-side orchestration of several streams —, pt_image.hpp and
     pt_image_launch.hpp — the host half and the launch interface of the image-space passes —, pt_scene_layout.hpp — the host-only layout step of the
     scene build; the records it fills, which the kernels read, are pt_scene_records.hpp and part of it —, pt_launch_plan.hpp — the host-only planning
-    of the intersect launches —, pt_stream_sched.hpp and pt_image_history.hpp — the host-only scheduler and image bookkeeping —, pt_options.hpp — the option table —, pt_image_args.hpp and pt_motion_pack.hpp — the argument table of the image-space calls and the motion packing —, pt_despeckle.hip with pt_despeckle_rule.hpp and pt_despeckle_host.hpp — an image-space pass, as pt_reproject.hip is — and pt_bvh.hip, pt_refit.hip with pt_refit_plan.hpp and pt_refit_state.hpp, and pt_move.hip with pt_scene_move.hpp, pt_move_host.hpp and
+    of the intersect launches —, pt_stream_sched.hpp and pt_image_history.hpp — the host-only scheduler and image bookkeeping —, pt_options.hpp — the option table —, pt_image_args.hpp and pt_motion_pack.hpp — the argument table of the image-space calls and the motion packing —, pt_despeckle.hip with pt_despeckle_rule.hpp and pt_despeckle_host.hpp, and pt_tonemap.hip with pt_tonemap_rule.hpp and pt_tonemap_host.hpp — image-space passes, as pt_reproject.hip is — and pt_bvh.hip, pt_refit.hip with pt_refit_plan.hpp and pt_refit_state.hpp, and pt_move.hip with pt_scene_move.hpp, pt_move_host.hpp and
     pt_move_launch.hpp — the scene-build kernels — are not part of it.)"""
     import hashlib
     d = os.path.join(HERE, "csrc", "hip")

@@ -781,3 +781,6 @@ int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* ru
 
 // the outlier rejection (include/pt_despeckle.h): both calls on historyMerge's path
 #include "pt_despeckle_host.hpp"
+
+// the display image (include/pt_tonemap.h): metered exposure, tone curve and sRGB transfer on pt_read_display_mean's path
+#include "pt_tonemap_host.hpp"

@@ -93,3 +93,17 @@ struct DespeckleJob {
     float4* outFrame = nullptr; float4* outStats = nullptr; float* scale = nullptr; unsigned* clamped = nullptr;
 };
 hipError_t despeckleLaunch(const DespeckleJob& j, hipStream_t s);
+
+// ---- the display image of include/pt_tonemap.h (pt_tonemap.hip)
+struct TonemapJob {
+    // image: W*H float4 in pixel order, read only.  perPixel: it is FRAME (rgb a running sum, divided by the pixel's own count a); else rgb is a
+    // mean already and a carries FRAME.a
+    const float4* image = nullptr; bool perPixel = false;
+    int W = 0, H = 0;
+    // either or both of: hist[PT_TONEMAP_BINS] (zeroed first): steps 1-2;  bytes[W*H*3], top row first: steps 4-5 under the values below
+    unsigned* hist = nullptr;
+    unsigned char* bytes = nullptr;
+    float exposure = 1.0f, white = 1.0f;
+    int curve = 0, transfer = 0;                                  // 0 .. 2 and 0 .. 1 (checked by the caller)
+};
+hipError_t tonemapLaunch(const TonemapJob& j, hipStream_t s);

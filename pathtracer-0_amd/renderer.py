@@ -173,6 +173,10 @@ def lib():
         if hasattr(L, "pt_despeckle"):                        # include/pt_despeckle.h
             L.pt_despeckle.argtypes = [vp, C.POINTER(DespeckleRule), vp, vp, C.POINTER(C.c_int64)]
             L.pt_despeckle_frame.argtypes = [vp, C.POINTER(DespeckleRule), vp, C.POINTER(C.c_int64)]
+        if hasattr(L, "pt_tonemap"):                          # include/pt_tonemap.h
+            L.pt_tonemap.argtypes = [vp, C.POINTER(TonemapRule), vp, C.c_float, vp, C.POINTER(C.c_float), vp]
+            L.pt_tonemap_save_png.argtypes = [vp, C.POINTER(TonemapRule), vp, C.c_float, C.c_char_p, C.POINTER(C.c_float)]
+            L.pt_tonemap_srgb_thresholds.argtypes = [vp]
         if hasattr(L, "pt_reproject_frame_through"):          # include/pt_reproject_through.h
             L.pt_reproject_frame_through.argtypes = [vp, C.POINTER(ThroughRule), C.POINTER(ReprojectThroughRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         if hasattr(L, "pt_reproject_frame_bilinear"):         # include/pt_reproject_bilinear.h
@@ -210,6 +214,22 @@ class ValidateRule(C.Structure):
 class DespeckleRule(C.Structure):
     """pt_despeckle_rule of include/pt_despeckle.h"""
     _fields_ = [("radius", C.c_int), ("sigmas", C.c_float), ("min_taps", C.c_int), ("own_z", C.c_float), ("normal_tol", C.c_float), ("min_lum", C.c_float)]
+
+
+class TonemapRule(C.Structure):
+    """pt_tonemap_rule of include/pt_tonemap.h"""
+    _fields_ = [("curve", C.c_int), ("transfer", C.c_int), ("exposure", C.c_float), ("key", C.c_float), ("lo_pct", C.c_float), ("hi_pct", C.c_float),
+                ("min_exposure", C.c_float), ("max_exposure", C.c_float), ("white", C.c_float), ("adapt", C.c_float)]
+
+
+TONEMAP_BINS = 512      # PT_TONEMAP_BINS
+
+
+def tonemap_srgb_thresholds():
+    """T of include/pt_tonemap.h's step 5 (pt_tonemap_srgb_thresholds): 256 float32; needs no device"""
+    out = np.zeros(256, dtype=np.float32)
+    _check(lib().pt_tonemap_srgb_thresholds(out.ctypes.data))
+    return out
 
 
 class ReprojectThroughRule(C.Structure):
@@ -641,6 +661,50 @@ class Renderer:
         scale = np.zeros((self.H, self.W), dtype=np.float32) if want_scale else None
         _check(self._L.pt_despeckle_frame(self._h, C.byref(rule), scale.ctypes.data if want_scale else None, C.byref(n)))
         return (n.value, scale) if want_scale else n.value
+
+    # --- the display image: metered exposure, tone curve, sRGB transfer (include/pt_tonemap.h) -------
+    # defaults of tonemap_rule: PROVISIONAL — common choices (the ACES fit, sRGB, a key of 0.18, the 10 % .. 95 % ranks metered), not tuned on this
+    # project's workloads
+    TONEMAP_DEFAULTS = dict(curve=2, transfer=1, exposure=0.0, key=0.18, lo_pct=0.10, hi_pct=0.95, min_exposure=2.0 ** -10, max_exposure=2.0 ** 10,
+                            white=4.0, adapt=1.0)
+
+    def tonemap_rule(self, **kw):
+        """the pt_tonemap_rule of these fields; a field not given takes TONEMAP_DEFAULTS'"""
+        unknown = set(kw) - set(self.TONEMAP_DEFAULTS)
+        assert not unknown, f"no such field of pt_tonemap_rule: {sorted(unknown)}"
+        v = dict(self.TONEMAP_DEFAULTS, **kw)
+        return TonemapRule(int(v["curve"]), int(v["transfer"]), float(v["exposure"]), float(v["key"]), float(v["lo_pct"]), float(v["hi_pct"]),
+                           float(v["min_exposure"]), float(v["max_exposure"]), float(v["white"]), float(v["adapt"]))
+
+    def _tonemap_image(self, image):
+        if image is None:
+            return None
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        assert image.size == self.W * self.H * 4, "an (H, W, 4) float32 image in FRAME order: rgb a mean, a = FRAME.a"
+        return image
+
+    def tonemap(self, image=None, prev_exposure=0.0, rule=None, want_hist=False):
+        """The display image (pt_tonemap) of the current FRAME, or of `image` — (H, W, 4) float32 in FRAME order, rgb a mean and a = FRAME.a:
+        what denoise*, denoise_guided*, despeckle and fill_frame return.  Exposed (metered from the luminance histogram, damped towards
+        prev_exposure by rule.adapt, or rule.exposure), tone-mapped and encoded.  Read only.  Returns ((H, W, 3) uint8, top row first, the
+        exposure applied — feed it back as prev_exposure of the next step), and with want_hist the histogram (512 uint32) behind them."""
+        rule = self.tonemap_rule() if rule is None else rule
+        image = self._tonemap_image(image)
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        e = C.c_float(0.0)
+        hist = np.zeros(TONEMAP_BINS, dtype=np.uint32) if want_hist else None
+        _check(self._L.pt_tonemap(self._h, C.byref(rule), None if image is None else image.ctypes.data, float(prev_exposure), out.ctypes.data,
+                                  C.byref(e), hist.ctypes.data if want_hist else None))
+        return (out, e.value, hist) if want_hist else (out, e.value)
+
+    def tonemap_png(self, path, image=None, prev_exposure=0.0, rule=None):
+        """tonemap's image written as an 8-bit RGB PNG (pt_tonemap_save_png); returns the exposure applied"""
+        rule = self.tonemap_rule() if rule is None else rule
+        image = self._tonemap_image(image)
+        e = C.c_float(0.0)
+        _check(self._L.pt_tonemap_save_png(self._h, C.byref(rule), None if image is None else image.ctypes.data, float(prev_exposure),
+                                           os.fsencode(path), C.byref(e)))
+        return e.value
 
     # --- luminance moments and the variance-guided filter (include/pt_guided.h) ---------------------
     # defaults of denoise_guided / read_display_denoised_guided: sigma_lum and min_frames from scripts/guided_quality.py's grid on C3 and C6
