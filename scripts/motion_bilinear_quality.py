@@ -128,8 +128,8 @@ def main():
     wl0, wl1 = pt.scenes.m1_moving(0, W, H), pt.scenes.m1_moving(STEP, W, H)
     fr, T = image()
     if a.probe:
-        # each kernel five times per floor: the moved call (k_reproject<true, .>), the bilinear call under a moved camera in the moved scene
-        # (k_reproject_bilinear<.>) and the moved bilinear call (k_reproject_moved_bilinear<.>), all on the same image
+        # each kernel five times per floor: the moved call (k_reproject<true, ., false>), the bilinear call under a moved camera in the moved scene
+        # (k_reproject<false, ., true>) and the moved bilinear call (k_reproject<true, ., true>), all on the same image
         r = renderer.Renderer(W, H)
         r.load_workload(wl0)
         for i in range(5):
