@@ -1,5 +1,5 @@
 // pt_device.hpp — device-side data layout and the per-lane building blocks of the wavefront
-// path tracer (gfx950).  The kernels that schedule them live in pt_hip.hip.
+// path tracer (gfx950).  The kernels that schedule them live in pt_kernels.hpp.
 //
 // Reference semantics restated here (all citations into /root/reference/src/shaders/frag.glsl):
 //   rayBox :408-419, rayTri :351-372, rayEllipsoid :373-384, rayBVH :452-537, rayScene :548-653,
@@ -287,7 +287,7 @@ PM_DEV uint32_t skipSixDraws(uint32_t state) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Path state of one lane (registers); stored SoA in groups of float4 (see pt_hip.hip)
+// Path state of one lane (registers); stored SoA in groups of float4 (see pt_kernels.hpp)
 // ------------------------------------------------------------------------------------------------
 // flags word of a path slot (G1.w): bits 0-11 bounce, 12-22 sample (the loop counters of frag.glsl:820 / :898; their bounds are
 // floats in the shader, here up to 4095 / 2047), 23 FL_INCNZ, 24-27 size of the refraction-index stack (0..10), then the booleans

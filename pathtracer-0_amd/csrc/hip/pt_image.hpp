@@ -1,7 +1,7 @@
 // pt_image.hpp — the host half of the image-space passes behind the C ABI (included by pt_hip.hip inside its extern "C" block, where pt_ctx and
 // its helpers are in scope; not a translation unit).  T in pixel order, the feature and seen-through records, the a-trous and the variance-guided
 // filter, the reprojection across camera moves (also through mirror and glass chains, and with bilinear taps) and moved geometry (also with bilinear taps), the history validation, steering and the prefill.  The kernels are pt_denoise.hip's, pt_guided.hip's
-// and pt_reproject.hip's, behind pt_image_launch.hpp; the kernels of the records are pt_hip.hip's.
+// and pt_reproject.hip's, behind pt_image_launch.hpp; the kernels of the records are pt_kernels.hpp's.
 
 // ---- T in pixel order (include/pt_adaptive.h, include/pt_guided.h): a group's streams each hold the slots of their own shard, so T travels through the host
 namespace {

@@ -1,6 +1,6 @@
 // pt_image_history.hpp — what the current image is a picture of: the camera record of every ring image, the generations of the scene, the validity
 // of the mark (include/pt_motion.h) and of the hold (include/pt_validate.h), the keys of the four feature-record caches, and whose frame constants
-// are on the device.  Plain C++: no HIP runtime call and no context.  pt_hip.hip and pt_image.hpp keep the device buffers these words describe and
+// are on the device.  Plain C++: no HIP runtime call and no context.  pt_context.hpp, pt_stream_dev.hpp, pt_hip.hip and pt_image.hpp keep the device buffers these words describe and
 // ask every question here; tests/c/image_history_check.cpp asks the same questions from scripts of calls, so every call order can be run on a CPU.
 //
 // THE RULES:

@@ -1,6 +1,6 @@
 // pt_launch_plan.hpp — the host-only planning of an intersect launch (which kernel, block size, LDS split, grid and the constants the hand-written
 // kernel is handed), of the path pool's size and of the frame ring's.  Pure integer arithmetic: no HIP runtime call and no context.  launchExtend and
-// submitBatch (pt_hip.hip) fill the inputs from the context and act on the result; tests/c/launch_plan_check.cpp runs it on the CPU.
+// submitBatch (pt_stream_dev.hpp) fill the inputs from the context and act on the result; tests/c/launch_plan_check.cpp runs it on the CPU.
 #pragma once
 #include "pt_options.hpp"
 
@@ -15,7 +15,7 @@
 
 namespace ptp {
 
-constexpr int PLAN_BLOCK = 256;                       // lanes of a k_extend block, and what pool sizes are rounded to (BLOCK of pt_hip.hip)
+constexpr int PLAN_BLOCK = 256;                       // lanes of a k_extend block, and what pool sizes are rounded to (BLOCK of pt_kernels.hpp)
 static_assert(POOL_SLOT_STEP == PLAN_BLOCK, "option 0 rounds the caller's pool to the blocks the planner sizes pools by");
 constexpr size_t LDS_PER_CU = 160 * 1024;             // gfx950; one block may take all of it
 

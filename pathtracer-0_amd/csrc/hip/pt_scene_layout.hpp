@@ -1,5 +1,5 @@
 // pt_scene_layout.hpp — the host-only half of the scene build: validates the reference's buffers and lays out every device-private record array
-// (pt_scene_records.hpp, pt_device.hpp) and the modes that depend on the scene.  No HIP runtime call and no context: buildScene (pt_hip.hip) uploads
+// (pt_scene_records.hpp, pt_device.hpp) and the modes that depend on the scene.  No HIP runtime call and no context: buildScene (pt_context.hpp) uploads
 // the result; tests/c/scene_layout_check.cpp runs it on the CPU.
 #pragma once
 #include "../../../include/pt_api.h"
@@ -19,7 +19,7 @@ namespace ptl {
 using namespace ptd;
 
 using LayoutOptions = ptp::Options;          // the layout reads the members whose rows of the option table say they rebuild the scene, and asmNodes80Limit
-constexpr int EXTEND_BLOCK = 256;            // lanes of a k_extend block: one traversal stack each beside the LDS tile (BLOCK of pt_hip.hip)
+constexpr int EXTEND_BLOCK = 256;            // lanes of a k_extend block: one traversal stack each beside the LDS tile (BLOCK of pt_kernels.hpp)
 
 // raw SSBO contents (host copies, glBufferData semantics)
 struct SceneBuffers {

@@ -1,6 +1,6 @@
 // pt_stream_sched.hpp — the host side of the frame stream: which batch joins the running stream, how long the next group of iterations is, what a
 // look at the device's scheduler words means, which batches retire.  Plain C++: no HIP runtime call and no context.  Everything that touches the
-// device goes through the `Dev` the caller hands in: pt_hip.hip supplies the launches (StreamDev), tests/c/stream_sched_check.cpp a model of the
+// device goes through the `Dev` the caller hands in: pt_stream_dev.hpp supplies the launches (StreamDev), tests/c/stream_sched_check.cpp a model of the
 // device, so every decision below can be single-stepped on a CPU.
 //
 // A batch is SUBMITTED (its jobs are appended to the running stream, or a new stream starts) and later RETIRED (all its pixel-frame jobs done: its

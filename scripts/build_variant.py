@@ -22,5 +22,5 @@ inc = os.path.join(out_dir, f"{name}_hsaco.inc")
 build.assemble_extend(out_inc=inc, defines=asm)
 d = os.path.join(build.HERE, "csrc", "hip")
 out = os.path.join(out_dir, f"{name}.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc"] + build.HIP_FLAGS + hip + [f'-DPT_EXTEND_INC="{inc}"', "-o", out, os.path.join(d, "pt_hip.hip"), os.path.join(d, "pt_bvh.hip"), os.path.join(d, "pt_denoise.hip"), os.path.join(d, "pt_reproject.hip"), os.path.join(d, "pt_guided.hip")])
+subprocess.check_call(["/opt/rocm/bin/hipcc"] + build.HIP_FLAGS + hip + [f'-DPT_EXTEND_INC="{inc}"', "-o", out] + [os.path.join(d, f) for f in build.HIP_UNITS])
 print(out)

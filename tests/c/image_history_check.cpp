@@ -4,7 +4,7 @@
 //
 //   image_history_check SCRIPTS       one trace per script on stdout, nothing on stderr, exit 0
 //
-// THE STAND-IN does around the history what pt_hip.hip and pt_image.hpp do around it, in their order, with every HIP call, launch and buffer left
+// THE STAND-IN does around the history what pt_hip.hip (with pt_context.hpp and pt_stream_dev.hpp) and pt_image.hpp do around it, in their order, with every HIP call, launch and buffer left
 // out; work in flight, the image's luminance moments and the scene build never refuse here.  A SCRIPT is a block of lines:
 //   script NAME
 //   create W H                        pt_create
@@ -54,7 +54,7 @@ struct Ctx {
     int fail(const Refused& r) { return r.code ? fail(r.code, r.msg) : 0; }
     const FrameIn* current() const { return bound ? &in : nullptr; }      // currentInputs
 
-    // ---- pt_hip.hip
+    // ---- pt_hip.hip, pt_context.hpp (recordCamera), pt_stream_dev.hpp (submitBatch)
     void recordCamera() { hist.written(current()); }
     int claimFrameConstants() { hist.frameConstantsTaken(); return 0; }
     int setBuffer(const std::string& binding, bool ok) {

@@ -23,7 +23,7 @@
 //   snapshot(seq)        the words as they are now.  "eager": it has landed whenever the host asks.  "lazy": it lands only when the host waits for it
 //                        (snapshots land in the order of their launches)
 //
-// A SCRIPT is a block of lines (the host side of each is what pt_hip.hip does around the scheduler: Host below):
+// A SCRIPT is a block of lines (the host side of each is what pt_stream_dev.hpp does around the scheduler: Host below):
 //   script NAME
 //   create PIXELS POOLSLOTS D eager|lazy IMAGES SEQ0      pixels per frame, pt_set_option 0 (0 = automatic), a job's life, landing, ring images, the
 //                                                         group sequence number the context starts from
