@@ -80,6 +80,8 @@ struct pt_ctx {
     // records with their last segments (`rays`, W*H x 2 float4; include/pt_through.h)
     struct Records { Dev<float4> recs, rays; } rec[ptp::RC_COUNT];
     Dev<float4> dDnCol[2], dDnGuide, dDnOut;      // the filters' colour ping-pong, packed guide (2 float4 per pixel) and output
+    bool filteredThere = false;     // dDnOut holds the image of the last filter call (include/pt_bloom.h's PT_BLOOM_SRC_FILTERED): set and cleared where it is written
+    Dev<float4> dBloomPyr, dBloomOut;      // include/pt_bloom.h: the pyramid (all levels in one allocation) and the composed image (W*H float4)
     // reprojection (include/pt_reproject.h): one flag byte per material (1 = view-dependent, buildScene); the scratch images, the kept counts
     // (two), the packed candidates of k_through_pack (W*H x 2 float4)
     Dev<unsigned char> dMatVD;

@@ -172,7 +172,9 @@ int denoiseImage(pt_ctx* c, int iterations, const float (&sigma)[4], pt_ctx** on
     if ((rc = wholeFrame(c, PT_ERR_UNSUPPORTED, "pt_denoise", &on, &frame))) return rc;
     if ((rc = currentRecords(on, nullptr, "pt_denoise"))) return rc;
     if ((rc = ensureFilterScratch(on))) return rc;
+    on->filteredThere = false;
     HIP_TRY(denoiseLaunch(frame, on->rec[ptp::RC_FEAT].recs, c->W, c->H, iterations, sigma, on->dDnCol[0], on->dDnCol[1], on->dDnGuide, on->dDnOut, on->stream));
+    on->filteredThere = true;
     *onOut = on;
     return 0;
 }
@@ -231,8 +233,9 @@ int filteredImage(pt_ctx* c, bool fill, bool filter, int iterations, const float
     j.W = c->W; j.H = c->H; j.iterations = iterations; j.minFrames = minFrames; j.floorA = floorA;
     std::copy(sigma, sigma + 4, j.sigma);
     j.col0 = on->dDnCol[0]; j.col1 = on->dDnCol[1]; j.guide = on->dDnGuide;
-    if (filter) j.out = on->dDnOut;
+    if (filter) { j.out = on->dDnOut; on->filteredThere = false; }
     HIP_TRY(guidedLaunch(j, on->stream));
+    if (filter) on->filteredThere = true;
     *onOut = on;
     return 0;
 }
@@ -591,6 +594,7 @@ int selectGuided(pt_ctx* c, const pt_guided_rule& r, float floorA, const char* w
     if ((rc = ensureFilterScratch(on))) return rc;
     HIP_TRY(on->dSelMask.ensure(maskBytes(on) + 4));
     if (!j.stats) {
+        on->filteredThere = false;
         HIP_TRY(hipMemsetAsync(on->dDnOut, 0, (size_t)c->W * c->H * 16, on->stream));
         j.stats = on->dDnOut;
     }
@@ -784,3 +788,6 @@ int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* ru
 
 // the display image (include/pt_tonemap.h): metered exposure, tone curve and sRGB transfer on pt_read_display_mean's path
 #include "pt_tonemap_host.hpp"
+
+// ---- the glare and the display image of a device-resident image (include/pt_bloom.h)
+#include "pt_bloom_host.hpp"

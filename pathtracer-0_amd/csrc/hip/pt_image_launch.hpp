@@ -107,3 +107,15 @@ struct TonemapJob {
     int curve = 0, transfer = 0;                                  // 0 .. 2 and 0 .. 1 (checked by the caller)
 };
 hipError_t tonemapLaunch(const TonemapJob& j, hipStream_t s);
+
+// ---- the glare of include/pt_bloom.h (pt_bloom.hip)
+struct BloomJob {
+    // image: W*H float4 in pixel order, read only.  perPixel: it is FRAME (rgb a running sum, divided by the pixel's own count a); else rgb is a
+    // mean already and a carries FRAME.a
+    const float4* image = nullptr; bool perPixel = false;
+    int W = 0, H = 0, levels = 0;                                 // levels: 1 .. PT_BLOOM_MAX_LEVELS (checked by the caller)
+    float T = 0.0f, spread = 1.0f, norm = 1.0f, intensity = 0.0f; // T = threshold / exposure and norm: pt_bloom_rule.hpp's
+    // pyramid: ptp::bloomPyramid(W, H, levels).texels float4 of scratch;  out: W*H float4, the composed image (not `image`)
+    float4* pyramid = nullptr; float4* out = nullptr;
+};
+hipError_t bloomLaunch(const BloomJob& j, hipStream_t s);

@@ -177,6 +177,11 @@ def lib():
             L.pt_tonemap.argtypes = [vp, C.POINTER(TonemapRule), vp, C.c_float, vp, C.POINTER(C.c_float), vp]
             L.pt_tonemap_save_png.argtypes = [vp, C.POINTER(TonemapRule), vp, C.c_float, C.c_char_p, C.POINTER(C.c_float)]
             L.pt_tonemap_srgb_thresholds.argtypes = [vp]
+        if hasattr(L, "pt_bloom"):                            # include/pt_bloom.h
+            tm, bl = C.POINTER(TonemapRule), C.POINTER(BloomRule)
+            L.pt_bloom.argtypes = [vp, bl, ci, vp, C.c_float, vp]
+            L.pt_tonemap_bloom.argtypes = [vp, tm, bl, ci, vp, C.c_float, vp, C.POINTER(C.c_float), vp]
+            L.pt_tonemap_bloom_save_png.argtypes = [vp, tm, bl, ci, vp, C.c_float, C.c_char_p, C.POINTER(C.c_float)]
         if hasattr(L, "pt_reproject_frame_through"):          # include/pt_reproject_through.h
             L.pt_reproject_frame_through.argtypes = [vp, C.POINTER(ThroughRule), C.POINTER(ReprojectThroughRule), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         if hasattr(L, "pt_reproject_frame_bilinear"):         # include/pt_reproject_bilinear.h
@@ -230,6 +235,25 @@ def tonemap_srgb_thresholds():
     out = np.zeros(256, dtype=np.float32)
     _check(lib().pt_tonemap_srgb_thresholds(out.ctypes.data))
     return out
+
+
+class BloomRule(C.Structure):
+    """pt_bloom_rule of include/pt_bloom.h"""
+    _fields_ = [("levels", C.c_int), ("intensity", C.c_float), ("threshold", C.c_float), ("spread", C.c_float)]
+
+
+BLOOM_SRC_FRAME, BLOOM_SRC_HOST, BLOOM_SRC_FILTERED = 0, 1, 2      # PT_BLOOM_SRC_*
+# defaults of bloom_rule: PROVISIONAL — common choices (six levels, a faint glare of the light above an exposed luminance of 1), not tuned on this
+# project's workloads (DESIGN.md 2.25)
+BLOOM_DEFAULTS = dict(levels=6, intensity=0.05, threshold=1.0, spread=0.75)
+
+
+def bloom_rule(**kw):
+    """the pt_bloom_rule of these fields; a field not given takes BLOOM_DEFAULTS'"""
+    unknown = set(kw) - set(BLOOM_DEFAULTS)
+    assert not unknown, f"no such field of pt_bloom_rule: {sorted(unknown)}"
+    v = dict(BLOOM_DEFAULTS, **kw)
+    return BloomRule(int(v["levels"]), float(v["intensity"]), float(v["threshold"]), float(v["spread"]))
 
 
 class ReprojectThroughRule(C.Structure):
@@ -704,6 +728,52 @@ class Renderer:
         e = C.c_float(0.0)
         _check(self._L.pt_tonemap_save_png(self._h, C.byref(rule), None if image is None else image.ctypes.data, float(prev_exposure),
                                            os.fsencode(path), C.byref(e)))
+        return e.value
+
+    # --- HDR glare ahead of the tone curve, and the display image of a device-resident image (include/pt_bloom.h) -------
+    bloom_rule = staticmethod(bloom_rule)
+
+    def _bloom_source(self, image):
+        """(PT_BLOOM_SRC_*, the host image or None) of an `image` argument: None is FRAME, the string "filtered" the image the last filter call
+        left on the device, an array a host image"""
+        if image is None:
+            return BLOOM_SRC_FRAME, None
+        if isinstance(image, str):
+            assert image == "filtered", 'a source by name is "filtered"'
+            return BLOOM_SRC_FILTERED, None
+        return BLOOM_SRC_HOST, self._tonemap_image(image)
+
+    def bloom(self, image=None, exposure=1.0, bloom=None):
+        """The float image with its glare (pt_bloom): (H, W, 4) float32, rgb a mean and a the source's a.  image: None (the current FRAME),
+        "filtered" (what the last denoise* / denoise_guided* / read_display_denoised* call left on the device) or an (H, W, 4) float32 image in
+        FRAME order.  exposure only scales bloom.threshold.  Read only."""
+        bloom = bloom_rule() if bloom is None else bloom
+        source, image = self._bloom_source(image)
+        out = np.zeros((self.H, self.W, 4), dtype=np.float32)
+        _check(self._L.pt_bloom(self._h, C.byref(bloom), source, None if image is None else image.ctypes.data, float(exposure), out.ctypes.data))
+        return out
+
+    def tonemap_bloom(self, image=None, prev_exposure=0.0, rule=None, bloom=None, want_hist=False):
+        """tonemap with the glare between the metering and the curve (pt_tonemap_bloom), all on the device; `image` as bloom's.  The exposure
+        and the histogram are tonemap's of the same source whatever the bloom rule.  Returns what tonemap returns."""
+        rule = self.tonemap_rule() if rule is None else rule
+        bloom = bloom_rule() if bloom is None else bloom
+        source, image = self._bloom_source(image)
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        e = C.c_float(0.0)
+        hist = np.zeros(TONEMAP_BINS, dtype=np.uint32) if want_hist else None
+        _check(self._L.pt_tonemap_bloom(self._h, C.byref(rule), C.byref(bloom), source, None if image is None else image.ctypes.data, float(prev_exposure),
+                                        out.ctypes.data, C.byref(e), hist.ctypes.data if want_hist else None))
+        return (out, e.value, hist) if want_hist else (out, e.value)
+
+    def tonemap_bloom_save_png(self, path, image=None, prev_exposure=0.0, rule=None, bloom=None):
+        """tonemap_bloom's image written as an 8-bit RGB PNG (pt_tonemap_bloom_save_png); returns the exposure applied"""
+        rule = self.tonemap_rule() if rule is None else rule
+        bloom = bloom_rule() if bloom is None else bloom
+        source, image = self._bloom_source(image)
+        e = C.c_float(0.0)
+        _check(self._L.pt_tonemap_bloom_save_png(self._h, C.byref(rule), C.byref(bloom), source, None if image is None else image.ctypes.data,
+                                                 float(prev_exposure), os.fsencode(path), C.byref(e)))
         return e.value
 
     # --- luminance moments and the variance-guided filter (include/pt_guided.h) ---------------------
