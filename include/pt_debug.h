@@ -70,6 +70,11 @@ int pt_debug_intersect(pt_ctx* ctx, const float* o, const float* d, float* out, 
  * batches.  PT_ERR_ARG: a null argument, an unknown array, a buffer too small, a multi-stream context, a scene that is not built (an upload or a
  * rebuilding option since the last render). */
 int pt_debug_scene_records(pt_ctx* ctx, int which, void* out, size_t cap, size_t* bytes);
+/* The device time of ONE launch of a pose kernel of include/pt_pose.h (scripts/pose_probe.py): which = 0 one lane per float4, 1 one lane per
+ * triangle; the best of reps launches, HIP events on the pose's stream, written into a scratch copy (nothing of the context changes).
+ * PT_ERR_ARG: a null or destroyed pose, n_parts == 0, null xforms, xform_bytes != n_parts * 96, reps < 1, an unknown kernel. */
+struct pt_pose;
+int pt_debug_pose_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int which, int reps, float* ms_best);
 
 #ifdef __cplusplus
 }

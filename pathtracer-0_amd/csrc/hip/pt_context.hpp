@@ -16,6 +16,29 @@ int fail(const ptp::Refused& r) { return r.code ? fail(r.code, r.msg) : 0; }    
 }  // namespace
 
 struct MultiCtx;
+struct pt_pose;
+struct pt_ctx;
+namespace {
+int settleScene(pt_ctx* c);                                   // pt_pose_host.hpp
+int settledScene(pt_ctx* c, SceneBuffers** b);                // below
+size_t hostTriangleCount(const pt_ctx* c);                    // below
+
+// A context's host copies of the bindings and textures.  Bindings 3 and 10 (tris, bvhdata) may be BEHIND a pose (include/pt_pose.h): the posed
+// binding 3 and the refit binding 10 then lie in the pose's plan on the device.  So those two members, and the buffers as a whole, are reachable
+// through ONE path only, settledScene(), which brings them up to date first; every other member is read and written directly.
+class HostScene : private SceneBuffers {
+  public:
+    using SceneBuffers::origin; using SceneBuffers::rotation; using SceneBuffers::mouse; using SceneBuffers::params; using SceneBuffers::imp;
+    using SceneBuffers::ellip; using SceneBuffers::mtl; using SceneBuffers::bvhtree; using SceneBuffers::leaftris; using SceneBuffers::objidx;
+    using SceneBuffers::sky; using SceneBuffers::skyW; using SceneBuffers::skyH; using SceneBuffers::textures;
+  private:
+    friend int settleScene(pt_ctx* c);                        // the download itself
+    friend int settledScene(pt_ctx* c, SceneBuffers** b);
+    friend size_t hostTriangleCount(const pt_ctx* c);         // (a settle changes no length)
+};
+
+}  // namespace
+
 struct pt_ctx {
     MultiCtx* multi = nullptr;      // != nullptr: a multi-GPU group (pt_create_multi, pt_multi.hpp); everything below then lives in its per-device contexts
     int device = 0, W = 0, H = 0, shardRank = 0, shardCount = 1;
@@ -24,7 +47,10 @@ struct pt_ctx {
     // spatial partition (opt.cuPartition) as built: the intersect launches on a stream whose CU mask holds that many eighths of every XCD's CUs, the shading
     // launches on the complement; events order extend(i) -> shade(i) -> extend(i+1), everything else stays on `stream`
     int cuPartitionBuilt = 0; hipStream_t sExt = nullptr, sShade = nullptr; hipEvent_t evExt = nullptr, evShade = nullptr, evHost = nullptr;
-    SceneBuffers buf;               // raw SSBO contents and textures (host copies, glBufferData semantics): what layoutScene reads
+    HostScene buf;                  // raw SSBO contents and textures (host copies, glBufferData semantics): what layoutScene reads, through settledScene()
+    // include/pt_pose.h: the poses created on this context, and the one whose plan holds the bindings 3 and 10 that the host copies are BEHIND
+    // (nullptr: they are current)
+    std::vector<pt_pose*> poses; pt_pose* behind = nullptr;
     Dev<uchar4> dTexels; Dev<TexRec> dTexTable;      // all textures beyond the sky in one allocation + the bindless-style table
     bool sceneDirty = true, frameInDirty = true;
     bool trans = false, anySubsurface = false, ambiguousTriObj = false, anyMaps = false; Dev<int> dTriObj;
@@ -90,7 +116,7 @@ struct pt_ctx {
     Dev<float4> dFill; Dev<unsigned> dFillCount;      // include/pt_fill.h: FRAME' (W*H float4) and k_gd_fill's count
     // include/pt_motion.h.  The mark: Rh (feat), the primitives' positions then on the device (3 float4 each) and on the host (9 floats per
     // triangle, 10 per ellipsoid); the positions now are packed per call into dMoveTri / dMoveEl
-    struct Mark { int nTri = 0, nEl = 0; std::vector<float> tri, el; Dev<float4> feat, dTri, dEl; } mark;
+    struct Mark { int nTri = 0, nEl = 0; std::vector<float> tri, el; Dev<float4> feat, dTri, dEl; bool triOnDevice = false; } mark;      // triOnDevice: tri is still to be fetched from dTri
     Dev<float4> dMoveTri, dMoveEl;
     // include/pt_validate.h.  The hold (on a group's first stream): the held FRAME and T in pixel order (W*H float4 each); pt_history_merge's
     // kappa (W*H floats, only when asked for)
@@ -119,10 +145,27 @@ size_t shardSlots(int W, int H, int count) {
 
 // The scene build's device half: lays the buffers out on the host (layoutScene, pt_scene_layout.hpp), uploads the arrays, wires DevScene, and only then
 // takes the layout's flags and modes into the context: a refused scene leaves the context as it was (sceneDirty stays set).
+// THE access path to the host copies of bindings 3 and 10 and to the buffers as a whole: settles (settleScene, pt_pose_host.hpp: downloads what
+// the two are behind by; nothing when they are current), then hands out the buffers
+int settledScene(pt_ctx* c, SceneBuffers** b) {
+    if (const int rc = settleScene(c)) return rc;
+    *b = &c->buf;
+    return 0;
+}
+size_t hostTriangleCount(const pt_ctx* c) { return c->buf.tris.size() / 40; }
+void posesStale(pt_ctx* c);            // ... an accepted upload of binding 3 or 10-13, or a pt_move_geometry: the context's poses no longer describe it
+void posesDestroy(pt_ctx* c);          // ... pt_destroy
+// ... motionPack's triangle records (pt_motion_pack.hpp) of the posed binding 3 that on->behind holds, made on the device into `out` on on->stream:
+// then == nullptr: the mark's own (flags 0); else flagged against the mark's records.  *nTri: the triangles
+int poseMotionRecords(pt_ctx* on, const float4* then, int nThen, Dev<float4>& out, int* nTri);
+int markPositionsToHost(pt_ctx* on);   // mark.tri from mark.dTri, for a mark whose records were made on the device
+
 int buildScene(pt_ctx* c) {
+    SceneBuffers* host = nullptr;
+    if (const int rc = settledScene(c, &host)) return rc;
+    const SceneBuffers& b = *host;
     SceneLayout L; std::string err;
-    if (const int rc = layoutScene(c->buf, c->opt, L, err)) return fail(rc, err);
-    const SceneBuffers& b = c->buf;
+    if (const int rc = layoutScene(b, c->opt, L, err)) return fail(rc, err);
     hipStream_t s = c->stream;
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(c->dNodes.upload(L.nodes.data(), L.nodes.size() * 16, s));

@@ -188,6 +188,7 @@ int pt_create_multi(pt_ctx** out, const int* devices, int n_devices, int width, 
 
 int pt_destroy(pt_ctx* c) {
     if (!c) return PT_OK;
+    posesDestroy(c);                                              // include/pt_pose.h: a context's poses go with it
     if (c->multi) { multiFree(c); delete c; return PT_OK; }
     hipSetDevice(c->device);
     flushStream(c);
@@ -216,9 +217,13 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
             if (rc) { if (k != c->multi->kids[0]) c->multi->staleBindings.insert(binding); return rc; }
         }
         c->multi->staleBindings.erase(binding);
+        if (binding == PT_BIND_TRIANGLES || (binding >= PT_BIND_BVHDATA && binding <= PT_BIND_OBJINDICES)) posesStale(c);
         return PT_OK;
     }
     if (bytes % 4) return fail(PT_ERR_ARG, "pt_set_buffer: size must be a multiple of 4 bytes");
+    const bool poseBinding = binding == PT_BIND_TRIANGLES || (binding >= PT_BIND_BVHDATA && binding <= PT_BIND_OBJINDICES);      // what a pose's rest pose and plan were made from
+    SceneBuffers* host = nullptr;                                 // host copies behind a pose (include/pt_pose.h): current before a scene binding is stored
+    if (poseBinding || binding == PT_BIND_ELLIPSOIDS) { if (const int rc = settledScene(c, &host)) return rc; }
     c->hist.uploadBegins();                                       // (a refused upload has dropped the record caches all the same)
     const float* f = static_cast<const float*>(data); const int32_t* i = static_cast<const int32_t*>(data); size_t n = bytes / 4;
     switch (binding) {
@@ -226,10 +231,10 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
         case PT_BIND_ROTATION: if (n < 3) return fail(PT_ERR_ARG, "ROTATION needs 3 floats"); c->buf.rotation.assign(f, f + 3); return PT_OK;
         case PT_BIND_MOUSE: if (n < 3) return fail(PT_ERR_ARG, "MOUSE_POS needs 3 floats"); c->buf.mouse.assign(f, f + 3); return PT_OK;
         case PT_BIND_PARAMS: if (n < 12) return fail(PT_ERR_ARG, "Parameters needs 12 floats"); c->buf.params.assign(f, f + 12); return PT_OK;
-        case PT_BIND_TRIANGLES: if (n % 40) return fail(PT_ERR_ARG, "triangle buffer must be 40 floats per triangle"); c->buf.tris.assign(f, f + n); break;
+        case PT_BIND_TRIANGLES: if (n % 40) return fail(PT_ERR_ARG, "triangle buffer must be 40 floats per triangle"); host->tris.assign(f, f + n); break;
         case PT_BIND_IMPLICITS: c->buf.imp.assign(f, f + n); break;
         case PT_BIND_ELLIPSOIDS: c->buf.ellip.assign(f, f + n); break;
-        case PT_BIND_BVHDATA: c->buf.bvhdata.assign(f, f + n); break;
+        case PT_BIND_BVHDATA: host->bvhdata.assign(f, f + n); break;
         case PT_BIND_BVHTREE: if (n % 3) return fail(PT_ERR_ARG, "BVHtree must be 3 ints per node"); c->buf.bvhtree.assign(i, i + n); break;
         case PT_BIND_LEAFTRIS: c->buf.leaftris.assign(i, i + n); break;
         case PT_BIND_OBJINDICES: c->buf.objidx.assign(i, i + n); break;
@@ -238,6 +243,7 @@ int pt_set_buffer(pt_ctx* c, int binding, const void* data, size_t bytes) {
     }
     c->sceneDirty = true;
     c->hist.sceneBufferAccepted(binding);
+    if (poseBinding) posesStale(c);
     return PT_OK;
 }
 

@@ -357,10 +357,23 @@ int reprojectImage(pt_ctx* c, const char* who, bool moved, float maxHistory, flo
     ReprojMotion g{};
     if (moved) {
         std::vector<float> tri, el; int nTri = 0, nEl = 0;
-        ptp::motionPositions(on->buf.tris, on->buf.ellip, tri, &nTri, el, &nEl);
-        const ptp::MotionThen then{m.tri.data(), m.nTri, m.el.data(), m.nEl};
-        ptp::motionPack(tri, nTri, el, nEl, &then, pt, pe);
-        HIP_TRY(on->dMoveTri.upload(pt.data(), pt.size() * 4, on->stream));
+        if (on->behind) {
+            // host copies behind a pose (include/pt_pose.h): the triangles' records are made where the posed binding 3 lies, against the mark's
+            // device records; the ellipsoids stay on the host path
+            if ((rc = poseMotionRecords(on, on->mark.dTri, m.nTri, on->dMoveTri, &nTri))) return rc;
+            const std::vector<float> noTris; int zero = 0;
+            ptp::motionPositions(noTris, on->buf.ellip, tri, &zero, el, &nEl);
+            const ptp::MotionThen then{nullptr, 0, m.el.data(), m.nEl};
+            ptp::motionPack(tri, 0, el, nEl, &then, pt, pe);
+        } else {
+            if (m.triOnDevice && (rc = markPositionsToHost(on))) return rc;      // a mark taken while they were behind
+            SceneBuffers* host = nullptr;
+            if ((rc = settledScene(on, &host))) return rc;        // (current: nothing is downloaded)
+            ptp::motionPositions(host->tris, host->ellip, tri, &nTri, el, &nEl);
+            const ptp::MotionThen then{m.tri.data(), m.nTri, m.el.data(), m.nEl};
+            ptp::motionPack(tri, nTri, el, nEl, &then, pt, pe);
+            HIP_TRY(on->dMoveTri.upload(pt.data(), pt.size() * 4, on->stream));
+        }
         HIP_TRY(on->dMoveEl.upload(pe.data(), pe.size() * 4, on->stream));
         g = ReprojMotion{on->dMoveTri, m.dTri, nTri, m.nTri, on->dMoveEl, m.dEl, nEl, m.nEl};
         j.motion = &g;
@@ -457,10 +470,23 @@ int motionMark(pt_ctx* c) {
     HIP_TRY(m.feat.ensure(n * 64));
     HIP_TRY(hipMemcpyAsync(m.feat, on->rec[ptp::RC_FEAT_H].recs, n * 64, hipMemcpyDeviceToDevice, on->stream));
     // (b), (c) where the primitives are
-    ptp::motionPositions(on->buf.tris, on->buf.ellip, m.tri, &m.nTri, m.el, &m.nEl);
     std::vector<float> pt, pe;
-    ptp::motionPack(m.tri, m.nTri, m.el, m.nEl, nullptr, pt, pe);
-    HIP_TRY(m.dTri.upload(pt.data(), pt.size() * 4, on->stream));
+    if (on->behind) {
+        // host copies behind a pose (include/pt_pose.h): motionPack's triangle records are made on the device from the posed binding 3; the host
+        // positions are fetched from them if a later reprojection finds the host copies current again
+        if ((rc = poseMotionRecords(on, nullptr, 0, m.dTri, &m.nTri))) return rc;
+        m.tri.clear(); m.triOnDevice = true;
+        const std::vector<float> noTris; std::vector<float> noPos; int zero = 0;
+        ptp::motionPositions(noTris, on->buf.ellip, noPos, &zero, m.el, &m.nEl);
+        ptp::motionPack(noPos, 0, m.el, m.nEl, nullptr, pt, pe);
+    } else {
+        SceneBuffers* host = nullptr;
+        if ((rc = settledScene(on, &host))) return rc;            // (current: nothing is downloaded)
+        ptp::motionPositions(host->tris, host->ellip, m.tri, &m.nTri, m.el, &m.nEl);
+        ptp::motionPack(m.tri, m.nTri, m.el, m.nEl, nullptr, pt, pe);
+        HIP_TRY(m.dTri.upload(pt.data(), pt.size() * 4, on->stream));
+        m.triOnDevice = false;
+    }
     HIP_TRY(m.dEl.upload(pe.data(), pe.size() * 4, on->stream));
     HIP_TRY(hipStreamSynchronize(on->stream));
     on->hist.markTaken();                                         // (d)
@@ -782,6 +808,9 @@ int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* ru
 
 // the in-place move of a scene's triangles (include/pt_move.h) and the read-back of the scene's record arrays
 #include "pt_move_host.hpp"
+
+// triangles animated by per-part matrices on the device (include/pt_pose.h), on the in-place move's path
+#include "pt_pose_host.hpp"
 
 // the outlier rejection (include/pt_despeckle.h): both calls on historyMerge's path
 #include "pt_despeckle_host.hpp"

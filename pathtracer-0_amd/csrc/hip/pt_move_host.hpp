@@ -36,14 +36,14 @@ void moveAccepted(pt_ctx* c, bool ellip) {
 }
 
 // the slow path of a single context: the new buffers become the host copies and the scene is built; a scene that does not build leaves them as they were
-int moveRebuild(pt_ctx* c, std::vector<float>& data, const float* tris, size_t triBytes, const float* ellip, size_t ellipBytes) {
+int moveRebuild(pt_ctx* c, SceneBuffers& host, std::vector<float>& data, const float* tris, size_t triBytes, const float* ellip, size_t ellipBytes) {
     std::vector<float> newTris(tris, tris + triBytes / 4), newEllip;
     if (ellip) newEllip.assign(ellip, ellip + ellipBytes / 4);
-    c->buf.tris.swap(newTris); c->buf.bvhdata.swap(data);
+    host.tris.swap(newTris); host.bvhdata.swap(data);
     if (ellip) c->buf.ellip.swap(newEllip);
     const int rc = buildScene(c);
     if (rc) {
-        c->buf.tris.swap(newTris); c->buf.bvhdata.swap(data);
+        host.tris.swap(newTris); host.bvhdata.swap(data);
         if (ellip) c->buf.ellip.swap(newEllip);
         return rc;
     }
@@ -55,8 +55,9 @@ int moveRebuild(pt_ctx* c, std::vector<float>& data, const float* tris, size_t t
 int moveMulti(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes, const float* ellip, size_t ellipBytes, double* rootCost) {
     if (!c->multi->staleBindings.empty())
         return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
-    const pt_ctx* first = c->multi->kids[0];
-    if (moveDigest(first->buf) != P->digest || first->buf.bvhdata.size() * 4 != P->dataBytes) return moveForeignPlan();
+    SceneBuffers* host = nullptr;                                 // the first stream's copies (a group's streams are never behind a pose)
+    if (const int rc = settledScene(c->multi->kids[0], &host)) return rc;
+    if (moveDigest(*host) != P->digest || host->bvhdata.size() * 4 != P->dataBytes) return moveForeignPlan();
     std::vector<float> data(std::max<size_t>(P->dataBytes / 4, 1));
     std::vector<double> cost(std::max(P->s.nRoots, 1));
     int rc;
@@ -73,9 +74,51 @@ int moveMulti(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes, c
     return PT_OK;
 }
 
-}  // namespace
+// THE PATCH on the device: from here on the context's records change.  P's dTris / dData hold the new binding 3 and the refit binding 10, its stream
+// is idle; the kernels run on the context's.  roots: the context's root records with the new boxes (moveRoots).  Synchronous; *unordered: a node box
+// the patch wrote has min > max or a NaN.
+int movePatchRecords(pt_ctx* c, pt_refit_plan* P, const std::vector<ObjRoot>& roots, const float* ellip, int* unordered) {
+    const hipStream_t s = c->stream;
+    PtMovePatch p{};
+    p.tris = P->dTris; p.data = P->dData; p.child = P->dMapChild; p.triRecs = c->dTris; p.nTriRecs = c->sc.nTriRecs; p.shade = c->dShade; p.nTris = c->sc.nTris;
+    p.nodes = c->dNodes; p.nodes80 = c->dNodes80; p.nInner = c->sc.nNodes; p.stride = c->built.asmNodeStride; p.flag = P->dFlag;
+    HIP_TRY(ptMovePatchLaunch(p, s));
+    HIP_TRY(hipMemcpyAsync(c->dRoots, roots.data(), roots.size() * sizeof(ObjRoot), hipMemcpyHostToDevice, s));
+    std::vector<EllipRec> recs;
+    if (ellip) {
+        recs.resize(c->dEllip.bytes / sizeof(EllipRec));
+        std::memset(recs.data(), 0, recs.size() * sizeof(EllipRec));
+        ptl::moveEllipsoids(ellip, recs);
+        HIP_TRY(hipMemcpyAsync(c->dEllip, recs.data(), recs.size() * sizeof(EllipRec), hipMemcpyHostToDevice, s));
+    }
+    *unordered = 0;
+    HIP_TRY(hipMemcpyAsync(unordered, P->dFlag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
 
-int pt_move_geometry(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+// the map of the record order, made by the first call and kept while bfs_nodes holds (reads the host copies, settled)
+int moveEnsureMap(pt_ctx* c, pt_refit_plan* P) {
+    if (P->mapValid && P->mapBfsNodes == c->opt.bfsNodes) return 0;
+    std::string err;
+    SceneBuffers* host = nullptr;
+    if (const int rc = settledScene(c, &host)) return rc;
+    P->mapValid = false;
+    if (const int rc = ptl::moveMapOrder(*host, c->opt, P->map, err)) return fail(rc, err);
+    HIP_TRY(P->dMapChild.upload(P->map.child.data(), P->map.child.size() * 4, P->stream));
+    HIP_TRY(hipStreamSynchronize(P->stream));
+    P->mapBfsNodes = c->opt.bfsNodes; P->mapValid = true;
+    return 0;
+}
+// whether the map is of what was built (it is while the digest holds; the scene build decides otherwise)
+bool moveMapFits(const pt_ctx* c, const pt_refit_plan* P) {
+    const ptl::MoveMap& map = P->map;
+    return map.nInner == c->sc.nNodes && map.numObj == c->sc.numObj &&
+           c->dRoots.bytes / sizeof(ObjRoot) == (size_t)std::max(map.numObj, 8) + (map.numObj > 8 ? 64 : 0) && (size_t)map.nRows * 32 == P->dataBytes;
+}
+
+// pt_move_geometry itself; the entry point below adds what the call means for the context's poses (include/pt_pose.h), whose slow paths come here
+int moveGeometry(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
     if (!c) return fail(PT_ERR_ARG, "pt_move_geometry: null context");
     if (!pt_refit_live_(P)) return fail(PT_ERR_ARG, "pt_move_geometry: null or destroyed plan");
     if (!tris) return fail(PT_ERR_ARG, "pt_move_geometry: null tris");
@@ -90,11 +133,13 @@ int pt_move_geometry(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triB
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = flushStream(c))) return rc;                         // submitted frames are rendered in the old scene
+    SceneBuffers* host = nullptr;                                 // the host copies are read below, and the plan may be the pose's they are behind on
+    if ((rc = settledScene(c, &host))) return rc;
     if (c->sceneDirty && (rc = buildScene(c))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (moveDigest(c->buf) != P->digest || c->buf.bvhdata.size() * 4 != P->dataBytes) return moveForeignPlan();
+    if (moveDigest(*host) != P->digest || host->bvhdata.size() * 4 != P->dataBytes) return moveForeignPlan();
     if (ellip) { std::string err; if ((rc = ptl::ellipsoidsUsable(ellip, ellipBytes / 4, c->sc.numMat, err))) return fail(rc, err); }
-    bool rebuild = c->asmWhyNot == MOVE_UNORDERED || (ellip && !ptl::ellipPatchable(c->buf.ellip, ellip, ellipBytes / 4)) || c->buf.tris.size() / 40 != (size_t)P->nTris;
+    bool rebuild = c->asmWhyNot == MOVE_UNORDERED || (ellip && !ptl::ellipPatchable(c->buf.ellip, ellip, ellipBytes / 4)) || host->tris.size() / 40 != (size_t)P->nTris;
 
     // the refit: the plan's working copy only.  Then the material check, where the records' ids are the plan's triangles'
     if ((rc = pt_refit_device_(P, tris, triBytes, "pt_move_geometry"))) return rc;
@@ -106,20 +151,10 @@ int pt_move_geometry(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triB
         HIP_TRY(hipStreamSynchronize(ps));
         if (flag) return fail(PT_ERR_SCENE, MOVE_TRIMAT);
     }
-    // the map of the record order, made by the first call and kept while bfs_nodes holds
-    if (!rebuild && (!P->mapValid || P->mapBfsNodes != c->opt.bfsNodes)) {
-        std::string err;
-        P->mapValid = false;
-        if ((rc = ptl::moveMapOrder(c->buf, c->opt, P->map, err))) return fail(rc, err);
-        HIP_TRY(P->dMapChild.upload(P->map.child.data(), P->map.child.size() * 4, ps));
-        HIP_TRY(hipStreamSynchronize(ps));
-        P->mapBfsNodes = c->opt.bfsNodes; P->mapValid = true;
-    }
+    if (!rebuild && (rc = moveEnsureMap(c, P))) return rc;
     ptl::MoveMap& map = P->map;
     std::vector<ObjRoot> roots(c->dRoots.bytes / sizeof(ObjRoot));
-    if (!rebuild && (map.nInner != c->sc.nNodes || map.numObj != c->sc.numObj || roots.size() != (size_t)std::max(map.numObj, 8) + (map.numObj > 8 ? 64 : 0) ||
-                     (size_t)map.nRows * 32 != P->dataBytes))
-        rebuild = true;                                           // (not what was built: cannot happen while the digest holds; the scene build decides)
+    if (!rebuild && !moveMapFits(c, P)) rebuild = true;           // (not what was built: cannot happen while the digest holds; the scene build decides)
 
     std::vector<float> data(P->dataBytes / 4);
     std::vector<double> cost(std::max(P->s.nRoots, 1));
@@ -129,39 +164,33 @@ int pt_move_geometry(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triB
     HIP_TRY(hipStreamSynchronize(ps));
 
     if (!rebuild) {
-        // ---- the patch: from here on the context's records change.  The plan's stream is idle; the kernels run on the context's
+        // ---- the patch: from here on the context's records change
         map.asmStride = c->built.asmNodeStride; map.asmGroupShift = c->asmGroupShift; map.asmNoRootCull = c->opt.asmNoRootCull;
         ptl::moveRoots(map, data.data(), roots.data());
-        const hipStream_t s = c->stream;
-        PtMovePatch p{};
-        p.tris = P->dTris; p.data = P->dData; p.child = P->dMapChild; p.triRecs = c->dTris; p.nTriRecs = c->sc.nTriRecs; p.shade = c->dShade; p.nTris = c->sc.nTris;
-        p.nodes = c->dNodes; p.nodes80 = c->dNodes80; p.nInner = c->sc.nNodes; p.stride = c->built.asmNodeStride; p.flag = P->dFlag;
-        HIP_TRY(ptMovePatchLaunch(p, s));
-        HIP_TRY(hipMemcpyAsync(c->dRoots, roots.data(), roots.size() * sizeof(ObjRoot), hipMemcpyHostToDevice, s));
-        std::vector<EllipRec> recs;
-        if (ellip) {
-            recs.resize(c->dEllip.bytes / sizeof(EllipRec));
-            std::memset(recs.data(), 0, recs.size() * sizeof(EllipRec));
-            ptl::moveEllipsoids(ellip, recs);
-            HIP_TRY(hipMemcpyAsync(c->dEllip, recs.data(), recs.size() * sizeof(EllipRec), hipMemcpyHostToDevice, s));
-        }
         int unordered = 0;
-        HIP_TRY(hipMemcpyAsync(&unordered, P->dFlag, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        c->buf.tris.assign(tris, tris + triBytes / 4);
-        c->buf.bvhdata.swap(data);
+        if ((rc = movePatchRecords(c, P, roots, ellip, &unordered))) return rc;
+        host->tris.assign(tris, tris + triBytes / 4);
+        host->bvhdata.swap(data);
         if (ellip) c->buf.ellip.assign(ellip, ellip + ellipBytes / 4);
         moveAccepted(c, ellip != nullptr);
         if (unordered && c->built.asmEligible && c->built.asmNodeStride == 80) {      // the modes assume ordered boxes: the scene build decides
             if ((rc = buildScene(c))) { c->sceneDirty = true; return rc; }
             rebuild = true;
         }
-    } else if ((rc = moveRebuild(c, data, tris, triBytes, ellip, ellipBytes))) {
+    } else if ((rc = moveRebuild(c, *host, data, tris, triBytes, ellip, ellipBytes))) {
         return rc;
     }
     if (rootCost) std::copy(cost.begin(), cost.begin() + P->s.nRoots, rootCost);
     if (inPlace) *inPlace = rebuild ? 0 : 1;
     return PT_OK;
+}
+
+}  // namespace
+
+int pt_move_geometry(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+    const int rc = moveGeometry(c, P, tris, triBytes, ellip, ellipBytes, rootCost, inPlace);
+    if (!rc) posesStale(c);                                       // binding 3 is no longer what a pose's rest pose would give
+    return rc;
 }
 
 // One device record array of the built scene read back (tests): which = 0 nodes, 1 nodes80, 2 tris, 3 shade, 4 roots, 5 ellip, 6 triObj

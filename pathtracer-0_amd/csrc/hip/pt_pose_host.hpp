@@ -1,0 +1,300 @@
+// pt_pose_host.hpp — the host half of include/pt_pose.h behind the C ABI (included at the end of pt_image.hpp after pt_move_host.hpp, inside
+// pt_hip.hip's extern "C" block, where pt_ctx, the in-place move and their helpers are in scope; not a translation unit).  The kernels are
+// pt_pose.hip's, behind pt_pose_launch.hpp; the refit is pt_refit.hip's second half (pt_refit_kernels_); the patch of the context's records is
+// pt_move_host.hpp's (movePatchRecords), fed from the rows of binding 10 that k_pose_gather collects; the argument checks and the CPU statement
+// of the rule are pt_pose_rule.hpp's.
+//
+// What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
+// kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
+// (c->behind == pose), dTris and dData are the bindings 3 and 10 a settle delivers: a refused pose is undone by running the last accepted one again.
+extern "C++" {
+#include "pt_pose_launch.hpp"
+#include "pt_pose_rule.hpp"
+#include <set>
+}
+#include "../../../include/pt_pose.h"
+
+struct pt_pose {
+    pt_ctx* ctx = nullptr;              // the context (a group's: the group) it was created on and belongs to
+    int device = 0, nParts = 0; int64_t nTris = 0;
+    pt_refit_plan* plan = nullptr;      // its own, over the context's bindings 10-13
+    Dev<float> dRest, dScratch, dX, dRows; Dev<int32_t> dPart, dRowIds;
+    bool scratchReady = false;          // dScratch holds the rest pose's static triangles (pt_pose_triangles, the slow paths)
+    int rowsFor = -1, nRows = 0;        // dRowIds lists the rows of the plan's map made under this bfs_nodes
+    std::vector<float> accepted;        // the matrices of the last accepted pose; empty: none yet (the rest pose), or n_parts == 0
+    bool stale = false;                 // the scene was uploaded since pt_pose_create
+};
+
+namespace {
+
+std::mutex g_posesMutex;
+std::set<pt_pose*> g_poses;             // the live poses: a destroyed one is refused, not followed
+constexpr PtPoseKernel POSE_KERNEL = PT_POSE_PER_QUAD;      // the faster of the two at 100 k and at 1 M triangles (scripts/pose_probe.py); pt_debug_pose_time runs either
+
+bool poseLive(pt_pose* p) {
+    std::lock_guard<std::mutex> g(g_posesMutex);
+    return p && g_poses.count(p);
+}
+
+// the pose of `xforms` (host; nullptr: the rest pose) into dst, which holds the rest pose's static triangles; asynchronous on the plan's stream
+int poseInto(pt_pose* P, const float* xforms, float* dst) {
+    const hipStream_t st = P->plan->stream;
+    if (!xforms || P->nParts == 0) {
+        if (P->nTris) HIP_TRY(hipMemcpyAsync(dst, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
+    HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
+    HIP_TRY(ptPoseLaunch(P->dRest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
+    return 0;
+}
+
+// P = the rule applied to the rest pose, on the host; the plan's working copies are not touched
+int poseToHost(pt_pose* P, const float* xforms, float* out) {
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    if (!P->scratchReady) {
+        HIP_TRY(P->dScratch.reset(P->nTris ? (size_t)P->nTris * 160 : 16));
+        if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
+        P->scratchReady = true;
+    }
+    if (const int rc = poseInto(P, xforms, P->dScratch)) return rc;
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(out, P->dScratch, (size_t)P->nTris * 160, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+void poseFree(pt_pose* P) {
+    hipSetDevice(P->device);
+    pt_refit_destroy(P->plan);
+    delete P;
+}
+
+// ---- what pt_context.hpp declares
+
+int settleScene(pt_ctx* c) {
+    pt_pose* P = c->behind;
+    if (!P) return 0;
+    pt_refit_plan* plan = P->plan;
+    HIP_TRY(hipSetDevice(c->device));
+    c->buf.tris.resize((size_t)P->nTris * 40);
+    c->buf.bvhdata.resize(plan->dataBytes / 4);
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(c->buf.tris.data(), plan->dTris, (size_t)P->nTris * 160, hipMemcpyDeviceToHost, plan->stream));
+    if (plan->dataBytes) HIP_TRY(hipMemcpyAsync(c->buf.bvhdata.data(), plan->dData, plan->dataBytes, hipMemcpyDeviceToHost, plan->stream));
+    HIP_TRY(hipStreamSynchronize(plan->stream));
+    c->behind = nullptr;
+    return 0;
+}
+
+int poseMotionRecords(pt_ctx* on, const float4* then, int nThen, Dev<float4>& out, int* nTri) {
+    const pt_pose* P = on->behind;                                // (its plan's stream is idle: every pose call ends synchronised)
+    const int n = (int)P->nTris;
+    HIP_TRY(hipSetDevice(on->device));
+    HIP_TRY(out.ensure(std::max<size_t>((size_t)n * 48, 16)));    // (kept from call to call: the count cannot change while the context is behind)
+    if (n == 0) HIP_TRY(hipMemsetAsync(out, 0, 16, on->stream)); // (motionPack's one zero record)
+    HIP_TRY(ptPoseMotionLaunch(P->plan->dTris, n, then, nThen, out, on->stream));
+    *nTri = n;
+    return 0;
+}
+
+int markPositionsToHost(pt_ctx* on) {
+    pt_ctx::Mark& m = on->mark;
+    std::vector<float> recs((size_t)m.nTri * 12);
+    HIP_TRY(hipSetDevice(on->device));
+    if (m.nTri) HIP_TRY(hipMemcpyAsync(recs.data(), m.dTri, recs.size() * 4, hipMemcpyDeviceToHost, on->stream));
+    HIP_TRY(hipStreamSynchronize(on->stream));
+    m.tri.resize((size_t)m.nTri * 9);
+    for (size_t t = 0; t < (size_t)m.nTri; t++)
+        for (int v = 0; v < 3; v++) std::memcpy(&m.tri[9 * t + 3 * v], &recs[12 * t + 4 * v], 12);
+    m.triOnDevice = false;
+    return 0;
+}
+
+void posesStale(pt_ctx* c) { for (pt_pose* p : c->poses) p->stale = true; }
+
+void posesDestroy(pt_ctx* c) {
+    c->behind = nullptr;                                          // (nobody will read the host copies again)
+    for (pt_pose* p : c->poses) {
+        { std::lock_guard<std::mutex> g(g_posesMutex); g_poses.erase(p); }
+        poseFree(p);
+    }
+    c->poses.clear();
+}
+
+// the slow paths: P on the host, then pt_move_geometry's own sequence with the pose's plan
+int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+    int rc;
+    if (!c->multi && (rc = settleScene(c))) return rc;            // (the move uploads into the plan's working copy)
+    std::vector<float> tris((size_t)P->nTris * 40);
+    if ((rc = poseToHost(P, xforms, tris.data()))) return rc;
+    // (a group's sequence goes through pt_set_buffer, which marks the context's poses stale: these uploads are the pose's own — binding 3 is the rule
+    //  applied to the rest pose, the trees are the plan's — so every pose stays what it was, as on the in-place path)
+    std::vector<char> was;
+    for (const pt_pose* p : c->poses) was.push_back(p->stale);
+    rc = moveGeometry(c, P->plan, tris.data(), tris.size() * 4, ellip, ellipBytes, rootCost, inPlace);
+    for (size_t k = 0; k < was.size(); k++) c->poses[k]->stale = was[k] != 0;
+    if (rc) return rc;
+    P->accepted.assign(xforms, xforms + xformBytes / 4);
+    return PT_OK;
+}
+
+}  // namespace
+
+int pt_pose_create(pt_ctx* c, const int32_t* triPart, size_t partBytes, int nParts, pt_pose** out) {
+    const size_t nTris = c ? hostTriangleCount(firstStream(c)) : 0;
+    if (int rc = fail(ptp::checkPoseCreate(c, triPart, partBytes, nParts, out, nTris))) return rc;
+    int rc;
+    if (c->multi) {
+        if (!c->multi->staleBindings.empty())
+            return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
+        rc = multiRun(*c->multi, [](pt_ctx* k) {
+            HIP_TRY(hipSetDevice(k->device));
+            if (const int r = flushStream(k)) return r;
+            return k->sceneDirty ? buildScene(k) : 0;
+        });
+        if (rc) return rc;
+    } else {
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = flushStream(c))) return rc;
+        if (c->sceneDirty && (rc = buildScene(c))) return rc;
+    }
+    pt_ctx* on = firstStream(c);
+    SceneBuffers* host = nullptr;
+    if ((rc = settledScene(on, &host))) return rc;
+    const SceneBuffers& b = *host;
+    pt_refit_plan* plan = nullptr;
+    if ((rc = pt_refit_create(on->device, b.bvhdata.data(), b.bvhdata.size() * 4, b.bvhtree.data(), b.bvhtree.size() * 4, b.leaftris.data(), b.leaftris.size() * 4,
+                              b.objidx.data(), b.objidx.size() * 4, (int64_t)nTris, &plan)))
+        return rc;
+    pt_pose* P = new pt_pose();
+    P->ctx = c; P->device = on->device; P->nParts = nParts; P->nTris = (int64_t)nTris; P->plan = plan;
+    const hipStream_t st = plan->stream;
+    auto upload = [&]() {
+        HIP_TRY(hipSetDevice(P->device));
+        HIP_TRY(P->dRest.upload(b.tris.data(), nTris * 160, st));
+        HIP_TRY(P->dPart.upload(triPart, nTris * 4, st));
+        HIP_TRY(P->dX.reset(std::max<size_t>((size_t)nParts * 96, 16)));
+        if (nTris) HIP_TRY(hipMemcpyAsync(plan->dTris, P->dRest, nTris * 160, hipMemcpyDeviceToDevice, st));      // the static triangles, once
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    };
+    if ((rc = upload())) { const std::string msg = g_err; poseFree(P); return fail(rc, msg); }
+    { std::lock_guard<std::mutex> g(g_posesMutex); g_poses.insert(P); }
+    c->poses.push_back(P);
+    *out = P;
+    return PT_OK;
+}
+
+int pt_pose_triangles(pt_pose* P, const float* xforms, size_t xformBytes, float* trisOut, size_t triBytes) {
+    const bool live = poseLive(P);
+    if (int rc = fail(ptp::checkPoseTriangles(live, xforms, xformBytes, live ? P->nParts : 0, trisOut, triBytes, live ? (size_t)P->nTris : 0))) return rc;
+    return poseToHost(P, xforms, trisOut);
+}
+
+int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+    const bool live = poseLive(P);
+    if (int rc = fail(ptp::checkPoseGeometry(c, live, live && P->ctx == c, xforms, xformBytes, live ? P->nParts : 0, ellip, ellipBytes))) return rc;
+    if (P->stale) return fail(PT_ERR_SCENE, "pt_pose_geometry: the scene was uploaded since pt_pose_create");
+    if (c->multi) return poseSlow(c, P, xforms, xformBytes, ellip, ellipBytes, rootCost, inPlace);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if ((rc = flushStream(c))) return rc;                         // submitted frames are rendered in the old scene
+    if (c->sceneDirty && (rc = buildScene(c))) return rc;         // (settles)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (ellip) { std::string err; if ((rc = ptl::ellipsoidsUsable(ellip, ellipBytes / 4, c->sc.numMat, err))) return fail(rc, err); }
+    pt_refit_plan* plan = P->plan;
+    if (c->asmWhyNot == MOVE_UNORDERED || (ellip && !ptl::ellipPatchable(c->buf.ellip, ellip, ellipBytes / 4)))
+        return poseSlow(c, P, xforms, xformBytes, ellip, ellipBytes, rootCost, inPlace);
+    // the map of the record order reads the host copies: made (rarely: the first call, a changed bfs_nodes) before the working copies change
+    if (!plan->mapValid || plan->mapBfsNodes != c->opt.bfsNodes) {
+        if ((rc = moveEnsureMap(c, plan))) return rc;            // (settles)
+    }
+    if (!moveMapFits(c, plan)) return poseSlow(c, P, xforms, xformBytes, ellip, ellipBytes, rootCost, inPlace);
+    ptl::MoveMap& map = plan->map;
+    const hipStream_t ps = plan->stream;
+    if (P->rowsFor != plan->mapBfsNodes) {
+        std::vector<int32_t> ids;
+        ptl::moveRowIds(map, ids);
+        HIP_TRY(P->dRowIds.upload(ids.data(), ids.size() * 4, ps));
+        HIP_TRY(P->dRows.reset(std::max<size_t>(ids.size() * 32, 16)));
+        HIP_TRY(hipStreamSynchronize(ps));
+        P->nRows = (int)ids.size(); P->rowsFor = plan->mapBfsNodes;
+    }
+
+    // pose + refit: the plan's working copies only.  A refusal puts back what a settle would have delivered
+    if (!(rc = poseInto(P, xforms, plan->dTris))) rc = pt_refit_kernels_(plan, "pt_pose_geometry");
+    if (rc) {
+        const std::string msg = g_err;
+        if (c->behind == P) {
+            int rc2 = poseInto(P, P->accepted.empty() ? nullptr : P->accepted.data(), plan->dTris);
+            if (!rc2) rc2 = pt_refit_kernels_(plan, "pt_pose_geometry");
+            if (rc2) return rc2;
+        }
+        return fail(rc, msg);
+    }
+    // the rows the root and group records need, the costs, the root records: the plan's stream is idle afterwards
+    std::vector<float> rows((size_t)P->nRows * 8);
+    std::vector<double> cost(std::max(plan->s.nRoots, 1));
+    std::vector<ObjRoot> roots(c->dRoots.bytes / sizeof(ObjRoot));
+    HIP_TRY(ptPoseGatherLaunch(plan->dData, P->dRowIds, P->nRows, P->dRows, ps));
+    if (P->nRows) HIP_TRY(hipMemcpyAsync(rows.data(), P->dRows, rows.size() * 4, hipMemcpyDeviceToHost, ps));
+    if (plan->s.nRoots > 0) HIP_TRY(hipMemcpyAsync(cost.data(), plan->dRootCost, (size_t)plan->s.nRoots * 8, hipMemcpyDeviceToHost, ps));
+    HIP_TRY(hipMemcpyAsync(roots.data(), c->dRoots, roots.size() * sizeof(ObjRoot), hipMemcpyDeviceToHost, ps));
+    HIP_TRY(hipStreamSynchronize(ps));
+
+    // ---- the patch: from here on the context's records change
+    map.asmStride = c->built.asmNodeStride; map.asmGroupShift = c->asmGroupShift; map.asmNoRootCull = c->opt.asmNoRootCull;
+    ptl::moveRootsGathered(map, rows.data(), roots.data());
+    int unordered = 0;
+    if ((rc = movePatchRecords(c, plan, roots, ellip, &unordered))) return rc;
+    c->behind = P;                                                // a pose the context was behind on before is superseded
+    P->accepted.assign(xforms, xforms + xformBytes / 4);
+    if (ellip) c->buf.ellip.assign(ellip, ellip + ellipBytes / 4);
+    moveAccepted(c, ellip != nullptr);
+    bool rebuilt = false;
+    if (unordered && c->built.asmEligible && c->built.asmNodeStride == 80) {      // the modes assume ordered boxes: the scene build decides (and settles)
+        if ((rc = buildScene(c))) { c->sceneDirty = true; return rc; }
+        rebuilt = true;
+    }
+    if (rootCost) std::copy(cost.begin(), cost.begin() + plan->s.nRoots, rootCost);
+    if (inPlace) *inPlace = rebuilt ? 0 : 1;
+    return PT_OK;
+}
+
+void pt_pose_destroy(pt_pose* P) {
+    if (!P) return;
+    {
+        std::lock_guard<std::mutex> g(g_posesMutex);
+        if (!g_poses.erase(P)) return;                            // not a live pose: destroyed already, by this call or with its context
+    }
+    pt_ctx* c = P->ctx;
+    if (c->behind == P) settleScene(c);                           // the posed bindings become the host copies they describe
+    if (c->behind == P) c->behind = nullptr;                      // (a failed download: the copies stay the last settled ones)
+    c->poses.erase(std::remove(c->poses.begin(), c->poses.end(), P), c->poses.end());
+    poseFree(P);
+}
+
+// include/pt_debug.h: the device time of one pose launch (the best of reps), into the pose's scratch copy
+int pt_debug_pose_time(pt_pose* P, const float* xforms, size_t xformBytes, int which, int reps, float* msBest) {
+    const bool live = poseLive(P);
+    if (!live || !msBest || reps < 1 || (which != PT_POSE_PER_QUAD && which != PT_POSE_PER_TRIANGLE) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
+        return fail(PT_ERR_ARG, "pt_debug_pose_time: bad argument");
+    std::vector<float> tris((size_t)P->nTris * 40);
+    int rc = poseToHost(P, xforms, tris.data());                  // (the scratch copy and the matrices are in place afterwards)
+    if (rc) return rc;
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    const hipStream_t st = P->plan->stream;
+    float best = 0.0f;
+    for (int k = 0; k < reps && !rc; k++) {
+        hipEventRecord(e0, st);
+        const hipError_t e = ptPoseLaunch(P->dRest, P->dPart, P->nTris, P->dX, P->dScratch, (PtPoseKernel)which, st);
+        hipEventRecord(e1, st);
+        float ms = 0.0f;
+        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_pose_time: the launch failed");
+        if (k == 0 || ms < best) best = ms;
+    }
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (!rc) *msBest = best;
+    return rc;
+}

@@ -177,10 +177,15 @@ bool pt_refit_live_(pt_refit_plan* P) {
 }
 
 int pt_refit_device_(pt_refit_plan* P, const float* tris, size_t tri_bytes, const char* who) {
+    REFIT_TRY(hipSetDevice(P->device));
+    if (tri_bytes) REFIT_TRY(hipMemcpyAsync(P->dTris, tris, tri_bytes, hipMemcpyHostToDevice, P->stream));
+    return pt_refit_kernels_(P, who);
+}
+
+int pt_refit_kernels_(pt_refit_plan* P, const char* who) {
     const ptr::RefitSchedule& s = P->s;
     const hipStream_t st = P->stream;
     REFIT_TRY(hipSetDevice(P->device));
-    if (tri_bytes) REFIT_TRY(hipMemcpyAsync(P->dTris, tris, tri_bytes, hipMemcpyHostToDevice, st));
     REFIT_TRY(hipMemsetAsync(P->dFlag, 0, 4, st));
     const int nLeaves = s.nLeaves();
     if (nLeaves > 0)

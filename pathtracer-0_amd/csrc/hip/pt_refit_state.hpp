@@ -37,3 +37,5 @@ struct pt_refit_plan {
 // (`who` heads the text), PT_ERR_HIP.
 bool pt_refit_live_(pt_refit_plan* plan);
 int pt_refit_device_(pt_refit_plan* plan, const float* tris, size_t tri_bytes, const char* who);
+// ... and its second half alone, for a caller whose kernels have left binding 3 in plan->dTris on the plan's stream (include/pt_pose.h)
+int pt_refit_kernels_(pt_refit_plan* plan, const char* who);

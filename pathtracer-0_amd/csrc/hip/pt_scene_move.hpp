@@ -68,13 +68,30 @@ inline int moveMapOrder(const SceneBuffers& in, const LayoutOptions& opt, MoveMa
 
 // The root boxes and, beyond 8 objects, the 64 group boxes of `roots` (numObj, at least 8, records, then the groups) from the rows of binding 10;
 // references and padding of the root records stay
-inline void moveRoots(const MoveMap& m, const float* bvhdata, ObjRoot* roots) {
-    for (int o = 0; o < m.numObj; o++) rootRecordBox(bvhdata + 8 * (size_t)m.rootNode[o], roots[o]);
+// (root(o): object o's root row; child(o, side): the row of a child of an inner root.  Asked for nothing else)
+template <class Root, class Child>
+inline void moveRootsFrom(const MoveMap& m, Root root, Child child, ObjRoot* roots) {
+    for (int o = 0; o < m.numObj; o++) rootRecordBox(root(o), roots[o]);
     if (m.numObj <= 8) return;
     std::vector<ObjRoot> groups;
-    cullGroups(m.numObj, m.asmNoRootCull, [&](int o) { return bvhdata + 8 * (size_t)m.rootNode[o]; }, [&](int o) { return m.rootLeaf[o] != 0; },
-               [&](int o, int side) { return bvhdata + 8 * (size_t)m.child[2 * (size_t)m.rootRef[o] + side]; }, groups);
+    cullGroups(m.numObj, m.asmNoRootCull, root, [&](int o) { return m.rootLeaf[o] != 0; }, child, groups);
     std::copy(groups.begin(), groups.end(), roots + std::max(m.numObj, 8));
+}
+inline void moveRoots(const MoveMap& m, const float* bvhdata, ObjRoot* roots) {
+    moveRootsFrom(m, [&](int o) { return bvhdata + 8 * (size_t)m.rootNode[o]; },
+                  [&](int o, int side) { return bvhdata + 8 * (size_t)m.child[2 * (size_t)m.rootRef[o] + side]; }, roots);
+}
+// The same from gathered rows (include/pt_pose.h): three per object — its root's, then, of an inner root, its two children's — whose node ids
+// moveRowIds lists (a leaf root's two spare entries name the root again: never read)
+inline void moveRowIds(const MoveMap& m, std::vector<int32_t>& ids) {
+    ids.resize(3 * (size_t)m.numObj);
+    for (int o = 0; o < m.numObj; o++) {
+        ids[3 * (size_t)o] = m.rootNode[o];
+        for (int side = 0; side < 2; side++) ids[3 * (size_t)o + 1 + side] = m.rootLeaf[o] ? m.rootNode[o] : m.child[2 * (size_t)m.rootRef[o] + side];
+    }
+}
+inline void moveRootsGathered(const MoveMap& m, const float* rows, ObjRoot* roots) {
+    moveRootsFrom(m, [&](int o) { return rows + 24 * (size_t)o; }, [&](int o, int side) { return rows + 24 * (size_t)o + 8 * (size_t)(1 + side); }, roots);
 }
 
 // What binding 7 must keep for a patch: the count and every material index (ellipMaps could change otherwise).  Both buffers were or are checked

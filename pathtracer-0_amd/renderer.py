@@ -196,6 +196,13 @@ def lib():
         if hasattr(L, "pt_move_geometry"):                    # include/pt_move.h, and its read-back in include/pt_debug.h
             L.pt_move_geometry.argtypes = [vp, vp, vp, sz, vp, sz, vp, C.POINTER(ci)]
             L.pt_debug_scene_records.argtypes = [vp, ci, vp, sz, C.POINTER(sz)]
+        if hasattr(L, "pt_pose_create"):                      # include/pt_pose.h, and its kernel timer in include/pt_debug.h
+            L.pt_pose_create.argtypes = [vp, vp, sz, ci, C.POINTER(vp)]
+            L.pt_pose_geometry.argtypes = [vp, vp, vp, sz, vp, sz, vp, C.POINTER(ci)]
+            L.pt_pose_triangles.argtypes = [vp, vp, sz, vp, sz]
+            L.pt_pose_destroy.argtypes = [vp]
+            L.pt_pose_destroy.restype = None
+            L.pt_debug_pose_time.argtypes = [vp, vp, sz, ci, ci, C.POINTER(C.c_float)]
         _LIB = L
     return _LIB
 
@@ -333,6 +340,54 @@ class RefitPlan:
             pass
 
 
+def pose_records(M, N=None):
+    """The 24-float records of include/pt_pose.h for one matrix per part: M is (n_parts, 3, 4) (or 4 x 4, whose last row is dropped), N is
+    (n_parts, 3, 3) for the normals.  N not given: the inverse transpose of M's linear part, computed in binary64 and then rounded."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim == 2:
+        M = M[None]
+    assert M.ndim == 3 and M.shape[1] in (3, 4) and M.shape[2] == 4, "M must be (n_parts, 3, 4) or (n_parts, 4, 4)"
+    M = M[:, :3, :]
+    if N is None:
+        N = np.transpose(np.linalg.inv(M[:, :, :3]), (0, 2, 1)) if len(M) else np.zeros((0, 3, 3))
+    N = np.asarray(N, dtype=np.float64).reshape(-1, 3, 3)
+    assert len(N) == len(M), "one N per M"
+    out = np.zeros((len(M), 24), np.float32)
+    out[:, :12] = M.reshape(len(M), 12)
+    out[:, 12:21] = N.reshape(len(M), 9)
+    return out
+
+
+class Pose:
+    """A pose object of include/pt_pose.h (Renderer.pose_create): the context's binding 3 as the rest pose, a part id per triangle and a refit plan
+    of its own, on the device.  It belongs to its Renderer, whose close() destroys it."""
+
+    def __init__(self, renderer, tri_part, n_parts):
+        self._L = renderer._L
+        if not hasattr(self._L, "pt_pose_create"):
+            raise RuntimeError("this libpt_hip.so has no pt_pose_create (include/pt_pose.h): no fallback")
+        part = np.ascontiguousarray(tri_part, dtype=np.int32)
+        self.n_parts, self.n_tris, self.n_roots = int(n_parts), part.size, getattr(renderer, "_n_roots", 0)
+        self._h = C.c_void_p()
+        _check(self._L.pt_pose_create(renderer._h, part.ctypes.data, part.nbytes, self.n_parts, C.byref(self._h)))
+
+    def _xforms(self, xforms):
+        x = np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1)
+        return x, (x.ctypes.data if x.size else None)
+
+    def triangles(self, xforms):
+        """the posed binding 3 (the rule alone: nothing of the context changes)"""
+        x, xp = self._xforms(xforms)
+        out = np.empty(self.n_tris * 40, np.float32)
+        _check(self._L.pt_pose_triangles(self._h, xp, x.nbytes, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pt_pose_destroy(self._h)
+            self._h = None
+
+
 class Renderer:
     """One render context.  `devices=[...]`: ONE context made of several wavefront streams (pt_create_multi): one entry per stream —
     several GPUs ([0, 1, ...]), several independent streams on one GPU ([0, 0]: their kernels overlap, 11-24 % faster than one: include/pt_api.h), or both
@@ -372,6 +427,8 @@ class Renderer:
         a = np.ascontiguousarray(array)
         assert a.dtype in (np.float32, np.int32), "SSBO contents are float32 or int32"
         _check(self._L.pt_set_buffer(self._h, int(binding), a.ctypes.data, a.nbytes))
+        if int(binding) == 13:
+            self._n_roots = int(a.reshape(-1)[0]) if a.size else 0      # (what a Pose's root_cost is sized by)
 
     def set_texture(self, index, rgba8):
         a = np.ascontiguousarray(rgba8, dtype=np.uint8)
@@ -594,6 +651,28 @@ class Renderer:
         cost = np.zeros(plan.n_roots, np.float64)
         in_place = C.c_int(-1)
         _check(self._L.pt_move_geometry(self._h, plan._h, t.ctypes.data, t.nbytes, None if e is None else e.ctypes.data, 0 if e is None else e.nbytes,
+                                        cost.ctypes.data, C.byref(in_place)))
+        return cost, bool(in_place.value)
+
+    # --- triangles animated by per-part matrices on the device (include/pt_pose.h) -------------------
+    pose_records = staticmethod(pose_records)
+
+    def pose_create(self, tri_part, n_parts):
+        """A Pose over this context's scene as it is now (pt_pose_create): binding 3 is the rest pose, tri_part[k] in [-1, n_parts) the part of
+        triangle k (-1: static)."""
+        return Pose(self, tri_part, n_parts)
+
+    def pose_geometry(self, pose, xforms, ellip=None):
+        """move_geometry of the rest pose under `xforms` (n_parts records of 24 floats: pose_records), with the posed triangles, the refit and the
+        patch of the records made on the device (pt_pose_geometry): no triangle data crosses the bus; the host copies of bindings 3 and 10 are
+        brought up to date when something reads them.  Returns (root_cost, in_place) as move_geometry does."""
+        if not hasattr(self._L, "pt_pose_geometry"):
+            raise RuntimeError("this libpt_hip.so has no pt_pose_geometry (include/pt_pose.h): no fallback")
+        x, xp = pose._xforms(xforms)
+        e = None if ellip is None else np.ascontiguousarray(ellip, dtype=np.float32)
+        cost = np.zeros(pose.n_roots, np.float64)
+        in_place = C.c_int(-1)
+        _check(self._L.pt_pose_geometry(self._h, pose._h, xp, x.nbytes, None if e is None else e.ctypes.data, 0 if e is None else e.nbytes,
                                         cost.ctypes.data, C.byref(in_place)))
         return cost, bool(in_place.value)
 
