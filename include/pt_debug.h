@@ -75,6 +75,14 @@ int pt_debug_scene_records(pt_ctx* ctx, int which, void* out, size_t cap, size_t
  * PT_ERR_ARG: a null or destroyed pose, n_parts == 0, null xforms, xform_bytes != n_parts * 96, reps < 1, an unknown kernel. */
 struct pt_pose;
 int pt_debug_pose_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int which, int reps, float* ms_best);
+/* The same for a skinned pose of include/pt_skin.h (scripts/skin_probe.py): which = 0 one lane per float4, 1 one lane per corner.  PT_ERR_ARG: as
+ * above, and a pose that pt_skin_create did not make.  pt_debug_pose_time in turn refuses a skinned pose with PT_ERR_ARG: it has no part table. */
+int pt_debug_skin_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int which, int reps, float* ms_best);
+/* The pose's scratch copy (40 floats per triangle) as the last pt_pose_triangles, pt_debug_pose_time or pt_debug_skin_time left it.
+ * pt_debug_skin_time fills it with the rest pose before its launches, so what is read after it is the work of the kernel it was asked for: the
+ * tests compare both statements with the model this way.  PT_ERR_ARG: a null or destroyed pose, null tris_out, tri_bytes != n_tris * 160, no
+ * scratch copy yet. */
+int pt_debug_pose_scratch(struct pt_pose* pose, float* tris_out, size_t tri_bytes);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,9 @@
 // pt_hip.hip's extern "C" block, where pt_ctx, the in-place move and their helpers are in scope; not a translation unit).  The kernels are
 // pt_pose.hip's, behind pt_pose_launch.hpp; the refit is pt_refit.hip's second half (pt_refit_kernels_); the patch of the context's records is
 // pt_move_host.hpp's (movePatchRecords), fed from the rows of binding 10 that k_pose_gather collects; the argument checks and the CPU statement
-// of the rule are pt_pose_rule.hpp's.
+// of the rule are pt_pose_rule.hpp's.  A skinned pose (include/pt_skin.h, pt_skin_create) is the same object under a second rule: its two corner
+// tables instead of the part ids, pt_skin.hip's kernel behind pt_skin_launch.hpp instead of k_pose, pt_skin_rule.hpp's checks; poseInto is
+// the one place that tells them apart.
 //
 // What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
 // kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
@@ -10,15 +12,20 @@
 extern "C++" {
 #include "pt_pose_launch.hpp"
 #include "pt_pose_rule.hpp"
+#include "pt_skin_launch.hpp"
+#include "pt_skin_rule.hpp"
 #include <set>
 }
 #include "../../../include/pt_pose.h"
+#include "../../../include/pt_skin.h"
 
 struct pt_pose {
     pt_ctx* ctx = nullptr;              // the context (a group's: the group) it was created on and belongs to
     int device = 0, nParts = 0; int64_t nTris = 0;
     pt_refit_plan* plan = nullptr;      // its own, over the context's bindings 10-13
     Dev<float> dRest, dScratch, dX, dRows; Dev<int32_t> dPart, dRowIds;
+    bool skinned = false;               // include/pt_skin.h: the rule blends records per corner, from dBone / dWeight (12 words per triangle); no dPart
+    Dev<int32_t> dBone; Dev<float> dWeight;
     bool scratchReady = false;          // dScratch holds the rest pose's static triangles (pt_pose_triangles, the slow paths)
     int rowsFor = -1, nRows = 0;        // dRowIds lists the rows of the plan's map made under this bfs_nodes
     std::vector<float> accepted;        // the matrices of the last accepted pose; empty: none yet (the rest pose), or n_parts == 0
@@ -30,6 +37,7 @@ namespace {
 std::mutex g_posesMutex;
 std::set<pt_pose*> g_poses;             // the live poses: a destroyed one is refused, not followed
 constexpr PtPoseKernel POSE_KERNEL = PT_POSE_PER_QUAD;      // the faster of the two at 100 k and at 1 M triangles (scripts/pose_probe.py); pt_debug_pose_time runs either
+constexpr PtSkinKernel SKIN_KERNEL = PT_SKIN_PER_CORNER;    // faster with four slots at 100 k and at 1 M triangles, tied at 100 k and 2 % slower at 1 M with two: the shorter summed over both slot counts at 1 M (scripts/skin_probe.py); pt_debug_skin_time runs either
 
 bool poseLive(pt_pose* p) {
     std::lock_guard<std::mutex> g(g_posesMutex);
@@ -45,7 +53,8 @@ int poseInto(pt_pose* P, const float* xforms, float* dst) {
     }
     HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
     HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
-    HIP_TRY(ptPoseLaunch(P->dRest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
+    if (P->skinned) HIP_TRY(ptSkinLaunch(P->dRest, P->dBone, P->dWeight, P->nTris, P->dX, dst, SKIN_KERNEL, st));
+    else HIP_TRY(ptPoseLaunch(P->dRest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
     return 0;
 }
 
@@ -138,11 +147,8 @@ int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, cons
     return PT_OK;
 }
 
-}  // namespace
-
-int pt_pose_create(pt_ctx* c, const int32_t* triPart, size_t partBytes, int nParts, pt_pose** out) {
-    const size_t nTris = c ? hostTriangleCount(firstStream(c)) : 0;
-    if (int rc = fail(ptp::checkPoseCreate(c, triPart, partBytes, nParts, out, nTris))) return rc;
+// pt_pose_create and pt_skin_create after their argument checks: triPart, or the two corner tables of a skin
+int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, const int32_t* bone, const float* weight, pt_pose** out) {
     int rc;
     if (c->multi) {
         if (!c->multi->staleBindings.empty())
@@ -167,12 +173,15 @@ int pt_pose_create(pt_ctx* c, const int32_t* triPart, size_t partBytes, int nPar
                               b.objidx.data(), b.objidx.size() * 4, (int64_t)nTris, &plan)))
         return rc;
     pt_pose* P = new pt_pose();
-    P->ctx = c; P->device = on->device; P->nParts = nParts; P->nTris = (int64_t)nTris; P->plan = plan;
+    P->ctx = c; P->device = on->device; P->nParts = nParts; P->nTris = (int64_t)nTris; P->plan = plan; P->skinned = bone != nullptr;
     const hipStream_t st = plan->stream;
     auto upload = [&]() {
         HIP_TRY(hipSetDevice(P->device));
         HIP_TRY(P->dRest.upload(b.tris.data(), nTris * 160, st));
-        HIP_TRY(P->dPart.upload(triPart, nTris * 4, st));
+        if (P->skinned) {
+            HIP_TRY(P->dBone.upload(bone, nTris * 48, st));
+            HIP_TRY(P->dWeight.upload(weight, nTris * 48, st));
+        } else HIP_TRY(P->dPart.upload(triPart, nTris * 4, st));
         HIP_TRY(P->dX.reset(std::max<size_t>((size_t)nParts * 96, 16)));
         if (nTris) HIP_TRY(hipMemcpyAsync(plan->dTris, P->dRest, nTris * 160, hipMemcpyDeviceToDevice, st));      // the static triangles, once
         HIP_TRY(hipStreamSynchronize(st));
@@ -183,6 +192,20 @@ int pt_pose_create(pt_ctx* c, const int32_t* triPart, size_t partBytes, int nPar
     c->poses.push_back(P);
     *out = P;
     return PT_OK;
+}
+
+}  // namespace
+
+int pt_pose_create(pt_ctx* c, const int32_t* triPart, size_t partBytes, int nParts, pt_pose** out) {
+    const size_t nTris = c ? hostTriangleCount(firstStream(c)) : 0;
+    if (int rc = fail(ptp::checkPoseCreate(c, triPart, partBytes, nParts, out, nTris))) return rc;
+    return poseCreate(c, nTris, nParts, triPart, nullptr, nullptr, out);
+}
+
+int pt_skin_create(pt_ctx* c, const int32_t* bone, size_t boneBytes, const float* weight, size_t weightBytes, int nParts, pt_pose** out) {
+    const size_t nTris = c && bone && weight && out ? hostTriangleCount(firstStream(c)) : 0;     // (the context is read only once no argument is null)
+    if (int rc = fail(ptp::checkSkinCreate(c, bone, boneBytes, weight, weightBytes, nParts, out, nTris))) return rc;
+    return poseCreate(c, nTris, nParts, nullptr, bone, weight, out);
 }
 
 int pt_pose_triangles(pt_pose* P, const float* xforms, size_t xformBytes, float* trisOut, size_t triBytes) {
@@ -279,6 +302,7 @@ int pt_debug_pose_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
     const bool live = poseLive(P);
     if (!live || !msBest || reps < 1 || (which != PT_POSE_PER_QUAD && which != PT_POSE_PER_TRIANGLE) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
         return fail(PT_ERR_ARG, "pt_debug_pose_time: bad argument");
+    if (P->skinned) return fail(PT_ERR_ARG, "pt_debug_pose_time: a skinned pose has no part table (pt_debug_skin_time times its kernels)");
     std::vector<float> tris((size_t)P->nTris * 40);
     int rc = poseToHost(P, xforms, tris.data());                  // (the scratch copy and the matrices are in place afterwards)
     if (rc) return rc;
@@ -297,4 +321,46 @@ int pt_debug_pose_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
     hipEventDestroy(e0); hipEventDestroy(e1);
     if (!rc) *msBest = best;
     return rc;
+}
+
+// include/pt_debug.h: the device time of one skin launch (the best of reps), into the pose's scratch copy
+int pt_debug_skin_time(pt_pose* P, const float* xforms, size_t xformBytes, int which, int reps, float* msBest) {
+    const bool live = poseLive(P);
+    if (!live || !P->skinned || !msBest || reps < 1 || (which != PT_SKIN_PER_QUAD && which != PT_SKIN_PER_CORNER) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
+        return fail(PT_ERR_ARG, "pt_debug_skin_time: bad argument");
+    // the scratch copy is the whole rest pose again and the matrices are in place: what pt_debug_pose_scratch reads afterwards is this kernel's alone
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    if (!P->scratchReady) HIP_TRY(P->dScratch.reset(P->nTris ? (size_t)P->nTris * 160 : 16));
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
+    P->scratchReady = true;
+    HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
+    HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int rc = 0;
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    float best = 0.0f;
+    for (int k = 0; k < reps && !rc; k++) {
+        hipEventRecord(e0, st);
+        const hipError_t e = ptSkinLaunch(P->dRest, P->dBone, P->dWeight, P->nTris, P->dX, P->dScratch, (PtSkinKernel)which, st);
+        hipEventRecord(e1, st);
+        float ms = 0.0f;
+        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_skin_time: the launch failed");
+        if (k == 0 || ms < best) best = ms;
+    }
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (!rc) *msBest = best;
+    return rc;
+}
+
+// include/pt_debug.h: the pose's scratch copy as the last pt_pose_triangles / pt_debug_pose_time / pt_debug_skin_time left it
+int pt_debug_pose_scratch(pt_pose* P, float* trisOut, size_t triBytes) {
+    const bool live = poseLive(P);
+    if (!live || !trisOut || !P->scratchReady || triBytes != (size_t)P->nTris * 160) return fail(PT_ERR_ARG, "pt_debug_pose_scratch: bad argument");
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(trisOut, P->dScratch, triBytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
 }

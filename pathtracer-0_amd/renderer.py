@@ -203,6 +203,10 @@ def lib():
             L.pt_pose_destroy.argtypes = [vp]
             L.pt_pose_destroy.restype = None
             L.pt_debug_pose_time.argtypes = [vp, vp, sz, ci, ci, C.POINTER(C.c_float)]
+        if hasattr(L, "pt_skin_create"):                      # include/pt_skin.h, and its kernel timer in include/pt_debug.h
+            L.pt_skin_create.argtypes = [vp, vp, sz, vp, sz, ci, C.POINTER(vp)]
+            L.pt_debug_skin_time.argtypes = [vp, vp, sz, ci, ci, C.POINTER(C.c_float)]
+            L.pt_debug_pose_scratch.argtypes = [vp, vp, sz]
         _LIB = L
     return _LIB
 
@@ -362,14 +366,22 @@ class Pose:
     """A pose object of include/pt_pose.h (Renderer.pose_create): the context's binding 3 as the rest pose, a part id per triangle and a refit plan
     of its own, on the device.  It belongs to its Renderer, whose close() destroys it."""
 
-    def __init__(self, renderer, tri_part, n_parts):
+    def __init__(self, renderer, tri_part, n_parts, skin=None):
+        """skin: (corner_bone, corner_weight) of include/pt_skin.h instead of tri_part (Renderer.skin_create)"""
         self._L = renderer._L
-        if not hasattr(self._L, "pt_pose_create"):
-            raise RuntimeError("this libpt_hip.so has no pt_pose_create (include/pt_pose.h): no fallback")
-        part = np.ascontiguousarray(tri_part, dtype=np.int32)
-        self.n_parts, self.n_tris, self.n_roots = int(n_parts), part.size, getattr(renderer, "_n_roots", 0)
+        name, header = ("pt_pose_create", "include/pt_pose.h") if skin is None else ("pt_skin_create", "include/pt_skin.h")
+        if not hasattr(self._L, name):
+            raise RuntimeError(f"this libpt_hip.so has no {name} ({header}): no fallback")
         self._h = C.c_void_p()
-        _check(self._L.pt_pose_create(renderer._h, part.ctypes.data, part.nbytes, self.n_parts, C.byref(self._h)))
+        if skin is None:
+            part = np.ascontiguousarray(tri_part, dtype=np.int32)
+            self.n_parts, self.n_tris, self.n_roots = int(n_parts), part.size, getattr(renderer, "_n_roots", 0)
+            _check(self._L.pt_pose_create(renderer._h, part.ctypes.data, part.nbytes, self.n_parts, C.byref(self._h)))
+            return
+        bone = np.ascontiguousarray(skin[0], dtype=np.int32).reshape(-1)
+        weight = np.ascontiguousarray(skin[1], dtype=np.float32).reshape(-1)
+        self.n_parts, self.n_tris, self.n_roots = int(n_parts), bone.size // 12, getattr(renderer, "_n_roots", 0)
+        _check(self._L.pt_skin_create(renderer._h, bone.ctypes.data, bone.nbytes, weight.ctypes.data, weight.nbytes, self.n_parts, C.byref(self._h)))
 
     def _xforms(self, xforms):
         x = np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1)
@@ -661,6 +673,12 @@ class Renderer:
         """A Pose over this context's scene as it is now (pt_pose_create): binding 3 is the rest pose, tri_part[k] in [-1, n_parts) the part of
         triangle k (-1: static)."""
         return Pose(self, tri_part, n_parts)
+
+    def skin_create(self, corner_bone, corner_weight, n_parts):
+        """A skinned Pose over this context's scene as it is now (pt_skin_create, include/pt_skin.h): 12 bone ids and 12 weights per triangle,
+        corner c, slot s at 12*k + 4*c + s; a corner's used slots first, -1 in the others; a corner without slots is static.  pose_geometry,
+        Pose.triangles and pose_records work on it as on a Pose of pose_create."""
+        return Pose(self, None, n_parts, skin=(corner_bone, corner_weight))
 
     def pose_geometry(self, pose, xforms, ellip=None):
         """move_geometry of the rest pose under `xforms` (n_parts records of 24 floats: pose_records), with the posed triangles, the refit and the

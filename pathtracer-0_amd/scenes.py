@@ -492,6 +492,99 @@ def m2_relit(step=0, W=96, H=54, **kw):
     return wl
 
 
+def m3_tube(W=96, H=54, sample_res=8, max_bounces=8, n_seg=12, n_around=10):
+    """M3's rest pose, the skinning workload of include/pt_skin.h (not a BASELINE config): M1's room without M1's movers plus an upright tube
+    with smooth normals, n_seg rings of 2 * n_around triangles along its axis (+y) and a disc that closes its lower end.  The tube's triangles
+    are the last ones of binding 3 (the room's come first), the disc's n_around the very last: info["tube"] = (first, n_side, n_cap) and
+    info["axis"] = (cx, y0, y1, cz) say where."""
+    sc = _new_scene()
+    _cornell_materials(sc)
+    o = Obj()
+    _cornell_room(o, boxes=False)
+    o.group("tube")
+    o.usemtl("green")
+    cx, cz, y0, y1, rad = 0.1, 0.2, 0.05, 1.45, 0.12
+    verts, normals, faces = [], [], []
+    for i in range(n_seg + 1):
+        y = y0 + (y1 - y0) * i / n_seg
+        for j in range(n_around):
+            u = 2 * math.pi * (j + 0.37) / n_around              # (no normal with an exactly-zero component: SURVEY.md Q-4)
+            verts.append((cx + rad * math.cos(u), y, cz + rad * math.sin(u)))
+            normals.append((math.cos(u), 0.0123, math.sin(u)))
+    for i in range(n_seg):
+        for j in range(n_around):
+            a, b = i * n_around + j, i * n_around + (j + 1) % n_around
+            c, d = b + n_around, a + n_around
+            faces += [(a, c, b), (a, d, c)]
+    first_v = o.nv
+    o.mesh(verts, normals, faces)
+    centre, down = o.v((cx, y0, cz)), o.vn((0.0, -1.0, 0.0))
+    for j in range(n_around):
+        o.f(centre, first_v + 1 + j, first_v + 1 + (j + 1) % n_around, down)
+    sc.addObjectText(o.text(), 0, parentDirectory="")
+    wl = _finish("M3", sc, W, H, CORNELL_CAM, CORNELL_ROT, (0, 0, 0), sample_res, max_bounces)
+    n_side = 2 * n_seg * n_around
+    wl.info["tube"] = (wl.buffers[3].size // 40 - n_side - n_around, n_side, n_around)
+    wl.info["axis"] = (cx, y0, y1, cz)
+    return wl
+
+
+def ramp_weights(t, n_bones):
+    """The two tables of include/pt_skin.h for corners at parameter t in [0, 1] along a chain of n_bones joints (t < 0: a static corner): a
+    linear ramp between the two nearest joints, one slot where the ramp is 0 or 1.  t: any shape -> (bone, weight) of shape t.shape + (4,)."""
+    t = np.asarray(t, np.float64)
+    bone = np.full(t.shape + (4,), -1, np.int32)
+    weight = np.zeros(t.shape + (4,), np.float32)
+    s = np.round(np.clip(t, 0.0, 1.0) * (n_bones - 1) * 4096.0) / 4096.0      # (in steps of 1/4096: a corner at a joint's height has one slot)
+    i0 = np.minimum(np.floor(s).astype(np.int64), n_bones - 1)
+    f = (s - i0).astype(np.float32)
+    used, two = t >= 0.0, (t >= 0.0) & (f > 0.0)
+    bone[..., 0] = np.where(used, i0, -1)
+    weight[..., 0] = np.where(two, np.float32(1.0) - f, np.where(used, 1.0, 0.0))
+    bone[..., 1] = np.where(two, i0 + 1, -1)
+    weight[..., 1] = np.where(two, f, 0.0)
+    return bone, weight
+
+
+def chain_records(n_bones, pivots, axis, angle):
+    """n_bones records of 24 floats (include/pt_pose.h): joint i turned by i * angle about `axis`, each joint hinged at pivots[i] on the joint
+    below it, so the chain stays connected.  Binary64, rounded once; N is the rotation itself."""
+    a = np.asarray(axis, np.float64); a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    R1 = np.eye(3) + math.sin(angle) * K + (1 - math.cos(angle)) * (K @ K)
+    out = np.zeros((n_bones, 24), np.float32)
+    A, t = np.eye(3), np.zeros(3)                                  # joint i - 1: x -> A x + t
+    for i in range(n_bones):
+        if i:
+            p = np.asarray(pivots[i], np.float64)
+            A, t = A @ R1, A @ (p - R1 @ p) + t                  # first the hinge at p, then the joints below
+        out[i, :12] = np.concatenate([A, t.reshape(3, 1)], axis=1).reshape(12)
+        out[i, 12:21] = A.reshape(9)
+    return out
+
+
+def m3_bending(step=0, W=96, H=54, n_bones=5, a=0.04, **kw):
+    """M3 at `step`: (the rest pose's workload, corner_bone, corner_weight, the records).  The tables (12 words per triangle) weight each corner
+    of the tube's side between its two nearest joints by its height; the disc and the room are static.  Joint i is turned by i * step * a about
+    +z.  Two corners at one rest vertex get the same words, so the posed tube has no cracks."""
+    wl = m3_tube(W, H, **kw)
+    first, n_side, _ = wl.info["tube"]
+    cx, y0, y1, cz = wl.info["axis"]
+    tris = wl.buffers[3].reshape(-1, 40)
+    t = np.full((tris.shape[0], 3), -1.0)
+    y = tris[first:first + n_side, 1:12:4].astype(np.float64)       # the three vertices' y
+    t[first:first + n_side] = np.clip((y - y0) / (y1 - y0), 0.0, 1.0)
+    bone, weight = ramp_weights(t, n_bones)
+    return wl, bone.reshape(-1), weight.reshape(-1), m3_records(wl, step, n_bones, a)
+
+
+def m3_records(wl, step, n_bones=5, a=0.04):
+    """the records of m3_bending(step) alone, for a workload of m3_tube: the hinge of joint i lies on the axis half way between joints i - 1 and i"""
+    cx, y0, y1, cz = wl.info["axis"]
+    pivots = [(cx, y0 + (y1 - y0) * max(i - 0.5, 0.0) / (n_bones - 1), cz) for i in range(n_bones)]
+    return chain_records(n_bones, pivots, (0.0, 0.0, 1.0), float(step) * a)
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then
@@ -577,6 +670,8 @@ def build(name, W=None, H=None, **kw):
         return m1_moving(kw.pop("step", 0), W or 96, H or 54, **kw)
     if name == "M2":
         return m2_relit(kw.pop("step", 0), W or 96, H or 54, **kw)
+    if name == "M3":
+        return m3_tube(W or 96, H or 54, **kw)
     cfg = CONFIGS[name]
     W = cfg["W"] if W is None else W
     H = cfg["H"] if H is None else H
