@@ -83,6 +83,15 @@ int pt_debug_skin_time(struct pt_pose* pose, const float* xforms, size_t xform_b
  * tests compare both statements with the model this way.  PT_ERR_ARG: a null or destroyed pose, null tris_out, tri_bytes != n_tris * 160, no
  * scratch copy yet. */
 int pt_debug_pose_scratch(struct pt_pose* pose, float* tris_out, size_t tri_bytes);
+/* The device time of ONE launch of k_morph_corners of include/pt_morph.h (scripts/morph_probe.py) under the given weights: the best of reps
+ * launches, HIP events on the pose's stream, written into the pose's morphed rest pose (nothing of the context changes; the weights that
+ * pt_morph_weights set stay).  pt_debug_pose_time and pt_debug_skin_time keep working on the unmorphed rest pose.  PT_ERR_ARG: what
+ * pt_morph_weights refuses, reps < 1, null ms_best. */
+int pt_debug_morph_time(struct pt_pose* pose, const float* weights, size_t weight_bytes, int reps, float* ms_best);
+/* Runs the morph kernel alone with the weights last set (also when all of them are zero) and downloads the morphed rest pose, 40 floats per
+ * triangle: the tests hold the kernel to the model this way.  PT_ERR_ARG: a null or destroyed pose, a pose without a morph, null tris_out,
+ * tri_bytes != n_tris * 160. */
+int pt_debug_morph_rest(struct pt_pose* pose, float* tris_out, size_t tri_bytes);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@
  * pt_refit_create's.  pt_debug_pose_time (include/pt_debug.h) refuses a skinned pose with PT_ERR_ARG: it launches the kernels of the one-record
  * rule on a part table the skin does not have; pt_debug_skin_time times the skin's.
  *
+ * (Morph targets — per-corner offsets under one weight per target, applied to the rest pose ahead of this rule — are include/pt_morph.h's.)
  * NOT BUILT: dual-quaternion blending; more than four slots; 16-bit packed tables (48 bytes per triangle instead of 96); posed ellipsoids; JNI
  * natives; rebuilding degraded trees.
  */

@@ -4,7 +4,9 @@
 // pt_move_host.hpp's (movePatchRecords), fed from the rows of binding 10 that k_pose_gather collects; the argument checks and the CPU statement
 // of the rule are pt_pose_rule.hpp's.  A skinned pose (include/pt_skin.h, pt_skin_create) is the same object under a second rule: its two corner
 // tables instead of the part ids, pt_skin.hip's kernel behind pt_skin_launch.hpp instead of k_pose, pt_skin_rule.hpp's checks; poseInto is
-// the one place that tells them apart.
+// the one place that tells them apart.  A morph (include/pt_morph.h, pt_morph_attach) belongs to either kind: pt_morph.hip's kernel behind
+// pt_morph_launch.hpp writes the morphed copy of the rest pose's affected corners, which poseInto hands to the pose's rule in place of dRest;
+// pt_morph_rule.hpp's checks and inverted index.
 //
 // What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
 // kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
@@ -14,10 +16,13 @@ extern "C++" {
 #include "pt_pose_rule.hpp"
 #include "pt_skin_launch.hpp"
 #include "pt_skin_rule.hpp"
+#include "pt_morph_launch.hpp"
+#include "pt_morph_rule.hpp"
 #include <set>
 }
 #include "../../../include/pt_pose.h"
 #include "../../../include/pt_skin.h"
+#include "../../../include/pt_morph.h"
 
 struct pt_pose {
     pt_ctx* ctx = nullptr;              // the context (a group's: the group) it was created on and belongs to
@@ -29,6 +34,12 @@ struct pt_pose {
     bool scratchReady = false;          // dScratch holds the rest pose's static triangles (pt_pose_triangles, the slow paths)
     int rowsFor = -1, nRows = 0;        // dRowIds lists the rows of the plan's map made under this bfs_nodes
     std::vector<float> accepted;        // the matrices of the last accepted pose; empty: none yet (the rest pose), or n_parts == 0
+    // include/pt_morph.h: nTargets > 0 once a morph is attached.  dMorphRest is a second copy of the rest pose, of which the kernel rewrites the
+    // affected corners (all of them, on every morphed call) and nothing else
+    int nTargets = 0; int64_t nAffected = 0;
+    Dev<float> dMorphRest, dMorphW; Dev<int32_t> dMorphCorner, dMorphRow; Dev<ptp::MorphEntry> dMorphEntry;
+    std::vector<float> weights;         // as pt_morph_weights set them last (after the attach: zeros)
+    std::vector<float> acceptedWeights; // those of the last accepted pose; empty: every weight 0 (none accepted yet, or accepted before the attach)
     bool stale = false;                 // the scene was uploaded since pt_pose_create
 };
 
@@ -44,22 +55,36 @@ bool poseLive(pt_pose* p) {
     return p && g_poses.count(p);
 }
 
-// the pose of `xforms` (host; nullptr: the rest pose) into dst, which holds the rest pose's static triangles; asynchronous on the plan's stream
-int poseInto(pt_pose* P, const float* xforms, float* dst) {
+// the morphed rest pose under `weights` (host, nTargets floats) into dMorphRest; asynchronous on the plan's stream
+int morphRest(pt_pose* P, const float* weights) {
     const hipStream_t st = P->plan->stream;
-    if (!xforms || P->nParts == 0) {
+    HIP_TRY(hipMemcpyAsync(P->dMorphW, weights, (size_t)P->nTargets * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ptMorphLaunch(P->dRest, P->dMorphCorner, P->dMorphRow, P->dMorphEntry, P->dMorphW, P->nAffected, P->dMorphRest, st));
+    return 0;
+}
+
+// the pose of `xforms` (host; nullptr: the rest pose, unmorphed) under the morph weights `weights` (host; empty: no morph, or every weight 0) into
+// dst, which holds the rest pose's static triangles; asynchronous on the plan's stream
+int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights, float* dst) {
+    const hipStream_t st = P->plan->stream;
+    if (!xforms || P->nParts == 0) {                              // (n_parts == 0: a morph has no entries)
         if (P->nTris) HIP_TRY(hipMemcpyAsync(dst, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
         return 0;
     }
+    // every weight +-0: the morphed rest pose is the rest pose, bit for bit (the header's consequence 1), and the launch is skipped
+    bool morphed = false;
+    for (const float w : weights) morphed = morphed || w != 0.0f;
+    if (morphed) { if (const int rc = morphRest(P, weights.data())) return rc; }
+    const float* rest = morphed ? (const float*)P->dMorphRest : (const float*)P->dRest;
     HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
     HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
-    if (P->skinned) HIP_TRY(ptSkinLaunch(P->dRest, P->dBone, P->dWeight, P->nTris, P->dX, dst, SKIN_KERNEL, st));
-    else HIP_TRY(ptPoseLaunch(P->dRest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
+    if (P->skinned) HIP_TRY(ptSkinLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dX, dst, SKIN_KERNEL, st));
+    else HIP_TRY(ptPoseLaunch(rest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
     return 0;
 }
 
 // P = the rule applied to the rest pose, on the host; the plan's working copies are not touched
-int poseToHost(pt_pose* P, const float* xforms, float* out) {
+int poseToHost(pt_pose* P, const float* xforms, const std::vector<float>& weights, float* out) {
     const hipStream_t st = P->plan->stream;
     HIP_TRY(hipSetDevice(P->device));
     if (!P->scratchReady) {
@@ -67,7 +92,7 @@ int poseToHost(pt_pose* P, const float* xforms, float* out) {
         if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
         P->scratchReady = true;
     }
-    if (const int rc = poseInto(P, xforms, P->dScratch)) return rc;
+    if (const int rc = poseInto(P, xforms, weights, P->dScratch)) return rc;
     if (P->nTris) HIP_TRY(hipMemcpyAsync(out, P->dScratch, (size_t)P->nTris * 160, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -135,7 +160,7 @@ int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, cons
     int rc;
     if (!c->multi && (rc = settleScene(c))) return rc;            // (the move uploads into the plan's working copy)
     std::vector<float> tris((size_t)P->nTris * 40);
-    if ((rc = poseToHost(P, xforms, tris.data()))) return rc;
+    if ((rc = poseToHost(P, xforms, P->weights, tris.data()))) return rc;
     // (a group's sequence goes through pt_set_buffer, which marks the context's poses stale: these uploads are the pose's own — binding 3 is the rule
     //  applied to the rest pose, the trees are the plan's — so every pose stays what it was, as on the in-place path)
     std::vector<char> was;
@@ -144,6 +169,7 @@ int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, cons
     for (size_t k = 0; k < was.size(); k++) c->poses[k]->stale = was[k] != 0;
     if (rc) return rc;
     P->accepted.assign(xforms, xforms + xformBytes / 4);
+    P->acceptedWeights = P->weights;
     return PT_OK;
 }
 
@@ -211,7 +237,7 @@ int pt_skin_create(pt_ctx* c, const int32_t* bone, size_t boneBytes, const float
 int pt_pose_triangles(pt_pose* P, const float* xforms, size_t xformBytes, float* trisOut, size_t triBytes) {
     const bool live = poseLive(P);
     if (int rc = fail(ptp::checkPoseTriangles(live, xforms, xformBytes, live ? P->nParts : 0, trisOut, triBytes, live ? (size_t)P->nTris : 0))) return rc;
-    return poseToHost(P, xforms, trisOut);
+    return poseToHost(P, xforms, P->weights, trisOut);
 }
 
 int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
@@ -245,11 +271,11 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     }
 
     // pose + refit: the plan's working copies only.  A refusal puts back what a settle would have delivered
-    if (!(rc = poseInto(P, xforms, plan->dTris))) rc = pt_refit_kernels_(plan, "pt_pose_geometry");
+    if (!(rc = poseInto(P, xforms, P->weights, plan->dTris))) rc = pt_refit_kernels_(plan, "pt_pose_geometry");
     if (rc) {
         const std::string msg = g_err;
         if (c->behind == P) {
-            int rc2 = poseInto(P, P->accepted.empty() ? nullptr : P->accepted.data(), plan->dTris);
+            int rc2 = poseInto(P, P->accepted.empty() ? nullptr : P->accepted.data(), P->acceptedWeights, plan->dTris);
             if (!rc2) rc2 = pt_refit_kernels_(plan, "pt_pose_geometry");
             if (rc2) return rc2;
         }
@@ -272,6 +298,7 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     if ((rc = movePatchRecords(c, plan, roots, ellip, &unordered))) return rc;
     c->behind = P;                                                // a pose the context was behind on before is superseded
     P->accepted.assign(xforms, xforms + xformBytes / 4);
+    P->acceptedWeights = P->weights;
     if (ellip) c->buf.ellip.assign(ellip, ellip + ellipBytes / 4);
     moveAccepted(c, ellip != nullptr);
     bool rebuilt = false;
@@ -304,7 +331,7 @@ int pt_debug_pose_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
         return fail(PT_ERR_ARG, "pt_debug_pose_time: bad argument");
     if (P->skinned) return fail(PT_ERR_ARG, "pt_debug_pose_time: a skinned pose has no part table (pt_debug_skin_time times its kernels)");
     std::vector<float> tris((size_t)P->nTris * 40);
-    int rc = poseToHost(P, xforms, tris.data());                  // (the scratch copy and the matrices are in place afterwards)
+    int rc = poseToHost(P, xforms, {}, tris.data());              // (the scratch copy and the matrices are in place afterwards; unmorphed)
     if (rc) return rc;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
@@ -361,6 +388,89 @@ int pt_debug_pose_scratch(pt_pose* P, float* trisOut, size_t triBytes) {
     const hipStream_t st = P->plan->stream;
     HIP_TRY(hipSetDevice(P->device));
     if (P->nTris) HIP_TRY(hipMemcpyAsync(trisOut, P->dScratch, triBytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+// ---- include/pt_morph.h
+
+int pt_morph_attach(pt_pose* P, int nTargets, const int64_t* targetStart, size_t startBytes, const int32_t* entryCorner, size_t cornerBytes, const float* entryDelta,
+                    size_t deltaBytes) {
+    const bool live = poseLive(P);
+    // which corners the pose's rule moves: from the part ids or the bone table, which lie on the device
+    std::vector<unsigned char> moved;
+    if (live && targetStart && entryCorner && entryDelta && !P->nTargets && P->nTris) {
+        const hipStream_t st = P->plan->stream;
+        HIP_TRY(hipSetDevice(P->device));
+        moved.resize((size_t)P->nTris * 3);
+        std::vector<int32_t> words((size_t)P->nTris * (P->skinned ? 12 : 1));
+        HIP_TRY(hipMemcpyAsync(words.data(), P->skinned ? P->dBone : P->dPart, words.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t q = 0; q < moved.size(); q++) moved[q] = (P->skinned ? words[4 * q] : words[q / 3]) >= 0;
+    }
+    if (int rc = fail(ptp::checkMorphAttach(live, live && P->nTargets, nTargets, targetStart, startBytes, entryCorner, cornerBytes, entryDelta, deltaBytes,
+                                            live ? (size_t)P->nTris : 0, moved.data())))
+        return rc;
+    if (P->stale) return fail(PT_ERR_SCENE, "pt_morph_attach: the scene was uploaded since pt_pose_create");
+    ptp::MorphRows rows;
+    ptp::morphRows(nTargets, targetStart, entryCorner, entryDelta, (size_t)P->nTris * 3, rows);
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    Dev<float> rest, w; Dev<int32_t> corner, row; Dev<ptp::MorphEntry> entry;       // the pose changes only once every allocation stands
+    HIP_TRY(rest.reset(P->nTris ? (size_t)P->nTris * 160 : 16));
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(rest, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(corner.upload(rows.corners.data(), rows.corners.size() * 4, st));
+    HIP_TRY(row.upload(rows.rowStart.data(), rows.rowStart.size() * 4, st));
+    HIP_TRY(entry.upload(rows.entries.data(), rows.entries.size() * sizeof(ptp::MorphEntry), st));
+    HIP_TRY(w.reset((size_t)nTargets * 4));
+    HIP_TRY(hipStreamSynchronize(st));
+    P->dMorphRest = std::move(rest); P->dMorphW = std::move(w); P->dMorphCorner = std::move(corner); P->dMorphRow = std::move(row); P->dMorphEntry = std::move(entry);
+    P->nTargets = nTargets; P->nAffected = (int64_t)rows.corners.size();
+    P->weights.assign((size_t)nTargets, 0.0f);
+    return PT_OK;
+}
+
+int pt_morph_weights(pt_pose* P, const float* weights, size_t weightBytes) {
+    const bool live = poseLive(P);
+    if (int rc = fail(ptp::checkMorphWeights(live, live && P->nTargets, weights, weightBytes, live ? P->nTargets : 0))) return rc;
+    P->weights.assign(weights, weights + P->nTargets);
+    return PT_OK;
+}
+
+// include/pt_debug.h: the device time of one k_morph_corners launch (the best of reps) under the given weights, into the morphed rest pose
+int pt_debug_morph_time(pt_pose* P, const float* weights, size_t weightBytes, int reps, float* msBest) {
+    const bool live = poseLive(P);
+    if (!msBest || reps < 1) return fail(PT_ERR_ARG, "pt_debug_morph_time: bad argument");
+    if (ptp::checkMorphWeights(live, live && P->nTargets, weights, weightBytes, live ? P->nTargets : 0).code) return fail(PT_ERR_ARG, "pt_debug_morph_time: bad argument");
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    HIP_TRY(hipMemcpyAsync(P->dMorphW, weights, (size_t)P->nTargets * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int rc = 0;
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    float best = 0.0f;
+    for (int k = 0; k < reps && !rc; k++) {
+        hipEventRecord(e0, st);
+        const hipError_t e = ptMorphLaunch(P->dRest, P->dMorphCorner, P->dMorphRow, P->dMorphEntry, P->dMorphW, P->nAffected, P->dMorphRest, st);
+        hipEventRecord(e1, st);
+        float ms = 0.0f;
+        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_morph_time: the launch failed");
+        if (k == 0 || ms < best) best = ms;
+    }
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (!rc) *msBest = best;
+    return rc;
+}
+
+// include/pt_debug.h: the kernel alone, under the weights last set (launched also when every weight is zero), and the morphed rest pose downloaded
+int pt_debug_morph_rest(pt_pose* P, float* trisOut, size_t triBytes) {
+    const bool live = poseLive(P);
+    if (!live || !P->nTargets || !trisOut || triBytes != (size_t)P->nTris * 160) return fail(PT_ERR_ARG, "pt_debug_morph_rest: bad argument");
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    if (const int rc = morphRest(P, P->weights.data())) return rc;
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(trisOut, P->dMorphRest, triBytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return PT_OK;
 }

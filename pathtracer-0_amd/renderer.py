@@ -207,6 +207,11 @@ def lib():
             L.pt_skin_create.argtypes = [vp, vp, sz, vp, sz, ci, C.POINTER(vp)]
             L.pt_debug_skin_time.argtypes = [vp, vp, sz, ci, ci, C.POINTER(C.c_float)]
             L.pt_debug_pose_scratch.argtypes = [vp, vp, sz]
+        if hasattr(L, "pt_morph_attach"):                     # include/pt_morph.h, and its kernel timer and read-back in include/pt_debug.h
+            L.pt_morph_attach.argtypes = [vp, ci, vp, sz, vp, sz, vp, sz]
+            L.pt_morph_weights.argtypes = [vp, vp, sz]
+            L.pt_debug_morph_time.argtypes = [vp, vp, sz, ci, C.POINTER(C.c_float)]
+            L.pt_debug_morph_rest.argtypes = [vp, vp, sz]
         _LIB = L
     return _LIB
 
@@ -393,6 +398,28 @@ class Pose:
         out = np.empty(self.n_tris * 40, np.float32)
         _check(self._L.pt_pose_triangles(self._h, xp, x.nbytes, out.ctypes.data, out.nbytes))
         return out
+
+    def morph_attach(self, targets):
+        """Attach morph targets (pt_morph_attach, include/pt_morph.h): targets is a list of (corners int32[m], deltas float32[m, 6]) — corner
+        3 * k + c of triangle k, and dx dy dz for its vertex, dnx dny dnz for its normal.  Once per pose; every weight is 0 afterwards."""
+        if not hasattr(self._L, "pt_morph_attach"):
+            raise RuntimeError("this libpt_hip.so has no pt_morph_attach (include/pt_morph.h): no fallback")
+        corners = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c, _ in targets]
+        deltas = [np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 6) for _, d in targets]
+        assert all(len(c) == len(d) for c, d in zip(corners, deltas)), "one delta of 6 floats per corner"
+        start = np.zeros(len(targets) + 1, np.int64)
+        start[1:] = np.cumsum([c.size for c in corners])
+        corner = np.concatenate(corners + [np.zeros(0, np.int32)])
+        delta = np.concatenate(deltas + [np.zeros((0, 6), np.float32)]).reshape(-1)
+        _check(self._L.pt_morph_attach(self._h, len(targets), start.ctypes.data, start.nbytes, corner.ctypes.data, corner.nbytes, delta.ctypes.data, delta.nbytes))
+        self.n_targets = len(targets)
+
+    def morph_weights(self, w):
+        """one weight per target for the next Renderer.pose_geometry and Pose.triangles (pt_morph_weights)"""
+        if not hasattr(self._L, "pt_morph_weights"):
+            raise RuntimeError("this libpt_hip.so has no pt_morph_weights (include/pt_morph.h): no fallback")
+        w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+        _check(self._L.pt_morph_weights(self._h, w.ctypes.data, w.nbytes))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -585,6 +585,48 @@ def m3_records(wl, step, n_bones=5, a=0.04):
     return chain_records(n_bones, pivots, (0.0, 0.0, 1.0), float(step) * a)
 
 
+def ring_bulges(tris, moving, heights, width, amp):
+    """Morph targets of include/pt_morph.h for the corners `moving` (3 * k + c) of binding 3: target t is a ring-shaped bulge at height
+    heights[t] (+y), a Gaussian profile of the given width.  The vertex delta runs along the corner's rest normal with the profile's amplitude;
+    the normal delta tilts the normal against the profile's slope.  Both are functions of the corner's own rest floats, computed in binary64
+    and rounded once, so corners that share a vertex get identical entries.  -> a list of (corners int32[m], deltas float32[m, 6])"""
+    tris = np.asarray(tris, np.float32).reshape(-1, 40)
+    q = np.asarray(moving, np.int64).reshape(-1)
+    k, c = q // 3, q % 3
+    v = np.stack([tris[k, 4 * c + j] for j in range(3)], axis=1).astype(np.float64)
+    n = np.stack([tris[k, 12 + 4 * c + j] for j in range(3)], axis=1).astype(np.float64)
+    out = []
+    for h in heights:
+        u = (v[:, 1] - h) / width
+        g = amp * np.exp(-u * u)
+        named = g > 0.01 * amp
+        slope = -2.0 * u * g / width                              # d(profile) / dy
+        d = np.zeros((q.size, 6))
+        d[:, :3] = g[:, None] * n
+        d[:, 4] = -slope                                          # first order: the normal leans away from the rising side
+        out.append((q[named].astype(np.int32), d[named].astype(np.float32)))
+    return out
+
+
+def m4_weights(step, n_targets=3):
+    """the morph weights of m4_bulging(step): target t swells and shrinks at its own pace; step 0 is the unmorphed pose"""
+    return np.abs(np.sin(0.4 * float(step) * (np.arange(n_targets) + 1.0))).astype(np.float32)
+
+
+def m4_bulging(step=0, W=96, H=54, n_bones=5, a=0.04, n_targets=3, **kw):
+    """M4 at `step`, the morph workload of include/pt_morph.h (not a BASELINE config): M3's tube and skin plus n_targets ring-shaped bulges at
+    evenly spaced heights of the tube's side.  -> (the rest pose's workload, corner_bone, corner_weight, the targets, the records, the morph
+    weights); only the last two depend on step."""
+    wl, bone, weight, X = m3_bending(step, W, H, n_bones, a, **kw)
+    wl.name = "M4"
+    first, n_side, _ = wl.info["tube"]
+    cx, y0, y1, cz = wl.info["axis"]
+    moving = np.arange(3 * first, 3 * (first + n_side))
+    heights = [y0 + (y1 - y0) * (t + 1.0) / (n_targets + 1.0) for t in range(n_targets)]
+    targets = ring_bulges(wl.buffers[3], moving, heights, 0.12 * (y1 - y0), 0.05)
+    return wl, bone, weight, targets, X, m4_weights(step, n_targets)
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then
@@ -672,6 +714,8 @@ def build(name, W=None, H=None, **kw):
         return m2_relit(kw.pop("step", 0), W or 96, H or 54, **kw)
     if name == "M3":
         return m3_tube(W or 96, H or 54, **kw)
+    if name == "M4":
+        return m4_bulging(kw.pop("step", 0), W or 96, H or 54, **kw)[0]
     cfg = CONFIGS[name]
     W = cfg["W"] if W is None else W
     H = cfg["H"] if H is None else H
