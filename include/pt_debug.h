@@ -92,6 +92,13 @@ int pt_debug_morph_time(struct pt_pose* pose, const float* weights, size_t weigh
  * triangle: the tests hold the kernel to the model this way.  PT_ERR_ARG: a null or destroyed pose, a pose without a morph, null tris_out,
  * tri_bytes != n_tris * 160. */
 int pt_debug_morph_rest(struct pt_pose* pose, float* tris_out, size_t tri_bytes);
+/* The device time of the two launches of include/pt_normals.h (scripts/normals_probe.py): the pose of xforms under the morph weights last set is
+ * written into the scratch copy once, with the pose rule's normals; then k_normals_faces plus one statement of the gather (which = 0 one lane
+ * per non-empty vertex, 1 one lane per corner with an id >= 0) run over it, the best of reps, HIP events on the pose's stream.  Nothing of the
+ * context changes, and the mode that pt_normals_mode set stays.  pt_debug_pose_scratch afterwards reads the work of the statement asked for.
+ * PT_ERR_ARG: a null or destroyed pose, a pose without normals, n_parts == 0, null xforms, xform_bytes != n_parts * 96, reps < 1, an unknown
+ * statement, null ms_best. */
+int pt_debug_normals_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int which, int reps, float* ms_best);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,7 @@
  * pose and refit again with both, so that a later settle delivers them; none accepted yet is the rest pose, unmorphed; a pose accepted before the
  * attach counts as accepted with every weight 0.
  *
+ * (A table without normal deltas, or a deformation too large for them: include/pt_normals.h recomputes the normals from the posed surface.)
  * NOT BUILT: a detach; more than 1024 targets; 16-bit packed tables; posed ellipsoids; JNI natives; rebuilding degraded trees.
  */
 #ifndef PT_MORPH_H

@@ -10,6 +10,7 @@
  *   - a part id per triangle, tri_part[k] in [-1, n_parts).  Part -1 is static: its triangles are the rest pose's, bit for bit;
  *   - a refit plan of its own (include/pt_refit.h) over the context's bindings 10-13.
  * (include/pt_skin.h makes a pose object under a second rule — up to four records blended per corner — that every call below takes as well.)
+ * (include/pt_normals.h attaches vertex ids to a pose object of either kind: the normals are then recomputed from the posed surface after the rule.)
  * (include/pt_morph.h attaches morph targets to a pose object of either kind: the rule then starts from the morphed rest pose.  NOT BUILT for
  *  any of the three: posed ellipsoids; JNI natives; rebuilding degraded trees.)
  *

@@ -38,6 +38,7 @@
  * rule on a part table the skin does not have; pt_debug_skin_time times the skin's.
  *
  * (Morph targets — per-corner offsets under one weight per target, applied to the rest pose ahead of this rule — are include/pt_morph.h's.)
+ * (Normals recomputed from the skinned surface, instead of the blended N this rule applies, are include/pt_normals.h's.)
  * NOT BUILT: dual-quaternion blending; more than four slots; 16-bit packed tables (48 bytes per triangle instead of 96); posed ellipsoids; JNI
  * natives; rebuilding degraded trees.
  */

@@ -6,7 +6,9 @@
 // tables instead of the part ids, pt_skin.hip's kernel behind pt_skin_launch.hpp instead of k_pose, pt_skin_rule.hpp's checks; poseInto is
 // the one place that tells them apart.  A morph (include/pt_morph.h, pt_morph_attach) belongs to either kind: pt_morph.hip's kernel behind
 // pt_morph_launch.hpp writes the morphed copy of the rest pose's affected corners, which poseInto hands to the pose's rule in place of dRest;
-// pt_morph_rule.hpp's checks and inverted index.
+// pt_morph_rule.hpp's checks and inverted index.  Normals (include/pt_normals.h, pt_normals_attach) belong to either kind too: pt_normals.hip's
+// two launches behind pt_normals_launch.hpp recompute the normals of the welded corners at the end of poseInto, from what the pose's rule wrote;
+// pt_normals_rule.hpp's checks and inverted index.
 //
 // What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
 // kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
@@ -18,11 +20,14 @@ extern "C++" {
 #include "pt_skin_rule.hpp"
 #include "pt_morph_launch.hpp"
 #include "pt_morph_rule.hpp"
+#include "pt_normals_launch.hpp"
+#include "pt_normals_rule.hpp"
 #include <set>
 }
 #include "../../../include/pt_pose.h"
 #include "../../../include/pt_skin.h"
 #include "../../../include/pt_morph.h"
+#include "../../../include/pt_normals.h"
 
 struct pt_pose {
     pt_ctx* ctx = nullptr;              // the context (a group's: the group) it was created on and belongs to
@@ -40,6 +45,13 @@ struct pt_pose {
     Dev<float> dMorphRest, dMorphW; Dev<int32_t> dMorphCorner, dMorphRow; Dev<ptp::MorphEntry> dMorphEntry;
     std::vector<float> weights;         // as pt_morph_weights set them last (after the attach: zeros)
     std::vector<float> acceptedWeights; // those of the last accepted pose; empty: every weight 0 (none accepted yet, or accepted before the attach)
+    // include/pt_normals.h: hasNormals once normals are attached.  The inverted index of pt_normals_rule.hpp (the listed triangles, the row starts
+    // of the non-empty vertices, their corners, per corner its row) and the face vectors, 16 bytes per triangle, indexed by triangle id
+    bool hasNormals = false; uint32_t normalsFlags = 0;
+    int64_t nNrmTris = 0, nNrmRows = 0, nNrmCorners = 0;
+    Dev<int32_t> dNrmTri, dNrmRow, dNrmCorner, dNrmCornerRow; Dev<float> dNrmFace;
+    int normalsMode = 0;                // as pt_normals_mode set it last (after the attach: 1)
+    int acceptedMode = 0;               // that of the last accepted pose (none accepted yet, or accepted before the attach: 0)
     bool stale = false;                 // the scene was uploaded since pt_pose_create
 };
 
@@ -48,6 +60,7 @@ namespace {
 std::mutex g_posesMutex;
 std::set<pt_pose*> g_poses;             // the live poses: a destroyed one is refused, not followed
 constexpr PtPoseKernel POSE_KERNEL = PT_POSE_PER_QUAD;      // the faster of the two at 100 k and at 1 M triangles (scripts/pose_probe.py); pt_debug_pose_time runs either
+constexpr PtNormalsKernel NORMALS_KERNEL = PT_NORMALS_PER_CORNER;   // 5 % slower on C4's mesh, 10 % faster on the 1 M height field: the shorter summed over both (71.9 against 77.4 us), and twice as fast on a table with one long row (scripts/normals_probe.py); pt_debug_normals_time runs either
 constexpr PtSkinKernel SKIN_KERNEL = PT_SKIN_PER_CORNER;    // faster with four slots at 100 k and at 1 M triangles, tied at 100 k and 2 % slower at 1 M with two: the shorter summed over both slot counts at 1 M (scripts/skin_probe.py); pt_debug_skin_time runs either
 
 bool poseLive(pt_pose* p) {
@@ -63,9 +76,18 @@ int morphRest(pt_pose* P, const float* weights) {
     return 0;
 }
 
-// the pose of `xforms` (host; nullptr: the rest pose, unmorphed) under the morph weights `weights` (host; empty: no morph, or every weight 0) into
-// dst, which holds the rest pose's static triangles; asynchronous on the plan's stream
-int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights, float* dst) {
+// the normals of dst's welded corners from dst's vertices, by the statement `which` of the gather; asynchronous on the plan's stream
+int normalsInto(pt_pose* P, float* dst, PtNormalsKernel which) {
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(ptNormalsFacesLaunch(dst, P->dNrmTri, P->nNrmTris, (P->normalsFlags & PT_NORMALS_FLIP) != 0, P->dNrmFace, st));
+    HIP_TRY(ptNormalsGatherLaunch(P->dNrmFace, P->dNrmRow, P->nNrmRows, P->dNrmCorner, P->dNrmCornerRow, P->nNrmCorners, dst, which, st));
+    return 0;
+}
+
+// the pose of `xforms` (host; nullptr: the rest pose, unmorphed, its normals as they are) under the morph weights `weights` (host; empty: no morph,
+// or every weight 0) and the normals mode `mode` (1: recomputed where normals are attached) into dst, which holds the rest pose's static
+// triangles; asynchronous on the plan's stream
+int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights, int mode, float* dst) {
     const hipStream_t st = P->plan->stream;
     if (!xforms || P->nParts == 0) {                              // (n_parts == 0: a morph has no entries)
         if (P->nTris) HIP_TRY(hipMemcpyAsync(dst, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
@@ -80,11 +102,12 @@ int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights,
     HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
     if (P->skinned) HIP_TRY(ptSkinLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dX, dst, SKIN_KERNEL, st));
     else HIP_TRY(ptPoseLaunch(rest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
+    if (P->hasNormals && mode == 1) return normalsInto(P, dst, NORMALS_KERNEL);
     return 0;
 }
 
 // P = the rule applied to the rest pose, on the host; the plan's working copies are not touched
-int poseToHost(pt_pose* P, const float* xforms, const std::vector<float>& weights, float* out) {
+int poseToHost(pt_pose* P, const float* xforms, const std::vector<float>& weights, int mode, float* out) {
     const hipStream_t st = P->plan->stream;
     HIP_TRY(hipSetDevice(P->device));
     if (!P->scratchReady) {
@@ -92,7 +115,7 @@ int poseToHost(pt_pose* P, const float* xforms, const std::vector<float>& weight
         if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
         P->scratchReady = true;
     }
-    if (const int rc = poseInto(P, xforms, weights, P->dScratch)) return rc;
+    if (const int rc = poseInto(P, xforms, weights, mode, P->dScratch)) return rc;
     if (P->nTris) HIP_TRY(hipMemcpyAsync(out, P->dScratch, (size_t)P->nTris * 160, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -160,7 +183,7 @@ int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, cons
     int rc;
     if (!c->multi && (rc = settleScene(c))) return rc;            // (the move uploads into the plan's working copy)
     std::vector<float> tris((size_t)P->nTris * 40);
-    if ((rc = poseToHost(P, xforms, P->weights, tris.data()))) return rc;
+    if ((rc = poseToHost(P, xforms, P->weights, P->normalsMode, tris.data()))) return rc;
     // (a group's sequence goes through pt_set_buffer, which marks the context's poses stale: these uploads are the pose's own — binding 3 is the rule
     //  applied to the rest pose, the trees are the plan's — so every pose stays what it was, as on the in-place path)
     std::vector<char> was;
@@ -170,6 +193,7 @@ int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, cons
     if (rc) return rc;
     P->accepted.assign(xforms, xforms + xformBytes / 4);
     P->acceptedWeights = P->weights;
+    P->acceptedMode = P->normalsMode;
     return PT_OK;
 }
 
@@ -237,7 +261,7 @@ int pt_skin_create(pt_ctx* c, const int32_t* bone, size_t boneBytes, const float
 int pt_pose_triangles(pt_pose* P, const float* xforms, size_t xformBytes, float* trisOut, size_t triBytes) {
     const bool live = poseLive(P);
     if (int rc = fail(ptp::checkPoseTriangles(live, xforms, xformBytes, live ? P->nParts : 0, trisOut, triBytes, live ? (size_t)P->nTris : 0))) return rc;
-    return poseToHost(P, xforms, P->weights, trisOut);
+    return poseToHost(P, xforms, P->weights, P->normalsMode, trisOut);
 }
 
 int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
@@ -271,11 +295,11 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     }
 
     // pose + refit: the plan's working copies only.  A refusal puts back what a settle would have delivered
-    if (!(rc = poseInto(P, xforms, P->weights, plan->dTris))) rc = pt_refit_kernels_(plan, "pt_pose_geometry");
+    if (!(rc = poseInto(P, xforms, P->weights, P->normalsMode, plan->dTris))) rc = pt_refit_kernels_(plan, "pt_pose_geometry");
     if (rc) {
         const std::string msg = g_err;
         if (c->behind == P) {
-            int rc2 = poseInto(P, P->accepted.empty() ? nullptr : P->accepted.data(), P->acceptedWeights, plan->dTris);
+            int rc2 = poseInto(P, P->accepted.empty() ? nullptr : P->accepted.data(), P->acceptedWeights, P->acceptedMode, plan->dTris);
             if (!rc2) rc2 = pt_refit_kernels_(plan, "pt_pose_geometry");
             if (rc2) return rc2;
         }
@@ -299,6 +323,7 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     c->behind = P;                                                // a pose the context was behind on before is superseded
     P->accepted.assign(xforms, xforms + xformBytes / 4);
     P->acceptedWeights = P->weights;
+    P->acceptedMode = P->normalsMode;
     if (ellip) c->buf.ellip.assign(ellip, ellip + ellipBytes / 4);
     moveAccepted(c, ellip != nullptr);
     bool rebuilt = false;
@@ -331,7 +356,7 @@ int pt_debug_pose_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
         return fail(PT_ERR_ARG, "pt_debug_pose_time: bad argument");
     if (P->skinned) return fail(PT_ERR_ARG, "pt_debug_pose_time: a skinned pose has no part table (pt_debug_skin_time times its kernels)");
     std::vector<float> tris((size_t)P->nTris * 40);
-    int rc = poseToHost(P, xforms, {}, tris.data());              // (the scratch copy and the matrices are in place afterwards; unmorphed)
+    int rc = poseToHost(P, xforms, {}, 0, tris.data());           // (the scratch copy and the matrices are in place afterwards; unmorphed, the rule's normals)
     if (rc) return rc;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
@@ -473,4 +498,72 @@ int pt_debug_morph_rest(pt_pose* P, float* trisOut, size_t triBytes) {
     if (P->nTris) HIP_TRY(hipMemcpyAsync(trisOut, P->dMorphRest, triBytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return PT_OK;
+}
+
+// ---- include/pt_normals.h
+
+int pt_normals_attach(pt_pose* P, const int32_t* cornerVertex, size_t vertexBytes, int64_t nVertices, uint32_t flags) {
+    const bool live = poseLive(P);
+    // which corners the pose's rule moves: from the part ids or the bone table, which lie on the device
+    std::vector<unsigned char> moved;
+    if (live && cornerVertex && !P->hasNormals && P->nTris) {
+        const hipStream_t st = P->plan->stream;
+        HIP_TRY(hipSetDevice(P->device));
+        moved.resize((size_t)P->nTris * 3);
+        std::vector<int32_t> words((size_t)P->nTris * (P->skinned ? 12 : 1));
+        HIP_TRY(hipMemcpyAsync(words.data(), P->skinned ? P->dBone : P->dPart, words.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t q = 0; q < moved.size(); q++) moved[q] = (P->skinned ? words[4 * q] : words[q / 3]) >= 0;
+    }
+    if (int rc = fail(ptp::checkNormalsAttach(live, live && P->hasNormals, cornerVertex, vertexBytes, nVertices, flags, live ? (size_t)P->nTris : 0, moved.data()))) return rc;
+    if (P->stale) return fail(PT_ERR_SCENE, "pt_normals_attach: the scene was uploaded since pt_pose_create");
+    ptp::NormalRows rows;
+    ptp::normalRows(cornerVertex, (size_t)P->nTris, nVertices, rows);
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    Dev<int32_t> tri, row, corner, cornerRow; Dev<float> face;       // the pose changes only once every allocation stands
+    HIP_TRY(tri.upload(rows.tris.data(), rows.tris.size() * 4, st));
+    HIP_TRY(row.upload(rows.rowStart.data(), rows.rowStart.size() * 4, st));
+    HIP_TRY(corner.upload(rows.corners.data(), rows.corners.size() * 4, st));
+    HIP_TRY(cornerRow.upload(rows.cornerRow.data(), rows.cornerRow.size() * 4, st));
+    HIP_TRY(face.reset(P->nTris ? (size_t)P->nTris * 16 : 16));
+    HIP_TRY(hipStreamSynchronize(st));
+    P->dNrmTri = std::move(tri); P->dNrmRow = std::move(row); P->dNrmCorner = std::move(corner); P->dNrmCornerRow = std::move(cornerRow); P->dNrmFace = std::move(face);
+    P->nNrmTris = (int64_t)rows.tris.size(); P->nNrmRows = (int64_t)rows.verts.size(); P->nNrmCorners = (int64_t)rows.corners.size();
+    P->normalsFlags = flags; P->hasNormals = true; P->normalsMode = 1;
+    return PT_OK;
+}
+
+int pt_normals_mode(pt_pose* P, int on) {
+    const bool live = poseLive(P);
+    if (int rc = fail(ptp::checkNormalsMode(live, live && P->hasNormals, on))) return rc;
+    P->normalsMode = on;
+    return PT_OK;
+}
+
+// include/pt_debug.h: the pose under the weights last set and the rule's normals into the scratch copy once, then the device time of the faces
+// launch plus the chosen statement of the gather over it (the best of reps)
+int pt_debug_normals_time(pt_pose* P, const float* xforms, size_t xformBytes, int which, int reps, float* msBest) {
+    const bool live = poseLive(P);
+    if (!live || !P->hasNormals || !msBest || reps < 1 || (which != PT_NORMALS_PER_VERTEX && which != PT_NORMALS_PER_CORNER) || !xforms || P->nParts < 1 ||
+        xformBytes != (size_t)P->nParts * 96)
+        return fail(PT_ERR_ARG, "pt_debug_normals_time: bad argument");
+    std::vector<float> tris((size_t)P->nTris * 40);
+    int rc = poseToHost(P, xforms, P->weights, 0, tris.data());     // (the scratch copy holds the pose's rule's work afterwards; synchronised)
+    if (rc) return rc;
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    const hipStream_t st = P->plan->stream;
+    float best = 0.0f;
+    for (int k = 0; k < reps && !rc; k++) {                          // (a launch reads vertices and writes normals: every repetition gives the same bits)
+        hipEventRecord(e0, st);
+        const int r = normalsInto(P, P->dScratch, (PtNormalsKernel)which);
+        hipEventRecord(e1, st);
+        float ms = 0.0f;
+        if (r || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_normals_time: the launch failed");
+        if (k == 0 || ms < best) best = ms;
+    }
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (!rc) *msBest = best;
+    return rc;
 }

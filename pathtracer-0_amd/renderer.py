@@ -212,6 +212,10 @@ def lib():
             L.pt_morph_weights.argtypes = [vp, vp, sz]
             L.pt_debug_morph_time.argtypes = [vp, vp, sz, ci, C.POINTER(C.c_float)]
             L.pt_debug_morph_rest.argtypes = [vp, vp, sz]
+        if hasattr(L, "pt_normals_attach"):                   # include/pt_normals.h, and its kernel timer in include/pt_debug.h
+            L.pt_normals_attach.argtypes = [vp, vp, sz, C.c_int64, C.c_uint32]
+            L.pt_normals_mode.argtypes = [vp, ci]
+            L.pt_debug_normals_time.argtypes = [vp, vp, sz, ci, ci, C.POINTER(C.c_float)]
         _LIB = L
     return _LIB
 
@@ -420,6 +424,24 @@ class Pose:
             raise RuntimeError("this libpt_hip.so has no pt_morph_weights (include/pt_morph.h): no fallback")
         w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
         _check(self._L.pt_morph_weights(self._h, w.ctypes.data, w.nbytes))
+
+    def normals_attach(self, corner_vertex, n_vertices=None, flip=False):
+        """Attach recomputed normals (pt_normals_attach, include/pt_normals.h): corner_vertex holds one id per corner (3 per triangle), -1 for a
+        corner that keeps the pose rule's normal; corners with the same id >= 0 are one vertex and get the same normal.  n_vertices: one more
+        than the largest id when not given.  Once per pose; the mode is 1 afterwards."""
+        if not hasattr(self._L, "pt_normals_attach"):
+            raise RuntimeError("this libpt_hip.so has no pt_normals_attach (include/pt_normals.h): no fallback")
+        ids = np.ascontiguousarray(corner_vertex, dtype=np.int32).reshape(-1)
+        if n_vertices is None:
+            n_vertices = int(ids.max()) + 1 if ids.size else 0
+        _check(self._L.pt_normals_attach(self._h, ids.ctypes.data, ids.nbytes, int(n_vertices), 1 if flip else 0))
+        self.n_vertices = int(n_vertices)
+
+    def normals_mode(self, on):
+        """0: the pose rule's normals, 1: recomputed, for the next Renderer.pose_geometry and Pose.triangles (pt_normals_mode)"""
+        if not hasattr(self._L, "pt_normals_mode"):
+            raise RuntimeError("this libpt_hip.so has no pt_normals_mode (include/pt_normals.h): no fallback")
+        _check(self._L.pt_normals_mode(self._h, int(on)))
 
     def close(self):
         if getattr(self, "_h", None):

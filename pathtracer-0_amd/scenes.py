@@ -627,6 +627,47 @@ def m4_bulging(step=0, W=96, H=54, n_bones=5, a=0.04, n_targets=3, **kw):
     return wl, bone, weight, targets, X, m4_weights(step, n_targets)
 
 
+def weld_corners(tris, moved, keep_creases=True):
+    """The vertex ids of include/pt_normals.h for binding 3 (40 floats per triangle): the corners `moved` (3 * k + c, those the pose's rule moves)
+    with a bitwise-equal rest position are one vertex; with keep_creases they must have a bitwise-equal rest normal as well, so a hard edge
+    stays hard.  Ids are dense and ascend with the first corner that names them.  All other corners get -1, and so does a corner whose vertex an
+    earlier corner of its own triangle names already (a degenerate triangle: an id may stand once per triangle).
+    -> (corner_vertex int32[3 * n_tris], n_vertices)"""
+    t = np.ascontiguousarray(tris, np.float32).reshape(-1, 40).view(np.uint32)
+    q = np.unique(np.asarray(moved, np.int64).reshape(-1))
+    ids = np.full(3 * t.shape[0], -1, np.int32)
+    if q.size == 0:
+        return ids, 0
+    k, c = q // 3, q % 3
+    cols = [4 * c + j for j in range(3)] + ([12 + 4 * c + j for j in range(3)] if keep_creases else [])
+    key = np.stack([t[k, col] for col in cols], axis=1)
+    _, first, inverse = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    inverse = inverse.reshape(-1)
+    order = np.argsort(np.argsort(first))                            # dense ids in the order of each vertex's first corner
+    g = order[inverse].astype(np.int32)
+    # once per triangle: q ascends, so a triangle's corners are neighbours
+    same1 = (k[1:] == k[:-1]) & (g[1:] == g[:-1])
+    same2 = (k[2:] == k[:-2]) & (g[2:] == g[:-2])
+    g[1:][same1] = -1
+    g[2:][same2] = -1
+    ids[q] = g
+    used = np.unique(g[g >= 0])
+    if used.size != int(first.size):                                 # an id that only dropped corners named: renumber densely
+        remap = np.full(int(first.size), -1, np.int32); remap[used] = np.arange(used.size, dtype=np.int32)
+        ids[ids >= 0] = remap[ids[ids >= 0]]
+    return ids, int(used.size)
+
+
+def m5_rippling(step=0, W=96, H=54, **kw):
+    """M5 at `step`, the workload of include/pt_normals.h (not a BASELINE config): M4's tube, skin and targets plus the welded vertex ids of the
+    tube's side, from which its normals are recomputed after every step.  -> what m4_bulging returns, then corner_vertex and n_vertices."""
+    wl, bone, weight, targets, X, w = m4_bulging(step, W, H, **kw)
+    wl.name = "M5"
+    first, n_side, _ = wl.info["tube"]
+    ids, n_vertices = weld_corners(wl.buffers[3], np.arange(3 * first, 3 * (first + n_side)), keep_creases=True)
+    return wl, bone, weight, targets, X, w, ids, n_vertices
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then
@@ -716,6 +757,8 @@ def build(name, W=None, H=None, **kw):
         return m3_tube(W or 96, H or 54, **kw)
     if name == "M4":
         return m4_bulging(kw.pop("step", 0), W or 96, H or 54, **kw)[0]
+    if name == "M5":
+        return m5_rippling(kw.pop("step", 0), W or 96, H or 54, **kw)[0]
     cfg = CONFIGS[name]
     W = cfg["W"] if W is None else W
     H = cfg["H"] if H is None else H
