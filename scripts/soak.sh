@@ -4,6 +4,8 @@
 # the timed region), rings and image ring wrap many times; the line's parity block compares frames of the timed workload with the oracle.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; T=${1:-soak}; O=$R/gpurun_out/$T; mkdir -p $O; cd $R
 timeout -k 10 900 python3 scripts/api_fuzz.py ${2:-100001} ${3:-1500} 2>&1 | tail -4 | tee $O/api_fuzz.txt
+# the image-space and geometry calls in random orders against a cold twin (scripts/image_fuzz.py, the same seeds); it exits with 2 at a device fault, and nothing more is started then
+IMAGE_FUZZ_OUT=$O timeout -k 10 900 python3 scripts/image_fuzz.py ${2:-100001} ${3:-1500} 2>&1 | tail -4 | tee $O/image_fuzz.txt; [ ${PIPESTATUS[0]} -eq 2 ] && exit 2
 timeout -k 10 900 python3 bench.py --steps 150 --warmup 2 > $O/soak.json 2> $O/soak.err; echo "soak rc=$?"
 python3 -c "
 import json

@@ -10,7 +10,7 @@
 //   create W H                        pt_create
 //   inputs K                          the four uploads of Parameters, ORIGIN, ROTATION and MOUSE_POS (each drops the record caches, as every upload
 //                                     does).  K: 0 not set (a context's first state only), 1 a camera, 2 another origin, 3 camera 1 with DEBUG = 1,
-//                                     4 camera 1 with a resolution that is not the image's
+//                                     4 camera 1 with a resolution that is not the image's, 5 and above: camera 1 at yet another origin each
 //   upload BINDING ok|refused         pt_set_buffer: camera (an ORIGIN equal to the one bound), geometry (3), implicits (5), materials (14), or
 //                                     other (6, which no upload takes); refused: the upload fails its check (camera: too short; geometry: a size
 //                                     that is no multiple of 40 floats; implicits and materials are never refused)
@@ -22,6 +22,9 @@
 //                                     1 or 2; R = 0 for feat), or under the image's camera (what pt_motion_mark and a reprojection from a changed
 //                                     camera ask for; nothing without a camera)
 //   mark | moved | hold | merge       pt_motion_mark, pt_reproject_frame_moved, pt_history_hold, pt_history_merge
+//   moved-bilinear                    pt_reproject_frame_moved_bilinear
+//   move                              an accepted pt_move_geometry or pt_pose_geometry without ellipsoids (moveAccepted of pt_move_host.hpp)
+//   despeckle-frame                   pt_despeckle_frame
 //   reproject plain|through|bilinear  pt_reproject_frame, pt_reproject_frame_through (rule 1), pt_reproject_frame_bilinear
 //   claim                             claimFrameConstants (pt_debug_intersect)
 // THE TRACE, per script line after `script`: "cache NAME hit|fill" for every record cache asked, "cache NAME invalidated" for every one that was
@@ -88,10 +91,11 @@ struct Ctx {
         if (!bound) return fail(PT_ERR_ARG, "Parameters (binding 4) not set");
         return ensureRecords(rule ? RC_THRU : RC_FEAT, in, rule);
     }
-    int reprojectImage(const char* who, bool moved, const pt_through_rule* chain) {
+    int reprojectImage(const char* who, bool moved, const pt_through_rule* chain, bool taps = false) {
         const std::string w(who);
         int rc;
         if ((rc = fail(hist.usableInputs(current(), w, "carry")))) return rc;
+        if (moved && taps && !hist.camera().valid && !hist.markValid()) return PT_OK;
         const ReprojectPlan plan = hist.planReproject(in, moved, w);
         if ((rc = fail(plan.refused))) return rc;
         if (plan.nothing) return PT_OK;
@@ -129,6 +133,19 @@ struct Ctx {
         hist.holdSpent();
         return 0;
     }
+    int despeckleFrame() {                                        // pt_despeckle_host.hpp with `store`
+        int rc;
+        if ((rc = fail(hist.usableInputs(current(), "pt_despeckle_frame", "tell apart")))) return rc;
+        if ((rc = currentRecords(nullptr))) return rc;
+        recordCamera();                                           // storeReprojected
+        return 0;
+    }
+    int moveAccepted() {                                          // pt_move_host.hpp
+        hist.uploadBegins();
+        hist.sceneBufferAccepted(PT_BIND_TRIANGLES);
+        hist.sceneBufferAccepted(PT_BIND_BVHDATA);
+        return 0;
+    }
     int W = 0, H = 0;
 };
 
@@ -136,7 +153,7 @@ static FrameIn inputsOf(int k) {
     FrameIn f{};
     const float P[12] = {0.5f, 1.0f, 32.0f, 0.5625f, 2.0f, 4.0f, 0.0f, 0.0f, 3.0f, 1.0f, 0.0f, 0.0f};
     for (int i = 0; i < 12; i++) f.params[i] = P[i];
-    f.origin[0] = k == 2 ? 1.25f : 0.0f; f.origin[1] = 1.0f; f.origin[2] = -4.0f;
+    f.origin[0] = k == 2 ? 1.25f : k >= 5 ? 0.125f * (float)k : 0.0f; f.origin[1] = 1.0f; f.origin[2] = -4.0f;
     f.mouse[0] = -1.0f; f.mouse[1] = -1.0f;
     if (k == 3) f.params[10] = 1.0f;
     if (k == 4) f.params[2] = 64.0f;
@@ -167,7 +184,7 @@ int main(int argc, char** argv) {
         int rc = 0;
         if (verb == "inputs") {
             ss >> k;
-            if (k < 0 || k > 4 || (k == 0 && c->bound)) return die("bad inputs: " + line);
+            if (k < 0 || (k == 0 && c->bound)) return die("bad inputs: " + line);
             for (int n = 0; n < 4 && k; n++) c->hist.uploadBegins();
             if (k) { c->bound = true; c->in = inputsOf(k); }
         } else if (verb == "upload") {
@@ -190,6 +207,9 @@ int main(int argc, char** argv) {
             else if (c->hist.camera().valid) rc = c->ensureRecords(rule ? RC_THRU_H : RC_FEAT_H, FrameIn(c->hist.camera().in), rule);
         } else if (verb == "mark") rc = c->motionMark();
         else if (verb == "moved") rc = c->reprojectImage("pt_reproject_frame_moved", true, nullptr);
+        else if (verb == "moved-bilinear") rc = c->reprojectImage("pt_reproject_frame_moved_bilinear", true, nullptr, true);
+        else if (verb == "move") rc = c->moveAccepted();
+        else if (verb == "despeckle-frame") rc = c->despeckleFrame();
         else if (verb == "hold") rc = c->historyHold();
         else if (verb == "merge") rc = c->historyMerge();
         else if (verb == "reproject") {
