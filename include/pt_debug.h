@@ -78,9 +78,13 @@ int pt_debug_pose_time(struct pt_pose* pose, const float* xforms, size_t xform_b
 /* The same for a skinned pose of include/pt_skin.h (scripts/skin_probe.py): which = 0 one lane per float4, 1 one lane per corner.  PT_ERR_ARG: as
  * above, and a pose that pt_skin_create did not make.  pt_debug_pose_time in turn refuses a skinned pose with PT_ERR_ARG: it has no part table. */
 int pt_debug_skin_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int which, int reps, float* ms_best);
-/* The pose's scratch copy (40 floats per triangle) as the last pt_pose_triangles, pt_debug_pose_time or pt_debug_skin_time left it.
- * pt_debug_skin_time fills it with the rest pose before its launches, so what is read after it is the work of the kernel it was asked for: the
- * tests compare both statements with the model this way.  PT_ERR_ARG: a null or destroyed pose, null tris_out, tri_bytes != n_tris * 160, no
+/* The same for a DQ pose of include/pt_skin_dq.h (scripts/skin_dq_probe.py): the best of reps of the conversion launch (k_dq_records) plus the
+ * blend launch (k_skin_dq_corners), one pair of HIP events around both.  PT_ERR_ARG: as above (there is one statement, so no `which`), and every
+ * pose that pt_skin_dq_create did not make.  pt_debug_pose_time and pt_debug_skin_time in turn refuse a DQ pose with PT_ERR_ARG. */
+int pt_debug_skin_dq_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int reps, float* ms_best);
+/* The pose's scratch copy (40 floats per triangle) as the last pt_pose_triangles, pt_debug_pose_time, pt_debug_skin_time or pt_debug_skin_dq_time
+ * left it.  pt_debug_skin_time and pt_debug_skin_dq_time fill it with the rest pose before their launches, so what is read after them is the work
+ * of the kernels they were asked for: the tests compare the statements with the model this way.  PT_ERR_ARG: a null or destroyed pose, null tris_out, tri_bytes != n_tris * 160, no
  * scratch copy yet. */
 int pt_debug_pose_scratch(struct pt_pose* pose, float* tris_out, size_t tri_bytes);
 /* The device time of ONE launch of k_morph_corners of include/pt_morph.h (scripts/morph_probe.py) under the given weights: the best of reps

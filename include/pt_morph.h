@@ -55,6 +55,7 @@
  * attach counts as accepted with every weight 0.
  *
  * (A table without normal deltas, or a deformation too large for them: include/pt_normals.h recomputes the normals from the posed surface.)
+ * (A pose of pt_skin_dq_create, include/pt_skin_dq.h, takes a morph as a pose of pt_skin_create does: its rule starts from the same morphed rest pose.)
  * NOT BUILT: a detach; more than 1024 targets; 16-bit packed tables; posed ellipsoids; JNI natives; rebuilding degraded trees.
  */
 #ifndef PT_MORPH_H

@@ -59,6 +59,7 @@
  * Nothing else is refused later.  THE LAST ACCEPTED POSE is the triple (records, weights, mode): a refusal while the context is behind on the pose
  * runs pose and refit again with all three, so that a later settle delivers them; a pose accepted before the attach counts as accepted with mode 0.
  *
+ * (A pose of pt_skin_dq_create, include/pt_skin_dq.h, takes normals as a pose of pt_skin_create does: they are recomputed from what its rule wrote.)
  * NOT BUILT: angle weights; a crease angle (scenes.weld_corners keeps hard edges by the rest normals instead); a detach; a scaled sum that
  * survives the overflow of the square; JNI natives.
  */

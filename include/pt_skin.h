@@ -39,7 +39,9 @@
  *
  * (Morph targets — per-corner offsets under one weight per target, applied to the rest pose ahead of this rule — are include/pt_morph.h's.)
  * (Normals recomputed from the skinned surface, instead of the blended N this rule applies, are include/pt_normals.h's.)
- * NOT BUILT: dual-quaternion blending; more than four slots; 16-bit packed tables (48 bytes per triangle instead of 96); posed ellipsoids; JNI
+ * (Dual-quaternion blending — the same tables under a rule that keeps the volume of what twists, where this one's blended matrix shrinks it —
+ * is include/pt_skin_dq.h's, pt_skin_dq_create.)
+ * NOT BUILT: more than four slots; 16-bit packed tables (48 bytes per triangle instead of 96); posed ellipsoids; JNI
  * natives; rebuilding degraded trees.
  */
 #ifndef PT_SKIN_H

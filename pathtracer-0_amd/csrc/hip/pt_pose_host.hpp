@@ -8,7 +8,9 @@
 // pt_morph_launch.hpp writes the morphed copy of the rest pose's affected corners, which poseInto hands to the pose's rule in place of dRest;
 // pt_morph_rule.hpp's checks and inverted index.  Normals (include/pt_normals.h, pt_normals_attach) belong to either kind too: pt_normals.hip's
 // two launches behind pt_normals_launch.hpp recompute the normals of the welded corners at the end of poseInto, from what the pose's rule wrote;
-// pt_normals_rule.hpp's checks and inverted index.
+// pt_normals_rule.hpp's checks and inverted index.  A DQ pose (include/pt_skin_dq.h, pt_skin_dq_create) is a skinned pose under a third rule: the same two
+// corner tables, pt_skin_dq.hip's two launches behind pt_skin_dq_launch.hpp (the records into dDq, a table the pose owns, then the corners)
+// instead of pt_skin.hip's one, pt_skin_dq_rule.hpp's CPU statement; again poseInto is the one place that tells them apart.
 //
 // What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
 // kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
@@ -18,6 +20,8 @@ extern "C++" {
 #include "pt_pose_rule.hpp"
 #include "pt_skin_launch.hpp"
 #include "pt_skin_rule.hpp"
+#include "pt_skin_dq_launch.hpp"
+#include "pt_skin_dq_rule.hpp"
 #include "pt_morph_launch.hpp"
 #include "pt_morph_rule.hpp"
 #include "pt_normals_launch.hpp"
@@ -26,6 +30,7 @@ extern "C++" {
 }
 #include "../../../include/pt_pose.h"
 #include "../../../include/pt_skin.h"
+#include "../../../include/pt_skin_dq.h"
 #include "../../../include/pt_morph.h"
 #include "../../../include/pt_normals.h"
 
@@ -36,6 +41,8 @@ struct pt_pose {
     Dev<float> dRest, dScratch, dX, dRows; Dev<int32_t> dPart, dRowIds;
     bool skinned = false;               // include/pt_skin.h: the rule blends records per corner, from dBone / dWeight (12 words per triangle); no dPart
     Dev<int32_t> dBone; Dev<float> dWeight;
+    bool dualQuat = false;              // include/pt_skin_dq.h: a skinned pose whose rule blends dual quaternions; dDq holds those of the records, 32 bytes each
+    Dev<float> dDq;
     bool scratchReady = false;          // dScratch holds the rest pose's static triangles (pt_pose_triangles, the slow paths)
     int rowsFor = -1, nRows = 0;        // dRowIds lists the rows of the plan's map made under this bfs_nodes
     std::vector<float> accepted;        // the matrices of the last accepted pose; empty: none yet (the rest pose), or n_parts == 0
@@ -100,7 +107,10 @@ int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights,
     const float* rest = morphed ? (const float*)P->dMorphRest : (const float*)P->dRest;
     HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
     HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
-    if (P->skinned) HIP_TRY(ptSkinLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dX, dst, SKIN_KERNEL, st));
+    if (P->dualQuat) {
+        HIP_TRY(ptSkinDqRecordsLaunch(P->dX, P->nParts, P->dDq, st));
+        HIP_TRY(ptSkinDqLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dDq, dst, st));
+    } else if (P->skinned) HIP_TRY(ptSkinLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dX, dst, SKIN_KERNEL, st));
     else HIP_TRY(ptPoseLaunch(rest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
     if (P->hasNormals && mode == 1) return normalsInto(P, dst, NORMALS_KERNEL);
     return 0;
@@ -197,8 +207,9 @@ int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, cons
     return PT_OK;
 }
 
-// pt_pose_create and pt_skin_create after their argument checks: triPart, or the two corner tables of a skin
-int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, const int32_t* bone, const float* weight, pt_pose** out) {
+// pt_pose_create, pt_skin_create and pt_skin_dq_create after their argument checks: triPart, or the two corner tables of a skin (dualQuat: under
+// include/pt_skin_dq.h's rule)
+int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, const int32_t* bone, const float* weight, bool dualQuat, pt_pose** out) {
     int rc;
     if (c->multi) {
         if (!c->multi->staleBindings.empty())
@@ -223,7 +234,7 @@ int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, cons
                               b.objidx.data(), b.objidx.size() * 4, (int64_t)nTris, &plan)))
         return rc;
     pt_pose* P = new pt_pose();
-    P->ctx = c; P->device = on->device; P->nParts = nParts; P->nTris = (int64_t)nTris; P->plan = plan; P->skinned = bone != nullptr;
+    P->ctx = c; P->device = on->device; P->nParts = nParts; P->nTris = (int64_t)nTris; P->plan = plan; P->skinned = bone != nullptr; P->dualQuat = dualQuat;
     const hipStream_t st = plan->stream;
     auto upload = [&]() {
         HIP_TRY(hipSetDevice(P->device));
@@ -233,6 +244,7 @@ int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, cons
             HIP_TRY(P->dWeight.upload(weight, nTris * 48, st));
         } else HIP_TRY(P->dPart.upload(triPart, nTris * 4, st));
         HIP_TRY(P->dX.reset(std::max<size_t>((size_t)nParts * 96, 16)));
+        if (P->dualQuat) HIP_TRY(P->dDq.reset(std::max<size_t>((size_t)nParts * 32, 16)));
         if (nTris) HIP_TRY(hipMemcpyAsync(plan->dTris, P->dRest, nTris * 160, hipMemcpyDeviceToDevice, st));      // the static triangles, once
         HIP_TRY(hipStreamSynchronize(st));
         return 0;
@@ -249,13 +261,19 @@ int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, cons
 int pt_pose_create(pt_ctx* c, const int32_t* triPart, size_t partBytes, int nParts, pt_pose** out) {
     const size_t nTris = c ? hostTriangleCount(firstStream(c)) : 0;
     if (int rc = fail(ptp::checkPoseCreate(c, triPart, partBytes, nParts, out, nTris))) return rc;
-    return poseCreate(c, nTris, nParts, triPart, nullptr, nullptr, out);
+    return poseCreate(c, nTris, nParts, triPart, nullptr, nullptr, false, out);
 }
 
 int pt_skin_create(pt_ctx* c, const int32_t* bone, size_t boneBytes, const float* weight, size_t weightBytes, int nParts, pt_pose** out) {
     const size_t nTris = c && bone && weight && out ? hostTriangleCount(firstStream(c)) : 0;     // (the context is read only once no argument is null)
     if (int rc = fail(ptp::checkSkinCreate(c, bone, boneBytes, weight, weightBytes, nParts, out, nTris))) return rc;
-    return poseCreate(c, nTris, nParts, nullptr, bone, weight, out);
+    return poseCreate(c, nTris, nParts, nullptr, bone, weight, false, out);
+}
+
+int pt_skin_dq_create(pt_ctx* c, const int32_t* bone, size_t boneBytes, const float* weight, size_t weightBytes, int nParts, pt_pose** out) {
+    const size_t nTris = c && bone && weight && out ? hostTriangleCount(firstStream(c)) : 0;     // (the context is read only once no argument is null)
+    if (int rc = fail(ptp::checkSkinCreate(c, bone, boneBytes, weight, weightBytes, nParts, out, nTris, nullptr, "pt_skin_dq_create"))) return rc;
+    return poseCreate(c, nTris, nParts, nullptr, bone, weight, true, out);
 }
 
 int pt_pose_triangles(pt_pose* P, const float* xforms, size_t xformBytes, float* trisOut, size_t triBytes) {
@@ -354,6 +372,7 @@ int pt_debug_pose_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
     const bool live = poseLive(P);
     if (!live || !msBest || reps < 1 || (which != PT_POSE_PER_QUAD && which != PT_POSE_PER_TRIANGLE) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
         return fail(PT_ERR_ARG, "pt_debug_pose_time: bad argument");
+    if (P->dualQuat) return fail(PT_ERR_ARG, "pt_debug_pose_time: a DQ pose has no part table (pt_debug_skin_dq_time times its kernels)");
     if (P->skinned) return fail(PT_ERR_ARG, "pt_debug_pose_time: a skinned pose has no part table (pt_debug_skin_time times its kernels)");
     std::vector<float> tris((size_t)P->nTris * 40);
     int rc = poseToHost(P, xforms, {}, 0, tris.data());           // (the scratch copy and the matrices are in place afterwards; unmorphed, the rule's normals)
@@ -380,6 +399,7 @@ int pt_debug_skin_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
     const bool live = poseLive(P);
     if (!live || !P->skinned || !msBest || reps < 1 || (which != PT_SKIN_PER_QUAD && which != PT_SKIN_PER_CORNER) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
         return fail(PT_ERR_ARG, "pt_debug_skin_time: bad argument");
+    if (P->dualQuat) return fail(PT_ERR_ARG, "pt_debug_skin_time: a DQ pose blends no matrices (pt_debug_skin_dq_time times its kernels)");
     // the scratch copy is the whole rest pose again and the matrices are in place: what pt_debug_pose_scratch reads afterwards is this kernel's alone
     const hipStream_t st = P->plan->stream;
     HIP_TRY(hipSetDevice(P->device));
@@ -406,7 +426,39 @@ int pt_debug_skin_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
     return rc;
 }
 
-// include/pt_debug.h: the pose's scratch copy as the last pt_pose_triangles / pt_debug_pose_time / pt_debug_skin_time left it
+// include/pt_debug.h: the device time of the two launches of a DQ pose, records then corners (the best of reps), into the pose's scratch copy
+int pt_debug_skin_dq_time(pt_pose* P, const float* xforms, size_t xformBytes, int reps, float* msBest) {
+    const bool live = poseLive(P);
+    if (!live || !P->dualQuat || !msBest || reps < 1 || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
+        return fail(PT_ERR_ARG, "pt_debug_skin_dq_time: bad argument");
+    // the scratch copy is the whole rest pose again and the matrices are in place: what pt_debug_pose_scratch reads afterwards is these kernels' alone
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    if (!P->scratchReady) HIP_TRY(P->dScratch.reset(P->nTris ? (size_t)P->nTris * 160 : 16));
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
+    P->scratchReady = true;
+    HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
+    HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int rc = 0;
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    float best = 0.0f;
+    for (int k = 0; k < reps && !rc; k++) {
+        hipEventRecord(e0, st);
+        hipError_t e = ptSkinDqRecordsLaunch(P->dX, P->nParts, P->dDq, st);
+        if (e == hipSuccess) e = ptSkinDqLaunch(P->dRest, P->dBone, P->dWeight, P->nTris, P->dDq, P->dScratch, st);
+        hipEventRecord(e1, st);
+        float ms = 0.0f;
+        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_skin_dq_time: the launch failed");
+        if (k == 0 || ms < best) best = ms;
+    }
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (!rc) *msBest = best;
+    return rc;
+}
+
+// include/pt_debug.h: the pose's scratch copy as the last pt_pose_triangles / pt_debug_pose_time / pt_debug_skin_time / pt_debug_skin_dq_time left it
 int pt_debug_pose_scratch(pt_pose* P, float* trisOut, size_t triBytes) {
     const bool live = poseLive(P);
     if (!live || !trisOut || !P->scratchReady || triBytes != (size_t)P->nTris * 160) return fail(PT_ERR_ARG, "pt_debug_pose_scratch: bad argument");

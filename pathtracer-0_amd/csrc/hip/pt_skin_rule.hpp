@@ -13,10 +13,10 @@ namespace ptp {
 // every check of pt_skin_create, in the order the header lists them
 enum SkinCheck { SK_OK, SK_NULL, SK_BONE_BYTES, SK_WEIGHT_BYTES, SK_N_PARTS, SK_BONE_ID, SK_BONE_ORDER, SK_WEIGHT, SK_COUNT };
 
-// nTris: the triangles of the context's binding 3 (read only once ctx is known not to be null)
+// nTris: the triangles of the context's binding 3 (read only once ctx is known not to be null); who: the entry point that answers
+// (pt_skin_dq_create of include/pt_skin_dq.h takes the same tables and refuses the same)
 inline Refused checkSkinCreate(const void* ctx, const int32_t* bone, size_t boneBytes, const float* weight, size_t weightBytes, int nParts, const void* out, size_t nTris,
-                               int* which = nullptr) {
-    const char* who = "pt_skin_create";
+                               int* which = nullptr, const char* who = "pt_skin_create") {
     auto refuse = [&](SkinCheck k, const char* text) {
         if (which) *which = k;
         return Refused{PT_ERR_ARG, std::string(who) + ": " + text};

@@ -207,6 +207,9 @@ def lib():
             L.pt_skin_create.argtypes = [vp, vp, sz, vp, sz, ci, C.POINTER(vp)]
             L.pt_debug_skin_time.argtypes = [vp, vp, sz, ci, ci, C.POINTER(C.c_float)]
             L.pt_debug_pose_scratch.argtypes = [vp, vp, sz]
+        if hasattr(L, "pt_skin_dq_create"):                   # include/pt_skin_dq.h, and its kernel timer in include/pt_debug.h
+            L.pt_skin_dq_create.argtypes = [vp, vp, sz, vp, sz, ci, C.POINTER(vp)]
+            L.pt_debug_skin_dq_time.argtypes = [vp, vp, sz, ci, C.POINTER(C.c_float)]
         if hasattr(L, "pt_morph_attach"):                     # include/pt_morph.h, and its kernel timer and read-back in include/pt_debug.h
             L.pt_morph_attach.argtypes = [vp, ci, vp, sz, vp, sz, vp, sz]
             L.pt_morph_weights.argtypes = [vp, vp, sz]
@@ -375,10 +378,16 @@ class Pose:
     """A pose object of include/pt_pose.h (Renderer.pose_create): the context's binding 3 as the rest pose, a part id per triangle and a refit plan
     of its own, on the device.  It belongs to its Renderer, whose close() destroys it."""
 
-    def __init__(self, renderer, tri_part, n_parts, skin=None):
-        """skin: (corner_bone, corner_weight) of include/pt_skin.h instead of tri_part (Renderer.skin_create)"""
+    def __init__(self, renderer, tri_part, n_parts, skin=None, blend="linear"):
+        """skin: (corner_bone, corner_weight) of include/pt_skin.h instead of tri_part (Renderer.skin_create); blend: "linear" for that header's
+        rule, "dq" for include/pt_skin_dq.h's"""
         self._L = renderer._L
+        if blend not in ("linear", "dq") or (skin is None and blend != "linear"):
+            raise ValueError(f"blend must be 'linear' or 'dq' (and 'dq' needs a skin), not {blend!r}")
+        self.blend = blend if skin is not None else None
         name, header = ("pt_pose_create", "include/pt_pose.h") if skin is None else ("pt_skin_create", "include/pt_skin.h")
+        if blend == "dq":
+            name, header = "pt_skin_dq_create", "include/pt_skin_dq.h"
         if not hasattr(self._L, name):
             raise RuntimeError(f"this libpt_hip.so has no {name} ({header}): no fallback")
         self._h = C.c_void_p()
@@ -390,7 +399,8 @@ class Pose:
         bone = np.ascontiguousarray(skin[0], dtype=np.int32).reshape(-1)
         weight = np.ascontiguousarray(skin[1], dtype=np.float32).reshape(-1)
         self.n_parts, self.n_tris, self.n_roots = int(n_parts), bone.size // 12, getattr(renderer, "_n_roots", 0)
-        _check(self._L.pt_skin_create(renderer._h, bone.ctypes.data, bone.nbytes, weight.ctypes.data, weight.nbytes, self.n_parts, C.byref(self._h)))
+        create = self._L.pt_skin_dq_create if blend == "dq" else self._L.pt_skin_create
+        _check(create(renderer._h, bone.ctypes.data, bone.nbytes, weight.ctypes.data, weight.nbytes, self.n_parts, C.byref(self._h)))
 
     def _xforms(self, xforms):
         x = np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1)
@@ -723,11 +733,12 @@ class Renderer:
         triangle k (-1: static)."""
         return Pose(self, tri_part, n_parts)
 
-    def skin_create(self, corner_bone, corner_weight, n_parts):
+    def skin_create(self, corner_bone, corner_weight, n_parts, blend="linear"):
         """A skinned Pose over this context's scene as it is now (pt_skin_create, include/pt_skin.h): 12 bone ids and 12 weights per triangle,
         corner c, slot s at 12*k + 4*c + s; a corner's used slots first, -1 in the others; a corner without slots is static.  pose_geometry,
-        Pose.triangles and pose_records work on it as on a Pose of pose_create."""
-        return Pose(self, None, n_parts, skin=(corner_bone, corner_weight))
+        Pose.triangles and pose_records work on it as on a Pose of pose_create.  blend="dq": the same tables under the dual-quaternion rule
+        (pt_skin_dq_create, include/pt_skin_dq.h), which keeps the volume of what twists; Pose.blend carries the choice."""
+        return Pose(self, None, n_parts, skin=(corner_bone, corner_weight), blend=blend)
 
     def pose_geometry(self, pose, xforms, ellip=None):
         """move_geometry of the rest pose under `xforms` (n_parts records of 24 floats: pose_records), with the posed triangles, the refit and the

@@ -668,6 +668,23 @@ def m5_rippling(step=0, W=96, H=54, **kw):
     return wl, bone, weight, targets, X, w, ids, n_vertices
 
 
+def m6_records(wl, step, n_bones=5, a=0.25):
+    """the records of m6_twisting(step) alone, for a workload of m3_tube: joint i turned by i * step * a about +y, the tube's axis, on which the
+    pivots lie (so the records are pure rotations about that axis: the chain twists and nothing bends)"""
+    cx, y0, y1, cz = wl.info["axis"]
+    pivots = [(cx, y0 + (y1 - y0) * max(i - 0.5, 0.0) / (n_bones - 1), cz) for i in range(n_bones)]
+    return chain_records(n_bones, pivots, (0.0, 1.0, 0.0), float(step) * a)
+
+
+def m6_twisting(step=0, W=96, H=54, n_bones=5, a=0.25, **kw):
+    """M6 at `step`, the workload of include/pt_skin_dq.h (not a BASELINE config): M3's tube and ramp weights, twisted instead of bent.  Between
+    two joints twisted against each other the linear skin of include/pt_skin.h pulls the tube's wall towards its axis; the dual-quaternion skin
+    keeps its radius.  -> what m3_bending returns: (the rest pose's workload, corner_bone, corner_weight, the records)."""
+    wl, bone, weight, _ = m3_bending(0, W, H, n_bones, **kw)
+    wl.name = "M6"
+    return wl, bone, weight, m6_records(wl, step, n_bones, a)
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then

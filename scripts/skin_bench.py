@@ -55,6 +55,12 @@ def setup(which):
         scenes.GPU_BVH = 0
         rest, bone, weight, X1 = scenes.m3_bending(1, W, H, n_bones=8, n_seg=224, n_around=224)
         return renderer, scenes, rest, bone, weight, 8, [X1, scenes.m3_records(rest, 2, n_bones=8)]
+    if which == "m6":                                              # scripts/skin_dq_bench.py: the same tube, twisted
+        import refit_bench as RB
+        pt, hostlib, renderer, scenes = RB._load()
+        scenes.GPU_BVH = 0
+        rest, bone, weight, X1 = scenes.m6_twisting(1, W, H, n_bones=8, n_seg=224, n_around=224)
+        return renderer, scenes, rest, bone, weight, 8, [X1, scenes.m6_records(rest, 2, n_bones=8)]
     import pose_bench as PB
     renderer, scenes, rest, parts, X = PB.setup(which)
     bone, weight = band_skin(parts, PB.N_PARTS, 2)
@@ -77,7 +83,8 @@ def verdict(which, what, a, b):
             f"{ms(sp)} ms: {'AIM MET' if bb - ba > sp else 'AIM MISSED'}")
 
 
-def timing(which):
+def timing(which, blend="linear"):
+    """blend: the rule of the skin route's pose ("dq": include/pt_skin_dq.h, scripts/skin_dq_bench.py)"""
     renderer, scenes, rest, bone, weight, n_parts, X = setup(which)
     n = bone.size // 12
     static = int((bone.reshape(-1, 4)[:, 0] < 0).sum())
@@ -88,7 +95,7 @@ def timing(which):
     r.load_workload(rest); r.reset_frame()
     r.render_batch(1, seeds[:1]); r.synchronize()
     t0 = rest.buffers[3]
-    probe = r.skin_create(bone, weight, n_parts)
+    probe = r.skin_create(bone, weight, n_parts, blend=blend)
     P = [probe.triangles(x) for x in X]                            # what the move_geometry route is fed
     probe.close()
 
@@ -103,7 +110,7 @@ def timing(which):
     for _ in range(5):
         for route in ("move_geometry", "skin"):
             assert r.move_geometry(plan, t0)[1]                     # the rest pose again, for both routes
-            pose = r.skin_create(bone, weight, n_parts) if route == "skin" else None
+            pose = r.skin_create(bone, weight, n_parts, blend=blend) if route == "skin" else None
 
             def move(k):
                 if route == "skin":
