@@ -74,6 +74,7 @@ struct Mtl {
 
 struct Hit {          // raySceneResult, frag.glsl:83-96 (only the members trace() consumes)
     vec3 loc, norm; int material; int id; int type; float distance; vec3 dir; float uvx, uvy; int parentID;
+    float bu, bv;     // (probes only) rayTri's (u, v) of the closest triangle the BVH loop found, (0, 0) with none
 };
 
 struct Mat3 { float m[3][3]; };   // math (row-major) matrix
@@ -502,7 +503,7 @@ Hit rayScene(Ctx& c, vec3 o, vec3 d) {
         }
     }
     Hit h;
-    h.type = hitType; h.id = hitID; h.uvx = uvx; h.uvy = uvy; h.parentID = parentID;
+    h.type = hitType; h.id = hitID; h.uvx = uvx; h.uvy = uvy; h.parentID = parentID; h.bu = bu; h.bv = bv;
     if (closest_t < 1e25f) {
         h.loc = madd(d, closest_t, o); h.dir = normalize(d); h.norm = N; h.material = hitMat; h.distance = closest_t;
         return h;
@@ -827,6 +828,19 @@ int orc_ray_scene(const orc_scene* s, const float* o, const float* d, float* out
     out[0] = h.distance; out[1] = h.loc.x; out[2] = h.loc.y; out[3] = h.loc.z;
     out[4] = h.norm.x; out[5] = h.norm.y; out[6] = h.norm.z; out[7] = (float)h.material;
     return h.id > -1 ? (h.type * 0x1000000 + h.id) : -1;
+}
+
+// orc_ray_scene for n rays, with rayTri's barycentrics: tuv[3 i ..] = distance (-1 on a miss), u, v of the closest triangle (of the one an
+// ellipsoid hit lies in front of, too); code[i] as orc_ray_scene returns it
+int orc_ray_hits(const orc_scene* s, const float* o, const float* d, int64_t n, float* tuv, int32_t* code) {
+    Ctx c; if (setupCtx(c, s)) return -100;
+    uint64_t dummy[C_N] = {0}; c.cnt = dummy; c.count = false;
+    for (int64_t i = 0; i < n; i++) {
+        Hit h = rayScene(c, v3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), v3(d[3 * i], d[3 * i + 1], d[3 * i + 2]));
+        tuv[3 * i] = h.distance; tuv[3 * i + 1] = h.bu; tuv[3 * i + 2] = h.bv;
+        code[i] = h.id > -1 ? (h.type * 0x1000000 + h.id) : -1;
+    }
+    return 0;
 }
 
 // RNG known-answer helper: advances *state n times, writes results and random() floats

@@ -36,6 +36,7 @@ def lib():
         L.orc_autofocus.argtypes = [C.POINTER(_Scene)]
         L.orc_autofocus.restype = C.c_float
         L.orc_ray_scene.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_ray_hits.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.orc_rng.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         L.orc_rotate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -124,6 +125,15 @@ def ray_scene(scene, o, d):
     o, d, out = np.array(o, np.float32), np.array(d, np.float32), np.zeros(8, np.float32)
     code = lib().orc_ray_scene(C.byref(scene.c), o.ctypes.data, d.ctypes.data, out.ctypes.data)
     return code, out
+
+
+def ray_hits(scene, o, d):
+    """ray_scene for n rays: (tuv (n, 3) float32 — distance (-1 on a miss) and rayTri's (u, v) of the closest triangle — and code (n,) int32)"""
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3); d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    tuv, code = np.zeros((o.shape[0], 3), np.float32), np.zeros(o.shape[0], np.int32)
+    if lib().orc_ray_hits(C.byref(scene.c), o.ctypes.data, d.ctypes.data, o.shape[0], tuv.ctypes.data, code.ctypes.data):
+        raise RuntimeError("oracle: orc_ray_hits failed")
+    return tuv, code
 
 
 def autofocus(scene):
