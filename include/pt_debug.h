@@ -83,8 +83,8 @@ int pt_debug_skin_time(struct pt_pose* pose, const float* xforms, size_t xform_b
  * pose that pt_skin_dq_create did not make.  pt_debug_pose_time and pt_debug_skin_time in turn refuse a DQ pose with PT_ERR_ARG. */
 int pt_debug_skin_dq_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int reps, float* ms_best);
 /* The pose's scratch copy (40 floats per triangle) as the last pt_pose_triangles, pt_debug_pose_time, pt_debug_skin_time or pt_debug_skin_dq_time
- * left it.  pt_debug_skin_time and pt_debug_skin_dq_time fill it with the rest pose before their launches, so what is read after them is the work
- * of the kernels they were asked for: the tests compare the statements with the model this way.  PT_ERR_ARG: a null or destroyed pose, null tris_out, tri_bytes != n_tris * 160, no
+ * left it.  pt_debug_pose_time, pt_debug_skin_time and pt_debug_skin_dq_time fill it with the rest pose before their launches, so what is read
+ * after any of them is the work of the kernels it was asked for: the tests compare the statements with the model this way.  PT_ERR_ARG: a null or destroyed pose, null tris_out, tri_bytes != n_tris * 160, no
  * scratch copy yet. */
 int pt_debug_pose_scratch(struct pt_pose* pose, float* tris_out, size_t tri_bytes);
 /* The device time of ONE launch of k_morph_corners of include/pt_morph.h (scripts/morph_probe.py) under the given weights: the best of reps

@@ -59,7 +59,7 @@ int pt_set_error_(int code, const std::string& msg) { return fail(code, msg); } 
 // a group context hands the call to the host thread of every device context and joins them (pt_multi.hpp)
 #define MULTI_ALL(c, call) do { if ((c) && (c)->multi) return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } while (0)
 // ... for the entry points that render: not while an upload reached only some of the streams
-#define MULTI_RENDER(c, call) do { if ((c) && (c)->multi) { if (!(c)->multi->staleBindings.empty()) return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering"); \
+#define MULTI_RENDER(c, call) do { if ((c) && (c)->multi) { if (!(c)->multi->staleBindings.empty()) return fail(PT_ERR_SCENE, MULTI_UPLOAD_FAILED); \
                                                           return multiRun(*(c)->multi, [=](pt_ctx* k) { return call; }); } } while (0)
 
 extern "C" {
@@ -488,7 +488,7 @@ int onEveryStream(pt_ctx* c, const std::function<int(pt_ctx*, int64_t*)>& fn, in
     if (nActive) *nActive = 0;
     if (c->multi) {
         MultiCtx& M = *c->multi;
-        if (!M.staleBindings.empty()) return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
+        if (!M.staleBindings.empty()) return fail(PT_ERR_SCENE, MULTI_UPLOAD_FAILED);
         std::vector<int64_t> counts((size_t)M.n, 0);
         int64_t* cp = counts.data();
         const std::vector<pt_ctx*>& kids = M.kids;

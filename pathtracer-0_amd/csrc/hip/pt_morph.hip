@@ -13,11 +13,10 @@
 // the library, so v + w * d is a rounded product and a rounded sum.  Corner ids and targets were range-checked on the host (checkMorphAttach).
 #include <hip/hip_runtime.h>
 
+#include "pt_geom_steps.hpp"
 #include "pt_morph_launch.hpp"
 
 namespace {
-
-constexpr int BLOCK = 256;
 
 // THE RULE, one entry: skipped when its weight compares equal to zero (or when `there` says the row has ended); every product rounded before
 // every sum.  Selects, no branch: behind a branch the compiler moves the entry's loads, and the row becomes a chain of round trips
@@ -60,9 +59,9 @@ __global__ void __launch_bounds__(BLOCK) k_morph_corners(const float4* __restric
 hipError_t ptMorphLaunch(const float* rest, const int32_t* corner, const int32_t* rowStart, const void* entries, const float* weights, int64_t nAffected, float* out,
                          hipStream_t s) {
     if (nAffected <= 0) return hipGetLastError();
-    const long long blocks = ((long long)nAffected + BLOCK - 1) / BLOCK;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_morph_corners, dim3((unsigned)blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(rest), corner, rowStart,
+    unsigned blocks;
+    if (!gridOf(nAffected, &blocks)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_morph_corners, dim3(blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(rest), corner, rowStart,
                        reinterpret_cast<const float4*>(entries), weights, (long long)nAffected, reinterpret_cast<float4*>(out));
     return hipGetLastError();
 }

@@ -53,8 +53,7 @@ int moveRebuild(pt_ctx* c, SceneBuffers& host, std::vector<float>& data, const f
 
 // a multi-stream / multi-GPU context: the sequence of include/pt_move.h through the public calls, then every replica builds
 int moveMulti(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes, const float* ellip, size_t ellipBytes, double* rootCost) {
-    if (!c->multi->staleBindings.empty())
-        return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
+    if (!c->multi->staleBindings.empty()) return fail(PT_ERR_SCENE, MULTI_UPLOAD_FAILED);
     SceneBuffers* host = nullptr;                                 // the first stream's copies (a group's streams are never behind a pose)
     if (const int rc = settledScene(c->multi->kids[0], &host)) return rc;
     if (moveDigest(*host) != P->digest || host->bvhdata.size() * 4 != P->dataBytes) return moveForeignPlan();
@@ -64,12 +63,7 @@ int moveMulti(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes, c
     if ((rc = pt_refit_run(P, tris, triBytes, data.data(), cost.data()))) return rc;
     if ((rc = pt_set_buffer(c, PT_BIND_TRIANGLES, tris, triBytes)) || (rc = pt_set_buffer(c, PT_BIND_BVHDATA, data.data(), P->dataBytes))) return rc;
     if (ellip && (rc = pt_set_buffer(c, PT_BIND_ELLIPSOIDS, ellip, ellipBytes))) return rc;
-    rc = multiRun(*c->multi, [](pt_ctx* k) {
-        HIP_TRY(hipSetDevice(k->device));
-        if (const int r = flushStream(k)) return r;
-        return k->sceneDirty ? buildScene(k) : 0;
-    });
-    if (rc) return rc;
+    if ((rc = multiFlushAndBuild(*c->multi))) return rc;
     if (rootCost) std::copy(cost.begin(), cost.begin() + P->s.nRoots, rootCost);
     return PT_OK;
 }
@@ -94,6 +88,21 @@ int movePatchRecords(pt_ctx* c, pt_refit_plan* P, const std::vector<ObjRoot>& ro
     *unordered = 0;
     HIP_TRY(hipMemcpyAsync(unordered, P->dFlag, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+// the tail of an in-place commit, of a move and of a pose (pt_pose_host.hpp) alike: movePatchRecords has succeeded and the caller has recorded its own
+// side (a move: the host copies of bindings 3 and 10; a pose: c->behind and its accepted state).  The ellipsoids' host copy, what pt_set_buffer
+// records, and — the modes assume ordered boxes — the scene build when the patch wrote an unordered box on an eligible 80-byte stride: the build
+// decides (and settles).  *rebuilt: it did
+int moveCommitted(pt_ctx* c, const float* ellip, size_t ellipBytes, int unordered, bool* rebuilt) {
+    if (ellip) c->buf.ellip.assign(ellip, ellip + ellipBytes / 4);
+    moveAccepted(c, ellip != nullptr);
+    *rebuilt = false;
+    if (unordered && c->built.asmEligible && c->built.asmNodeStride == 80) {
+        if (const int rc = buildScene(c)) { c->sceneDirty = true; return rc; }
+        *rebuilt = true;
+    }
     return 0;
 }
 
@@ -171,12 +180,7 @@ int moveGeometry(pt_ctx* c, pt_refit_plan* P, const float* tris, size_t triBytes
         if ((rc = movePatchRecords(c, P, roots, ellip, &unordered))) return rc;
         host->tris.assign(tris, tris + triBytes / 4);
         host->bvhdata.swap(data);
-        if (ellip) c->buf.ellip.assign(ellip, ellip + ellipBytes / 4);
-        moveAccepted(c, ellip != nullptr);
-        if (unordered && c->built.asmEligible && c->built.asmNodeStride == 80) {      // the modes assume ordered boxes: the scene build decides
-            if ((rc = buildScene(c))) { c->sceneDirty = true; return rc; }
-            rebuild = true;
-        }
+        if ((rc = moveCommitted(c, ellip, ellipBytes, unordered, &rebuild))) return rc;
     } else if ((rc = moveRebuild(c, *host, data, tris, triBytes, ellip, ellipBytes))) {
         return rc;
     }

@@ -127,6 +127,18 @@ int multiRun(MultiCtx& M, const std::function<int(pt_ctx*)>& f) {
     return rc ? fail(rc, err) : 0;
 }
 
+// what a group answers (PT_ERR_SCENE) to every call that renders or reads the scene while staleBindings is not empty
+const char* const MULTI_UPLOAD_FAILED = "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering";
+
+// every stream renders its submitted frames to the end (in the old scene) and builds its scene if an upload or an option dirtied it
+int multiFlushAndBuild(MultiCtx& M) {
+    return multiRun(M, [](pt_ctx* k) {
+        HIP_TRY(hipSetDevice(k->device));
+        if (const int r = flushStream(k)) return r;
+        return k->sceneDirty ? buildScene(k) : 0;
+    });
+}
+
 void multiFree(pt_ctx* g) {
     MultiCtx* M = g->multi;
     if (!M) return;

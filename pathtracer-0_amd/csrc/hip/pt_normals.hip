@@ -17,11 +17,10 @@
 // the rest of the library.  Every index was range-checked on the host (checkNormalsAttach, normalRows).
 #include <hip/hip_runtime.h>
 
+#include "pt_geom_steps.hpp"
 #include "pt_normals_launch.hpp"
 
 namespace {
-
-constexpr int BLOCK = 256;
 
 __global__ void __launch_bounds__(BLOCK) k_normals_faces(const float4* __restrict__ dst, const int* __restrict__ tris, long long nListed, int flip,
                                                         float4* __restrict__ faces) {
@@ -94,13 +93,6 @@ __global__ void __launch_bounds__(BLOCK) k_normals_gather_corner(const float4* _
     float4 N;
     if (!normalsOfRow(faces, corners, rowStart[r], rowStart[r + 1], N)) return;
     storeNormal(dst, corners[i], N);
-}
-
-bool gridOf(int64_t n, unsigned* blocks) {
-    const long long b = ((long long)n + BLOCK - 1) / BLOCK;
-    if (b > 0x7fffffffLL) return false;
-    *blocks = (unsigned)b;
-    return true;
 }
 
 }  // namespace

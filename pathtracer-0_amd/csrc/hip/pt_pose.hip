@@ -14,20 +14,10 @@
 // (checkPoseCreate); row ids are the refit plan's, range-checked by planRefit.
 #include <hip/hip_runtime.h>
 
+#include "pt_geom_steps.hpp"
 #include "pt_pose_launch.hpp"
 
 namespace {
-
-constexpr int BLOCK = 256;
-
-__device__ __forceinline__ float4 posePoint(const float4 r0, const float4 r1, const float4 r2, const float4 v) {
-    return make_float4(((r0.x * v.x + r0.y * v.y) + r0.z * v.z) + r0.w, ((r1.x * v.x + r1.y * v.y) + r1.z * v.z) + r1.w,
-                       ((r2.x * v.x + r2.y * v.y) + r2.z * v.z) + r2.w, v.w);
-}
-// N lies at floats 12-20 of the record: n3 = (n00, n01, n02, n10), n4 = (n11, n12, n20, n21), n22
-__device__ __forceinline__ float4 poseNormal(const float4 n3, const float4 n4, const float n22, const float4 v) {
-    return make_float4((n3.x * v.x + n3.y * v.y) + n3.z * v.z, (n3.w * v.x + n4.x * v.y) + n4.y * v.z, (n4.z * v.x + n4.w * v.y) + n22 * v.z, v.w);
-}
 
 __global__ void __launch_bounds__(BLOCK) k_pose_quads(const float4* __restrict__ rest, const int32_t* __restrict__ triPart, long long nQuads,
                                                      const float4* __restrict__ xforms, float4* __restrict__ out) {
@@ -89,25 +79,26 @@ __global__ void __launch_bounds__(BLOCK) k_pose_motion(const float4* __restrict_
 }  // namespace
 
 hipError_t ptPoseMotionLaunch(const float* tris, int nTris, const float4* then, int nThen, float4* out, hipStream_t s) {
-    if (nTris > 0)
-        hipLaunchKernelGGL(k_pose_motion, dim3((unsigned)((nTris + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(tris), nTris, then, nThen, out);
+    unsigned blocks;
+    if (nTris > 0 && gridOf(nTris, &blocks))                     // (an int's worth of lanes always fits a grid)
+        hipLaunchKernelGGL(k_pose_motion, dim3(blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(tris), nTris, then, nThen, out);
     return hipGetLastError();
 }
 
 hipError_t ptPoseLaunch(const float* rest, const int32_t* triPart, int64_t nTris, const float* xforms, float* out, PtPoseKernel which, hipStream_t s) {
     if (nTris <= 0) return hipGetLastError();
     const long long n = which == PT_POSE_PER_QUAD ? 6 * (long long)nTris : (long long)nTris;
-    const long long blocks = (n + BLOCK - 1) / BLOCK;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    unsigned blocks;
+    if (!gridOf(n, &blocks)) return hipErrorInvalidValue;
     const float4* r4 = reinterpret_cast<const float4*>(rest); const float4* x4 = reinterpret_cast<const float4*>(xforms); float4* o4 = reinterpret_cast<float4*>(out);
-    if (which == PT_POSE_PER_QUAD) hipLaunchKernelGGL(k_pose_quads, dim3((unsigned)blocks), dim3(BLOCK), 0, s, r4, triPart, n, x4, o4);
-    else hipLaunchKernelGGL(k_pose_tris, dim3((unsigned)blocks), dim3(BLOCK), 0, s, r4, triPart, n, x4, o4);
+    if (which == PT_POSE_PER_QUAD) hipLaunchKernelGGL(k_pose_quads, dim3(blocks), dim3(BLOCK), 0, s, r4, triPart, n, x4, o4);
+    else hipLaunchKernelGGL(k_pose_tris, dim3(blocks), dim3(BLOCK), 0, s, r4, triPart, n, x4, o4);
     return hipGetLastError();
 }
 
 hipError_t ptPoseGatherLaunch(const float* data, const int32_t* ids, int n, float* out, hipStream_t s) {
-    if (n > 0)
-        hipLaunchKernelGGL(k_pose_gather, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(data), ids, n,
-                           reinterpret_cast<float4*>(out));
+    unsigned blocks;
+    if (n > 0 && gridOf(n, &blocks))
+        hipLaunchKernelGGL(k_pose_gather, dim3(blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(data), ids, n, reinterpret_cast<float4*>(out));
     return hipGetLastError();
 }

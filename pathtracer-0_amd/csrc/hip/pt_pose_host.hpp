@@ -3,14 +3,18 @@
 // pt_pose.hip's, behind pt_pose_launch.hpp; the refit is pt_refit.hip's second half (pt_refit_kernels_); the patch of the context's records is
 // pt_move_host.hpp's (movePatchRecords), fed from the rows of binding 10 that k_pose_gather collects; the argument checks and the CPU statement
 // of the rule are pt_pose_rule.hpp's.  A skinned pose (include/pt_skin.h, pt_skin_create) is the same object under a second rule: its two corner
-// tables instead of the part ids, pt_skin.hip's kernel behind pt_skin_launch.hpp instead of k_pose, pt_skin_rule.hpp's checks; poseInto is
+// tables instead of the part ids, pt_skin.hip's kernel behind pt_skin_launch.hpp instead of k_pose, pt_skin_rule.hpp's checks; ruleLaunch is
 // the one place that tells them apart.  A morph (include/pt_morph.h, pt_morph_attach) belongs to either kind: pt_morph.hip's kernel behind
 // pt_morph_launch.hpp writes the morphed copy of the rest pose's affected corners, which poseInto hands to the pose's rule in place of dRest;
 // pt_morph_rule.hpp's checks and inverted index.  Normals (include/pt_normals.h, pt_normals_attach) belong to either kind too: pt_normals.hip's
 // two launches behind pt_normals_launch.hpp recompute the normals of the welded corners at the end of poseInto, from what the pose's rule wrote;
 // pt_normals_rule.hpp's checks and inverted index.  A DQ pose (include/pt_skin_dq.h, pt_skin_dq_create) is a skinned pose under a third rule: the same two
 // corner tables, pt_skin_dq.hip's two launches behind pt_skin_dq_launch.hpp (the records into dDq, a table the pose owns, then the corners)
-// instead of pt_skin.hip's one, pt_skin_dq_rule.hpp's CPU statement; again poseInto is the one place that tells them apart.
+// instead of pt_skin.hip's one, pt_skin_dq_rule.hpp's CPU statement; again ruleLaunch is the one place that tells them apart.
+//
+// One of each: ruleLaunch launches the pose's rule (pt_pose::rule says which of the three), for poseInto with the statements chosen below and for
+// the debug timers with the caller's; bestTime is the one timing loop of the five pt_debug_*_time calls; poseAccepted records a call's records,
+// weights and normals mode as the pose's last accepted state (PoseState), which a refused call hands back to poseInto.
 //
 // What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
 // kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
@@ -34,31 +38,39 @@ extern "C++" {
 #include "../../../include/pt_morph.h"
 #include "../../../include/pt_normals.h"
 
+// the rule of a pose: per-part matrices from dPart (include/pt_pose.h); records blended per corner from dBone / dWeight, 12 words per triangle and
+// no dPart (include/pt_skin.h); the same two tables under the dual-quaternion blend (include/pt_skin_dq.h)
+enum PoseRule { RULE_PARTS, RULE_SKIN, RULE_SKIN_DQ };
+
+// what a pose call is asked for, and what is kept of the last accepted one
+struct PoseState {
+    std::vector<float> xforms;          // the records; empty: none accepted yet (the rest pose, unmorphed, its normals as they are), or n_parts == 0
+    std::vector<float> weights;         // the morph weights; empty: every weight 0 (none accepted yet, or accepted before the attach)
+    int mode = 0;                       // the normals mode (none accepted yet, or accepted before the attach: 0)
+};
+
 struct pt_pose {
     pt_ctx* ctx = nullptr;              // the context (a group's: the group) it was created on and belongs to
     int device = 0, nParts = 0; int64_t nTris = 0;
     pt_refit_plan* plan = nullptr;      // its own, over the context's bindings 10-13
     Dev<float> dRest, dScratch, dX, dRows; Dev<int32_t> dPart, dRowIds;
-    bool skinned = false;               // include/pt_skin.h: the rule blends records per corner, from dBone / dWeight (12 words per triangle); no dPart
+    PoseRule rule = RULE_PARTS;
     Dev<int32_t> dBone; Dev<float> dWeight;
-    bool dualQuat = false;              // include/pt_skin_dq.h: a skinned pose whose rule blends dual quaternions; dDq holds those of the records, 32 bytes each
-    Dev<float> dDq;
+    Dev<float> dDq;                     // RULE_SKIN_DQ: the dual quaternions of the records, 32 bytes each
     bool scratchReady = false;          // dScratch holds the rest pose's static triangles (pt_pose_triangles, the slow paths)
     int rowsFor = -1, nRows = 0;        // dRowIds lists the rows of the plan's map made under this bfs_nodes
-    std::vector<float> accepted;        // the matrices of the last accepted pose; empty: none yet (the rest pose), or n_parts == 0
+    PoseState accepted;                 // the last accepted pose: a refused call is undone by running it again
     // include/pt_morph.h: nTargets > 0 once a morph is attached.  dMorphRest is a second copy of the rest pose, of which the kernel rewrites the
     // affected corners (all of them, on every morphed call) and nothing else
     int nTargets = 0; int64_t nAffected = 0;
     Dev<float> dMorphRest, dMorphW; Dev<int32_t> dMorphCorner, dMorphRow; Dev<ptp::MorphEntry> dMorphEntry;
     std::vector<float> weights;         // as pt_morph_weights set them last (after the attach: zeros)
-    std::vector<float> acceptedWeights; // those of the last accepted pose; empty: every weight 0 (none accepted yet, or accepted before the attach)
     // include/pt_normals.h: hasNormals once normals are attached.  The inverted index of pt_normals_rule.hpp (the listed triangles, the row starts
     // of the non-empty vertices, their corners, per corner its row) and the face vectors, 16 bytes per triangle, indexed by triangle id
     bool hasNormals = false; uint32_t normalsFlags = 0;
     int64_t nNrmTris = 0, nNrmRows = 0, nNrmCorners = 0;
     Dev<int32_t> dNrmTri, dNrmRow, dNrmCorner, dNrmCornerRow; Dev<float> dNrmFace;
     int normalsMode = 0;                // as pt_normals_mode set it last (after the attach: 1)
-    int acceptedMode = 0;               // that of the last accepted pose (none accepted yet, or accepted before the attach: 0)
     bool stale = false;                 // the scene was uploaded since pt_pose_create
 };
 
@@ -69,6 +81,7 @@ std::set<pt_pose*> g_poses;             // the live poses: a destroyed one is re
 constexpr PtPoseKernel POSE_KERNEL = PT_POSE_PER_QUAD;      // the faster of the two at 100 k and at 1 M triangles (scripts/pose_probe.py); pt_debug_pose_time runs either
 constexpr PtNormalsKernel NORMALS_KERNEL = PT_NORMALS_PER_CORNER;   // 5 % slower on C4's mesh, 10 % faster on the 1 M height field: the shorter summed over both (71.9 against 77.4 us), and twice as fast on a table with one long row (scripts/normals_probe.py); pt_debug_normals_time runs either
 constexpr PtSkinKernel SKIN_KERNEL = PT_SKIN_PER_CORNER;    // faster with four slots at 100 k and at 1 M triangles, tied at 100 k and 2 % slower at 1 M with two: the shorter summed over both slot counts at 1 M (scripts/skin_probe.py); pt_debug_skin_time runs either
+constexpr int RULE_KERNEL[3] = {POSE_KERNEL, SKIN_KERNEL, 0};    // by PoseRule: the statement poseInto runs (the DQ rule has one)
 
 bool poseLive(pt_pose* p) {
     std::lock_guard<std::mutex> g(g_posesMutex);
@@ -91,6 +104,23 @@ int normalsInto(pt_pose* P, float* dst, PtNormalsKernel which) {
     return 0;
 }
 
+bool hasBones(const pt_pose* P) { return P->rule != RULE_PARTS; }        // dBone / dWeight instead of dPart
+
+// the pose's rule from `rest` into dst, over the records that lie in dX, by the statement `which` of its kernel (a PtPoseKernel or a PtSkinKernel;
+// the DQ rule has one statement: the records into dDq, then the corners); asynchronous on the plan's stream
+hipError_t ruleLaunch(pt_pose* P, const float* rest, float* dst, int which) {
+    const hipStream_t st = P->plan->stream;
+    switch (P->rule) {
+        case RULE_PARTS: return ptPoseLaunch(rest, P->dPart, P->nTris, P->dX, dst, (PtPoseKernel)which, st);
+        case RULE_SKIN: return ptSkinLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dX, dst, (PtSkinKernel)which, st);
+        case RULE_SKIN_DQ: {
+            const hipError_t e = ptSkinDqRecordsLaunch(P->dX, P->nParts, P->dDq, st);
+            return e != hipSuccess ? e : ptSkinDqLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dDq, dst, st);
+        }
+    }
+    return hipErrorInvalidValue;
+}
+
 // the pose of `xforms` (host; nullptr: the rest pose, unmorphed, its normals as they are) under the morph weights `weights` (host; empty: no morph,
 // or every weight 0) and the normals mode `mode` (1: recomputed where normals are attached) into dst, which holds the rest pose's static
 // triangles; asynchronous on the plan's stream
@@ -107,13 +137,18 @@ int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights,
     const float* rest = morphed ? (const float*)P->dMorphRest : (const float*)P->dRest;
     HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
     HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
-    if (P->dualQuat) {
-        HIP_TRY(ptSkinDqRecordsLaunch(P->dX, P->nParts, P->dDq, st));
-        HIP_TRY(ptSkinDqLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dDq, dst, st));
-    } else if (P->skinned) HIP_TRY(ptSkinLaunch(rest, P->dBone, P->dWeight, P->nTris, P->dX, dst, SKIN_KERNEL, st));
-    else HIP_TRY(ptPoseLaunch(rest, P->dPart, P->nTris, P->dX, dst, POSE_KERNEL, st));
+    HIP_TRY(ruleLaunch(P, rest, dst, RULE_KERNEL[P->rule]));
     if (P->hasNormals && mode == 1) return normalsInto(P, dst, NORMALS_KERNEL);
     return 0;
+}
+// poseInto of a kept state: the one place that reads what its empty fields mean
+int poseStateInto(pt_pose* P, const PoseState& s, float* dst) { return poseInto(P, s.xforms.empty() ? nullptr : s.xforms.data(), s.weights, s.mode, dst); }
+
+// what this call was asked for is the pose's last accepted state
+void poseAccepted(pt_pose* P, const float* xforms, size_t xformBytes) {
+    P->accepted.xforms.assign(xforms, xforms + xformBytes / 4);
+    P->accepted.weights = P->weights;
+    P->accepted.mode = P->normalsMode;
 }
 
 // P = the rule applied to the rest pose, on the host; the plan's working copies are not touched
@@ -128,6 +163,63 @@ int poseToHost(pt_pose* P, const float* xforms, const std::vector<float>& weight
     if (const int rc = poseInto(P, xforms, weights, mode, P->dScratch)) return rc;
     if (P->nTris) HIP_TRY(hipMemcpyAsync(out, P->dScratch, (size_t)P->nTris * 160, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the scratch copy holds the whole rest pose again, the records `xforms` lie in dX and the plan's stream is idle: what pt_debug_pose_scratch reads
+// after a launch of the pose's rule into the scratch copy is that launch's work alone
+int scratchAtRest(pt_pose* P, const float* xforms) {
+    const hipStream_t st = P->plan->stream;
+    HIP_TRY(hipSetDevice(P->device));
+    if (!P->scratchReady) HIP_TRY(P->dScratch.reset(P->nTris ? (size_t)P->nTris * 160 : 16));
+    if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
+    P->scratchReady = true;
+    HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
+    HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// THE timing loop of include/pt_debug.h: the device time between a pair of events on `st` around what `enqueue` puts there (false: it could not),
+// the best of reps, into *msBest — which a failure leaves as it was.  The events are destroyed on every path
+extern "C++" template <class Enqueue>
+int bestTime(hipStream_t st, int reps, const char* who, Enqueue enqueue, float* msBest) {
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); }
+    } ev;
+    hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    float best = 0.0f;
+    for (int k = 0; k < reps; k++) {
+        hipEventRecord(e0, st);
+        const bool enqueued = enqueue();
+        hipEventRecord(e1, st);
+        float ms = 0.0f;
+        if (!enqueued || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return fail(PT_ERR_HIP, std::string(who) + ": the launch failed");
+        if (k == 0 || ms < best) best = ms;
+    }
+    *msBest = best;
+    return 0;
+}
+
+// the three rule timers after their checks: the statement `which` of the pose's rule from the rest pose into the scratch copy
+int ruleTime(pt_pose* P, const float* xforms, int which, int reps, const char* who, float* msBest) {
+    if (const int rc = scratchAtRest(P, xforms)) return rc;
+    return bestTime(P->plan->stream, reps, who, [&] { return ruleLaunch(P, P->dRest, P->dScratch, which) == hipSuccess; }, msBest);
+}
+
+// which corners the pose's rule moves, a byte per corner: from the part ids or the bone table, which lie on the device (no triangles: left empty)
+int movedCorners(pt_pose* P, std::vector<unsigned char>& moved) {
+    if (!P->nTris) return 0;
+    const hipStream_t st = P->plan->stream;
+    const bool bones = hasBones(P);
+    HIP_TRY(hipSetDevice(P->device));
+    moved.resize((size_t)P->nTris * 3);
+    std::vector<int32_t> words((size_t)P->nTris * (bones ? 12 : 1));
+    HIP_TRY(hipMemcpyAsync(words.data(), bones ? P->dBone : P->dPart, words.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t q = 0; q < moved.size(); q++) moved[q] = (bones ? words[4 * q] : words[q / 3]) >= 0;
     return 0;
 }
 
@@ -201,25 +293,17 @@ int poseSlow(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, cons
     rc = moveGeometry(c, P->plan, tris.data(), tris.size() * 4, ellip, ellipBytes, rootCost, inPlace);
     for (size_t k = 0; k < was.size(); k++) c->poses[k]->stale = was[k] != 0;
     if (rc) return rc;
-    P->accepted.assign(xforms, xforms + xformBytes / 4);
-    P->acceptedWeights = P->weights;
-    P->acceptedMode = P->normalsMode;
+    poseAccepted(P, xforms, xformBytes);
     return PT_OK;
 }
 
-// pt_pose_create, pt_skin_create and pt_skin_dq_create after their argument checks: triPart, or the two corner tables of a skin (dualQuat: under
-// include/pt_skin_dq.h's rule)
-int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, const int32_t* bone, const float* weight, bool dualQuat, pt_pose** out) {
+// pt_pose_create, pt_skin_create and pt_skin_dq_create after their argument checks: triPart under RULE_PARTS, the two corner tables of a skin
+// under the other two
+int poseCreate(pt_ctx* c, size_t nTris, int nParts, PoseRule rule, const int32_t* triPart, const int32_t* bone, const float* weight, pt_pose** out) {
     int rc;
     if (c->multi) {
-        if (!c->multi->staleBindings.empty())
-            return fail(PT_ERR_SCENE, "an earlier pt_set_buffer / pt_set_texture failed after it had reached some of the context's streams: repeat that upload before rendering");
-        rc = multiRun(*c->multi, [](pt_ctx* k) {
-            HIP_TRY(hipSetDevice(k->device));
-            if (const int r = flushStream(k)) return r;
-            return k->sceneDirty ? buildScene(k) : 0;
-        });
-        if (rc) return rc;
+        if (!c->multi->staleBindings.empty()) return fail(PT_ERR_SCENE, MULTI_UPLOAD_FAILED);
+        if ((rc = multiFlushAndBuild(*c->multi))) return rc;
     } else {
         HIP_TRY(hipSetDevice(c->device));
         if ((rc = flushStream(c))) return rc;
@@ -234,17 +318,17 @@ int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, cons
                               b.objidx.data(), b.objidx.size() * 4, (int64_t)nTris, &plan)))
         return rc;
     pt_pose* P = new pt_pose();
-    P->ctx = c; P->device = on->device; P->nParts = nParts; P->nTris = (int64_t)nTris; P->plan = plan; P->skinned = bone != nullptr; P->dualQuat = dualQuat;
+    P->ctx = c; P->device = on->device; P->nParts = nParts; P->nTris = (int64_t)nTris; P->plan = plan; P->rule = rule;
     const hipStream_t st = plan->stream;
     auto upload = [&]() {
         HIP_TRY(hipSetDevice(P->device));
         HIP_TRY(P->dRest.upload(b.tris.data(), nTris * 160, st));
-        if (P->skinned) {
+        if (hasBones(P)) {
             HIP_TRY(P->dBone.upload(bone, nTris * 48, st));
             HIP_TRY(P->dWeight.upload(weight, nTris * 48, st));
         } else HIP_TRY(P->dPart.upload(triPart, nTris * 4, st));
         HIP_TRY(P->dX.reset(std::max<size_t>((size_t)nParts * 96, 16)));
-        if (P->dualQuat) HIP_TRY(P->dDq.reset(std::max<size_t>((size_t)nParts * 32, 16)));
+        if (rule == RULE_SKIN_DQ) HIP_TRY(P->dDq.reset(std::max<size_t>((size_t)nParts * 32, 16)));
         if (nTris) HIP_TRY(hipMemcpyAsync(plan->dTris, P->dRest, nTris * 160, hipMemcpyDeviceToDevice, st));      // the static triangles, once
         HIP_TRY(hipStreamSynchronize(st));
         return 0;
@@ -261,19 +345,19 @@ int poseCreate(pt_ctx* c, size_t nTris, int nParts, const int32_t* triPart, cons
 int pt_pose_create(pt_ctx* c, const int32_t* triPart, size_t partBytes, int nParts, pt_pose** out) {
     const size_t nTris = c ? hostTriangleCount(firstStream(c)) : 0;
     if (int rc = fail(ptp::checkPoseCreate(c, triPart, partBytes, nParts, out, nTris))) return rc;
-    return poseCreate(c, nTris, nParts, triPart, nullptr, nullptr, false, out);
+    return poseCreate(c, nTris, nParts, RULE_PARTS, triPart, nullptr, nullptr, out);
 }
 
 int pt_skin_create(pt_ctx* c, const int32_t* bone, size_t boneBytes, const float* weight, size_t weightBytes, int nParts, pt_pose** out) {
     const size_t nTris = c && bone && weight && out ? hostTriangleCount(firstStream(c)) : 0;     // (the context is read only once no argument is null)
     if (int rc = fail(ptp::checkSkinCreate(c, bone, boneBytes, weight, weightBytes, nParts, out, nTris))) return rc;
-    return poseCreate(c, nTris, nParts, nullptr, bone, weight, false, out);
+    return poseCreate(c, nTris, nParts, RULE_SKIN, nullptr, bone, weight, out);
 }
 
 int pt_skin_dq_create(pt_ctx* c, const int32_t* bone, size_t boneBytes, const float* weight, size_t weightBytes, int nParts, pt_pose** out) {
     const size_t nTris = c && bone && weight && out ? hostTriangleCount(firstStream(c)) : 0;     // (the context is read only once no argument is null)
     if (int rc = fail(ptp::checkSkinCreate(c, bone, boneBytes, weight, weightBytes, nParts, out, nTris, nullptr, "pt_skin_dq_create"))) return rc;
-    return poseCreate(c, nTris, nParts, nullptr, bone, weight, true, out);
+    return poseCreate(c, nTris, nParts, RULE_SKIN_DQ, nullptr, bone, weight, out);
 }
 
 int pt_pose_triangles(pt_pose* P, const float* xforms, size_t xformBytes, float* trisOut, size_t triBytes) {
@@ -317,7 +401,7 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     if (rc) {
         const std::string msg = g_err;
         if (c->behind == P) {
-            int rc2 = poseInto(P, P->accepted.empty() ? nullptr : P->accepted.data(), P->acceptedWeights, P->acceptedMode, plan->dTris);
+            int rc2 = poseStateInto(P, P->accepted, plan->dTris);
             if (!rc2) rc2 = pt_refit_kernels_(plan, "pt_pose_geometry");
             if (rc2) return rc2;
         }
@@ -339,16 +423,9 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     int unordered = 0;
     if ((rc = movePatchRecords(c, plan, roots, ellip, &unordered))) return rc;
     c->behind = P;                                                // a pose the context was behind on before is superseded
-    P->accepted.assign(xforms, xforms + xformBytes / 4);
-    P->acceptedWeights = P->weights;
-    P->acceptedMode = P->normalsMode;
-    if (ellip) c->buf.ellip.assign(ellip, ellip + ellipBytes / 4);
-    moveAccepted(c, ellip != nullptr);
+    poseAccepted(P, xforms, xformBytes);
     bool rebuilt = false;
-    if (unordered && c->built.asmEligible && c->built.asmNodeStride == 80) {      // the modes assume ordered boxes: the scene build decides (and settles)
-        if ((rc = buildScene(c))) { c->sceneDirty = true; return rc; }
-        rebuilt = true;
-    }
+    if ((rc = moveCommitted(c, ellip, ellipBytes, unordered, &rebuilt))) return rc;       // (a rebuild settles)
     if (rootCost) std::copy(cost.begin(), cost.begin() + plan->s.nRoots, rootCost);
     if (inPlace) *inPlace = rebuilt ? 0 : 1;
     return PT_OK;
@@ -372,90 +449,26 @@ int pt_debug_pose_time(pt_pose* P, const float* xforms, size_t xformBytes, int w
     const bool live = poseLive(P);
     if (!live || !msBest || reps < 1 || (which != PT_POSE_PER_QUAD && which != PT_POSE_PER_TRIANGLE) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
         return fail(PT_ERR_ARG, "pt_debug_pose_time: bad argument");
-    if (P->dualQuat) return fail(PT_ERR_ARG, "pt_debug_pose_time: a DQ pose has no part table (pt_debug_skin_dq_time times its kernels)");
-    if (P->skinned) return fail(PT_ERR_ARG, "pt_debug_pose_time: a skinned pose has no part table (pt_debug_skin_time times its kernels)");
-    std::vector<float> tris((size_t)P->nTris * 40);
-    int rc = poseToHost(P, xforms, {}, 0, tris.data());           // (the scratch copy and the matrices are in place afterwards; unmorphed, the rule's normals)
-    if (rc) return rc;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    const hipStream_t st = P->plan->stream;
-    float best = 0.0f;
-    for (int k = 0; k < reps && !rc; k++) {
-        hipEventRecord(e0, st);
-        const hipError_t e = ptPoseLaunch(P->dRest, P->dPart, P->nTris, P->dX, P->dScratch, (PtPoseKernel)which, st);
-        hipEventRecord(e1, st);
-        float ms = 0.0f;
-        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_pose_time: the launch failed");
-        if (k == 0 || ms < best) best = ms;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (!rc) *msBest = best;
-    return rc;
+    if (P->rule == RULE_SKIN_DQ) return fail(PT_ERR_ARG, "pt_debug_pose_time: a DQ pose has no part table (pt_debug_skin_dq_time times its kernels)");
+    if (P->rule == RULE_SKIN) return fail(PT_ERR_ARG, "pt_debug_pose_time: a skinned pose has no part table (pt_debug_skin_time times its kernels)");
+    return ruleTime(P, xforms, which, reps, "pt_debug_pose_time", msBest);
 }
 
 // include/pt_debug.h: the device time of one skin launch (the best of reps), into the pose's scratch copy
 int pt_debug_skin_time(pt_pose* P, const float* xforms, size_t xformBytes, int which, int reps, float* msBest) {
     const bool live = poseLive(P);
-    if (!live || !P->skinned || !msBest || reps < 1 || (which != PT_SKIN_PER_QUAD && which != PT_SKIN_PER_CORNER) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
+    if (!live || !hasBones(P) || !msBest || reps < 1 || (which != PT_SKIN_PER_QUAD && which != PT_SKIN_PER_CORNER) || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
         return fail(PT_ERR_ARG, "pt_debug_skin_time: bad argument");
-    if (P->dualQuat) return fail(PT_ERR_ARG, "pt_debug_skin_time: a DQ pose blends no matrices (pt_debug_skin_dq_time times its kernels)");
-    // the scratch copy is the whole rest pose again and the matrices are in place: what pt_debug_pose_scratch reads afterwards is this kernel's alone
-    const hipStream_t st = P->plan->stream;
-    HIP_TRY(hipSetDevice(P->device));
-    if (!P->scratchReady) HIP_TRY(P->dScratch.reset(P->nTris ? (size_t)P->nTris * 160 : 16));
-    if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
-    P->scratchReady = true;
-    HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
-    HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    int rc = 0;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    float best = 0.0f;
-    for (int k = 0; k < reps && !rc; k++) {
-        hipEventRecord(e0, st);
-        const hipError_t e = ptSkinLaunch(P->dRest, P->dBone, P->dWeight, P->nTris, P->dX, P->dScratch, (PtSkinKernel)which, st);
-        hipEventRecord(e1, st);
-        float ms = 0.0f;
-        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_skin_time: the launch failed");
-        if (k == 0 || ms < best) best = ms;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (!rc) *msBest = best;
-    return rc;
+    if (P->rule == RULE_SKIN_DQ) return fail(PT_ERR_ARG, "pt_debug_skin_time: a DQ pose blends no matrices (pt_debug_skin_dq_time times its kernels)");
+    return ruleTime(P, xforms, which, reps, "pt_debug_skin_time", msBest);
 }
 
 // include/pt_debug.h: the device time of the two launches of a DQ pose, records then corners (the best of reps), into the pose's scratch copy
 int pt_debug_skin_dq_time(pt_pose* P, const float* xforms, size_t xformBytes, int reps, float* msBest) {
     const bool live = poseLive(P);
-    if (!live || !P->dualQuat || !msBest || reps < 1 || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
+    if (!live || P->rule != RULE_SKIN_DQ || !msBest || reps < 1 || !xforms || P->nParts < 1 || xformBytes != (size_t)P->nParts * 96)
         return fail(PT_ERR_ARG, "pt_debug_skin_dq_time: bad argument");
-    // the scratch copy is the whole rest pose again and the matrices are in place: what pt_debug_pose_scratch reads afterwards is these kernels' alone
-    const hipStream_t st = P->plan->stream;
-    HIP_TRY(hipSetDevice(P->device));
-    if (!P->scratchReady) HIP_TRY(P->dScratch.reset(P->nTris ? (size_t)P->nTris * 160 : 16));
-    if (P->nTris) HIP_TRY(hipMemcpyAsync(P->dScratch, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
-    P->scratchReady = true;
-    HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
-    HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    int rc = 0;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    float best = 0.0f;
-    for (int k = 0; k < reps && !rc; k++) {
-        hipEventRecord(e0, st);
-        hipError_t e = ptSkinDqRecordsLaunch(P->dX, P->nParts, P->dDq, st);
-        if (e == hipSuccess) e = ptSkinDqLaunch(P->dRest, P->dBone, P->dWeight, P->nTris, P->dDq, P->dScratch, st);
-        hipEventRecord(e1, st);
-        float ms = 0.0f;
-        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_skin_dq_time: the launch failed");
-        if (k == 0 || ms < best) best = ms;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (!rc) *msBest = best;
-    return rc;
+    return ruleTime(P, xforms, 0, reps, "pt_debug_skin_dq_time", msBest);
 }
 
 // include/pt_debug.h: the pose's scratch copy as the last pt_pose_triangles / pt_debug_pose_time / pt_debug_skin_time / pt_debug_skin_dq_time left it
@@ -474,17 +487,8 @@ int pt_debug_pose_scratch(pt_pose* P, float* trisOut, size_t triBytes) {
 int pt_morph_attach(pt_pose* P, int nTargets, const int64_t* targetStart, size_t startBytes, const int32_t* entryCorner, size_t cornerBytes, const float* entryDelta,
                     size_t deltaBytes) {
     const bool live = poseLive(P);
-    // which corners the pose's rule moves: from the part ids or the bone table, which lie on the device
     std::vector<unsigned char> moved;
-    if (live && targetStart && entryCorner && entryDelta && !P->nTargets && P->nTris) {
-        const hipStream_t st = P->plan->stream;
-        HIP_TRY(hipSetDevice(P->device));
-        moved.resize((size_t)P->nTris * 3);
-        std::vector<int32_t> words((size_t)P->nTris * (P->skinned ? 12 : 1));
-        HIP_TRY(hipMemcpyAsync(words.data(), P->skinned ? P->dBone : P->dPart, words.size() * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t q = 0; q < moved.size(); q++) moved[q] = (P->skinned ? words[4 * q] : words[q / 3]) >= 0;
-    }
+    if (live && targetStart && entryCorner && entryDelta && !P->nTargets) { if (const int rc = movedCorners(P, moved)) return rc; }
     if (int rc = fail(ptp::checkMorphAttach(live, live && P->nTargets, nTargets, targetStart, startBytes, entryCorner, cornerBytes, entryDelta, deltaBytes,
                                             live ? (size_t)P->nTris : 0, moved.data())))
         return rc;
@@ -523,21 +527,9 @@ int pt_debug_morph_time(pt_pose* P, const float* weights, size_t weightBytes, in
     HIP_TRY(hipSetDevice(P->device));
     HIP_TRY(hipMemcpyAsync(P->dMorphW, weights, (size_t)P->nTargets * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
-    int rc = 0;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    float best = 0.0f;
-    for (int k = 0; k < reps && !rc; k++) {
-        hipEventRecord(e0, st);
-        const hipError_t e = ptMorphLaunch(P->dRest, P->dMorphCorner, P->dMorphRow, P->dMorphEntry, P->dMorphW, P->nAffected, P->dMorphRest, st);
-        hipEventRecord(e1, st);
-        float ms = 0.0f;
-        if (e != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_morph_time: the launch failed");
-        if (k == 0 || ms < best) best = ms;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (!rc) *msBest = best;
-    return rc;
+    return bestTime(st, reps, "pt_debug_morph_time", [&] {
+        return ptMorphLaunch(P->dRest, P->dMorphCorner, P->dMorphRow, P->dMorphEntry, P->dMorphW, P->nAffected, P->dMorphRest, st) == hipSuccess;
+    }, msBest);
 }
 
 // include/pt_debug.h: the kernel alone, under the weights last set (launched also when every weight is zero), and the morphed rest pose downloaded
@@ -556,17 +548,8 @@ int pt_debug_morph_rest(pt_pose* P, float* trisOut, size_t triBytes) {
 
 int pt_normals_attach(pt_pose* P, const int32_t* cornerVertex, size_t vertexBytes, int64_t nVertices, uint32_t flags) {
     const bool live = poseLive(P);
-    // which corners the pose's rule moves: from the part ids or the bone table, which lie on the device
     std::vector<unsigned char> moved;
-    if (live && cornerVertex && !P->hasNormals && P->nTris) {
-        const hipStream_t st = P->plan->stream;
-        HIP_TRY(hipSetDevice(P->device));
-        moved.resize((size_t)P->nTris * 3);
-        std::vector<int32_t> words((size_t)P->nTris * (P->skinned ? 12 : 1));
-        HIP_TRY(hipMemcpyAsync(words.data(), P->skinned ? P->dBone : P->dPart, words.size() * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t q = 0; q < moved.size(); q++) moved[q] = (P->skinned ? words[4 * q] : words[q / 3]) >= 0;
-    }
+    if (live && cornerVertex && !P->hasNormals) { if (const int rc = movedCorners(P, moved)) return rc; }
     if (int rc = fail(ptp::checkNormalsAttach(live, live && P->hasNormals, cornerVertex, vertexBytes, nVertices, flags, live ? (size_t)P->nTris : 0, moved.data()))) return rc;
     if (P->stale) return fail(PT_ERR_SCENE, "pt_normals_attach: the scene was uploaded since pt_pose_create");
     ptp::NormalRows rows;
@@ -601,21 +584,7 @@ int pt_debug_normals_time(pt_pose* P, const float* xforms, size_t xformBytes, in
         xformBytes != (size_t)P->nParts * 96)
         return fail(PT_ERR_ARG, "pt_debug_normals_time: bad argument");
     std::vector<float> tris((size_t)P->nTris * 40);
-    int rc = poseToHost(P, xforms, P->weights, 0, tris.data());     // (the scratch copy holds the pose's rule's work afterwards; synchronised)
-    if (rc) return rc;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    const hipStream_t st = P->plan->stream;
-    float best = 0.0f;
-    for (int k = 0; k < reps && !rc; k++) {                          // (a launch reads vertices and writes normals: every repetition gives the same bits)
-        hipEventRecord(e0, st);
-        const int r = normalsInto(P, P->dScratch, (PtNormalsKernel)which);
-        hipEventRecord(e1, st);
-        float ms = 0.0f;
-        if (r || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_debug_normals_time: the launch failed");
-        if (k == 0 || ms < best) best = ms;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (!rc) *msBest = best;
-    return rc;
+    if (const int rc = poseToHost(P, xforms, P->weights, 0, tris.data())) return rc;       // (the scratch copy holds the pose's rule's work afterwards; synchronised)
+    // (a launch reads vertices and writes normals: every repetition gives the same bits)
+    return bestTime(P->plan->stream, reps, "pt_debug_normals_time", [&] { return normalsInto(P, P->dScratch, (PtNormalsKernel)which) == 0; }, msBest);
 }

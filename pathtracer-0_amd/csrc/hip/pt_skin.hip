@@ -13,26 +13,10 @@
 // the rest of the library, so a + w * x is a rounded product and a rounded sum.  Bone ids were range-checked on the host (checkSkinCreate).
 #include <hip/hip_runtime.h>
 
+#include "pt_geom_steps.hpp"
 #include "pt_skin_launch.hpp"
 
 namespace {
-
-constexpr int BLOCK = 256;
-
-__device__ __forceinline__ float4 scaled(const float w, const float4 x) { return make_float4(w * x.x, w * x.y, w * x.z, w * x.w); }
-__device__ __forceinline__ float4 added(const float4 a, const float w, const float4 x) {
-    return make_float4(a.x + w * x.x, a.y + w * x.y, a.z + w * x.z, a.w + w * x.w);
-}
-
-// the same arithmetic as pt_pose.hip's, on the blended rows
-__device__ __forceinline__ float4 posePoint(const float4 r0, const float4 r1, const float4 r2, const float4 v) {
-    return make_float4(((r0.x * v.x + r0.y * v.y) + r0.z * v.z) + r0.w, ((r1.x * v.x + r1.y * v.y) + r1.z * v.z) + r1.w,
-                       ((r2.x * v.x + r2.y * v.y) + r2.z * v.z) + r2.w, v.w);
-}
-// N lies at floats 12-20 of the record: n3 = (n00, n01, n02, n10), n4 = (n11, n12, n20, n21), n22
-__device__ __forceinline__ float4 poseNormal(const float4 n3, const float4 n4, const float n22, const float4 v) {
-    return make_float4((n3.x * v.x + n3.y * v.y) + n3.z * v.z, (n3.w * v.x + n4.x * v.y) + n4.y * v.z, (n4.z * v.x + n4.w * v.y) + n22 * v.z, v.w);
-}
 
 // the blend of three consecutive float4 of the records (from float4 `first`), slots in order; slot 0 is used
 __device__ __forceinline__ void blend3(const float4* __restrict__ xforms, const int first, const int4 b, const float4 w, float4& a0, float4& a1, float4& a2) {
@@ -63,7 +47,7 @@ __global__ void __launch_bounds__(BLOCK) k_skin_quads(const float4* __restrict__
     blend3(xforms, q < 3 ? 0 : 3, b, w, a0, a1, a2);               // (a normal lane blends floats 21-23 too: the padding, never used)
     const size_t at = 10 * (size_t)t + q;
     const float4 v = rest[at];
-    out[at] = q < 3 ? posePoint(a0, a1, a2, v) : poseNormal(a0, a1, a2.x, v);
+    out[at] = q < 3 ? posePoint(a0, a1, a2, v) : poseNormal(a0, a1, a2.x, v);      // (pt_pose.hip's arithmetic, on the blended rows)
 }
 
 __global__ void __launch_bounds__(BLOCK) k_skin_corners(const float4* __restrict__ rest, const int4* __restrict__ bone, const float4* __restrict__ weight, long long nCorners,
@@ -89,11 +73,11 @@ __global__ void __launch_bounds__(BLOCK) k_skin_corners(const float4* __restrict
 hipError_t ptSkinLaunch(const float* rest, const int32_t* bone, const float* weight, int64_t nTris, const float* xforms, float* out, PtSkinKernel which, hipStream_t s) {
     if (nTris <= 0) return hipGetLastError();
     const long long n = (which == PT_SKIN_PER_QUAD ? 6 : 3) * (long long)nTris;
-    const long long blocks = (n + BLOCK - 1) / BLOCK;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    unsigned blocks;
+    if (!gridOf(n, &blocks)) return hipErrorInvalidValue;
     const float4* r4 = reinterpret_cast<const float4*>(rest); const float4* x4 = reinterpret_cast<const float4*>(xforms); float4* o4 = reinterpret_cast<float4*>(out);
     const int4* b4 = reinterpret_cast<const int4*>(bone); const float4* w4 = reinterpret_cast<const float4*>(weight);
-    if (which == PT_SKIN_PER_QUAD) hipLaunchKernelGGL(k_skin_quads, dim3((unsigned)blocks), dim3(BLOCK), 0, s, r4, b4, w4, n, x4, o4);
-    else hipLaunchKernelGGL(k_skin_corners, dim3((unsigned)blocks), dim3(BLOCK), 0, s, r4, b4, w4, n, x4, o4);
+    if (which == PT_SKIN_PER_QUAD) hipLaunchKernelGGL(k_skin_quads, dim3(blocks), dim3(BLOCK), 0, s, r4, b4, w4, n, x4, o4);
+    else hipLaunchKernelGGL(k_skin_corners, dim3(blocks), dim3(BLOCK), 0, s, r4, b4, w4, n, x4, o4);
     return hipGetLastError();
 }

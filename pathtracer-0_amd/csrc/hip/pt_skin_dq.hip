@@ -12,16 +12,11 @@
 // a rounded sum, and sqrtf and / are the correctly rounded ones.  Bone ids were range-checked on the host (checkSkinCreate).
 #include <hip/hip_runtime.h>
 
+#include "pt_geom_steps.hpp"
 #include "pt_skin_dq_launch.hpp"
 
 namespace {
 
-constexpr int BLOCK = 256;
-
-__device__ __forceinline__ float4 scaled(const float w, const float4 x) { return make_float4(w * x.x, w * x.y, w * x.z, w * x.w); }
-__device__ __forceinline__ float4 added(const float4 a, const float w, const float4 x) {
-    return make_float4(a.x + w * x.x, a.y + w * x.y, a.z + w * x.z, a.w + w * x.w);
-}
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return ((a.x * b.x + a.y * b.y) + a.z * b.z) + a.w * b.w; }
 
 // one more slot onto the blend: the weight negated where the slot's real part lies across from the pivot's
@@ -89,27 +84,27 @@ __global__ void __launch_bounds__(BLOCK) k_skin_dq_corners(const float4* __restr
     const float t2 = 2.0f * (((dz * w - dw * z) + dy * x) - dx * y);
     const size_t at = 10 * (size_t)tri + c;
     const float4 v = rest[at], n = rest[at + 3];
-    // the same arithmetic as pt_pose.hip's, with M = [R | t] and N = R
-    out[at] = make_float4(((r00 * v.x + r01 * v.y) + r02 * v.z) + t0, ((r10 * v.x + r11 * v.y) + r12 * v.z) + t1, ((r20 * v.x + r21 * v.y) + r22 * v.z) + t2, v.w);
-    out[at + 3] = make_float4((r00 * n.x + r01 * n.y) + r02 * n.z, (r10 * n.x + r11 * n.y) + r12 * n.z, (r20 * n.x + r21 * n.y) + r22 * n.z, n.w);
+    // pt_pose.hip's arithmetic, on the record with M = [R | t] and N = R
+    out[at] = posePoint(make_float4(r00, r01, r02, t0), make_float4(r10, r11, r12, t1), make_float4(r20, r21, r22, t2), v);
+    out[at + 3] = poseNormal(make_float4(r00, r01, r02, r10), make_float4(r11, r12, r20, r21), r22, n);
 }
 
 }  // namespace
 
 hipError_t ptSkinDqRecordsLaunch(const float* xforms, int nParts, float* table, hipStream_t s) {
     if (nParts <= 0) return hipGetLastError();
-    const long long blocks = ((long long)nParts + BLOCK - 1) / BLOCK;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_dq_records, dim3((unsigned)blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(xforms), nParts, reinterpret_cast<float4*>(table));
+    unsigned blocks;
+    if (!gridOf(nParts, &blocks)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dq_records, dim3(blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(xforms), nParts, reinterpret_cast<float4*>(table));
     return hipGetLastError();
 }
 
 hipError_t ptSkinDqLaunch(const float* rest, const int32_t* bone, const float* weight, int64_t nTris, const float* table, float* out, hipStream_t s) {
     if (nTris <= 0) return hipGetLastError();
     const long long n = 3 * (long long)nTris;
-    const long long blocks = (n + BLOCK - 1) / BLOCK;
-    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_skin_dq_corners, dim3((unsigned)blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(rest), reinterpret_cast<const int4*>(bone),
+    unsigned blocks;
+    if (!gridOf(n, &blocks)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_skin_dq_corners, dim3(blocks), dim3(BLOCK), 0, s, reinterpret_cast<const float4*>(rest), reinterpret_cast<const int4*>(bone),
                        reinterpret_cast<const float4*>(weight), n, reinterpret_cast<const float4*>(table), reinterpret_cast<float4*>(out));
     return hipGetLastError();
 }

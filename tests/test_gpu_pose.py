@@ -74,6 +74,34 @@ def test_pose_triangles_equals_the_model(pt, renderer_mod, n):
     none.close(); pose.close(); r.close()
 
 
+@pytest.mark.parametrize("n", [43, 257])
+def test_both_statements_of_the_pose_kernel_equal_the_model(pt, renderer_mod, n):
+    """pt_debug_pose_time fills the scratch copy with the rest pose and runs the statement asked for, so pt_debug_pose_scratch reads that kernel's
+    work: one lane per float4 (a block ends inside the 43rd triangle) and one lane per triangle (the second block starts at the 257th), the only
+    place that holds k_pose_tris to the model.  The scene and the matrices are the test's above; the scratch copy holds another pose beforehand."""
+    b = dict(one_soup(pt, n))
+    t = b[3].reshape(-1, 40).copy()
+    t[::3, :24] = PM.special_triangles(len(t[::3]), seed=n).reshape(-1, 40)[:, :24]
+    b[3] = t.reshape(-1)
+    parts = PM.parts_mod4(n)
+    assert (parts < 0).any()
+    r = context(renderer_mod, b, MC.SKY, (MC.W, MC.H))
+    L = renderer_mod.lib()
+    pose = r.pose_create(parts, 3)
+    X = PM.matrices(3, 5)
+    want = PM.pose(b[3], parts, X)
+    pose.triangles(PM.matrices(3, 6))
+    x = np.ascontiguousarray(X, f32).reshape(-1)
+    for which in (0, 1):
+        best = C.c_float(-1.0)
+        assert L.pt_debug_pose_time(pose._h, x.ctypes.data, x.nbytes, which, 1, C.byref(best)) == 0, L.pt_last_error()
+        assert best.value >= 0.0
+        got = np.empty(n * 40, f32)
+        assert L.pt_debug_pose_scratch(pose._h, got.ctypes.data, got.nbytes) == 0, L.pt_last_error()
+        same_floats(got, want, (n, "statement", which))
+    pose.close(); r.close()
+
+
 # ------------------------------------------------------------------------------------------------ records and frames against the twin
 
 def pose_equals_twin(pt, renderer_mod, old, tex, size, parts, n_parts, X, tag, ellip=None, want_in_place=True, **opts):
