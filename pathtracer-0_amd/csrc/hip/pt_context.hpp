@@ -1,5 +1,5 @@
 // pt_context.hpp — a render context and what it owns (included by pt_hip.hip behind pt_kernels.hpp, whose State, Control and Batch it holds; not a
-// translation unit): the error text of the calling thread, struct pt_ctx, the pixels of a shard, the upload of the scene that pt_scene_layout.hpp
+// translation unit): the error text of the calling thread, struct pt_ctx, the upload of the scene that pt_scene_layout.hpp
 // laid out, the path pool, the frame inputs current at a call, and a context's accumulator slots to and from a whole host image.  Nothing here
 // launches a render kernel: that is pt_stream_dev.hpp.
 namespace {
@@ -127,21 +127,9 @@ struct pt_ctx {
 
 namespace {
 
-// tile-major enumeration of the pixels owned by `rank`
-void shardPixels(int W, int H, int rank, int count, std::vector<int32_t>& out) {
-    out.clear();
-    int ntx = (W + TILE_W - 1) / TILE_W, nty = (H + TILE_H - 1) / TILE_H;
-    for (int t = rank; t < ntx * nty; t += count) {
-        int tx = t % ntx, ty = t / ntx;
-        for (int y = ty * TILE_H; y < std::min(H, (ty + 1) * TILE_H); y++)
-            for (int x = tx * TILE_W; x < std::min(W, (tx + 1) * TILE_W); x++) out.push_back(y * W + x);
-    }
-}
-size_t shardSlots(int W, int H, int count) {
-    size_t mx = 0; std::vector<int32_t> tmp;
-    for (int r = 0; r < count; r++) { shardPixels(W, H, r, count, tmp); mx = std::max(mx, tmp.size()); }
-    return (mx + BLOCK - 1) / BLOCK * BLOCK;
-}
+// the pixels of a shard and their slots are pt_group_plan.hpp's (host only), in the kernels' tiles and blocks
+static_assert(TILE_W == ptp::SHARD_TILE_W && TILE_H == ptp::SHARD_TILE_H && BLOCK == ptp::SHARD_BLOCK,
+              "a shard's pixel list is dealt in the kernels' tiles, and its slots come in the blocks their launches cover");
 
 // The scene build's device half: lays the buffers out on the host (layoutScene, pt_scene_layout.hpp), uploads the arrays, wires DevScene, and only then
 // takes the layout's flags and modes into the context: a refused scene leaves the context as it was (sceneDirty stays set).

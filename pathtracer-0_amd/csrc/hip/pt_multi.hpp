@@ -18,6 +18,10 @@
 //
 // Host side: every stream's context is driven by its own host thread (the wavefront scheduler polls its device, pump()), so the
 // schedulers run concurrently; the group's entry points hand the call to the threads and join them.
+//
+// What is decided and what is done: the shard maps, the shape of a group (runs, transport, every refusal of pt_create_multi_part) and the gather
+// of one image (staging, copies, event edges, the collective's arguments) are pt_group_plan.hpp's, host only and run on the CPU by
+// tests/c/group_plan_check.cpp.  Here are the objects (workers, communicators, events, buffers) and the HIP and RCCL calls that carry a plan out.
 #pragma once
 #include <condition_variable>
 #include <dlfcn.h>
@@ -88,10 +92,9 @@ struct MultiCtx {
     int shardBase = 0, shardTotal = 0;  // they are shards shardBase .. shardBase+n-1 of shardTotal (== n: the whole image)
     std::vector<int> devices;           // per stream; equal entries adjacent
     std::vector<pt_ctx*> kids;
-    struct Run { int device, first, count; };      // the streams of one device
-    std::vector<Run> runs;
+    std::vector<ptp::GroupRun> runs;    // the streams of each device (ptp::planGroup)
+    ptp::GatherPlan plan;               // the gather of one image as data (ptp::planGather); multiGather issues it
     std::vector<Dev<float4>> staging;   // per run, on its device: its streams' accumulators side by side (several devices only)
-    bool useRccl = false;               // more than one distinct device (or PT_MULTI_FORCE_RCCL=1: the RCCL call path on a one-GPU box)
     bool virtualDevices = false;        // test mode PT_MULTI_VIRTUAL_DEVICES: the runs share one GPU, the transport between them is device copies
     std::vector<std::unique_ptr<Worker>> workers;
     std::vector<ncclComm_t> comms;      // one per run
@@ -109,13 +112,6 @@ namespace {
 
 // the context a group works on for a call that needs one device (its first stream's: the scene is replicated); a single context itself
 pt_ctx* firstStream(pt_ctx* c) { return c->multi ? c->multi->kids[0] : c; }
-
-// slot -> pixel of shards first .. first+count-1 of `total` into maps: nSlots per shard, shard-major, -1 = padding
-int shardMaps(int W, int H, int first, int count, int total, size_t nSlots, std::vector<int32_t>& maps) {
-    maps.resize((size_t)count * nSlots);
-    for (int r = 0; r < count; r++) { const int rc = pt_shard_map(W, H, first + r, total, maps.data() + (size_t)r * nSlots, nSlots); if (rc) return rc; }
-    return 0;
-}
 
 int multiRun(MultiCtx& M, const std::function<int(pt_ctx*)>& f) {
     for (int i = 0; i < M.n; i++) { pt_ctx* k = M.kids[i]; M.workers[i]->post([&f, k] { return f(k); }); }
@@ -161,16 +157,26 @@ void multiFree(pt_ctx* g) {
     g->multi = nullptr;
 }
 
+// k_unshard on stream s: the packed blocks of `shards` shards (nSlots each, shard-major) through their maps into the W x H image
+int launchUnshard(hipStream_t s, const float4* gathered, const int* maps, int nSlots, int shards, float4* full) {
+    const size_t total = (size_t)nSlots * shards;
+    hipLaunchKernelGGL(k_unshard, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, gathered, maps, nSlots, shards, full);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The ONE collective of an image: every stream completes image `age`; the shards of one device are copied into one block there, the
 // blocks go to devices[0] (ncclGather over xGMI when there are several devices), and — for a group that holds the whole image —
-// the un-tiling kernel writes the W x H image.  Stream-ordered on the root stream (kids[0]'s), not synchronised.
+// the un-tiling kernel writes the W x H image.  Stream-ordered on the root stream (kids[0]'s), not synchronised.  What is copied where, behind
+// which event, and the arguments of the collective are M.plan's (planGather, pt_group_plan.hpp); here are the calls.
 // *out: the whole image (shardTotal == n) or the group's packed block of n * nSlots accumulators, shard-major.
 int multiGather(pt_ctx* g, int age, float4** out) {
     MultiCtx& M = *g->multi;
+    const ptp::GatherPlan& P = M.plan;
     int rc;
     if ((rc = multiRun(M, [age](pt_ctx* k) { return pt_finish_image(k, age); }))) return rc;
     pt_ctx* root = M.kids[0];
-    const size_t nSlots = (size_t)root->nSlotsImg, total = nSlots * (size_t)M.n;
+    const size_t nSlots = (size_t)root->nSlotsImg, total = P.totalSlots;
     std::vector<float4*> img(M.n);
     for (int i = 0; i < M.n; i++) {
         pt_ctx* k = M.kids[i];
@@ -182,8 +188,8 @@ int multiGather(pt_ctx* g, int age, float4** out) {
         HIP_TRY(M.dFull.release());
         HIP_TRY(M.dAllMaps.release());
         HIP_TRY(M.dGathered.reset(total * 16));
-        if ((rc = shardMaps(g->W, g->H, M.shardBase, M.n, M.shardTotal, nSlots, M.maps))) return rc;
-        if (M.shardTotal == M.n) {
+        if ((rc = fail(ptp::shardMaps(g->W, g->H, M.shardBase, M.n, M.shardTotal, nSlots, M.maps)))) return rc;
+        if (P.untile) {
             HIP_TRY(M.dFull.reset((size_t)g->W * g->H * 16));
             HIP_TRY(M.dAllMaps.reset(total * 4));
             HIP_TRY(hipMemcpy(M.dAllMaps, M.maps.data(), total * 4, hipMemcpyHostToDevice));
@@ -193,28 +199,26 @@ int multiGather(pt_ctx* g, int age, float4** out) {
         HIP_TRY(hipSetDevice(M.devices[0]));
         M.gatherReady = true;
     }
-    // 1. per device: its streams' accumulators side by side, on the device's first stream (one stream: nothing to copy).  Without RCCL
-    //    (one device) the block IS the gathered buffer.
-    for (size_t ri = 0; ri < M.runs.size(); ri++) {
-        const auto& run = M.runs[ri];
-        if (run.count == 1 && M.useRccl) continue;
-        HIP_TRY(hipSetDevice(run.device));
-        pt_ctx* lead = M.kids[run.first];
-        if (M.useRccl) HIP_TRY(M.staging[ri].ensure((size_t)run.count * nSlots * 16));
-        float4* dst = M.useRccl ? M.staging[ri].p : M.dGathered + (size_t)run.first * nSlots;
-        for (int j = 0; j < run.count; j++) {
-            const int i = run.first + j;
-            if (j > 0) { HIP_TRY(hipEventRecord(M.ev[i], M.kids[i]->stream)); HIP_TRY(hipStreamWaitEvent(lead->stream, M.ev[i], 0)); }
-            HIP_TRY(hipMemcpyAsync(dst + (size_t)j * nSlots, img[i], nSlots * 16, hipMemcpyDeviceToDevice, lead->stream));
+    // 1. the copies, run by run on the run's device, and behind them the run's release
+    size_t ci = 0, li = 0;
+    for (size_t r = 0; r < M.runs.size(); r++) {
+        if (ci == P.copies.size() || P.copies[ci].run != (int)r) continue;
+        HIP_TRY(hipSetDevice(M.runs[r].device));
+        if (P.stagingBytes[r]) HIP_TRY(M.staging[r].ensure(P.stagingBytes[r]));
+        for (; ci < P.copies.size() && P.copies[ci].run == (int)r; ci++) {
+            const ptp::GatherCopy& c = P.copies[ci];
+            hipStream_t const lead = M.kids[c.lead]->stream;
+            if (c.waitFor >= 0) { HIP_TRY(hipEventRecord(M.ev[c.waitFor], M.kids[c.waitFor]->stream)); HIP_TRY(hipStreamWaitEvent(lead, M.ev[c.waitFor], 0)); }
+            HIP_TRY(hipMemcpyAsync((c.toStaging ? M.staging[r].p : M.dGathered.p) + c.dstSlot, img[c.shard], nSlots * 16, hipMemcpyDeviceToDevice, lead));
         }
-        // the other streams must not rotate their image rings past this image before the copies have read it
-        if (run.count > 1) {
-            HIP_TRY(hipEventRecord(M.ev[run.first], lead->stream));
-            for (int j = 1; j < run.count; j++) HIP_TRY(hipStreamWaitEvent(M.kids[run.first + j]->stream, M.ev[run.first], 0));
+        if (li < P.releases.size() && P.releases[li].run == (int)r) {
+            const ptp::GatherRelease& rel = P.releases[li++];
+            HIP_TRY(hipEventRecord(M.ev[rel.lead], M.kids[rel.lead]->stream));
+            for (int j = 0; j < rel.waiters; j++) HIP_TRY(hipStreamWaitEvent(M.kids[rel.firstWaiter + j]->stream, M.ev[rel.lead], 0));
         }
     }
-    // 2. across devices: ONE ncclGather, a block per device, root = devices[0]
-    if (M.useRccl) {
+    // 2. the sends: ONE ncclGather, a block per device, root = devices[0]
+    if (!P.sends.empty()) {
         if (!M.virtualDevices && (rc = g_rccl.load())) return rc;
         if (!M.virtualDevices && M.comms.empty()) {
             std::vector<int> devs;
@@ -224,34 +228,31 @@ int multiGather(pt_ctx* g, int age, float4** out) {
             if (e != ncclSuccess) { M.comms.clear(); return fail(PT_ERR_HIP, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(e)); }      // the next call starts over
         }
         if (!M.virtualDevices) RCCL_TRY(g_rccl.GroupStart());
-        for (size_t r = 0; r < M.runs.size(); r++) {
-            const auto& run = M.runs[r];
+        for (const ptp::GatherSend& s : P.sends) {
             // every exit from inside the group closes it: an open group would swallow the next call's collectives
-            { const hipError_t he = hipSetDevice(run.device); if (he != hipSuccess) { if (!M.virtualDevices) g_rccl.GroupEnd(); return fail(PT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(he)); } }
-            const float4* send = run.count == 1 ? img[run.first] : M.staging[r].p;
-            // recvbuff matters on the root only; the other ranks pass a valid local pointer that is never written
-            void* const recv = r == 0 ? (void*)M.dGathered : (void*)send;
-            const size_t floats = (size_t)run.count * nSlots * 4;
-            hipStream_t const strm = M.kids[run.first]->stream;
+            { const hipError_t he = hipSetDevice(M.runs[s.run].device); if (he != hipSuccess) { if (!M.virtualDevices) g_rccl.GroupEnd(); return fail(PT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(he)); } }
+            const float4* send = s.fromImage ? img[s.shard] : M.staging[s.run].p;
+            hipStream_t const strm = M.kids[s.shard]->stream;
             if (M.virtualDevices) {
-                // what ncclGather does with these arguments, by device copies: rank r's block lands at r * count in the root's receive buffer,
-                // and the root's stream continues once every block has arrived
-                hipError_t he = hipMemcpyAsync((float*)M.dGathered.p + r * floats, send, floats * 4, hipMemcpyDeviceToDevice, strm);
-                if (he == hipSuccess && r > 0) { he = hipEventRecord(M.ev[run.first], strm); if (he == hipSuccess) he = hipStreamWaitEvent(root->stream, M.ev[run.first], 0); }
+                // what ncclGather does with these arguments, by device copies: rank r's block lands at r * count in the root's receive buffer
+                // (the plan's rootOffset), and the root's stream continues once every block has arrived
+                hipError_t he = hipMemcpyAsync((float*)M.dGathered.p + s.rootOffset, send, s.floats * 4, hipMemcpyDeviceToDevice, strm);
+                if (he == hipSuccess && s.rootWaits) { he = hipEventRecord(M.ev[s.shard], strm); if (he == hipSuccess) he = hipStreamWaitEvent(root->stream, M.ev[s.shard], 0); }
                 if (he != hipSuccess) return fail(PT_ERR_HIP, std::string("virtual-device gather: ") + hipGetErrorString(he));
-                (void)recv;
                 continue;
             }
-            ncclResult_t e = g_rccl.Gather(send, recv, floats, ncclFloat, 0, M.comms[r], strm);
+            // recvbuff matters on the root only; the other ranks pass a valid local pointer that is never written
+            void* const recv = s.recvIsGathered ? (void*)M.dGathered : (void*)send;
+            ncclResult_t e = g_rccl.Gather(send, recv, s.floats, ncclFloat, 0, M.comms[s.run], strm);
             if (e != ncclSuccess) { g_rccl.GroupEnd(); return fail(PT_ERR_HIP, std::string("ncclGather: ") + g_rccl.GetErrorString(e)); }
         }
         if (!M.virtualDevices) RCCL_TRY(g_rccl.GroupEnd());
     }
     HIP_TRY(hipSetDevice(M.devices[0]));
     M.gathers++;
-    if (M.shardTotal != M.n) { *out = M.dGathered; return 0; }     // a part of the image: the host layer gathers the blocks of all processes
-    hipLaunchKernelGGL(k_unshard, dim3((unsigned)((total + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, root->stream, (const float4*)M.dGathered, M.dAllMaps, (int)nSlots, M.n, M.dFull);
-    HIP_TRY(hipGetLastError());
+    if (!P.untile) { *out = M.dGathered; return 0; }     // a part of the image: the host layer gathers the blocks of all processes
+    // 3. un-tile
+    if ((rc = launchUnshard(root->stream, M.dGathered, M.dAllMaps, (int)nSlots, M.n, M.dFull))) return rc;
     *out = M.dFull;
     return 0;
 }
