@@ -217,7 +217,8 @@ def test_a_checker_albedo_over_constant_illumination_comes_back_on_a_lattice():
 def _cpu_features(oracle, wl):
     """the feature records of include/pt_denoise.h from the oracle's rayScene along a float64 model of main()'s lens-centre ray (the records
     tests/test_gpu_features.py holds pt_read_features to); for scenes without textures"""
-    from test_gpu_features import _camera_dirs, _mats
+    from _reproject_ref64 import camera_dirs as _camera_dirs
+    from test_gpu_features import _mats
     h, w = wl.H, wl.W
     mats = _mats(wl)
     assert all(m[j] <= -1 for m in mats for j in (22, 23, 24, 32, 33, 35, 37, 39, 41))

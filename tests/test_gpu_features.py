@@ -3,6 +3,7 @@ ray, a bilinear-REPEAT model of map_Kd, pt_debug_intersect, and across context k
 import numpy as np
 import pytest
 
+from _reproject_ref64 import camera_dirs as _camera_dirs
 from test_gpu_parity import _no_vn_workload
 
 pytestmark = pytest.mark.gpu
@@ -28,22 +29,6 @@ def _mats(wl):
     me = int(m[0])
     n = (m.size - 1) // me
     return [m[me * k: me * k + me] for k in range(n)]
-
-
-def _camera_dirs(wl, W, H):
-    """main() frag.glsl:894-908 with the lens offset zero, in float64: normalize(ORIGIN + direction * focus - ORIGIN)"""
-    P = np.asarray(wl.buffers[4], np.float64)
-    ax, ay, az = np.asarray(wl.buffers[1], np.float64)
-    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
-    RX = np.array([[1, 0, 0], [0, cx, sx], [0, -sx, cx]])
-    RY = np.array([[cy, 0, -sy], [0, 1, 0], [sy, 0, cy]])
-    RZ = np.array([[cz, sz, 0], [-sz, cz, 0], [0, 0, 1]]) if az != 0 else np.eye(3)
-    M = RX @ RY @ RZ
-    y, x = np.mgrid[0:H, 0:W]
-    tcx, tcy = (x + 0.5) / W, (y + 0.5) / H
-    q = np.stack([(tcx * 2 - 1) * -1 * P[0], (tcy * 2 - 1) * P[3] * P[0], np.full(x.shape, P[1])], -1)
-    d = q @ M
-    return d / np.linalg.norm(d, axis=-1, keepdims=True)          # focus > 0 in every scene here: the focal distance only scales
 
 
 def _workloads(pt):

@@ -185,7 +185,7 @@ def test_fma_is_exactly_rounded():
 
 
 def _dirs(wl):
-    from test_gpu_features import _camera_dirs
+    from _reproject_ref64 import camera_dirs as _camera_dirs
     return _camera_dirs(wl, wl.W, wl.H).astype(f32)
 
 
