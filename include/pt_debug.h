@@ -103,6 +103,12 @@ int pt_debug_morph_rest(struct pt_pose* pose, float* tris_out, size_t tri_bytes)
  * PT_ERR_ARG: a null or destroyed pose, a pose without normals, n_parts == 0, null xforms, xform_bytes != n_parts * 96, reps < 1, an unknown
  * statement, null ms_best. */
 int pt_debug_normals_time(struct pt_pose* pose, const float* xforms, size_t xform_bytes, int which, int reps, float* ms_best);
+/* The device time of the launches of a rig of include/pt_rig.h (scripts/rig_probe.py) over the given locals: one launch of k_rig_level per level
+ * of the hierarchy, from the roots down, one pair of HIP events around all of them, the best of reps, on the pose's stream.  The rig's own tables
+ * are written (W and the records); nothing of the pose or the context changes.  PT_ERR_ARG: a null or destroyed rig, n_parts == 0, null locals,
+ * local_bytes != n_parts * 48, reps < 1, null ms_best. */
+struct pt_rig;
+int pt_debug_rig_time(struct pt_rig* rig, const float* locals, size_t local_bytes, int reps, float* ms_best);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
  *   - a refit plan of its own (include/pt_refit.h) over the context's bindings 10-13.
  * (include/pt_skin.h makes a pose object under a second rule — up to four records blended per corner — that every call below takes as well.)
  * (include/pt_normals.h attaches vertex ids to a pose object of either kind: the normals are then recomputed from the posed surface after the rule.)
+ * (include/pt_rig.h attaches a joint hierarchy to a pose object of any kind: the records are then made on the device from local joint transforms.)
  * (include/pt_morph.h attaches morph targets to a pose object of either kind: the rule then starts from the morphed rest pose.  NOT BUILT for
  *  any of the three: posed ellipsoids; JNI natives; rebuilding degraded trees.)
  *

@@ -13,8 +13,13 @@
 // instead of pt_skin.hip's one, pt_skin_dq_rule.hpp's CPU statement; again ruleLaunch is the one place that tells them apart.
 //
 // One of each: ruleLaunch launches the pose's rule (pt_pose::rule says which of the three), for poseInto with the statements chosen below and for
-// the debug timers with the caller's; bestTime is the one timing loop of the five pt_debug_*_time calls; poseAccepted records a call's records,
+// the debug timers with the caller's; bestTime is the one timing loop of the six pt_debug_*_time calls; poseAccepted records a call's records,
 // weights and normals mode as the pose's last accepted state (PoseState), which a refused call hands back to poseInto.
+//
+// A rig (include/pt_rig.h, pt_rig_create) belongs to a pose of any rule and makes that pose's records on the device: pt_rig.hip's launches behind
+// pt_rig_launch.hpp (the key blend, then one launch per level of the hierarchy) write them into the rig's dR, pt_rig_rule.hpp's checks, level
+// plan, clip interval and CPU statement.  poseGeometry is pt_pose_geometry after its argument checks, for the pose's own call and for the rig's
+// two: with the records also lying on the device, poseInto copies them from there into dX instead of uploading them, and nothing else differs.
 //
 // What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
 // kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
@@ -30,6 +35,8 @@ extern "C++" {
 #include "pt_morph_rule.hpp"
 #include "pt_normals_launch.hpp"
 #include "pt_normals_rule.hpp"
+#include "pt_rig_launch.hpp"
+#include "pt_rig_rule.hpp"
 #include <set>
 }
 #include "../../../include/pt_pose.h"
@@ -37,6 +44,7 @@ extern "C++" {
 #include "../../../include/pt_skin_dq.h"
 #include "../../../include/pt_morph.h"
 #include "../../../include/pt_normals.h"
+#include "../../../include/pt_rig.h"
 
 // the rule of a pose: per-part matrices from dPart (include/pt_pose.h); records blended per corner from dBone / dWeight, 12 words per triangle and
 // no dPart (include/pt_skin.h); the same two tables under the dual-quaternion blend (include/pt_skin_dq.h)
@@ -72,6 +80,20 @@ struct pt_pose {
     Dev<int32_t> dNrmTri, dNrmRow, dNrmCorner, dNrmCornerRow; Dev<float> dNrmFace;
     int normalsMode = 0;                // as pt_normals_mode set it last (after the attach: 1)
     bool stale = false;                 // the scene was uploaded since pt_pose_create
+    std::vector<pt_rig*> rigs;          // include/pt_rig.h: the rigs attached to this pose, which go with it
+};
+
+// a rig of include/pt_rig.h: one joint per record of its pose
+struct pt_rig {
+    pt_pose* pose = nullptr;
+    int n = 0;                          // joints == the pose's n_parts
+    ptp::RigPlan plan;                  // the joints by (depth, id) and the level starts
+    bool hasBind = false;
+    Dev<int32_t> dOrder, dParent;       // the plan's order; the parents by joint id
+    Dev<float> dBind, dLocals, dW, dR;  // 12 floats per joint: the inverse binds, the locals of a call (or a clip's blend), the world matrices; the records, 24 per joint
+    int nKeys = 0;                      // include/pt_rig.h step 5: > 0 once a clip is attached
+    std::vector<float> times;
+    Dev<float> dClip;                   // n_keys * n locals, key-major
 };
 
 namespace {
@@ -86,6 +108,12 @@ constexpr int RULE_KERNEL[3] = {POSE_KERNEL, SKIN_KERNEL, 0};    // by PoseRule:
 bool poseLive(pt_pose* p) {
     std::lock_guard<std::mutex> g(g_posesMutex);
     return p && g_poses.count(p);
+}
+
+std::set<pt_rig*> g_rigs;               // the live rigs, under g_posesMutex: a rig leaves with its pose at the latest
+bool rigLive(pt_rig* r) {
+    std::lock_guard<std::mutex> g(g_posesMutex);
+    return r && g_rigs.count(r);
 }
 
 // the morphed rest pose under `weights` (host, nTargets floats) into dMorphRest; asynchronous on the plan's stream
@@ -123,8 +151,9 @@ hipError_t ruleLaunch(pt_pose* P, const float* rest, float* dst, int which) {
 
 // the pose of `xforms` (host; nullptr: the rest pose, unmorphed, its normals as they are) under the morph weights `weights` (host; empty: no morph,
 // or every weight 0) and the normals mode `mode` (1: recomputed where normals are attached) into dst, which holds the rest pose's static
-// triangles; asynchronous on the plan's stream
-int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights, int mode, float* dst) {
+// triangles; asynchronous on the plan's stream.  onDevice: where the same records lie on the device already (a rig's dR): copied from there,
+// not uploaded
+int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights, int mode, float* dst, const float* onDevice = nullptr) {
     const hipStream_t st = P->plan->stream;
     if (!xforms || P->nParts == 0) {                              // (n_parts == 0: a morph has no entries)
         if (P->nTris) HIP_TRY(hipMemcpyAsync(dst, P->dRest, (size_t)P->nTris * 160, hipMemcpyDeviceToDevice, st));
@@ -136,7 +165,8 @@ int poseInto(pt_pose* P, const float* xforms, const std::vector<float>& weights,
     if (morphed) { if (const int rc = morphRest(P, weights.data())) return rc; }
     const float* rest = morphed ? (const float*)P->dMorphRest : (const float*)P->dRest;
     HIP_TRY(P->dX.ensure((size_t)P->nParts * 96));
-    HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
+    if (onDevice) HIP_TRY(hipMemcpyAsync(P->dX, onDevice, (size_t)P->nParts * 96, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(hipMemcpyAsync(P->dX, xforms, (size_t)P->nParts * 96, hipMemcpyHostToDevice, st));
     HIP_TRY(ruleLaunch(P, rest, dst, RULE_KERNEL[P->rule]));
     if (P->hasNormals && mode == 1) return normalsInto(P, dst, NORMALS_KERNEL);
     return 0;
@@ -225,6 +255,11 @@ int movedCorners(pt_pose* P, std::vector<unsigned char>& moved) {
 
 void poseFree(pt_pose* P) {
     hipSetDevice(P->device);
+    {
+        std::lock_guard<std::mutex> g(g_posesMutex);
+        for (pt_rig* r : P->rigs) g_rigs.erase(r);
+    }
+    for (pt_rig* r : P->rigs) delete r;
     pt_refit_destroy(P->plan);
     delete P;
 }
@@ -366,10 +401,11 @@ int pt_pose_triangles(pt_pose* P, const float* xforms, size_t xformBytes, float*
     return poseToHost(P, xforms, P->weights, P->normalsMode, trisOut);
 }
 
-int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
-    const bool live = poseLive(P);
-    if (int rc = fail(ptp::checkPoseGeometry(c, live, live && P->ctx == c, xforms, xformBytes, live ? P->nParts : 0, ellip, ellipBytes))) return rc;
-    if (P->stale) return fail(PT_ERR_SCENE, "pt_pose_geometry: the scene was uploaded since pt_pose_create");
+namespace {
+// pt_pose_geometry after its argument checks, under the name `who` of the call it serves; onDevice: as for poseInto
+int poseGeometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, const float* onDevice, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace,
+                 const char* who) {
+    if (P->stale) return fail(PT_ERR_SCENE, std::string(who) + ": the scene was uploaded since pt_pose_create");
     if (c->multi) return poseSlow(c, P, xforms, xformBytes, ellip, ellipBytes, rootCost, inPlace);
     HIP_TRY(hipSetDevice(c->device));
     int rc;
@@ -397,12 +433,12 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     }
 
     // pose + refit: the plan's working copies only.  A refusal puts back what a settle would have delivered
-    if (!(rc = poseInto(P, xforms, P->weights, P->normalsMode, plan->dTris))) rc = pt_refit_kernels_(plan, "pt_pose_geometry");
+    if (!(rc = poseInto(P, xforms, P->weights, P->normalsMode, plan->dTris, onDevice))) rc = pt_refit_kernels_(plan, who);
     if (rc) {
         const std::string msg = g_err;
         if (c->behind == P) {
             int rc2 = poseStateInto(P, P->accepted, plan->dTris);
-            if (!rc2) rc2 = pt_refit_kernels_(plan, "pt_pose_geometry");
+            if (!rc2) rc2 = pt_refit_kernels_(plan, who);
             if (rc2) return rc2;
         }
         return fail(rc, msg);
@@ -429,6 +465,13 @@ int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformByt
     if (rootCost) std::copy(cost.begin(), cost.begin() + plan->s.nRoots, rootCost);
     if (inPlace) *inPlace = rebuilt ? 0 : 1;
     return PT_OK;
+}
+}  // namespace
+
+int pt_pose_geometry(pt_ctx* c, pt_pose* P, const float* xforms, size_t xformBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+    const bool live = poseLive(P);
+    if (int rc = fail(ptp::checkPoseGeometry(c, live, live && P->ctx == c, xforms, xformBytes, live ? P->nParts : 0, ellip, ellipBytes))) return rc;
+    return poseGeometry(c, P, xforms, xformBytes, nullptr, ellip, ellipBytes, rootCost, inPlace, "pt_pose_geometry");
 }
 
 void pt_pose_destroy(pt_pose* P) {
@@ -587,4 +630,145 @@ int pt_debug_normals_time(pt_pose* P, const float* xforms, size_t xformBytes, in
     if (const int rc = poseToHost(P, xforms, P->weights, 0, tris.data())) return rc;       // (the scratch copy holds the pose's rule's work afterwards; synchronised)
     // (a launch reads vertices and writes normals: every repetition gives the same bits)
     return bestTime(P->plan->stream, reps, "pt_debug_normals_time", [&] { return normalsInto(P, P->dScratch, (PtNormalsKernel)which) == 0; }, msBest);
+}
+
+// ---- include/pt_rig.h
+
+namespace {
+
+// steps 1-4 over the locals at dLocals (device) into `records`, level by level from the roots down; asynchronous on the plan's stream
+int rigRun(pt_rig* G, const float* dLocals, float* records) {
+    const hipStream_t st = G->pose->plan->stream;
+    for (int l = 0; l < G->plan.levels(); l++) {
+        const int first = G->plan.levelStart[(size_t)l], count = G->plan.levelStart[(size_t)l + 1] - first;
+        HIP_TRY(ptRigLevelLaunch(G->dOrder, first, count, G->dParent, dLocals, G->hasBind ? (const float*)G->dBind : nullptr, G->dW, records, st));
+    }
+    return 0;
+}
+
+// the records of a call into dR: of `locals` (host), or with clip of the attached clip at time t (no NaN); asynchronous on the plan's stream
+int rigInto(pt_rig* G, bool clip, const float* locals, float t) {
+    const hipStream_t st = G->pose->plan->stream;
+    const size_t keyFloats = (size_t)G->n * PT_RIG_LOCAL_FLOATS;
+    HIP_TRY(hipSetDevice(G->pose->device));
+    if (G->n == 0) return 0;
+    const float* src = G->dLocals;
+    if (!clip) HIP_TRY(hipMemcpyAsync(G->dLocals, locals, keyFloats * 4, hipMemcpyHostToDevice, st));
+    else {
+        int k; float u;
+        const int exact = ptp::rigInterval(G->times.data(), G->nKeys, t, &k, &u);
+        if (exact >= 0) src = G->dClip + keyFloats * (size_t)exact;                  // a key's own locals, bit for bit
+        else HIP_TRY(ptRigBlendLaunch(G->dClip + keyFloats * (size_t)k, G->dClip + keyFloats * (size_t)(k + 1), u, G->n, G->dLocals, st));
+    }
+    return rigRun(G, src, G->dR);
+}
+
+// dR downloaded; the plan's stream is idle afterwards
+int rigDownload(pt_rig* G, float* out) {
+    const hipStream_t st = G->pose->plan->stream;
+    if (G->n) HIP_TRY(hipMemcpyAsync(out, G->dR, (size_t)G->n * 96, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// the two geometry calls after their argument checks: R on the device and, for the accepted state and the slow paths, on the host; then the pose's one path
+int rigGeometry(pt_ctx* c, pt_rig* G, bool clip, const float* locals, float t, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace, const char* who) {
+    pt_pose* P = G->pose;
+    if (P->stale) return fail(PT_ERR_SCENE, std::string(who) + ": the scene was uploaded since pt_pose_create");
+    std::vector<float> R((size_t)G->n * PT_POSE_RECORD_FLOATS);
+    int rc;
+    if ((rc = rigInto(G, clip, locals, t)) || (rc = rigDownload(G, R.data()))) return rc;
+    return poseGeometry(c, P, R.data(), R.size() * 4, G->n ? (const float*)G->dR : nullptr, ellip, ellipBytes, rootCost, inPlace, who);
+}
+
+}  // namespace
+
+int pt_rig_create(pt_pose* P, const int32_t* parent, size_t parentBytes, const float* invBind, size_t bindBytes, pt_rig** out) {
+    const bool live = poseLive(P);
+    if (int rc = fail(ptp::checkRigCreate(P, live, parent, parentBytes, invBind, bindBytes, out, live ? P->nParts : 0))) return rc;
+    pt_rig* G = new pt_rig();
+    G->pose = P; G->n = P->nParts; G->hasBind = invBind != nullptr;
+    ptp::rigPlan(parent, (size_t)G->n, G->plan);
+    const hipStream_t st = P->plan->stream;
+    const size_t n = (size_t)G->n;
+    auto upload = [&]() {
+        HIP_TRY(hipSetDevice(P->device));
+        HIP_TRY(G->dOrder.upload(G->plan.order.data(), n * 4, st));
+        HIP_TRY(G->dParent.upload(parent, n * 4, st));
+        HIP_TRY(G->dBind.upload(invBind, invBind ? n * 48 : 0, st));
+        HIP_TRY(G->dLocals.reset(std::max<size_t>(n * 48, 16)));
+        HIP_TRY(G->dW.reset(std::max<size_t>(n * 48, 16)));
+        HIP_TRY(G->dR.reset(std::max<size_t>(n * 96, 16)));
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    };
+    if (const int rc = upload()) { const std::string msg = g_err; delete G; return fail(rc, msg); }
+    { std::lock_guard<std::mutex> g(g_posesMutex); g_rigs.insert(G); }
+    P->rigs.push_back(G);
+    *out = G;
+    return PT_OK;
+}
+
+int pt_rig_records(pt_rig* G, const float* locals, size_t localBytes, float* recordsOut, size_t recordBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigRecords(live, locals, localBytes, recordsOut, recordBytes, live ? G->n : 0))) return rc;
+    if (const int rc = rigInto(G, false, locals, 0.0f)) return rc;
+    return rigDownload(G, recordsOut);
+}
+
+int pt_rig_clip_attach(pt_rig* G, int nKeys, const float* times, size_t timeBytes, const float* values, size_t valueBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigClipAttach(live, nKeys, times, timeBytes, values, valueBytes, live ? G->n : 0))) return rc;
+    const hipStream_t st = G->pose->plan->stream;
+    HIP_TRY(hipSetDevice(G->pose->device));
+    Dev<float> clip;                                              // the rig changes only once the allocation stands
+    HIP_TRY(clip.upload(values, valueBytes, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    G->dClip = std::move(clip);
+    G->times.assign(times, times + nKeys);
+    G->nKeys = nKeys;
+    return PT_OK;
+}
+
+int pt_rig_clip_records(pt_rig* G, float t, float* recordsOut, size_t recordBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigClipRecords(live, live && G->nKeys > 0, t, recordsOut, recordBytes, live ? G->n : 0))) return rc;
+    if (const int rc = rigInto(G, true, nullptr, t)) return rc;
+    return rigDownload(G, recordsOut);
+}
+
+int pt_rig_pose_geometry(pt_ctx* c, pt_rig* G, const float* locals, size_t localBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigGeometry(false, c, live, live && G->pose->ctx == c, locals, localBytes, false, 0.0f, live ? G->n : 0, ellip, ellipBytes))) return rc;
+    return rigGeometry(c, G, false, locals, 0.0f, ellip, ellipBytes, rootCost, inPlace, "pt_rig_pose_geometry");
+}
+
+int pt_rig_clip_pose_geometry(pt_ctx* c, pt_rig* G, float t, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigGeometry(true, c, live, live && G->pose->ctx == c, nullptr, 0, live && G->nKeys > 0, t, live ? G->n : 0, ellip, ellipBytes))) return rc;
+    return rigGeometry(c, G, true, nullptr, t, ellip, ellipBytes, rootCost, inPlace, "pt_rig_clip_pose_geometry");
+}
+
+void pt_rig_destroy(pt_rig* G) {
+    if (!G) return;
+    {
+        std::lock_guard<std::mutex> g(g_posesMutex);
+        if (!g_rigs.erase(G)) return;                             // not a live rig: destroyed already, by this call or with its pose
+    }
+    pt_pose* P = G->pose;
+    hipSetDevice(P->device);
+    P->rigs.erase(std::remove(P->rigs.begin(), P->rigs.end(), G), P->rigs.end());
+    delete G;
+}
+
+// include/pt_debug.h: the device time of the rig's launches over the given locals, every level from the roots down (the best of reps), into dR
+int pt_debug_rig_time(pt_rig* G, const float* locals, size_t localBytes, int reps, float* msBest) {
+    const bool live = rigLive(G);
+    if (!live || !msBest || reps < 1 || !locals || G->n < 1 || localBytes != (size_t)G->n * 48) return fail(PT_ERR_ARG, "pt_debug_rig_time: bad argument");
+    const hipStream_t st = G->pose->plan->stream;
+    HIP_TRY(hipSetDevice(G->pose->device));
+    HIP_TRY(hipMemcpyAsync(G->dLocals, locals, localBytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // (a launch reads locals and parents' W and writes W and R: every repetition gives the same bits)
+    return bestTime(st, reps, "pt_debug_rig_time", [&] { return rigRun(G, G->dLocals, G->dR) == 0; }, msBest);
 }

@@ -210,6 +210,17 @@ def lib():
         if hasattr(L, "pt_skin_dq_create"):                   # include/pt_skin_dq.h, and its kernel timer in include/pt_debug.h
             L.pt_skin_dq_create.argtypes = [vp, vp, sz, vp, sz, ci, C.POINTER(vp)]
             L.pt_debug_skin_dq_time.argtypes = [vp, vp, sz, ci, C.POINTER(C.c_float)]
+        if hasattr(L, "pt_rig_create"):                       # include/pt_rig.h, and its kernel timer in include/pt_debug.h
+            cf, cip = C.c_float, C.POINTER(ci)
+            L.pt_rig_create.argtypes = [vp, vp, sz, vp, sz, C.POINTER(vp)]
+            L.pt_rig_records.argtypes = [vp, vp, sz, vp, sz]
+            L.pt_rig_pose_geometry.argtypes = [vp, vp, vp, sz, vp, sz, vp, cip]
+            L.pt_rig_clip_attach.argtypes = [vp, ci, vp, sz, vp, sz]
+            L.pt_rig_clip_records.argtypes = [vp, cf, vp, sz]
+            L.pt_rig_clip_pose_geometry.argtypes = [vp, vp, cf, vp, sz, vp, cip]
+            L.pt_rig_destroy.argtypes = [vp]
+            L.pt_rig_destroy.restype = None
+            L.pt_debug_rig_time.argtypes = [vp, vp, sz, ci, C.POINTER(cf)]
         if hasattr(L, "pt_morph_attach"):                     # include/pt_morph.h, and its kernel timer and read-back in include/pt_debug.h
             L.pt_morph_attach.argtypes = [vp, ci, vp, sz, vp, sz, vp, sz]
             L.pt_morph_weights.argtypes = [vp, vp, sz]
@@ -382,6 +393,7 @@ class Pose:
         """skin: (corner_bone, corner_weight) of include/pt_skin.h instead of tri_part (Renderer.skin_create); blend: "linear" for that header's
         rule, "dq" for include/pt_skin_dq.h's"""
         self._L = renderer._L
+        self._renderer = renderer                                      # (what a Rig of this pose hands its context from)
         if blend not in ("linear", "dq") or (skin is None and blend != "linear"):
             raise ValueError(f"blend must be 'linear' or 'dq' (and 'dq' needs a skin), not {blend!r}")
         self.blend = blend if skin is not None else None
@@ -453,9 +465,94 @@ class Pose:
             raise RuntimeError("this libpt_hip.so has no pt_normals_mode (include/pt_normals.h): no fallback")
         _check(self._L.pt_normals_mode(self._h, int(on)))
 
+    def rig(self, parent, inv_bind=None):
+        """A Rig over this pose (pt_rig_create, include/pt_rig.h): parent[j] in [-1, j) per record of the pose, inv_bind (n_parts, 3, 4) or None.
+        It makes this pose's records on the device from local joint transforms or from a time into a keyed clip."""
+        return Rig(self, parent, inv_bind)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.pt_pose_destroy(self._h)
+            self._h = None
+
+
+def rig_locals(t=None, q=None, s=None, n=None):
+    """The 12-float locals of include/pt_rig.h for n joints: t (n, 3) translations (default 0), q (n, 4) quaternions as x y z w (default the
+    identity), s (n, 3) scales (default 1); the two padding floats are 0."""
+    given = [np.asarray(a) for a in (t, q, s) if a is not None]
+    n = int(n if n is not None else (given[0].reshape(-1, given[0].shape[-1]).shape[0] if given else 0))
+    out = np.zeros((n, 12), np.float32)
+    out[:, 7] = 1.0
+    out[:, 8:11] = 1.0
+    if t is not None:
+        out[:, 0:3] = np.asarray(t, np.float64).reshape(n, 3)
+    if q is not None:
+        out[:, 4:8] = np.asarray(q, np.float64).reshape(n, 4)
+    if s is not None:
+        out[:, 8:11] = np.asarray(s, np.float64).reshape(n, 3)
+    return out
+
+
+class Rig:
+    """A rig of include/pt_rig.h (Pose.rig): a joint per record of its pose, evaluated on the device.  It belongs to its Pose, whose close()
+    destroys it, as the Renderer's does."""
+
+    def __init__(self, pose, parent, inv_bind=None):
+        self._L, self._pose = pose._L, pose
+        if not hasattr(self._L, "pt_rig_create"):
+            raise RuntimeError("this libpt_hip.so has no pt_rig_create (include/pt_rig.h): no fallback")
+        p = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        b = None if inv_bind is None else np.ascontiguousarray(inv_bind, dtype=np.float32).reshape(-1)
+        self.n_parts, self.n_roots = pose.n_parts, pose.n_roots
+        self._h = C.c_void_p()
+        _check(self._L.pt_rig_create(pose._h, p.ctypes.data, p.nbytes, None if b is None else b.ctypes.data, 0 if b is None else b.nbytes, C.byref(self._h)))
+
+    @staticmethod
+    def _floats(a):
+        x = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        return x, (x.ctypes.data if x.size else None)
+
+    def records(self, locals):
+        """the records of these locals (n_parts x 12 floats: rig_locals), (n_parts, 24): the rule alone (pt_rig_records)"""
+        l, lp = self._floats(locals)
+        out = np.empty((self.n_parts, 24), np.float32)
+        _check(self._L.pt_rig_records(self._h, lp, l.nbytes, out.ctypes.data, out.nbytes))
+        return out
+
+    def _geometry(self, call, *args, ellip=None):
+        e = None if ellip is None else np.ascontiguousarray(ellip, dtype=np.float32)
+        cost = np.zeros(self.n_roots, np.float64)
+        in_place = C.c_int(-1)
+        _check(call(self._pose._renderer._h, self._h, *args, None if e is None else e.ctypes.data, 0 if e is None else e.nbytes, cost.ctypes.data, C.byref(in_place)))
+        return cost, bool(in_place.value)
+
+    def pose(self, locals, ellip=None):
+        """Renderer.pose_geometry of the pose under the records of these locals, made on the device (pt_rig_pose_geometry): no record is
+        uploaded.  Returns (root_cost, in_place)."""
+        l, lp = self._floats(locals)
+        return self._geometry(self._L.pt_rig_pose_geometry, lp, l.nbytes, ellip=ellip)
+
+    def clip(self, times, values):
+        """Attach a keyed clip (pt_rig_clip_attach): times (n_keys,) strictly increasing, values (n_keys, n_parts, 12) locals.  A second clip
+        replaces the first."""
+        t, tp = self._floats(times)
+        v, vp = self._floats(values)
+        _check(self._L.pt_rig_clip_attach(self._h, t.size, tp, t.nbytes, vp, v.nbytes))
+        self.n_keys = t.size
+
+    def records_at(self, t):
+        """the records of the clip at time t (pt_rig_clip_records): a normalised lerp between the two keys around t, clamped to the clip"""
+        out = np.empty((self.n_parts, 24), np.float32)
+        _check(self._L.pt_rig_clip_records(self._h, float(t), out.ctypes.data, out.nbytes))
+        return out
+
+    def pose_at(self, t, ellip=None):
+        """Rig.pose with the clip's records at time t (pt_rig_clip_pose_geometry): the step uploads one float"""
+        return self._geometry(self._L.pt_rig_clip_pose_geometry, float(t), ellip=ellip)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pt_rig_destroy(self._h)
             self._h = None
 
 

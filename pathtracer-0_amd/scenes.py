@@ -685,6 +685,38 @@ def m6_twisting(step=0, W=96, H=54, n_bones=5, a=0.25, **kw):
     return wl, bone, weight, m6_records(wl, step, n_bones, a)
 
 
+def m7_rig(wl, n_bones=5, a=0.16, times=(0.0, 1.0, 2.5), bends=(0.0, 1.0, -0.5)):
+    """The rig of m7_chained for a workload of m3_tube, in the terms of include/pt_rig.h: (parent int32[n_bones], inv_bind float32[n_bones, 12],
+    times float32[n_keys], values float32[n_keys, n_bones, 12]).  Joint i is the child of joint i - 1 and sits at M3's hinge i on the tube's
+    axis: its local translation is the step from the hinge below, its inverse bind the shift of its hinge to the origin.  In key k every joint
+    but the root turns locally by bends[k] * a about +z, so the bend accumulates down the chain: joint i's record is the turn by
+    i * bends[k] * a that m3_records makes, up to rounding.  Binary64, rounded once."""
+    cx, y0, y1, cz = wl.info["axis"]
+    pivots = np.array([(cx, y0 + (y1 - y0) * max(i - 0.5, 0.0) / (n_bones - 1), cz) for i in range(n_bones)])
+    parent = np.arange(-1, n_bones - 1, dtype=np.int32)
+    inv_bind = np.zeros((n_bones, 3, 4))
+    inv_bind[:, :, :3] = np.eye(3)
+    inv_bind[:, :, 3] = -pivots
+    values = np.zeros((len(times), n_bones, 12))
+    values[:, :, 8:11] = 1.0
+    values[:, 0, 0:3] = pivots[0]
+    values[:, 1:, 0:3] = pivots[1:] - pivots[:-1]
+    values[:, :, 7] = 1.0
+    for k, bend in enumerate(bends):
+        half = 0.5 * float(bend) * a
+        values[k, 1:, 6], values[k, 1:, 7] = math.sin(half), math.cos(half)      # (x y z w) of a turn about +z
+    return parent, inv_bind.reshape(n_bones, 12).astype(np.float32), np.asarray(times, np.float32), values.astype(np.float32)
+
+
+def m7_chained(W=96, H=54, n_bones=5, a=0.16, **kw):
+    """M7, the workload of include/pt_rig.h (not a BASELINE config): M3's tube and ramp weights with its joints as one chain, animated by a
+    clip of three keys instead of by records.  -> (the rest pose's workload, corner_bone, corner_weight, parent, inv_bind, times, values);
+    the last four are m7_rig's."""
+    wl, bone, weight, _ = m3_bending(0, W, H, n_bones, **kw)
+    wl.name = "M7"
+    return (wl, bone, weight) + m7_rig(wl, n_bones, a)
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then
