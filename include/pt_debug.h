@@ -109,6 +109,11 @@ int pt_debug_normals_time(struct pt_pose* pose, const float* xforms, size_t xfor
  * local_bytes != n_parts * 48, reps < 1, null ms_best. */
 struct pt_rig;
 int pt_debug_rig_time(struct pt_rig* rig, const float* locals, size_t local_bytes, int reps, float* ms_best);
+/* The device time of the one launch of k_rig_mix of include/pt_rig_mix.h (scripts/rig_mix_probe.py) over the given layers: one pair of HIP
+ * events around it, the best of reps, on the pose's stream.  The rig's locals are written (what pt_rig_mix_locals downloads); nothing of the pose
+ * or the context changes.  PT_ERR_ARG: a null or destroyed rig, n_parts == 0, layers that pt_rig_mix_locals refuses, reps < 1, null ms_best. */
+struct pt_rig_layer;
+int pt_debug_rig_mix_time(struct pt_rig* rig, const struct pt_rig_layer* layers, size_t layer_bytes, int reps, float* ms_best);
 
 #ifdef __cplusplus
 }

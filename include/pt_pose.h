@@ -12,6 +12,7 @@
  * (include/pt_skin.h makes a pose object under a second rule — up to four records blended per corner — that every call below takes as well.)
  * (include/pt_normals.h attaches vertex ids to a pose object of either kind: the normals are then recomputed from the posed surface after the rule.)
  * (include/pt_rig.h attaches a joint hierarchy to a pose object of any kind: the records are then made on the device from local joint transforms.)
+ * (include/pt_rig_mix.h mixes several keyed clips of such a rig, layered and masked per joint, into those transforms on the device.)
  * (include/pt_morph.h attaches morph targets to a pose object of either kind: the rule then starts from the morphed rest pose.  NOT BUILT for
  *  any of the three: posed ellipsoids; JNI natives; rebuilding degraded trees.)
  *

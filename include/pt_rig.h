@@ -72,6 +72,8 @@
  * OWNERSHIP.  A rig belongs to its pose: pt_pose_destroy and pt_destroy destroy it.  A destroyed rig is refused, not followed, for as long as
  * its address is not reused.  ORDER and threads: as include/pt_pose.h.  pt_debug_rig_time (include/pt_debug.h) times the rig's launches.
  *
+ * SEVERAL CLIPS AT ONCE (cross-fades, masked and additive layers, loops): include/pt_rig_mix.h.
+ *
  * NOT BUILT: sparse per-channel tracks, slerp, cubic keys, joints that write no record.
  */
 #ifndef PT_RIG_H

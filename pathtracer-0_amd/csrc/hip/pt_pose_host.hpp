@@ -19,7 +19,9 @@
 // A rig (include/pt_rig.h, pt_rig_create) belongs to a pose of any rule and makes that pose's records on the device: pt_rig.hip's launches behind
 // pt_rig_launch.hpp (the key blend, then one launch per level of the hierarchy) write them into the rig's dR, pt_rig_rule.hpp's checks, level
 // plan, clip interval and CPU statement.  poseGeometry is pt_pose_geometry after its argument checks, for the pose's own call and for the rig's
-// two: with the records also lying on the device, poseInto copies them from there into dX instead of uploading them, and nothing else differs.
+// calls: with the records also lying on the device, poseInto copies them from there into dX instead of uploading them, and nothing else differs.
+// A mix (include/pt_rig_mix.h) is a third source of a rig's locals beside the caller's and the clip's: pt_rig_mix.hip's one launch behind
+// pt_rig_mix_launch.hpp writes them into dLocals from the rig's clip and mask slots, pt_rig_mix_rule.hpp's checks, loop wrap and CPU statement.
 //
 // What the pose's plan holds.  plan->dTris: static triangles (part -1) are the rest pose's from creation on and are never written again by a
 // kernel (the slow path's upload writes the same values); the others hold the pose last run.  While the context is behind on this pose
@@ -36,6 +38,8 @@ extern "C++" {
 #include "pt_normals_launch.hpp"
 #include "pt_normals_rule.hpp"
 #include "pt_rig_launch.hpp"
+#include "pt_rig_mix_launch.hpp"
+#include "pt_rig_mix_rule.hpp"
 #include "pt_rig_rule.hpp"
 #include <set>
 }
@@ -45,6 +49,7 @@ extern "C++" {
 #include "../../../include/pt_morph.h"
 #include "../../../include/pt_normals.h"
 #include "../../../include/pt_rig.h"
+#include "../../../include/pt_rig_mix.h"
 
 // the rule of a pose: per-part matrices from dPart (include/pt_pose.h); records blended per corner from dBone / dWeight, 12 words per triangle and
 // no dPart (include/pt_skin.h); the same two tables under the dual-quaternion blend (include/pt_skin_dq.h)
@@ -94,6 +99,10 @@ struct pt_rig {
     int nKeys = 0;                      // include/pt_rig.h step 5: > 0 once a clip is attached
     std::vector<float> times;
     Dev<float> dClip;                   // n_keys * n locals, key-major
+    // include/pt_rig_mix.h: the clip slots (as the clip above, per slot; slots.nKeys[i] > 0 once slot i is filled) and the mask slots, n floats each
+    ptp::RigMixSlots slots;
+    std::vector<float> mixTimes[PT_RIG_MIX_SLOTS];
+    Dev<float> dMixClip[PT_RIG_MIX_SLOTS], dMixMask[PT_RIG_MIX_MASKS];
 };
 
 namespace {
@@ -646,14 +655,39 @@ int rigRun(pt_rig* G, const float* dLocals, float* records) {
     return 0;
 }
 
-// the records of a call into dR: of `locals` (host), or with clip of the attached clip at time t (no NaN); asynchronous on the plan's stream
-int rigInto(pt_rig* G, bool clip, const float* locals, float t) {
+// include/pt_rig_mix.h step 1 for every layer, and where its keys lie: the table k_rig_mix takes by value.  The layers were checked
+PtRigMixTable rigMixTable(pt_rig* G, const pt_rig_layer* layers, size_t layerBytes) {
+    PtRigMixTable T = {};
+    const size_t keyFloats = (size_t)G->n * PT_RIG_LOCAL_FLOATS;
+    T.nLayers = (int32_t)(layerBytes / sizeof(pt_rig_layer));
+    for (int l = 0; l < T.nLayers; l++) {
+        const pt_rig_layer& y = layers[l];
+        const ptp::RigMixStep s = ptp::rigMixStep(G->mixTimes[y.clip].data(), G->slots.nKeys[y.clip], y.wrap, y.t);
+        const float* keys = G->dMixClip[y.clip];
+        T.a[l] = keys + keyFloats * (size_t)s.ka; T.b[l] = keys + keyFloats * (size_t)s.kb; T.r[l] = keys;
+        T.mask[l] = y.mask >= 0 ? (const float*)G->dMixMask[y.mask] : nullptr;
+        T.u[l] = s.u; T.weight[l] = y.weight; T.mode[l] = y.mode;
+    }
+    return T;
+}
+
+// the mix of a table into dLocals; asynchronous on the plan's stream
+int rigMixInto(pt_rig* G, const PtRigMixTable& mix) {
+    HIP_TRY(hipSetDevice(G->pose->device));
+    HIP_TRY(ptRigMixLaunch(mix, G->n, G->dLocals, G->pose->plan->stream));
+    return 0;
+}
+
+// the records of a call into dR: of `locals` (host), with clip of the attached clip at time t (no NaN), or with mix of that table's layers;
+// asynchronous on the plan's stream
+int rigInto(pt_rig* G, bool clip, const float* locals, float t, const PtRigMixTable* mix = nullptr) {
     const hipStream_t st = G->pose->plan->stream;
     const size_t keyFloats = (size_t)G->n * PT_RIG_LOCAL_FLOATS;
     HIP_TRY(hipSetDevice(G->pose->device));
     if (G->n == 0) return 0;
     const float* src = G->dLocals;
-    if (!clip) HIP_TRY(hipMemcpyAsync(G->dLocals, locals, keyFloats * 4, hipMemcpyHostToDevice, st));
+    if (mix) { if (const int rc = rigMixInto(G, *mix)) return rc; }
+    else if (!clip) HIP_TRY(hipMemcpyAsync(G->dLocals, locals, keyFloats * 4, hipMemcpyHostToDevice, st));
     else {
         int k; float u;
         const int exact = ptp::rigInterval(G->times.data(), G->nKeys, t, &k, &u);
@@ -671,13 +705,14 @@ int rigDownload(pt_rig* G, float* out) {
     return 0;
 }
 
-// the two geometry calls after their argument checks: R on the device and, for the accepted state and the slow paths, on the host; then the pose's one path
-int rigGeometry(pt_ctx* c, pt_rig* G, bool clip, const float* locals, float t, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace, const char* who) {
+// the geometry calls after their argument checks: R on the device and, for the accepted state and the slow paths, on the host; then the pose's one path
+int rigGeometry(pt_ctx* c, pt_rig* G, bool clip, const float* locals, float t, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace, const char* who,
+                const PtRigMixTable* mix = nullptr) {
     pt_pose* P = G->pose;
     if (P->stale) return fail(PT_ERR_SCENE, std::string(who) + ": the scene was uploaded since pt_pose_create");
     std::vector<float> R((size_t)G->n * PT_POSE_RECORD_FLOATS);
     int rc;
-    if ((rc = rigInto(G, clip, locals, t)) || (rc = rigDownload(G, R.data()))) return rc;
+    if ((rc = rigInto(G, clip, locals, t, mix)) || (rc = rigDownload(G, R.data()))) return rc;
     return poseGeometry(c, P, R.data(), R.size() * 4, G->n ? (const float*)G->dR : nullptr, ellip, ellipBytes, rootCost, inPlace, who);
 }
 
@@ -771,4 +806,78 @@ int pt_debug_rig_time(pt_rig* G, const float* locals, size_t localBytes, int rep
     HIP_TRY(hipStreamSynchronize(st));
     // (a launch reads locals and parents' W and writes W and R: every repetition gives the same bits)
     return bestTime(st, reps, "pt_debug_rig_time", [&] { return rigRun(G, G->dLocals, G->dR) == 0; }, msBest);
+}
+
+// ---- include/pt_rig_mix.h
+
+int pt_rig_mix_clip(pt_rig* G, int slot, int nKeys, const float* times, size_t timeBytes, const float* values, size_t valueBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigMixClip(live, slot, nKeys, times, timeBytes, values, valueBytes, live ? G->n : 0))) return rc;
+    const hipStream_t st = G->pose->plan->stream;
+    HIP_TRY(hipSetDevice(G->pose->device));
+    Dev<float> clip;                                              // the rig changes only once the allocation stands
+    HIP_TRY(clip.upload(values, valueBytes, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    G->dMixClip[slot] = std::move(clip);
+    G->mixTimes[slot].assign(times, times + nKeys);
+    G->slots.nKeys[slot] = nKeys;
+    return PT_OK;
+}
+
+int pt_rig_mix_mask(pt_rig* G, int slot, const float* weights, size_t weightBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigMixMask(live, slot, weights, weightBytes, live ? G->n : 0))) return rc;
+    const hipStream_t st = G->pose->plan->stream;
+    HIP_TRY(hipSetDevice(G->pose->device));
+    Dev<float> mask;
+    HIP_TRY(mask.upload(weights, weightBytes, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    G->dMixMask[slot] = std::move(mask);
+    G->slots.mask[slot] = true;
+    return PT_OK;
+}
+
+int pt_rig_mix_locals(pt_rig* G, const pt_rig_layer* layers, size_t layerBytes, float* localsOut, size_t localBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigMixLayers(ptp::RIG_MIX_LOCALS, nullptr, live, true, live ? G->slots : ptp::RigMixSlots(), layers, layerBytes, localsOut, localBytes,
+                                             live ? G->n : 0)))
+        return rc;
+    const hipStream_t st = G->pose->plan->stream;
+    const PtRigMixTable T = rigMixTable(G, layers, layerBytes);
+    if (const int rc = rigMixInto(G, T)) return rc;
+    if (G->n) HIP_TRY(hipMemcpyAsync(localsOut, G->dLocals, localBytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+int pt_rig_mix_records(pt_rig* G, const pt_rig_layer* layers, size_t layerBytes, float* recordsOut, size_t recordBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigMixLayers(ptp::RIG_MIX_RECORDS, nullptr, live, true, live ? G->slots : ptp::RigMixSlots(), layers, layerBytes, recordsOut, recordBytes,
+                                             live ? G->n : 0)))
+        return rc;
+    const PtRigMixTable T = rigMixTable(G, layers, layerBytes);
+    if (const int rc = rigInto(G, false, nullptr, 0.0f, &T)) return rc;
+    return rigDownload(G, recordsOut);
+}
+
+int pt_rig_mix_pose_geometry(pt_ctx* c, pt_rig* G, const pt_rig_layer* layers, size_t layerBytes, const float* ellip, size_t ellipBytes, double* rootCost, int* inPlace) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigMixLayers(ptp::RIG_MIX_GEOMETRY, c, live, live && G->pose->ctx == c, live ? G->slots : ptp::RigMixSlots(), layers, layerBytes, ellip,
+                                             ellipBytes, live ? G->n : 0)))
+        return rc;
+    const PtRigMixTable T = rigMixTable(G, layers, layerBytes);
+    return rigGeometry(c, G, false, nullptr, 0.0f, ellip, ellipBytes, rootCost, inPlace, "pt_rig_mix_pose_geometry", &T);
+}
+
+// include/pt_debug.h: the device time of the mix's one launch over the given layers (the best of reps), into dLocals
+int pt_debug_rig_mix_time(pt_rig* G, const pt_rig_layer* layers, size_t layerBytes, int reps, float* msBest) {
+    const bool live = rigLive(G);
+    if (!live || !msBest || reps < 1 || G->n < 1) return fail(PT_ERR_ARG, "pt_debug_rig_mix_time: bad argument");
+    if (ptp::checkRigMixLayers(ptp::RIG_MIX_LOCALS, nullptr, true, true, G->slots, layers, layerBytes, msBest, (size_t)G->n * 48, G->n).code)      // (the layers' checks; no output here)
+        return fail(PT_ERR_ARG, "pt_debug_rig_mix_time: bad argument");
+    const hipStream_t st = G->pose->plan->stream;
+    HIP_TRY(hipSetDevice(G->pose->device));
+    const PtRigMixTable T = rigMixTable(G, layers, layerBytes);
+    // (a launch reads keys and masks and writes dLocals: every repetition gives the same bits)
+    return bestTime(st, reps, "pt_debug_rig_mix_time", [&] { return rigMixInto(G, T) == 0; }, msBest);
 }

@@ -221,6 +221,14 @@ def lib():
             L.pt_rig_destroy.argtypes = [vp]
             L.pt_rig_destroy.restype = None
             L.pt_debug_rig_time.argtypes = [vp, vp, sz, ci, C.POINTER(cf)]
+        if hasattr(L, "pt_rig_mix_clip"):                     # include/pt_rig_mix.h, and its kernel timer in include/pt_debug.h
+            cf, cip = C.c_float, C.POINTER(ci)
+            L.pt_rig_mix_clip.argtypes = [vp, ci, ci, vp, sz, vp, sz]
+            L.pt_rig_mix_mask.argtypes = [vp, ci, vp, sz]
+            L.pt_rig_mix_locals.argtypes = [vp, vp, sz, vp, sz]
+            L.pt_rig_mix_records.argtypes = [vp, vp, sz, vp, sz]
+            L.pt_rig_mix_pose_geometry.argtypes = [vp, vp, vp, sz, vp, sz, vp, cip]
+            L.pt_debug_rig_mix_time.argtypes = [vp, vp, sz, ci, C.POINTER(cf)]
         if hasattr(L, "pt_morph_attach"):                     # include/pt_morph.h, and its kernel timer and read-back in include/pt_debug.h
             L.pt_morph_attach.argtypes = [vp, ci, vp, sz, vp, sz, vp, sz]
             L.pt_morph_weights.argtypes = [vp, vp, sz]
@@ -493,6 +501,31 @@ def rig_locals(t=None, q=None, s=None, n=None):
     return out
 
 
+RIG_LAYER = np.dtype([("clip", np.int32), ("mask", np.int32), ("mode", np.int32), ("wrap", np.int32), ("t", np.float32), ("weight", np.float32)])      # pt_rig_layer, 24 bytes
+RIG_MIX_MODES = {"override": 0, "additive": 1}
+RIG_MIX_WRAPS = {"clamp": 0, "loop": 1}
+
+
+def rig_layers(layers):
+    """The 24-byte layer records of include/pt_rig_mix.h from a list of tuples (clip, t[, weight[, mask[, mode[, wrap]]]]) or dicts with those
+    keys; weight defaults to 1, mask to -1 (none), mode to "override" (or "additive", or the number), wrap to "clamp" (or "loop", or the
+    number).  An array of RIG_LAYER passes through."""
+    if isinstance(layers, np.ndarray) and layers.dtype == RIG_LAYER:
+        return np.ascontiguousarray(layers).reshape(-1)
+    names = ("clip", "t", "weight", "mask", "mode", "wrap")
+    out = np.zeros(len(layers), RIG_LAYER)
+    for i, y in enumerate(layers):
+        d = dict(weight=1.0, mask=-1, mode=0, wrap=0)
+        d.update(y if isinstance(y, dict) else dict(zip(names, y)))
+        unknown = set(d) - set(names)
+        if unknown or "clip" not in d or "t" not in d:
+            raise ValueError(f"rig_layers: layer {i} needs clip and t and knows {names}")
+        mode, wrap = d["mode"], d["wrap"]
+        out[i] = (int(d["clip"]), int(d["mask"]), RIG_MIX_MODES[mode] if isinstance(mode, str) else int(mode), RIG_MIX_WRAPS[wrap] if isinstance(wrap, str) else int(wrap),
+                  np.float32(d["t"]), np.float32(d["weight"]))
+    return out
+
+
 class Rig:
     """A rig of include/pt_rig.h (Pose.rig): a joint per record of its pose, evaluated on the device.  It belongs to its Pose, whose close()
     destroys it, as the Renderer's does."""
@@ -549,6 +582,42 @@ class Rig:
     def pose_at(self, t, ellip=None):
         """Rig.pose with the clip's records at time t (pt_rig_clip_pose_geometry): the step uploads one float"""
         return self._geometry(self._L.pt_rig_clip_pose_geometry, float(t), ellip=ellip)
+
+    def _mix_call(self, name):
+        if not hasattr(self._L, name):
+            raise RuntimeError(f"this libpt_hip.so has no {name} (include/pt_rig_mix.h): no fallback")
+        return getattr(self._L, name)
+
+    def mix_clip(self, slot, times, values):
+        """Fill clip slot `slot` of include/pt_rig_mix.h (pt_rig_mix_clip): times and values as Rig.clip takes them.  A second attach to a
+        slot replaces the first; Rig.clip's own clip is another thing."""
+        t, tp = self._floats(times)
+        v, vp = self._floats(values)
+        _check(self._mix_call("pt_rig_mix_clip")(self._h, int(slot), t.size, tp, t.nbytes, vp, v.nbytes))
+
+    def mask(self, slot, weights):
+        """Fill mask slot `slot` (pt_rig_mix_mask): one weight in [0, 1] per joint"""
+        w, wp = self._floats(weights)
+        _check(self._mix_call("pt_rig_mix_mask")(self._h, int(slot), wp, w.nbytes))
+
+    def mix_locals(self, layers):
+        """the mixed locals of these layers (rig_layers, or what it takes), (n_parts, 12): the mix alone (pt_rig_mix_locals)"""
+        y = rig_layers(layers)
+        out = np.empty((self.n_parts, 12), np.float32)
+        _check(self._mix_call("pt_rig_mix_locals")(self._h, y.ctypes.data if y.size else None, y.nbytes, out.ctypes.data, out.nbytes))
+        return out
+
+    def mix_records(self, layers):
+        """the records of the mixed locals, (n_parts, 24) (pt_rig_mix_records)"""
+        y = rig_layers(layers)
+        out = np.empty((self.n_parts, 24), np.float32)
+        _check(self._mix_call("pt_rig_mix_records")(self._h, y.ctypes.data if y.size else None, y.nbytes, out.ctypes.data, out.nbytes))
+        return out
+
+    def mix(self, layers, ellip=None):
+        """Rig.pose with the records of the mixed locals (pt_rig_mix_pose_geometry): the step uploads the layers, 24 bytes each"""
+        y = rig_layers(layers)
+        return self._geometry(self._mix_call("pt_rig_mix_pose_geometry"), y.ctypes.data if y.size else None, y.nbytes, ellip=ellip)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -717,6 +717,37 @@ def m7_chained(W=96, H=54, n_bones=5, a=0.16, **kw):
     return (wl, bone, weight) + m7_rig(wl, n_bones, a)
 
 
+def m8_rig(wl, n_bones=5, a=0.16, b=0.25):
+    """The rig of m8_mixed for a workload of m3_tube, in the terms of include/pt_rig_mix.h: (parent, inv_bind, clips, mask).  parent and
+    inv_bind are m7_rig's.  clips[0] is m7_rig's bend about +z; clips[1] has its own key times and twists every joint but the root locally by
+    twists[k] * b about +y, the tube's axis, as m6_records does.  Each is (times float32[n_keys], values float32[n_keys, n_bones, 12]); key 0 of
+    both is the rest pose.  mask float32[n_bones] ramps from 0 at the root to 1 at the tip."""
+    parent, inv_bind, times, bend = m7_rig(wl, n_bones, a)
+    _, _, times2, twist = m7_rig(wl, n_bones, b, times=(0.0, 0.75, 2.0, 3.0), bends=(0.0, 1.0, -1.0, 0.5))
+    twist[:, :, 5], twist[:, :, 6] = twist[:, :, 6].copy(), 0.0        # (x y z w): the turn about +z becomes the same turn about +y
+    mask = (np.arange(n_bones) / max(n_bones - 1, 1)).astype(np.float32)
+    return parent, inv_bind, [(times, bend), (times2, twist)], mask
+
+
+def m8_layers(step):
+    """the layers of m8_mixed at `step`, as renderer.rig_layers takes them: the bend looping as the base, the twist looping at its own pace
+    faded in and out over it, and the bend once more, slower, added through the mask (slot 0)"""
+    s = float(step)
+    fade = 0.5 - 0.5 * math.cos(0.2 * s)
+    return [dict(clip=0, t=0.3 * s, wrap="loop"),
+            dict(clip=1, t=0.4 * s, weight=fade, wrap="loop"),
+            dict(clip=0, t=0.45 * s, weight=0.75, mask=0, mode="additive", wrap="loop")]
+
+
+def m8_mixed(step=0, W=96, H=54, n_bones=5, **kw):
+    """M8 at `step`, the workload of include/pt_rig_mix.h (not a BASELINE config): M7's chain with two clips in slots, M7's bend and a twist
+    about the tube's axis, and a mask that ramps from the root to the tip.  -> (the rest pose's workload, corner_bone, corner_weight, parent,
+    inv_bind, clips, mask, layers); only the layers depend on step (m8_layers), the four before them are m8_rig's."""
+    wl, bone, weight, _ = m3_bending(0, W, H, n_bones, **kw)
+    wl.name = "M8"
+    return (wl, bone, weight) + m8_rig(wl, n_bones) + (m8_layers(step),)
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then
