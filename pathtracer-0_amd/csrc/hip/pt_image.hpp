@@ -812,6 +812,12 @@ int pt_read_display_denoised_guided_through(pt_ctx* c, const pt_through_rule* ru
 // triangles animated by per-part matrices on the device (include/pt_pose.h), on the in-place move's path
 #include "pt_pose_host.hpp"
 
+// a joint hierarchy, keyed clips and their layered mix making a pose's records on the device (include/pt_rig.h, include/pt_rig_mix.h)
+#include "pt_rig_host.hpp"
+
+// the pose family's timers and readers of include/pt_debug.h
+#include "pt_geom_debug_host.hpp"
+
 // the outlier rejection (include/pt_despeckle.h): both calls on historyMerge's path
 #include "pt_despeckle_host.hpp"
 

@@ -1,5 +1,5 @@
-// pt_rig_launch.hpp — the launch interface of the kernels of pt_rig.hip (include/pt_rig.h), called by the host half of the pose,
-// pt_pose_host.hpp.  Every pointer is device memory, 16-byte aligned; a launch is asynchronous on the given stream and returns
+// pt_rig_launch.hpp — the launch interface of the kernels of pt_rig.hip (include/pt_rig.h), called by the host half of the rig,
+// pt_rig_host.hpp.  Every pointer is device memory, 16-byte aligned; a launch is asynchronous on the given stream and returns
 // hipGetLastError().  The launches of one evaluation go to one stream, the blend (when there is one) first, then the levels from the roots
 // down: the kernel boundaries between them are the only ordering.
 #pragma once

@@ -1,5 +1,5 @@
-// pt_rig_mix_launch.hpp — the launch interface of the kernel of pt_rig_mix.hip (include/pt_rig_mix.h), called by the host half of the pose,
-// pt_pose_host.hpp.  Every pointer is device memory, 16-byte aligned (a mask: 4-byte); the launch is asynchronous on the given stream and returns
+// pt_rig_mix_launch.hpp — the launch interface of the kernel of pt_rig_mix.hip (include/pt_rig_mix.h), called by the host half of the rig,
+// pt_rig_host.hpp.  Every pointer is device memory, 16-byte aligned (a mask: 4-byte); the launch is asynchronous on the given stream and returns
 // hipGetLastError().  It goes to the pose's stream ahead of the rig's levels: the kernel boundary between them is the only ordering.
 #pragma once
 #include <hip/hip_runtime.h>

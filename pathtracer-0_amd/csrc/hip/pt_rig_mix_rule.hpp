@@ -3,7 +3,7 @@
 // kernel, and ptp::rigMix, a plain C++ statement of steps 2-7 that k_rig_mix (pt_rig_mix.hip) is the device statement of.  The key blend and
 // the interval are pt_rig_rule.hpp's (ptp::rigBlend, ptp::rigInterval), used and not restated.  Plain C++: no HIP runtime call and no context, so
 // tests/c/rig_mix_rule_check.cpp runs all of it on a CPU.  Whether a rig is live, whose its pose is and which slots are filled are the
-// registry's and the rig's to say (pt_pose_host.hpp); they arrive here as answers.  Binary32 throughout, every product rounded before every
+// registry's and the rig's to say (pt_rig_host.hpp); they arrive here as answers.  Binary32 throughout, every product rounded before every
 // sum, in the written order (the file is compiled with -ffp-contract=off wherever it is compiled).
 #pragma once
 #include "../../../include/pt_rig_mix.h"

@@ -2,7 +2,7 @@
 // failing check as a code and one text each, in the header's order), the depth and level plan of a hierarchy, a clip's interval and u, and a plain
 // C++ statement of steps 1-5 that k_rig_level and k_rig_blend (pt_rig.hip) are the device statements of.  Plain C++: no HIP runtime call and no
 // context, so tests/c/rig_rule_check.cpp runs all of it on a CPU.  Whether a rig is live and whose its pose is are the registry's to say
-// (pt_pose_host.hpp); they arrive here as answers.  Binary32 throughout, every product rounded before every sum, in the written order (the file
+// (pt_rig_host.hpp); they arrive here as answers.  Binary32 throughout, every product rounded before every sum, in the written order (the file
 // is compiled with -ffp-contract=off wherever it is compiled); sqrt and / are correctly rounded.
 #pragma once
 #include "../../../include/pt_rig.h"

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import _move_cases as MC
+import _pose_model as PM
 import _rig_model as RM
 from test_gpu_move import context, frame, records, same_image, same_records
 from test_gpu_pose import one_soup, same_floats
@@ -360,3 +361,46 @@ def test_destroyed_rigs_and_rigs_of_destroyed_poses_are_refused(pt, renderer_mod
     refused(h2)
     assert L.pt_rig_create(hp, parent.ctypes.data, parent.nbytes, None, 0, C.byref(out2)) == -1 and L.pt_last_error().decode() == "pt_rig_create: the pose is not live"
     g2._h = None; p2._h = None
+
+
+# ------------------------------------------------------------------------------------------------ the timers' argument checks
+
+def test_every_timer_of_the_family_refuses_under_its_own_name(pt, renderer_mod):
+    """The seven pt_debug_*_time calls of the pose family share their argument checks: each one, with one argument wrong at a time (a null
+    msBest, reps == 0, null data, a byte count off by 4, a destroyed handle), answers -1 and "<name>: bad argument" before anything is
+    enqueued, leaves *msBest alone, and times a good call afterwards.  Two triangles, one moving; one part, one joint."""
+    L = renderer_mod.lib()
+    r = context(renderer_mod, one_soup(pt, 2), MC.SKY, (MC.W, MC.H))
+    bone, weight = np.full((2, 12), -1, np.int32), np.zeros((2, 12), f32)
+    bone[0, 0::4], weight[0, 0::4] = 0, 1.0
+    parts = np.array([0, -1], np.int32)
+    part, skin, dq = r.pose_create(parts, 1), r.skin_create(bone, weight, 1), r.skin_create(bone, weight, 1, blend="dq")
+    part.morph_attach([(np.array([0], np.int32), np.full((1, 6), 0.25, f32))])
+    part.normals_attach(np.array([0, 1, 2, -1, -1, -1], np.int32))
+    rig = make_rig(part, RM.chain(1))
+    rig.mix_clip(0, np.array([0.0], f32), RM.random_locals(1, 1))
+    gone = r.pose_create(parts, 1)                                          # destroyed below, after the last create: its address is not handed out again
+    gone_rig = make_rig(gone, RM.chain(1))
+    dead, dead_rig = C.c_void_p(gone._h.value), C.c_void_p(gone_rig._h.value)
+    gone.close(); gone_rig._h = None                                        # the rig went with its pose
+    x = np.ascontiguousarray(PM.matrices(1), f32).reshape(-1)
+    w = np.array([0.5], f32)
+    l = np.ascontiguousarray(RM.random_locals(1, 2), f32).reshape(-1)
+    y = renderer_mod.rig_layers([(0, 0.0)])
+    assert (x.nbytes, w.nbytes, l.nbytes, y.nbytes) == (96, 4, 48, 24)
+    # (the call, its handle, a destroyed one, the data, the arguments between the byte count and reps)
+    timers = [("pt_debug_pose_time", part._h, dead, x, (0,)), ("pt_debug_skin_time", skin._h, dead, x, (0,)), ("pt_debug_skin_dq_time", dq._h, dead, x, ()),
+              ("pt_debug_normals_time", part._h, dead, x, (0,)), ("pt_debug_morph_time", part._h, dead, w, ()), ("pt_debug_rig_time", rig._h, dead_rig, l, ()),
+              ("pt_debug_rig_mix_time", rig._h, dead_rig, y, ())]
+    for name, h, destroyed, data, which in timers:
+        call, best = getattr(L, name), C.c_float(-2.0)
+        p, nb, ms = data.ctypes.data, data.nbytes, C.byref(best)
+        bad = {"null msBest": (h, p, nb, *which, 1, None), "reps == 0": (h, p, nb, *which, 0, ms), "null data": (h, None, nb, *which, 1, ms),
+               "four bytes more": (h, p, nb + 4, *which, 1, ms), "four bytes less": (h, p, nb - 4, *which, 1, ms), "destroyed": (destroyed, p, nb, *which, 1, ms)}
+        for what, args in bad.items():
+            assert call(*args) == -1, (name, what)
+            assert L.pt_last_error().decode() == f"{name}: bad argument", (name, what, L.pt_last_error())
+            assert best.value == -2.0, (name, what)
+        assert call(h, p, nb, *which, 1, ms) == 0, (name, L.pt_last_error())
+        assert best.value >= 0.0, name
+    r.close()

@@ -372,3 +372,48 @@ def test_destroyed_rigs_and_rigs_of_destroyed_poses_are_refused(pt, renderer_mod
     refused(h2)
     assert not loc.any() and not rec.any()
     g2._h = None; p2._h = None
+
+
+# ------------------------------------------------------------------------------------------------ one rig, every source, any order
+
+def test_one_rig_answers_locals_clip_and_mix_calls_in_any_order(bench, renderer_mod):
+    """The caller's locals, the own clip and a mix share the rig's dLocals, and a time at a key reads the clip in place: seven calls of the three
+    sources interleaved on one rig, each against its model bit for bit, then the same calls in reverse order, each the same bits as before.
+    Five joints over three levels, one of them three joints wide; the mix has two layers over its base, one masked and one additive."""
+    r, static = bench
+    n = 5
+    parent, bind = np.array([-1, 0, 1, 0, 0], np.int32), RM.random_binds(n, 3)
+    pose = r.pose_create(static, n)
+    rig = make_rig(pose, parent, bind)
+    times, values = np.array([0.0, 1.0, 2.5], f32), np.stack([RM.random_locals(n, 40 + k) for k in range(3)])
+    clips = {0: (np.array([0.5, 2.0], f32), np.stack([RM.random_locals(n, 50 + k) for k in range(2)])),
+             1: (np.array([0.0, 1.0, 3.0], f32), np.stack([RM.random_locals(n, 55 + k, unnormalised=False) for k in range(3)]))}
+    masks = {0: np.array([0.0, 1.0, 0.25, 0.5, 1.0], f32)}
+    rig.clip(times, values)
+    fill(rig, clips, masks)
+    A, B = RM.random_locals(n, 60), RM.random_locals(n, 61)
+    layers = [MM.layer(1, 1.5), MM.layer(0, 1.0, 0.75, 0), MM.layer(1, 0.5, 0.5, -1, MM.ADDITIVE)]
+    y = pack(renderer_mod, layers)
+    at = lambda t: RM.clip_records(parent, times, values, f32(t), bind)
+    assert RM.interval(times, f32(1.0))[0] == 1 and RM.interval(times, f32(1.75))[0] < 0 and RM.interval(times, f32(0.0))[0] == 0
+    calls = [("records(A)", lambda: rig.records(A), RM.records(parent, A, bind)),
+             ("records_at(key 1)", lambda: rig.records_at(1.0), at(1.0)),
+             ("mix_records", lambda: rig.mix_records(y), MM.mix_records(parent, clips, masks, layers, bind)),
+             ("records_at(between keys 1 and 2)", lambda: rig.records_at(1.75), at(1.75)),
+             ("records(B)", lambda: rig.records(B), RM.records(parent, B, bind)),
+             ("mix_locals", lambda: rig.mix_locals(y), MM.mix_locals(clips, masks, layers, n)),
+             ("records_at(key 0)", lambda: rig.records_at(0.0), at(0.0))]
+    forward = []
+    for tag, call, want in calls:
+        forward.append(call())
+        same_floats(forward[-1], want, tag)
+    for (tag, call, _), was in reversed(list(zip(calls, forward))):
+        assert np.array_equal(call().view(np.uint32), was.view(np.uint32)), (tag, "reversed")
+    assert len({a.tobytes() for a in forward}) == len(forward)              # seven different answers: none is another call's left over
+    times2, values2 = np.array([0.25, 1.0], f32), np.stack([RM.random_locals(n, 70), RM.random_locals(n, 71)])
+    rig.clip(times2, values2)                                               # the own clip replaced, by one of another key count: the slots stay
+    for t in (0.25, 0.5, 1.0, 2.5):
+        same_floats(rig.records_at(t), RM.clip_records(parent, times2, values2, f32(t), bind), ("replaced", t))
+    one = [MM.layer(1, 1.5)]
+    same_floats(rig.mix_records(pack(renderer_mod, one)), MM.mix_records(parent, clips, masks, one, bind), "slot 1 after rig.clip")
+    rig.close(); pose.close()
