@@ -114,6 +114,11 @@ int pt_debug_rig_time(struct pt_rig* rig, const float* locals, size_t local_byte
  * or the context changes.  PT_ERR_ARG: a null or destroyed rig, n_parts == 0, layers that pt_rig_mix_locals refuses, reps < 1, null ms_best. */
 struct pt_rig_layer;
 int pt_debug_rig_mix_time(struct pt_rig* rig, const struct pt_rig_layer* layers, size_t layer_bytes, int reps, float* ms_best);
+/* The device time of the one launch of k_rig_ik of include/pt_rig_ik.h (scripts/rig_ik_probe.py) over the given locals under the goals that are
+ * set: the locals are uploaded, the levels ahead of the solve run once, then one pair of HIP events around the launch, the best of reps, on the
+ * pose's stream.  The rig's locals are written (what pt_rig_ik_locals downloads); nothing of the pose or the context changes.  PT_ERR_ARG: a null
+ * or destroyed rig, n_parts == 0, no table or no goals set, null locals, local_bytes != n_parts * 48, reps < 1, null ms_best. */
+int pt_debug_rig_ik_time(struct pt_rig* rig, const float* locals, size_t local_bytes, int reps, float* ms_best);
 
 #ifdef __cplusplus
 }

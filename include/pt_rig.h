@@ -73,6 +73,7 @@
  * its address is not reused.  ORDER and threads: as include/pt_pose.h.  pt_debug_rig_time (include/pt_debug.h) times the rig's launches.
  *
  * SEVERAL CLIPS AT ONCE (cross-fades, masked and additive layers, loops): include/pt_rig_mix.h.
+ * GOALS IN WORLD SPACE (two-bone chains and aims solved between a call's locals and its levels): include/pt_rig_ik.h.
  *
  * NOT BUILT: sparse per-channel tracks, slerp, cubic keys, joints that write no record.
  */

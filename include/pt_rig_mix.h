@@ -58,6 +58,7 @@
  *   but its kernel arguments and downloads R, as the rig's calls do.
  *   One OVERRIDE / CLAMP layer on a slot equals pt_rig_clip_records of the same clip at the same t, bit for bit.
  *   The calls of include/pt_rig.h behave exactly as before.
+ *   While goals are set (include/pt_rig_ik.h) pt_rig_mix_records and pt_rig_mix_pose_geometry solve them over the mixed locals; pt_rig_mix_locals stays the mix alone.
  *
  * REFUSALS, all PT_ERR_ARG, in this order (the first failing check answers):
  *   pt_rig_mix_clip           a null or destroyed rig; a slot outside [0, 16); n_keys < 1; null times, or null values with n_parts > 0;

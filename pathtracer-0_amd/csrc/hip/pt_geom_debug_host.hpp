@@ -1,9 +1,9 @@
-// pt_geom_debug_host.hpp — the pose family's host half of include/pt_debug.h: the seven timers (pt_debug_pose_time, _skin_time, _skin_dq_time,
-// _morph_time, _normals_time, _rig_time, _rig_mix_time) and the two readers (pt_debug_pose_scratch, pt_debug_morph_rest).  Included at the end of
+// pt_geom_debug_host.hpp — the pose family's host half of include/pt_debug.h: the eight timers (pt_debug_pose_time, _skin_time, _skin_dq_time,
+// _morph_time, _normals_time, _rig_time, _rig_mix_time, _rig_ik_time) and the two readers (pt_debug_pose_scratch, pt_debug_morph_rest).  Included at the end of
 // pt_image.hpp after pt_pose_host.hpp and pt_rig_host.hpp, inside pt_hip.hip's extern "C" block; not a translation unit.
 //
 // It takes the objects and their steps from those two files: ruleLaunch, morphRest, normalsInto, poseToHost, scratchStands and restInto of the
-// pose; localsFromCaller, localsFromMix, rigMixTable and rigRun of the rig.  Nothing here is called by them.
+// pose; localsFromCaller, localsFromMix, rigMixTable, rigRun and rigRunLevels of the rig.  Nothing here is called by them.
 //
 // What a reader must know.  A timer refuses with "<name>: bad argument" before anything is enqueued, and ahead of any longer sentence about a
 // pose of the wrong rule; it leaves *msBest alone unless it succeeds.  What is timed is what bestTime's `enqueue` puts on the plan's stream,
@@ -151,4 +151,22 @@ int pt_debug_rig_mix_time(pt_rig* G, const pt_rig_layer* layers, size_t layerByt
     const PtRigMixTable T = rigMixTable(G, layers, layerBytes);
     // (a launch reads keys and masks and writes dLocals: every repetition gives the same bits)
     return bestTime(G->pose->plan->stream, reps, "pt_debug_rig_mix_time", [&] { return localsFromMix(G, T) != nullptr; }, msBest);
+}
+
+// the device time of the solve's one launch under the goals set (the best of reps): the given locals uploaded into dLocals and copied aside, the
+// levels ahead of the solve once, then k_rig_ik reading the copy and writing dLocals
+int pt_debug_rig_ik_time(pt_rig* G, const float* locals, size_t localBytes, int reps, float* msBest) {
+    if (!rigTimable(G, reps, msBest) || !G->ikActive() || !locals || localBytes != (size_t)G->n * JOINT_BYTES) return fail(PT_ERR_ARG, "pt_debug_rig_ik_time: bad argument");
+    const hipStream_t st = G->pose->plan->stream;
+    const float* at = localsFromCaller(G, locals);                // (selects the pose's device)
+    if (!at) return PT_ERR_HIP;
+    Dev<float> aside;
+    HIP_TRY(aside.reset(localBytes));
+    HIP_TRY(hipMemcpyAsync(aside, at, localBytes, hipMemcpyDeviceToDevice, st));
+    if (const int rc = rigRunLevels(G, at, G->dR, 0, G->ikWindow.before)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    // (a launch reads the copy and W and writes dLocals: every repetition gives the same bits, those pt_rig_ik_locals downloads)
+    return bestTime(st, reps, "pt_debug_rig_ik_time", [&] {
+        return ptRigIkLaunch(G->dIkRows, G->dIkCons, G->dIkGoals, (int)G->nIk, G->dW, aside, G->dLocals, st) == hipSuccess;
+    }, msBest);
 }

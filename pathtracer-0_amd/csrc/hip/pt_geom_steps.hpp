@@ -1,4 +1,4 @@
-// pt_geom_steps.hpp — the steps that the geometry units share: pt_pose.hip, pt_skin.hip, pt_skin_dq.hip, pt_rig.hip, pt_rig_mix.hip, pt_morph.hip and pt_normals.hip include
+// pt_geom_steps.hpp — the steps that the geometry units share: pt_pose.hip, pt_skin.hip, pt_skin_dq.hip, pt_rig.hip, pt_rig_mix.hip, pt_rig_ik.hip, pt_morph.hip and pt_normals.hip include
 // it after <hip/hip_runtime.h>, and nobody else does.  Not a launch header: the host half of the pose never sees it, and no render kernel is
 // here, so kernel_source_hash() does not cover it.  Every unit that includes it is compiled with -ffp-contract=off, so each a * b + c below is
 // a rounded product and a rounded sum, in the order written: the CPU statements of the *_rule.hpp files are the specification of that order.

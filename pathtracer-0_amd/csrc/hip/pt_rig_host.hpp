@@ -1,22 +1,29 @@
-// pt_rig_host.hpp — the rig object behind the C ABI: the entry points of include/pt_rig.h and include/pt_rig_mix.h (their timers are
-// pt_geom_debug_host.hpp's).  Included at the end of pt_image.hpp after pt_pose_host.hpp, inside pt_hip.hip's extern "C" block; not a translation unit.
+// pt_rig_host.hpp — the rig object behind the C ABI: the entry points of include/pt_rig.h, include/pt_rig_mix.h and include/pt_rig_ik.h (their
+// timers are pt_geom_debug_host.hpp's).  Included at the end of pt_image.hpp after pt_pose_host.hpp, inside pt_hip.hip's extern "C" block; not a translation unit.
 //
 // It takes: the kernels behind pt_rig_launch.hpp (the key blend, one launch per level of the hierarchy) and pt_rig_mix_launch.hpp (the mix's one
-// launch); the argument checks, level plan, clip interval, loop wrap and CPU statements of pt_rig_rule.hpp and pt_rig_mix_rule.hpp; and from
+// launch) and pt_rig_ik_launch.hpp (the solve's one launch); the argument checks, level plan, clip interval, loop wrap, independence check and
+// level window of pt_rig_rule.hpp, pt_rig_mix_rule.hpp and pt_rig_ik_rule.hpp; and from
 // pt_pose_host.hpp poseGeometry, poseLive, the registry mutex, staleRefused and the pose's plan, on whose stream a rig does all its work.
 //
 // What a reader must know.  A rig belongs to a pose of any rule and makes that pose's records on the device.  Every record call reads: check,
 // source, tail.  A source (localsFromCaller, localsFromClip, localsFromMix) makes the call's locals available on the device and returns where;
 // all three share dLocals, except that a time at a key reads that key's locals in the clip, in place.  A tail runs the levels over them into dR
 // and downloads the records (rigRecords), or does that and hands them to poseGeometry with dR as the records on the device (rigGeometry).
+// While goals are set (pt_rig_ik_goals) over a table with constraints, one stage sits between source and levels: rigLevels runs it.  It brings
+// the locals into dLocals if the source answered elsewhere (a clip's keys are never written), runs the levels that make the first joints'
+// parents' world matrices, then k_rig_ik on dLocals, then the levels from the shallowest first joint down (ptp::RigIkWindow).
 // A rig without joints enqueues nothing.  Every call ends with the plan's stream idle.
 extern "C++" {
+#include "pt_rig_ik_launch.hpp"
+#include "pt_rig_ik_rule.hpp"
 #include "pt_rig_launch.hpp"
 #include "pt_rig_mix_launch.hpp"
 #include "pt_rig_mix_rule.hpp"
 #include "pt_rig_rule.hpp"
 }
 #include "../../../include/pt_rig.h"
+#include "../../../include/pt_rig_ik.h"
 #include "../../../include/pt_rig_mix.h"
 
 // a rig of include/pt_rig.h: one joint per record of its pose
@@ -37,6 +44,13 @@ struct pt_rig {
     Clip mixClip[PT_RIG_MIX_SLOTS];     // pt_rig_mix_clip's
     Dev<float> dMixMask[PT_RIG_MIX_MASKS];      // pt_rig_mix_mask's, n floats each
     ptp::RigMixSlots slots;             // which slots are filled, as the checks of pt_rig_mix_rule.hpp take it: kept in step with the two lines above
+    std::vector<int32_t> parent;        // the parents by joint id, as dParent holds them: what pt_rig_ik_attach checks against
+    size_t nIk = 0;                     // the constraints of pt_rig_ik_attach's table
+    ptp::RigIkWindow ikWindow;          // the levels around the solve
+    Dev<int32_t> dIkRows;               // ptp::RigIkRow, 16 bytes per constraint
+    Dev<float> dIkCons, dIkGoals;       // the table and pt_rig_ik_goals', 32 bytes per constraint each
+    bool ikGoals = false;               // goals are set
+    bool ikActive() const { return ikGoals && nIk > 0; }
 };
 
 namespace {
@@ -59,10 +73,11 @@ void rigsFree(pt_pose* P) {
 
 // THE store of a table of the rig (a clip's keys, a mask): staged, uploaded and synchronised on the plan's stream, then moved into place — the
 // rig changes only once the allocation stands
-int rigStore(pt_rig* G, const float* values, size_t bytes, Dev<float>& into) {
+extern "C++" template <class T>
+int rigStore(pt_rig* G, const void* values, size_t bytes, Dev<T>& into) {
     const hipStream_t st = G->pose->plan->stream;
     HIP_TRY(hipSetDevice(G->pose->device));
-    Dev<float> staged;
+    Dev<T> staged;
     HIP_TRY(staged.upload(values, bytes, st));
     HIP_TRY(hipStreamSynchronize(st));
     into = std::move(staged);
@@ -134,14 +149,32 @@ const float* localsFromMix(pt_rig* G, const PtRigMixTable& mix) {
 
 // ---- the tails
 
-// steps 1-4 over the locals at `at` (device) into `records`, level by level from the roots down; asynchronous on the plan's stream
-int rigRun(pt_rig* G, const float* at, float* records) {
+// steps 1-4 over the locals at `at` (device) into `records`, the levels [from, to) from the roots down; asynchronous on the plan's stream
+int rigRunLevels(pt_rig* G, const float* at, float* records, int from, int to) {
     const hipStream_t st = G->pose->plan->stream;
-    for (int l = 0; l < G->plan.levels(); l++) {
+    for (int l = from; l < to; l++) {
         const int first = G->plan.levelStart[(size_t)l], count = G->plan.levelStart[(size_t)l + 1] - first;
         HIP_TRY(ptRigLevelLaunch(G->dOrder, first, count, G->dParent, at, G->hasBind ? (const float*)G->dBind : nullptr, G->dW, records, st));
     }
     return 0;
+}
+int rigRun(pt_rig* G, const float* at, float* records) { return rigRunLevels(G, at, records, 0, G->plan.levels()); }
+
+// include/pt_rig_ik.h's stage up to the solve (the rig has joints and ikActive()): the locals at `at` brought into dLocals unless they lie
+// there, the levels ahead of the solve, and k_rig_ik in place on dLocals
+int rigIkSolve(pt_rig* G, const float* at) {
+    const hipStream_t st = G->pose->plan->stream;
+    if (at != (const float*)G->dLocals) HIP_TRY(hipMemcpyAsync(G->dLocals, at, (size_t)G->n * JOINT_BYTES, hipMemcpyDeviceToDevice, st));
+    if (const int rc = rigRunLevels(G, G->dLocals, G->dR, 0, G->ikWindow.before)) return rc;
+    HIP_TRY(ptRigIkLaunch(G->dIkRows, G->dIkCons, G->dIkGoals, (int)G->nIk, G->dW, G->dLocals, G->dLocals, st));
+    return 0;
+}
+
+// the levels of a tail over the locals at `at`: all of them, or with goals set the stage of include/pt_rig_ik.h
+int rigLevels(pt_rig* G, const float* at, float* records) {
+    if (!G->ikActive()) return rigRun(G, at, records);
+    if (const int rc = rigIkSolve(G, at)) return rc;
+    return rigRunLevels(G, G->dLocals, records, G->ikWindow.from, G->plan.levels());
 }
 
 // the records of the locals at `at` (a source's answer) into dR, and downloaded; the plan's stream is idle afterwards
@@ -149,7 +182,7 @@ int rigRecords(pt_rig* G, const float* at, float* out) {
     const hipStream_t st = G->pose->plan->stream;
     if (!at) return PT_ERR_HIP;
     if (G->n) {
-        if (const int rc = rigRun(G, at, G->dR)) return rc;
+        if (const int rc = rigLevels(G, at, G->dR)) return rc;
         HIP_TRY(hipMemcpyAsync(out, G->dR, (size_t)G->n * RECORD_BYTES, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -172,6 +205,7 @@ int pt_rig_create(pt_pose* P, const int32_t* parent, size_t parentBytes, const f
     if (int rc = fail(ptp::checkRigCreate(P, live, parent, parentBytes, invBind, bindBytes, out, live ? P->nParts : 0))) return rc;
     pt_rig* G = new pt_rig();
     G->pose = P; G->n = P->nParts; G->hasBind = invBind != nullptr;
+    G->parent.assign(parent, parent + G->n);
     ptp::rigPlan(parent, (size_t)G->n, G->plan);
     const hipStream_t st = P->plan->stream;
     const size_t n = (size_t)G->n;
@@ -277,4 +311,48 @@ int pt_rig_mix_pose_geometry(pt_ctx* c, pt_rig* G, const pt_rig_layer* layers, s
     if (int rc = mixRefused(ptp::RIG_MIX_GEOMETRY, c, G, layers, layerBytes, ellip, ellipBytes)) return rc;
     if (G->pose->stale) return staleRefused("pt_rig_mix_pose_geometry");
     return rigGeometry(c, G, localsFromMix(G, rigMixTable(G, layers, layerBytes)), ellip, ellipBytes, rootCost, inPlace, "pt_rig_mix_pose_geometry");
+}
+
+// ---- include/pt_rig_ik.h
+
+int pt_rig_ik_attach(pt_rig* G, const pt_rig_ik_constraint* cons, size_t bytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigIkAttach(live, cons, bytes, live ? G->parent.data() : nullptr, live ? G->n : 0))) return rc;
+    const size_t n = bytes / sizeof(pt_rig_ik_constraint);
+    std::vector<ptp::RigIkRow> rows(n);
+    for (size_t k = 0; k < n; k++) rows[k] = ptp::rigIkRow(G->parent.data(), cons[k]);
+    Dev<int32_t> dRows;
+    Dev<float> dCons;
+    if (const int rc = rigStore(G, rows.data(), n * sizeof(ptp::RigIkRow), dRows)) return rc;
+    if (const int rc = rigStore(G, cons, bytes, dCons)) return rc;
+    G->dIkRows = std::move(dRows); G->dIkCons = std::move(dCons);     // (both stand: the rig changes now)
+    G->nIk = n;
+    G->ikWindow = ptp::rigIkWindow(G->parent.data(), (size_t)G->n, cons, n);
+    G->ikGoals = false;
+    G->dIkGoals.release();
+    return PT_OK;
+}
+
+int pt_rig_ik_goals(pt_rig* G, const pt_rig_ik_goal* goals, size_t bytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigIkGoals(live, goals, bytes, live ? G->nIk : 0))) return rc;
+    if (!goals) { G->ikGoals = false; return PT_OK; }
+    if (const int rc = rigStore(G, goals, bytes, G->dIkGoals)) return rc;
+    G->ikGoals = true;
+    return PT_OK;
+}
+
+int pt_rig_ik_locals(pt_rig* G, const float* locals, size_t localBytes, float* localsOut, size_t outBytes) {
+    const bool live = rigLive(G);
+    if (int rc = fail(ptp::checkRigIkLocals(live, locals, localBytes, localsOut, outBytes, live ? G->n : 0))) return rc;
+    const hipStream_t st = G->pose->plan->stream;
+    const float* at = localsFromCaller(G, locals);
+    if (!at) return PT_ERR_HIP;
+    if (G->n) {
+        if (G->ikActive())
+            if (const int rc = rigIkSolve(G, at)) return rc;
+        HIP_TRY(hipMemcpyAsync(localsOut, G->dLocals, outBytes, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return PT_OK;
 }

@@ -229,6 +229,11 @@ def lib():
             L.pt_rig_mix_records.argtypes = [vp, vp, sz, vp, sz]
             L.pt_rig_mix_pose_geometry.argtypes = [vp, vp, vp, sz, vp, sz, vp, cip]
             L.pt_debug_rig_mix_time.argtypes = [vp, vp, sz, ci, C.POINTER(cf)]
+        if hasattr(L, "pt_rig_ik_attach"):                    # include/pt_rig_ik.h, and its kernel timer in include/pt_debug.h
+            L.pt_rig_ik_attach.argtypes = [vp, vp, sz]
+            L.pt_rig_ik_goals.argtypes = [vp, vp, sz]
+            L.pt_rig_ik_locals.argtypes = [vp, vp, sz, vp, sz]
+            L.pt_debug_rig_ik_time.argtypes = [vp, vp, sz, ci, C.POINTER(C.c_float)]
         if hasattr(L, "pt_morph_attach"):                     # include/pt_morph.h, and its kernel timer and read-back in include/pt_debug.h
             L.pt_morph_attach.argtypes = [vp, ci, vp, sz, vp, sz, vp, sz]
             L.pt_morph_weights.argtypes = [vp, vp, sz]
@@ -526,6 +531,46 @@ def rig_layers(layers):
     return out
 
 
+RIG_IK_CONSTRAINT = np.dtype([("kind", np.int32), ("joint", np.int32), ("flags", np.int32), ("pad", np.int32), ("axis", np.float32, 3), ("padf", np.float32)])      # 32 bytes
+RIG_IK_GOAL = np.dtype([("target", np.float32, 3), ("weight", np.float32), ("pole", np.float32, 3), ("padf", np.float32)])      # pt_rig_ik_goal, 32 bytes
+RIG_IK_KINDS = {"two_bone": 0, "aim": 1}
+RIG_IK_POLE = 1
+
+
+def rig_ik_constraints(constraints):
+    """The 32-byte constraint records of include/pt_rig_ik.h from a list of tuples (kind, joint[, pole[, axis]]) or dicts with those keys: kind
+    "two_bone" (joint is the tip) or "aim" (or the number), pole whether a two-bone goal's pole is read, axis the aim's unit axis in the
+    joint's frame.  An array of RIG_IK_CONSTRAINT passes through."""
+    if isinstance(constraints, np.ndarray) and constraints.dtype == RIG_IK_CONSTRAINT:
+        return np.ascontiguousarray(constraints).reshape(-1)
+    names = ("kind", "joint", "pole", "axis")
+    out = np.zeros(len(constraints), RIG_IK_CONSTRAINT)
+    for i, c in enumerate(constraints):
+        d = dict(pole=False, axis=(0.0, 0.0, 0.0))
+        d.update(c if isinstance(c, dict) else dict(zip(names, c)))
+        if set(d) - set(names) or "kind" not in d or "joint" not in d:
+            raise ValueError(f"rig_ik_constraints: constraint {i} needs kind and joint and knows {names}")
+        kind = d["kind"]
+        out[i] = (RIG_IK_KINDS[kind] if isinstance(kind, str) else int(kind), int(d["joint"]), RIG_IK_POLE if d["pole"] else 0, 0, np.asarray(d["axis"], np.float32), 0.0)
+    return out
+
+
+def rig_ik_goals(goals):
+    """The 32-byte goal records of include/pt_rig_ik.h, one per constraint, from a list of tuples (target[, weight[, pole]]) or dicts with those
+    keys, in world space; weight defaults to 1.  An array of RIG_IK_GOAL passes through."""
+    if isinstance(goals, np.ndarray) and goals.dtype == RIG_IK_GOAL:
+        return np.ascontiguousarray(goals).reshape(-1)
+    names = ("target", "weight", "pole")
+    out = np.zeros(len(goals), RIG_IK_GOAL)
+    for i, g in enumerate(goals):
+        d = dict(weight=1.0, pole=(0.0, 0.0, 0.0))
+        d.update(g if isinstance(g, dict) else dict(zip(names, g)))
+        if set(d) - set(names) or "target" not in d:
+            raise ValueError(f"rig_ik_goals: goal {i} needs target and knows {names}")
+        out[i] = (np.asarray(d["target"], np.float32), np.float32(d["weight"]), np.asarray(d["pole"], np.float32), 0.0)
+    return out
+
+
 class Rig:
     """A rig of include/pt_rig.h (Pose.rig): a joint per record of its pose, evaluated on the device.  It belongs to its Pose, whose close()
     destroys it, as the Renderer's does."""
@@ -618,6 +663,35 @@ class Rig:
         """Rig.pose with the records of the mixed locals (pt_rig_mix_pose_geometry): the step uploads the layers, 24 bytes each"""
         y = rig_layers(layers)
         return self._geometry(self._mix_call("pt_rig_mix_pose_geometry"), y.ctypes.data if y.size else None, y.nbytes, ellip=ellip)
+
+    def _ik_call(self, name):
+        if not hasattr(self._L, name):
+            raise RuntimeError(f"this libpt_hip.so has no {name} (include/pt_rig_ik.h): no fallback")
+        return getattr(self._L, name)
+
+    def ik(self, constraints):
+        """Attach the constraint table of include/pt_rig_ik.h (pt_rig_ik_attach): rig_ik_constraints, or what it takes.  It replaces the table
+        (an empty list: none) and clears the goals."""
+        c = rig_ik_constraints(constraints)
+        _check(self._ik_call("pt_rig_ik_attach")(self._h, c.ctypes.data if c.size else None, c.nbytes))
+        self.n_constraints = c.size
+
+    def ik_goals(self, goals):
+        """Set the goals (pt_rig_ik_goals), one per constraint, in world space: rig_ik_goals, or what it takes.  While they are set every
+        record call of the rig solves the constraints between its source and its levels.  None: off."""
+        if goals is None:
+            _check(self._ik_call("pt_rig_ik_goals")(self._h, None, 0))
+            return
+        g = rig_ik_goals(goals)
+        keep = np.zeros(1, RIG_IK_GOAL)                          # (an empty array of goals is not None: goals for an empty table)
+        _check(self._ik_call("pt_rig_ik_goals")(self._h, g.ctypes.data if g.size else keep.ctypes.data, g.nbytes))
+
+    def ik_locals(self, locals):
+        """these locals after the solve under the goals set, (n_parts, 12): the rule alone (pt_rig_ik_locals)"""
+        l, lp = self._floats(locals)
+        out = np.empty((self.n_parts, 12), np.float32)
+        _check(self._ik_call("pt_rig_ik_locals")(self._h, lp, l.nbytes, out.ctypes.data, out.nbytes))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -748,6 +748,30 @@ def m8_mixed(step=0, W=96, H=54, n_bones=5, **kw):
     return (wl, bone, weight) + m8_rig(wl, n_bones) + (m8_layers(step),)
 
 
+M9_CONSTRAINTS = [dict(kind="two_bone", joint=4, pole=True)]            # joints 2-3-4 of the chain: root 2, mid 3, tip 4
+
+
+def m9_goals(wl, step, n_bones=5):
+    """the goals of m9_reaching at `step`, as renderer.rig_ik_goals takes them: the target circles beside the tube at the height of the chain's
+    mid, within the two bones' reach of the chain's root; the pole stands off to the side the target circles on, so the chain bends outwards"""
+    cx, y0, y1, cz = wl.info["axis"]
+    bone = (y1 - y0) / (n_bones - 1)
+    s = 0.35 * float(step)
+    root_y = y0 + 1.5 * bone                                           # hinge 2
+    target = (cx + 0.9 * bone * math.cos(s), root_y + bone, cz + 0.9 * bone * math.sin(s))
+    pole = (cx + 4.0 * bone * math.cos(s + 0.6), root_y + 0.5 * bone, cz + 4.0 * bone * math.sin(s + 0.6))
+    return [dict(target=target, weight=1.0, pole=pole)]
+
+
+def m9_reaching(step=0, W=96, H=54, n_bones=5, **kw):
+    """M9 at `step`, the workload of include/pt_rig_ik.h (not a BASELINE config): M8's tube, clips, mask and layers, with joints 2-3-4 as a
+    two-bone chain whose tip follows a target circling beside the tube, bent towards a pole.  -> what m8_mixed returns, then the constraints
+    (M9_CONSTRAINTS) and the goals of the step (m9_goals)."""
+    out = m8_mixed(step, W, H, n_bones, **kw)
+    out[0].name = "M9"
+    return out + (list(M9_CONSTRAINTS), m9_goals(out[0], step, n_bones))
+
+
 def asset_workload(directory, W, H, cam=CORNELL_CAM, rot=CORNELL_ROT, sky=(30, 40, 60), sample_res=8, max_bounces=8, name="asset",
                    scale=1.0, shift=0.0, rotate=0.0, **pk):
     """The reference's way of loading a model (dispatch.java:219-229 + :869-882): texture 0 is the sky, then
